@@ -7,7 +7,7 @@ One "step" = one pass of the hot path over one batch of clips already resident i
     audio (B,N) -> HIP mel front-end -> HIP Onsets&Frames engine -> piano rolls (B,88,T) x2
 through the product API (`model.run_on_batch({'audio': ...})` with the front-end in `model.frontend`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B] [--mode infer|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B] [--mode infer|train] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU.  `python bench.py --gpus N` on its own starts the N ranks itself (fresh child processes with
@@ -20,9 +20,15 @@ torchrun the ranks already exist.  WORLD_SIZE != --gpus is an error, never a sil
                           625 frames per GPU, clip-level data parallelism (amt_tools_amd.dp.DataParallelOptimizer: ONE flat RCCL
                           gradient all-reduce inside optimizer.step(), amt_tools/train.py:126-141 unchanged).  Weak scaling.
 
-Rank 0 prints ONE JSON line (contract in the task description) with two extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run does only what that
+headline needs: set up, warm up, time --steps steps, write --dump-outputs, print the line.  --full adds everything else:
   roofline     -- dominant kernel of the timed region, timed live with HIP events on the launch stream
   cpu_baseline -- the oracle (numpy front-end + torch-CPU fp32 model restatement) on a bounded sample
+  and, in infer mode at N = 1, the bf16-vs-x3 / oracle parity leg, the HCQT (config 3) leg and the training-step probes.
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32): the piano rolls in infer mode, the
+loss and the weights in train mode; above 64 MB in all, the same seeded sample of rows (clips) of every array.  The inputs depend only
+on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -92,10 +98,14 @@ def parse(argv=None):
                                                             '768: 38.6, 1024: 40.2, 1536: 39.5, 2048: 40.4 M frames/s -- and 8 for train, the reference batch)')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'f16', 'x3'])
     ap.add_argument('--of2', action='store_true', help='train mode: OnsetsFrames2 as shipped (model_complexity 3, offset head)')
-    ap.add_argument('--cpu-seconds', type=float, default=15.0, help='wall-time budget of the CPU-baseline sample (0 = skip)')
-    ap.add_argument('--no-train-probe', action='store_true', help='skip the one-GPU training-step time (BASELINE metric ii) appended to the default line')
-    ap.add_argument('--no-hcqt', action='store_true', help='skip the BASELINE config-3 leg (OnsetsFrames + HCQT 6 x 72) appended to the default line')
-    ap.add_argument('--no-parity', action='store_true', help='skip the bf16-vs-x3 / oracle cell-mismatch count and the x3 throughput leg')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline figure: per-kernel HIP-event timings and the roofline '
+                                                        'block, the CPU baseline and, in infer mode at N = 1, the parity, HCQT and training legs')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last step returned as '
+                                                                        'DIR/<name>.npy (float32, at most 64 MB in all: a seeded row sample above that)')
+    ap.add_argument('--cpu-seconds', type=float, default=15.0, help='with --full: wall-time budget of the CPU-baseline sample (0 = skip)')
+    ap.add_argument('--no-train-probe', action='store_true', help='with --full: skip the one-GPU training-step time (BASELINE metric ii)')
+    ap.add_argument('--no-hcqt', action='store_true', help='with --full: skip the BASELINE config-3 leg (OnsetsFrames + HCQT 6 x 72)')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the bf16-vs-x3 / oracle cell-mismatch count and the x3 throughput leg')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for N > 1 ('nccl' = RCCL; 'gloo' only for the "
                                                       "single-GPU smoke test of the multi-process path)")
     ap.add_argument('--share-device', action='store_true', help='test only: every rank uses cuda:0')
@@ -334,6 +344,23 @@ def build_model(device, precision):
     model.change_device()
     model.eval()
     return model, mel, sd
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every tensor as <path>/<name>.npy in float32.  When they add up to more than DUMP_BYTES, each array keeps the same
+    share of its rows (first axis), drawn with a fixed seed: arrays with the same number of rows (the clips of the piano rolls) keep the same rows."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: torch.as_tensor(v).detach() for k, v in arrays.items()}
+    total = sum(v.numel() * 4 for v in arrays.values())
+    keep = min(1.0, DUMP_BYTES / max(total, 1))
+    for name, v in arrays.items():
+        if keep < 1.0 and v.dim() > 0 and v.shape[0] > 1:
+            rows = np.sort(np.random.default_rng(seed).choice(v.shape[0], max(1, int(v.shape[0] * keep)), replace=False))
+            v = v[torch.from_numpy(rows).to(v.device)]
+        np.save(os.path.join(path, f'{name}.npy'), v.float().cpu().numpy())
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -732,11 +759,12 @@ def run_infer(args, rank, world, device):
         out = step()
     assert out[tools.KEY_ONSETS].shape == (B, 88, CLIP_FRAMES)
 
-    # per-kernel HIP events on the launch stream, live in the timed region
-    L = _lib.lib()
-    eng = model._get_engine(torch.device(device))
-    _lib.check(L.amtx_of_profile_enable(eng.handle, 1))
-    mel._prof_events = []
+    if args.full:
+        # per-kernel HIP events on the launch stream, live in the timed region
+        L = _lib.lib()
+        eng = model._get_engine(torch.device(device))
+        _lib.check(L.amtx_of_profile_enable(eng.handle, 1))
+        mel._prof_events = []
 
     # a generation-2 garbage collection of the interpreter (tens of ms with torch + numpy loaded) that lands in the first
     # steps of the timed loop stalls the enqueueing thread long enough for the GPU queue to run dry: seen as 15 instead of
@@ -757,37 +785,42 @@ def run_infer(args, rank, world, device):
         nd = min(B, DISTINCT_CLIPS)
         np.savez(os.path.join(args.dump, f'rank{rank}.npz'), onsets=out[tools.KEY_ONSETS][:nd].cpu().numpy().astype(np.uint8),
                  multi_pitch=out[tools.KEY_MULTIPITCH][:nd].cpu().numpy().astype(np.uint8), clip_ids=np.arange(nd) * world + rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if torch.is_tensor(v)})
 
-    stage_ms = (C.c_double * L.amtx_of_num_stages())()
-    nfw = C.c_int(0)
-    _lib.check(L.amtx_of_profile_read(eng.handle, stage_ms, C.byref(nfw)))
-    _lib.check(L.amtx_of_profile_enable(eng.handle, 0))
-    per_launch = {L.amtx_of_stage_name(i).decode(): stage_ms[i] / max(1, nfw.value) for i in range(L.amtx_of_num_stages())}
-    fe_ms = {}
-    for name, e0, e1 in mel._prof_events:
-        fe_ms.setdefault(name, []).append(e0.elapsed_time(e1))
-    mel._prof_events = None
-    for name, v in fe_ms.items():
-        per_launch[name] = float(np.mean(v))
+    if args.full:
+        stage_ms = (C.c_double * L.amtx_of_num_stages())()
+        nfw = C.c_int(0)
+        _lib.check(L.amtx_of_profile_read(eng.handle, stage_ms, C.byref(nfw)))
+        _lib.check(L.amtx_of_profile_enable(eng.handle, 0))
+        per_launch = {L.amtx_of_stage_name(i).decode(): stage_ms[i] / max(1, nfw.value) for i in range(L.amtx_of_num_stages())}
+        fe_ms = {}
+        for name, e0, e1 in mel._prof_events:
+            fe_ms.setdefault(name, []).append(e0.elapsed_time(e1))
+        mel._prof_events = None
+        for name, v in fe_ms.items():
+            per_launch[name] = float(np.mean(v))
 
-    if eng.conv_stack_fused(B, CLIP_FRAMES):
-        # the engine's stage timer books the fused convolution kernel under conv2_pool and launches nothing for conv3_pool
-        per_launch['conv_stack'] = per_launch.pop('conv2_pool')
-        per_launch.pop('conv3_pool', None)
+        if eng.conv_stack_fused(B, CLIP_FRAMES):
+            # the engine's stage timer books the fused convolution kernel under conv2_pool and launches nothing for conv3_pool
+            per_launch['conv_stack'] = per_launch.pop('conv2_pool')
+            per_launch.pop('conv3_pool', None)
     if rank != 0:
         return None
     frames_per_launch = B * CLIP_FRAMES
     total_frames = world * B * CLIP_FRAMES * args.steps
-    dom = max(per_launch, key=per_launch.get)
-    dur_s = per_launch[dom] * 1e-3
-    if dom in STAGE_FLOPS:
-        ach = STAGE_FLOPS[dom] * frames_per_launch / dur_s / 1e12
-        roof = {'kernel': dom, 'bound': 'mfma', 'achieved': ach, 'peak': PEAK_MFMA_BF16_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': ach / PEAK_MFMA_BF16_TFLOPS, 'traffic': None}
-    else:
-        ach = STAGE_BYTES[dom] * frames_per_launch / dur_s / 1e9
-        roof = {'kernel': dom, 'bound': 'hbm', 'achieved': ach, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                'frac': ach / PEAK_HBM_GBS, 'traffic': None}
+    roof = None
+    if args.full:
+        dom = max(per_launch, key=per_launch.get)
+        dur_s = per_launch[dom] * 1e-3
+        if dom in STAGE_FLOPS:
+            ach = STAGE_FLOPS[dom] * frames_per_launch / dur_s / 1e12
+            roof = {'kernel': dom, 'bound': 'mfma', 'achieved': ach, 'peak': PEAK_MFMA_BF16_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': ach / PEAK_MFMA_BF16_TFLOPS, 'traffic': None}
+        else:
+            ach = STAGE_BYTES[dom] * frames_per_launch / dur_s / 1e9
+            roof = {'kernel': dom, 'bound': 'hbm', 'achieved': ach, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                    'frac': ach / PEAK_HBM_GBS, 'traffic': None}
     # HBM traffic from the committed PMC passes (profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate
     # passes, FETCH_SIZE doubled per MI355X_MICROARCH.md -- counters and timing cannot share a run), scaled to this launch's clips
     hbm_measured = None
@@ -797,7 +830,7 @@ def run_infer(args, rank, world, device):
         src = pmc.get('_source', 'profiles/pmc_traffic.json')
         kernels = {k: v for k, v in pmc.items() if isinstance(v, dict) and 'hbm_bytes_corrected' in v}
         # the dominant stage's own kernel (entries are per kernel; a kernel that serves several stages cannot be attributed to one)
-        own = [v for v in kernels.values() if v.get('stages') == [dom]]
+        own = [v for v in kernels.values() if v.get('stages') == [dom]] if roof is not None else []
         if own:
             roof['traffic'] = own[0]['hbm_bytes_corrected'] * B / own[0]['clips']
             roof['traffic_unit'] = 'bytes per launch'
@@ -809,12 +842,13 @@ def run_infer(args, rank, world, device):
     except (OSError, ValueError, KeyError):
         pass
     sus = sustained_matrix_rate()
-    if sus is not None and roof['bound'] == 'mfma':
-        roof['sustained_peak'] = sus[0]
-        roof['frac_of_sustained_matrix_rate'] = roof['achieved'] / sus[0]
-        roof['sustained_peak_source'] = sus[1]
-    roof['avg_launch_ms'] = per_launch[dom]
-    roof['kernel_ms_per_step'] = {k: round(v, 4) for k, v in sorted(per_launch.items(), key=lambda kv: -kv[1])}
+    if roof is not None:
+        if sus is not None and roof['bound'] == 'mfma':
+            roof['sustained_peak'] = sus[0]
+            roof['frac_of_sustained_matrix_rate'] = roof['achieved'] / sus[0]
+            roof['sustained_peak_source'] = sus[1]
+        roof['avg_launch_ms'] = per_launch[dom]
+        roof['kernel_ms_per_step'] = {k: round(v, 4) for k, v in sorted(per_launch.items(), key=lambda kv: -kv[1])}
     fps = total_frames / elapsed
     ms_per_step = elapsed / args.steps * 1e3
     config = {'workload': 'OnsetsFrames(mc=2)+MelSpec(229 bins, n_fft 2048, hop 512) inference, synthetic 22.05 kHz clips of 319999 '
@@ -838,8 +872,11 @@ def run_infer(args, rank, world, device):
         'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': {'bf16': 'bf16', 'f16': 'f16', 'x3': 'bf16x3'}[args.precision], 'data': 'synthetic',
-        'config': config, 'roofline': roof,
+        'config': config,
     }
+    if not args.full:
+        return res
+    res['roofline'] = roof
     oracle_rolls = None
     if world == 1 and args.cpu_seconds > 0:
         res['cpu_baseline'], oracle_rolls = cpu_baseline(args.cpu_seconds, sd)
@@ -1028,6 +1065,8 @@ def run_train(args, rank, world, device):
         torch.cuda.synchronize()
         np.savez(os.path.join(args.dump, f'rank{rank}.npz'), loss=float(loss.detach()),
                  **{k: v.detach().float().cpu().contiguous().numpy() for k, v in step.model.state_dict().items() if not k.startswith('frontend.')})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': loss, **{k: v for k, v in step.model.state_dict().items() if not k.startswith('frontend.')}})
     if rank != 0:
         return None
     ms = elapsed / args.steps * 1e3
@@ -1054,7 +1093,7 @@ def run_train(args, rank, world, device):
                      'note': f'{flops / 1e6:.1f} MFLOP per clip-frame (SURVEY 8d: ~3x forward) x frames / step time; at 8 clips per GPU the step is '
                              f'latency-bound (4 x 625 dependent recurrence steps), see DESIGN.md 5.4'},
     }
-    if world == 1 and args.cpu_seconds > 0 and not args.of2:
+    if args.full and world == 1 and args.cpu_seconds > 0 and not args.of2:
         res['cpu_baseline'] = cpu_train_baseline(args.cpu_seconds)
     return res
 

@@ -76,3 +76,28 @@ def test_eight_ranks_rendezvous_and_relay_one_line():
     assert len(lines) == 1
     rec = json.loads(lines[0])
     assert rec['n_gpus'] == 8 and rec['ms_per_step'] == 8.0 and rec['process_group'] == 'gloo'
+
+
+def test_dump_outputs_writes_float32_within_the_cap_and_one_seeded_row_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; above the byte cap every array with the same row count keeps the same seeded rows, so
+    two runs (and two builds) write the same clips."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 40_000)
+    g = torch.Generator().manual_seed(0)
+    arrays = {'onsets': (torch.rand(64, 8, 20, generator=g) > 0.5).float(), 'multi_pitch': torch.rand(64, 8, 20, generator=g),
+              'loss': torch.tensor(1.25, dtype=torch.float64)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['loss.npy', 'multi_pitch.npy', 'onsets.npy']
+    got = {f[:-4]: np.load(tmp_path / 'a' / f) for f in files}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 40_000
+    assert float(got['loss']) == 1.25
+    rows = np.sort(np.random.default_rng(0).choice(64, got['onsets'].shape[0], replace=False))
+    assert 0 < len(rows) < 64
+    for k in ('onsets', 'multi_pitch'):
+        assert np.array_equal(got[k], arrays[k].numpy()[rows])
+        assert np.array_equal(got[k], np.load(tmp_path / 'b' / f'{k}.npy'))
