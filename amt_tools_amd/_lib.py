@@ -116,6 +116,12 @@ _SIGNATURES = {
     'amtx_conv3x3_train_workspace_bytes': (C.c_size_t, [_L, _I, _I, _I]),
     'amtx_conv3x3_train_fwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     'amtx_conv3x3_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    'amtx_tab_model_create': (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, _I]),
+    'amtx_tab_model_destroy': (_I, [_P]),
+    'amtx_tab_model_set_tensor': (_I, [_P, C.c_char_p, _P, _L]),
+    'amtx_tab_model_finalize': (_I, [_P]),
+    'amtx_tab_workspace_bytes': (C.c_size_t, [_P, _I, _I]),
+    'amtx_tab_forward': (_I, [_P, _P, _L, _L, _L, _L, _I, _I, _P, C.c_size_t, _P, _P, _P]),
 }
 
 

@@ -827,17 +827,139 @@ class SoftmaxGroups(OutputLayer):
         return winners.transpose(-2, -1)
 
 
+def tab_window_view(feats, frame_width=9):
+    """The shared sequence behind a TabCNN window tensor, or None.  `feats` is (B, T, C, F, W); TabCNN.pre_proc hands over an `unfold`
+    view whose T and W strides are equal, so window t's column w is column t + w of ONE sequence of T + W - 1 columns that starts at the
+    view's own first element.  Returns dict(offset=<storage offset in elements>, num_windows=T, num_cols=T + W - 1,
+    strides=(b, c, f, t)) when that holds and the whole extent lies inside the tensor's storage; None for anything else (a contiguous
+    copy of the windows, unequal strides, an as_strided view that reaches past its storage)."""
+    if not torch.is_tensor(feats) or feats.dim() != 5 or feats.shape[-1] != frame_width or feats.dtype != torch.float32:
+        return None
+    B, T, Cc, Fd, W = feats.shape
+    sb, st, sc, sf, sw = feats.stride()
+    if st != sw or st <= 0 or min(sb, sc, sf) < 0 or min(B, T, Cc, Fd) <= 0:
+        return None
+    ncols = T + W - 1
+    off = feats.storage_offset()
+    last = off + (B - 1) * sb + (Cc - 1) * sc + (Fd - 1) * sf + (ncols - 1) * st
+    if off < 0 or (last + 1) * feats.element_size() > feats.untyped_storage().nbytes():
+        return None
+    return dict(offset=off, num_windows=T, num_cols=ncols, strides=(sb, sc, sf, st))
+
+
+class _TabEngine(object):
+    """ctypes handle of an amtx_tab_model + its workspace, bound to one device."""
+
+    WORKSPACE_CAP = 1 << 30      # bytes: longer inputs run as several calls over independent chunks of windows (and of clips)
+
+    def __init__(self, model, device):
+        self.device = device
+        self.handle = C.c_void_p()
+        L = _lib.lib()
+        with torch.cuda.device(device):
+            _lib.check(L.amtx_tab_model_create(C.byref(self.handle), int(model.dim_in), int(model.in_channels), int(model.model_complexity),
+                                               int(model.profile.get_num_dofs()), int(model.profile.num_pitches + 1),
+                                               {'bf16': 0, 'x3': 1}[model.precision]), 'amtx_tab_model_create')
+        self.G = int(model.profile.get_num_dofs())
+        self.C = int(model.profile.num_pitches + 1)
+        self.version = None
+        self.workspace = None
+        self.forwards = 0                               # engine calls made (tests)
+
+    def sync_weights(self, model):
+        sd = model.state_dict()
+        items = [(k, v) for k, v in sd.items() if v.dtype.is_floating_point and not k.startswith('frontend.')]
+        version = tuple((k, v._version, v.data_ptr()) for k, v in items)
+        if version == self.version:
+            return
+        L = _lib.lib()
+        flat = torch.cat([v.detach().reshape(-1).to(torch.float32) for _, v in items]).cpu().numpy()   # one device-to-host copy
+        off = 0
+        for k, v in items:
+            n = v.numel()
+            _lib.check(L.amtx_tab_model_set_tensor(self.handle, k.encode(), _lib.ptr(flat[off:off + n]), n), 'amtx_tab_model_set_tensor')
+            off += n
+        with torch.cuda.device(self.device):
+            _lib.check(L.amtx_tab_model_finalize(self.handle), 'amtx_tab_model_finalize')
+        self.version = version
+
+    def workspace_bytes(self, batch, num_windows):
+        return int(_lib.lib().amtx_tab_workspace_bytes(self.handle, int(batch), int(num_windows)))
+
+    def _chunks(self, B, T):
+        """[(b0, b1, t0, t1)] covering (B, T) with every chunk's workspace under WORKSPACE_CAP (one window of one clip at the least)."""
+        cap = self.WORKSPACE_CAP
+        if self.workspace_bytes(B, T) <= cap:
+            return [(0, B, 0, T)]
+        bc = B
+        while bc > 1 and self.workspace_bytes(bc, 1) > cap:
+            bc = (bc + 1) // 2
+        lo, hi = 1, T                                    # the most windows per call at bc clips
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if self.workspace_bytes(bc, mid) <= cap:
+                lo = mid
+            else:
+                hi = mid - 1
+        return [(b0, min(B, b0 + bc), t0, min(T, t0 + lo)) for b0 in range(0, B, bc) for t0 in range(0, T, lo)]
+
+    def forward(self, feats, view):
+        """feats: the (B, T, C, F, 9) window view, `view` = tab_window_view(feats).  Returns logits (B, T, G*C) fp32 and tablature
+        (B, G, T) int64."""
+        L = _lib.lib()
+        B, T = feats.shape[:2]
+        sb, sc, sf, st = view['strides']
+        G, Cn = self.G, self.C
+        logits = torch.empty((B, T, G * Cn), dtype=torch.float32, device=feats.device)
+        tab = torch.empty((B, G, T), dtype=torch.int64, device=feats.device)
+        chunks = self._chunks(B, T)
+        need = max(self.workspace_bytes(b1 - b0, t1 - t0) for b0, b1, t0, t1 in chunks)
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = None
+            self.workspace = _lib.alloc_workspace(need, feats.device)
+        base = feats.data_ptr()                          # element (0, 0, 0, 0, 0): column 0 of clip 0's sequence
+        esz = feats.element_size()
+        with torch.cuda.device(feats.device):
+            stream = _lib.current_stream(feats.device)
+            for b0, b1, t0, t1 in chunks:
+                whole = len(chunks) == 1
+                lg = logits if whole else torch.empty((b1 - b0, t1 - t0, G * Cn), dtype=torch.float32, device=feats.device)
+                tb = tab if whole else torch.empty((b1 - b0, G, t1 - t0), dtype=torch.int64, device=feats.device)
+                ptr = C.c_void_p(base + (b0 * sb + t0 * st) * esz)     # windows are independent: a chunk starts at its first column
+                _lib.check(L.amtx_tab_forward(self.handle, ptr, sb, sc, sf, st, b1 - b0, t1 - t0, _lib.ptr(self.workspace),
+                                              self.workspace.numel(), _lib.ptr(lg), _lib.ptr(tb), stream), 'amtx_tab_forward')
+                if not whole:
+                    logits[b0:b1, t0:t1] = lg
+                    tab[b0:b1, :, t0:t1] = tb
+        self.forwards += 1
+        return logits, tab
+
+    def __del__(self):
+        try:
+            _lib.lib().amtx_tab_model_destroy(self.handle)
+        except Exception:
+            pass
+
+
 class TabCNN(TranscriptionModel):
-    """TabCNN, BASELINE config 1 (behaviour contract: amt_tools/models/tabcnn.py:17-221).  CPU plumbing on stock torch ops -- there
-    is no HIP kernel work for this model; it exists so that the reference's CQT + TabCNN experiment runs
-    against this package's FeatureModule / TranscriptionModel objects unchanged.  Module names and indices (`conv.{0,2,4}`,
+    """TabCNN, BASELINE config 1 (behaviour contract: amt_tools/models/tabcnn.py:17-221).  Module names and indices (`conv.{0,2,4}`,
     `dense.{0,3}`) are the reference's, so its checkpoints load; the 9-frame context windows are built on the model's device with a
-    strided `unfold` view instead of the reference's device -> NumPy -> device round trip (tabcnn.py:122-127)."""
+    strided `unfold` view instead of the reference's device -> NumPy -> device round trip (tabcnn.py:122-127).
+
+    Execution paths
+    * inference on a CUDA (ROCm) device -- eval mode, fp32 input, nothing for autograd to record, model_complexity 1 -- with the window
+      view pre_proc makes -> the HIP engine behind include/amtx.h (`amtx_tab_forward`, csrc/tab.hip): the convolutions run once per
+      sequence instead of once per window (3.5x less arithmetic at dim_in 192), logits and tablature come out of the same call.
+      `precision` 'x3' (default: split-bf16, fp32-class logits) or 'bf16' (the throughput mode).
+    * everything else (training, CPU, eval with grad enabled, a contiguous copy of the windows) -> stock torch ops, unchanged.  An
+      inference call the engine would take but whose configuration it does not build is recorded by autograd.note_fallback."""
 
     CONTEXT = 9      # frames seen by one prediction (tabcnn.py:40)
 
-    def __init__(self, dim_in, profile, in_channels=1, model_complexity=1, device='cpu'):
+    def __init__(self, dim_in, profile, in_channels=1, model_complexity=1, device='cpu', precision='x3'):
         super().__init__(dim_in, profile, in_channels, model_complexity, self.CONTEXT, device)
+        assert precision in ('bf16', 'x3')
+        self.precision = precision
         self.online = False
         widths = (32 * model_complexity, 64 * model_complexity, 64 * model_complexity)
         layers, c_prev = [], self.in_channels
@@ -850,6 +972,51 @@ class TabCNN(TranscriptionModel):
         self.fc_embedding_size = 128 * model_complexity
         self.dense = nn.Sequential(nn.Linear(self.conv_embedding_size, self.fc_embedding_size), nn.ReLU(), nn.Dropout(0.50),
                                    SoftmaxGroups(self.fc_embedding_size, self.profile.get_num_dofs(), self.profile.num_pitches + 1))
+
+    # ---- engine management (device handles never enter state_dict / pickles, SURVEY finding F11) ----
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_engine', None)
+        state.pop('_engine_tab', None)
+        return state
+
+    def engine_unsupported(self):
+        """Why the HIP engine does not build this configuration, or None when it does."""
+        C_ = self.profile.num_pitches + 1
+        G = self.profile.get_num_dofs()
+        if self.model_complexity != 1:
+            return f'model_complexity={self.model_complexity} (1 is built)'
+        if not 1 <= self.in_channels <= 8:
+            return f'in_channels={self.in_channels} (1 to 8 are built)'
+        if not 9 <= self.dim_in <= 2048:
+            return f'dim_in={self.dim_in} (9 to 2048 are built)'
+        if C_ > 32 or G * C_ > 256:
+            return f'num_classes={C_}, num_groups={G} (num_classes <= 32 and num_groups x num_classes <= 256 are built)'
+        return None
+
+    def _get_engine(self, device):
+        eng = self.__dict__.get('_engine')
+        if eng is None or eng.device != device:
+            eng = _TabEngine(self, device)
+            self.__dict__['_engine'] = eng
+        eng.sync_weights(self)
+        return eng
+
+    def _engine_view(self, feats):
+        """The window view's geometry when this forward pass belongs to the HIP engine, else None."""
+        if not (torch.is_tensor(feats) and feats.is_cuda and feats.dtype == torch.float32 and not self.training):
+            return None
+        if torch.is_grad_enabled() and (feats.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return None
+        view = tab_window_view(feats, self.frame_width)
+        if view is None or tuple(feats.shape[2:4]) != (self.in_channels, self.dim_in):
+            return None
+        why = self.engine_unsupported()
+        if why is not None:
+            from . import autograd
+            autograd.note_fallback('TabCNN.forward', f'no HIP engine for {why}')
+            return None
+        return view
 
     def toggle_online(self):
         self.online = not self.online
@@ -869,6 +1036,12 @@ class TabCNN(TranscriptionModel):
         return batch
 
     def forward(self, feats):
+        self.__dict__.pop('_engine_tab', None)
+        view = self._engine_view(feats)
+        if view is not None:
+            logits, tab = self._get_engine(feats.device).forward(feats.detach(), view)
+            self.__dict__['_engine_tab'] = (logits, tab)          # post_proc takes the tablature for these logits
+            return {tools.KEY_TABLATURE: logits}
         B, T = feats.shape[:2]
         embeddings = self.conv(feats.reshape(B * T, self.in_channels, self.dim_in, self.frame_width))
         return {tools.KEY_TABLATURE: self.dense(embeddings.reshape(B, T, -1))}
@@ -879,5 +1052,9 @@ class TabCNN(TranscriptionModel):
         logits = output[tools.KEY_TABLATURE]
         if tools.KEY_TABLATURE in batch:
             output[tools.KEY_LOSS] = {tools.KEY_LOSS_TOTAL: head.get_loss(logits, batch[tools.KEY_TABLATURE])}
-        output[tools.KEY_TABLATURE] = head.finalize_output(logits)
+        engine = self.__dict__.pop('_engine_tab', None)
+        if engine is not None and engine[0] is logits:
+            output[tools.KEY_TABLATURE] = engine[1]
+        else:
+            output[tools.KEY_TABLATURE] = head.finalize_output(logits)
         return output

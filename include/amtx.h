@@ -341,6 +341,31 @@ int amtx_notes_rows(const int32_t* pairs, const int32_t* counts, int batch, int 
                     int64_t times_stride, int low_pitch, double* rows, double* onset_col, int64_t rows_capacity, int32_t* clip_offsets,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * TabCNN inference engine (amt_tools/models/tabcnn.py:17-221; TabCNN.forward + SoftmaxGroups.finalize_output,
+ * models/common.py:305-483).  The reference convolves each frame's 9-frame context window separately; the three unpadded 3x3
+ * convolutions are run ONCE per sequence instead (column w of window t is sequence column t + w) and window t's 2x2 max-pool reads
+ * sequence columns {t, t+1}: the same dot products with 3.5x less arithmetic at dim_in 192.
+ * Built: model_complexity 1, in_channels 1 .. 8, dim_in 9 .. 2048, num_classes <= 32, num_groups x num_classes <= 256; anything else
+ * answers AMTX_ERR_UNSUPPORTED.  precision AMTX_PREC_X3 (fp32-class) or AMTX_PREC_BF16.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct amtx_tab_model amtx_tab_model;
+int amtx_tab_model_create(amtx_tab_model** model, int dim_in, int in_channels, int model_complexity, int num_groups, int num_classes,
+                          int precision /* AMTX_PREC_BF16 / AMTX_PREC_X3 */);
+int amtx_tab_model_destroy(amtx_tab_model* model);
+/* `name` is a TabCNN state_dict key: conv.{0,2,4}.{weight,bias}, dense.0.{weight,bias}, dense.3.output_layer.{weight,bias} (host fp32, the
+ * reference's layout); a wrong name or element count is an error.  finalize packs every tensor (all ten must have been set). */
+int amtx_tab_model_set_tensor(amtx_tab_model* model, const char* name, const float* host, int64_t numel);
+int amtx_tab_model_finalize(amtx_tab_model* model);
+/* monotone in batch and num_windows; 0 for a bad argument */
+size_t amtx_tab_workspace_bytes(const amtx_tab_model* model, int batch, int num_windows);
+/* feats: fp32 element (b, c, f, col) at feats[b*stride_b + c*stride_c + f*stride_f + col*stride_t], num_windows + 8 columns per clip;
+ * window t covers columns t .. t+8 (TabCNN.pre_proc's zero-padded sequence).  Outputs (either may be null, not both):
+ * logits (batch, num_windows, G*C) fp32, tablature (batch, G, num_windows) int64 -- per group the first most likely class, the last
+ * class as -1.  workspace: 256-byte aligned, amtx_tab_workspace_bytes(model, batch, num_windows) bytes. */
+int amtx_tab_forward(const amtx_tab_model* model, const float* feats, int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t,
+                     int batch, int num_windows, void* workspace, size_t workspace_bytes, float* logits, int64_t* tablature, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
