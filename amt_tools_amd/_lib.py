@@ -122,6 +122,10 @@ _SIGNATURES = {
     'amtx_tab_model_finalize': (_I, [_P]),
     'amtx_tab_workspace_bytes': (C.c_size_t, [_P, _I, _I]),
     'amtx_tab_forward': (_I, [_P, _P, _L, _L, _L, _L, _I, _I, _P, C.c_size_t, _P, _P, _P]),
+    'amtx_tab_pool_train_fwd': (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _P, _P]),
+    'amtx_tab_pool_train_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    'amtx_softmax_groups_loss_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
+    'amtx_softmax_groups_loss': (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
 }
 
 

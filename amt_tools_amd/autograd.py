@@ -8,7 +8,8 @@ the 61 ms of GPU time of a step at 8 clips x 625 frames).  Here:
     cell states saved) and ONE backward (amtx_bilstm_h_train_bwd -> dL/d(xproj)); the input projection and every parameter gradient
     are GEMMs over B*T on csrc/train.hip (matmul_f32);
   * Conv3x3Function / LinearFunction: forward, input and weight gradients as split-bf16 implicit GEMMs (csrc/train.hip);
-  * BNReLUPoolFunction (csrc/bn.hip), BCELogitsLossFunction (csrc/head.hip).
+  * BNReLUPoolFunction (csrc/bn.hip), BCELogitsLossFunction (csrc/head.hip);
+  * TabCNN's window pool and grouped softmax loss: TabWindowPoolFunction, SoftmaxGroupsLossFunction (csrc/tabtrain.hip).
 Arithmetic: fp32 in / out with split-bf16 (3-MFMA) products, fp32 accumulation -- fp32-class accuracy.  No vendor BLAS / MIOpen kernel
 runs in a step; a layer whose shape the kernels do not take goes to the stock ATen op AND is recorded (`fallbacks()`,
 `training_backend()`), or raises under `AMTX_STRICT_TRAINING=1`.
@@ -20,7 +21,8 @@ import torch
 from . import _lib
 
 __all__ = ['bilstm', 'bilstm_multi', 'BiLSTMFunction', 'bce_logits_loss', 'BCELogitsLossFunction', 'bn_relu_pool', 'BNReLUPoolFunction',
-           'matmul_f32', 'linear', 'LinearFunction', 'conv3x3', 'Conv3x3Function', 'training_backend', 'note_fallback', 'fallbacks', 'fallback_total',
+           'matmul_f32', 'linear', 'LinearFunction', 'conv3x3', 'Conv3x3Function', 'tab_conv3x3', 'tab_window_pool', 'TabWindowPoolFunction',
+           'softmax_groups_loss', 'SoftmaxGroupsLossFunction', 'training_backend', 'note_fallback', 'fallbacks', 'fallback_total',
            'reset_fallbacks']
 
 HIDDEN_SIZES = (128, 256, 384, 512)  # hidden sizes per direction the training recurrences are built for (model_complexity 2 .. 5)
@@ -445,3 +447,116 @@ def bn_relu_pool(x, bn, pool):
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return BNReLUPoolFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, bool(pool))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# TabCNN training on shared-window sequences (csrc/tabtrain.hip; the convolutions are Conv3x3Function, models.TabCNN)
+# ---------------------------------------------------------------------------------------------------------------------------
+def tab_conv_supported(conv, input_grad):
+    """An unpadded nn.Conv2d(3x3, stride 1) of TabCNN that tab_conv3x3 can run as a padded convolution over a whole sequence;
+    `input_grad`: whether its input will need a gradient (every layer but the first)."""
+    if not (USE_HIP_DENSE and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (3, 3) and conv.padding == (0, 0)
+            and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None
+            and conv.weight.dtype == torch.float32):
+        return False
+    if conv.in_channels == 1 and not input_grad:
+        return conv.out_channels % 8 == 0     # direct first-layer kernel forward, K = 9 weight-gradient GEMM
+    return conv.out_channels % 4 == 0         # c_in a multiple of 4, or padded to one with zero channels
+
+
+def tab_conv3x3(x, conv):
+    """TabCNN's unpadded conv as a padded ("same") one on Conv3x3Function: x is (B, c_in, cols, F) -- the sequence's columns on the
+    kernels' frame axis, TabCNN's frequency rows on their bin axis -- so the weight goes in with its two spatial axes swapped (a
+    differentiable transpose).  Valid output (row r, column v) is the result's (v + 1, r + 1); its border is wrong and stays unread.
+    Input channel counts the implicit GEMMs do not take are zero-padded to a multiple of 4, as conv3x3 does."""
+    weight = conv.weight.transpose(-1, -2)
+    c_in = x.shape[1]
+    if c_in % 4 != 0 and not (c_in == 1 and not x.requires_grad):
+        pad = (-c_in) % 4
+        x = torch.nn.functional.pad(x, (0, 0, 0, 0, 0, pad))
+        weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, pad))
+    return Conv3x3Function.apply(x, weight, conv.bias)
+
+
+class TabWindowPoolFunction(torch.autograd.Function):
+    """TabCNN.conv's last ReLU + MaxPool2d((2, 2)) + flatten for every window of a sequence (amt_tools/models/tabcnn.py:172-175).
+    y3 (B, C, num_windows + 8, F): conv3's padded ("same") map over the whole zero-padded sequence, any strides (Conv3x3Function's is
+    channels-last).  Window t reads rows {2h+3, 2h+4} and columns {t+3, t+4}.  Returns fc's input rows (B * num_windows, C * H),
+    H = (F - 6) // 2, channel-major as the reference flattens; the backward is a gather into a channels-last map (amtx_tab_pool_train_*)."""
+
+    @staticmethod
+    def forward(ctx, y3, num_windows):
+        B, Cc, cols, F = y3.shape
+        T = int(num_windows)
+        assert cols == T + 8 and F >= 8 and y3.dtype == torch.float32 and y3.is_cuda
+        H = (F - 6) // 2
+        L = _lib.lib()
+        dev = y3.device
+        x = torch.empty((B * T, Cc * H), dtype=torch.float32, device=dev)
+        rec = torch.empty((B * T, Cc * H), dtype=torch.uint8, device=dev)
+        sb, sc, scol, sf = y3.stride()
+        with torch.cuda.device(dev):
+            _lib.check(L.amtx_tab_pool_train_fwd(_lib.ptr(y3), sb, sc, scol, sf, B, Cc, F, T, _lib.ptr(x), _lib.ptr(rec), _lib.current_stream(dev)),
+                       'amtx_tab_pool_train_fwd')
+        ctx.save_for_backward(rec)
+        ctx.dims = (B, Cc, F, T)
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        rec, = ctx.saved_tensors
+        B, Cc, F, T = ctx.dims
+        L = _lib.lib()
+        dev = dx.device
+        dx = dx.contiguous()
+        dmap = torch.empty((B, Cc, T + 8, F), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        with torch.cuda.device(dev):
+            _lib.check(L.amtx_tab_pool_train_bwd(_lib.ptr(dx), _lib.ptr(rec), B, Cc, F, T, _lib.ptr(dmap), _lib.current_stream(dev)),
+                       'amtx_tab_pool_train_bwd')
+        return dmap, None
+
+
+def tab_window_pool(y3, num_windows):
+    """(B, C, num_windows + 8, F) conv3 map -> (B * num_windows, C * H) pooled window rows, differentiably."""
+    return TabWindowPoolFunction.apply(y3, num_windows)
+
+
+class SoftmaxGroupsLossFunction(torch.autograd.Function):
+    """SoftmaxGroups.get_loss (amt_tools/models/common.py:369-440): logits (B, T, G*C) -- a strided row view such as
+    `padded[..., :G*C]` is read in place --, labels (B, G, T) class indices (-1 = the last class; any dtype get_loss accepts),
+    optional per-(group, class) weights -> sum over groups, mean over frames, mean over the batch, with d loss / d logits from the
+    same kernel pass (amtx_softmax_groups_loss)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, num_groups, num_classes):
+        B, T, K = logits.shape
+        G, Cn = int(num_groups), int(num_classes)
+        assert K == G * Cn and tuple(labels.shape) == (B, G, T)
+        L = _lib.lib()
+        x = logits.detach()
+        if x.dtype != torch.float32:
+            x = x.float()
+        if not (x.stride(2) == 1 and x.stride(0) == T * x.stride(1) and x.stride(1) >= K):
+            x = x.contiguous()
+        y = labels.detach().to(device=x.device, dtype=torch.int64).contiguous()
+        w = weight.detach().to(device=x.device, dtype=torch.float32).contiguous() if weight is not None else None
+        need_grad = logits.requires_grad
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        grad = torch.empty((B, T, K), dtype=torch.float32, device=x.device) if need_grad else None
+        ws = _workspace(int(L.amtx_softmax_groups_loss_workspace_bytes(B, T, G, Cn)), x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(L.amtx_softmax_groups_loss(_lib.ptr(x), x.stride(1), _lib.ptr(y), _lib.ptr(w), B, T, G, Cn, _lib.ptr(loss), _lib.ptr(grad),
+                                                  _lib.ptr(ws), ws.numel(), _lib.current_stream(x.device)), 'amtx_softmax_groups_loss')
+        ctx.save_for_backward(*([grad] if grad is not None else []))
+        ctx.dtype = logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        return ((saved[0] * g).to(ctx.dtype) if saved else None), None, None, None, None
+
+
+def softmax_groups_loss(logits, labels, num_groups, num_classes, weight=None):
+    """(B, T, G*C) fp32 CUDA logits, (B, G, T) labels -> scalar loss attached to the autograd graph of `logits`."""
+    return SoftmaxGroupsLossFunction.apply(logits, labels, weight, num_groups, num_classes)

@@ -951,10 +951,18 @@ class TabCNN(TranscriptionModel):
       view pre_proc makes -> the HIP engine behind include/amtx.h (`amtx_tab_forward`, csrc/tab.hip): the convolutions run once per
       sequence instead of once per window (3.5x less arithmetic at dim_in 192), logits and tablature come out of the same call.
       `precision` 'x3' (default: split-bf16, fp32-class logits) or 'bf16' (the throughput mode).
-    * everything else (training, CPU, eval with grad enabled, a contiguous copy of the windows) -> stock torch ops, unchanged.  An
+    * training on a CUDA device with the window view pre_proc makes (`use_hip_train`, on by default) -> the same shared-window
+      dataflow with gradients: the three convolutions as padded 3x3 convolutions over each whole sequence on the
+      split-bf16 training GEMMs (autograd.tab_conv3x3), ReLU between them as ATen glue, conv3's ReLU + 2x2 pool of every window in one
+      kernel (autograd.TabWindowPoolFunction), the module's own Dropouts, fc and the output layer on autograd.LinearFunction, and in
+      post_proc the grouped softmax loss with its gradient (autograd.SoftmaxGroupsLossFunction).  A CUDA training forward that cannot
+      take it (a contiguous copy of the windows, an unsupported layer, `use_hip_train` off) is recorded by autograd.note_fallback
+      ('TabCNN.train') and runs stock -- or raises under AMTX_STRICT_TRAINING=1.
+    * everything else (CPU, eval with grad enabled, a contiguous copy of the windows in eval mode) -> stock torch ops, unchanged.  An
       inference call the engine would take but whose configuration it does not build is recorded by autograd.note_fallback."""
 
     CONTEXT = 9      # frames seen by one prediction (tabcnn.py:40)
+    use_hip_train = True   # False: CUDA training forwards take the stock per-window path (MIOpen / hipBLASLt), on the record
 
     def __init__(self, dim_in, profile, in_channels=1, model_complexity=1, device='cpu', precision='x3'):
         super().__init__(dim_in, profile, in_channels, model_complexity, self.CONTEXT, device)
@@ -1035,8 +1043,61 @@ class TabCNN(TranscriptionModel):
         batch[tools.KEY_FEATS] = windows.permute(0, 3, 1, 2, 4)           # (B, T', C, F, W)
         return batch
 
+    def train_unsupported(self, feats):
+        """Why a training forward on the CUDA tensor `feats` cannot take the shared-window HIP path, or None when it can."""
+        from . import autograd
+        if not self.use_hip_train:
+            return 'TabCNN.use_hip_train is off'
+        if not autograd.USE_HIP_DENSE:
+            return 'autograd.USE_HIP_DENSE is off'
+        if feats.dtype != torch.float32:
+            return f'{feats.dtype} features'
+        if tab_window_view(feats, self.frame_width) is None:
+            return 'the windows are not a shared-window view (a contiguous copy?)'
+        if tuple(feats.shape[2:4]) != (self.in_channels, self.dim_in):
+            return f'feature shape {tuple(feats.shape[2:4])} is not ({self.in_channels}, {self.dim_in})'
+        if self.dim_in < 8:
+            return f'dim_in={self.dim_in}'
+        for i, idx in enumerate((0, 2, 4)):
+            if not autograd.tab_conv_supported(self.conv[idx], i > 0 or feats.requires_grad):
+                return f'conv.{idx} ({self.conv[idx]})'
+        if not isinstance(self.conv[6], nn.MaxPool2d) or self.conv[6].kernel_size not in (2, (2, 2)):
+            return 'conv.6 is not MaxPool2d((2, 2))'
+        fc, out = self.dense[0], self.dense[-1].output_layer
+        if fc.weight.dtype != torch.float32 or fc.in_features % 4 or fc.out_features % 4 or out.in_features % 4:
+            return f'dense layers {fc.in_features} -> {fc.out_features} -> {out.out_features}'
+        return None
+
+    def _forward_hip_train(self, feats):
+        """The training forward on shared-window sequences: returns the (B, T, G*C) logits."""
+        from . import autograd
+        view = tab_window_view(feats, self.frame_width)
+        B, T = feats.shape[:2]
+        sb, sc, sf, st = view['strides']
+        # the sequence behind the windows, on the kernels' axes: (B, C, cols, F) -- cols as frames, frequency rows as bins
+        seq = feats.as_strided((B, self.in_channels, view['num_cols'], self.dim_in), (sb, sc, st, sf), view['offset'])
+        y = torch.relu(autograd.tab_conv3x3(seq, self.conv[0]))
+        y = torch.relu(autograd.tab_conv3x3(y, self.conv[2]))
+        y = autograd.tab_conv3x3(y, self.conv[4])               # conv3's ReLU is in the pool kernel
+        x = self.conv[-1](autograd.tab_window_pool(y, T))       # (B*T, C3*H) in the reference's flatten order, then Dropout(0.25)
+        fc = self.dense[0]
+        x = self.dense[2](torch.relu(autograd.linear(x, fc.weight, fc.bias)))
+        head = self.dense[-1].output_layer
+        n = head.out_features
+        pad = (-n) % 4                                          # G*C = 126 at 6 x 21: zero rows up to a multiple of 4
+        w = F.pad(head.weight, (0, 0, 0, pad)) if pad else head.weight
+        b = F.pad(head.bias, (0, pad)) if pad else head.bias
+        logits = autograd.linear(x, w, b)[:, :n]
+        return logits.reshape(B, T, n)
+
     def forward(self, feats):
         self.__dict__.pop('_engine_tab', None)
+        if self.training and torch.is_tensor(feats) and feats.is_cuda:
+            from . import autograd
+            why = self.train_unsupported(feats)
+            if why is None:
+                return {tools.KEY_TABLATURE: self._forward_hip_train(feats)}
+            autograd.note_fallback('TabCNN.train', why)
         view = self._engine_view(feats)
         if view is not None:
             logits, tab = self._get_engine(feats.device).forward(feats.detach(), view)
@@ -1051,7 +1112,14 @@ class TabCNN(TranscriptionModel):
         head = self.dense[-1]
         logits = output[tools.KEY_TABLATURE]
         if tools.KEY_TABLATURE in batch:
-            output[tools.KEY_LOSS] = {tools.KEY_LOSS_TOTAL: head.get_loss(logits, batch[tools.KEY_TABLATURE])}
+            labels = batch[tools.KEY_TABLATURE]
+            if (self.training and self.use_hip_train and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3
+                    and tuple(labels.shape) == (logits.shape[0], head.num_groups, logits.shape[1])):
+                from .autograd import softmax_groups_loss
+                loss = softmax_groups_loss(logits, labels, head.num_groups, head.num_classes, head.weights)
+            else:
+                loss = head.get_loss(logits, labels)
+            output[tools.KEY_LOSS] = {tools.KEY_LOSS_TOTAL: loss}
         engine = self.__dict__.pop('_engine_tab', None)
         if engine is not None and engine[0] is logits:
             output[tools.KEY_TABLATURE] = engine[1]

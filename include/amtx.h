@@ -366,6 +366,29 @@ size_t amtx_tab_workspace_bytes(const amtx_tab_model* model, int batch, int num_
 int amtx_tab_forward(const amtx_tab_model* model, const float* feats, int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t,
                      int batch, int num_windows, void* workspace, size_t workspace_bytes, float* logits, int64_t* tablature, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * TabCNN TRAINING on shared-window sequences (amt_tools/models/tabcnn.py:140-180 in train mode; amt_tools_amd/models.py runs the three
+ * convolutions as padded 3x3 convolutions over each zero-padded sequence on amtx_conv3x3_train_fwd / amtx_conv3x3_bwd).  Deterministic.
+ * ------------------------------------------------------------------------------------------------ */
+/* TabCNN.conv's last ReLU + MaxPool2d((2, 2)) + flatten (tabcnn.py:172-175).  map: conv3's "same" map, element (b, c, col, f) at
+ * map[b*stride_b + c*stride_c + col*stride_col + f*stride_f], num_windows + 8 columns, num_bins (>= 8) rows.  Window t's pool reads rows
+ * {2h+3, 2h+4} and columns {t+3, t+4}, h < H = (num_bins - 6) / 2.  Writes x (batch*num_windows, channels*H) fp32, row b*T + t, column
+ * c*H + h = ReLU(2x2 max) and record (same shape, uint8): the winning position (0..3, row-major; the first on ties) | 4 when the max
+ * was > 0. */
+int amtx_tab_pool_train_fwd(const float* map, int64_t stride_b, int64_t stride_c, int64_t stride_col, int64_t stride_f, int batch,
+                            int channels, int num_bins, int num_windows, float* x, uint8_t* record, void* stream);
+/* its backward: dx (batch*num_windows, channels*H) + record -> dmap (batch, num_windows + 8, num_bins, channels) contiguous
+ * (channels-last), every element written (zeros included): a gather from the at most two windows whose recorded winner a position is. */
+int amtx_tab_pool_train_bwd(const float* dx, const uint8_t* record, int batch, int channels, int num_bins, int num_windows, float* dmap,
+                            void* stream);
+/* SoftmaxGroups.get_loss (models/common.py:369-440) forward and backward in one pass: logits (batch*num_frames, G*C) fp32 with row
+ * stride ld, targets (batch, G, num_frames) int64 (-1 = the last class; any other value outside [0, C) makes the loss NaN), weight =
+ * optional per-(group, class) weights (G*C).  *loss = mean_b mean_t sum_g w[g][target] NLL, grad (optional, (batch*num_frames, G*C)
+ * contiguous) = d loss / d logits.  workspace: amtx_softmax_groups_loss_workspace_bytes(batch, num_frames, G, C). */
+size_t amtx_softmax_groups_loss_workspace_bytes(int batch, int num_frames, int num_groups, int num_classes);
+int amtx_softmax_groups_loss(const float* logits, int64_t ld, const int64_t* targets, const float* weight, int batch, int num_frames,
+                             int num_groups, int num_classes, float* loss, float* grad, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

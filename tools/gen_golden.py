@@ -248,6 +248,50 @@ def gen_tabcnn(name, seed, dim_in, B, T):
     print(name, 'logits', rec['logits'].shape, 'loss', rec['loss_total'], 'range', profile.low, profile.high)
 
 
+TAB_TRAIN_CASES = (dict(seed=61, dim_in=192, in_channels=1, B=2, T=30, weighted=False),
+                   dict(seed=62, dim_in=72, in_channels=6, B=2, T=17, weighted=True))
+TAB_FC_ROW_STEP = 16      # dense.0.weight's gradient is stored as every 16th row: (128, 5952) at dim_in 192 would be 3 MB
+
+
+def gen_tabcnn_train(name):
+    """Training-mode golden of the reference's TabCNN (model_complexity 1, GuitarProfile(num_frets=19), every Dropout p = 0): per case
+    the loss and the gradient of all ten parameters.  Case 1 uses weighted SoftmaxGroups (dense[-1].set_weights), the reference's
+    per-group loop branch (models/common.py:413-432)."""
+    rec = {}
+    for i, case in enumerate(TAB_TRAIN_CASES):
+        seed, dim_in, cin, B, T = case['seed'], case['dim_in'], case['in_channels'], case['B'], case['T']
+        profile = rtools.GuitarProfile(num_frets=19)
+        model = TabCNN(dim_in, profile, cin, 1)
+        sd_np = synth_tabcnn_state_dict(seed, dim_in=dim_in, in_channels=cin, model_complexity=1, num_groups=6, num_classes=21)
+        assert list(model.state_dict().keys()) == list(sd_np.keys())
+        model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd_np.items()})
+        for mod in model.modules():
+            if isinstance(mod, torch.nn.Dropout):
+                mod.p = 0.0
+        rng = np.random.default_rng(seed + 300)
+        if case['weighted']:
+            weights = rng.uniform(0.25, 2.0, size=6 * 21).astype(np.float32)
+            model.dense[-1].set_weights(weights)
+            rec[f'c{i}_weights'] = weights
+        model.train()
+        feats = features(seed + 100, B, cin, dim_in, T)
+        tab = np.random.default_rng(seed + 200).integers(-1, 20, size=(B, 6, T)).astype(np.int64)
+        out = model.run_on_batch({rtools.KEY_FEATS: torch.from_numpy(feats), rtools.KEY_TABLATURE: torch.from_numpy(tab)})
+        loss = out[rtools.KEY_LOSS][rtools.KEY_LOSS_TOTAL]
+        loss.backward()
+        keys = [k for k, _ in model.named_parameters()]
+        rec[f'c{i}_keys'] = np.array(keys)
+        for k, prm in model.named_parameters():
+            g = prm.grad.detach().numpy()
+            rec[f'c{i}_grad_{k}'] = g[::TAB_FC_ROW_STEP].copy() if k == 'dense.0.weight' else g.copy()
+        rec.update({f'c{i}_seed': seed, f'c{i}_dim_in': dim_in, f'c{i}_in_channels': cin, f'c{i}_weighted': case['weighted'],
+                    f'c{i}_feats': feats, f'c{i}_tablature': tab, f'c{i}_wsum': weight_checksum(sd_np), f'c{i}_loss': loss.item()})
+        print(name, i, 'loss', loss.item())
+    rec['num_cases'] = len(TAB_TRAIN_CASES)
+    rec['fc_row_step'] = TAB_FC_ROW_STEP
+    np.savez_compressed(os.path.join(OUT, name), **rec)
+
+
 def gen_labels_and_cache(name, cache_name, seed, T, n_notes, hop=512, sr=22050):
     """Ground-truth rasterisation (tools/utils.py:1665-1737,2329-2378,2508-2552) of random notes -- some out of the piano's
     range or outside the time grid -- and a feature cache file written by the reference's own save_dict_npz
@@ -385,6 +429,9 @@ def gen_rms_norm(name):
 
 
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'tabcnn_train':
+        gen_tabcnn_train('tabcnn_train.npz')
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'rms_norm':
         gen_rms_norm('rms_norm.npz')
         sys.exit(0)
