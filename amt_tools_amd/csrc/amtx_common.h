@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/amtx.h"
 
@@ -45,8 +46,8 @@ int amtx_grant_lds(const void* kernel, size_t bytes);
     } while (0)
 
 // ------------------------------------------------------------------ 16-bit operand format of this translation unit
-// conv.hip, convf.hip, gemm.hip and lstm.hip are compiled TWICE (amt_tools_amd/build.py): as they are, with bf16 operands, and with
-// -DAMTX_F16 into a second object whose public functions carry the suffix _f16 (amtx_f16_names.h) and whose 16-bit values are IEEE
+// conv.hip, convf.hip, convg.hip, gemm.hip, lstm.hip and pack.hip are compiled TWICE (amt_tools_amd/build.py, F16_TWINS):
+// as they are, with bf16 operands, and with -DAMTX_F16 into a second object whose public functions carry the suffix _f16 (amtx_f16_names.h) and whose 16-bit values are IEEE
 // half precision: the same matrix rate on gfx950 (v_mfma_f32_16x16x32_f16), three more mantissa bits -- the engine's precision 'f16'.
 // In that build every name below that says "bf16" means "the 16-bit operand format of this build": bf16_t is a raw 16-bit pattern
 // either way, and no kernel touches the bits except through these helpers.
@@ -140,6 +141,8 @@ static __device__ __forceinline__ amtx_f32x4 amtx_mfma_16x16x32(uint4 a, uint4 b
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(amtx_mfma_x8, a), __builtin_bit_cast(amtx_mfma_x8, b), c, 0, 0, 0);
 #endif
 }
+// the name the kernels call it by (cqt.hip, cqt_dec.hip and train.hip are never compiled with AMTX_F16: bf16 there)
+static __device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) { return amtx_mfma_16x16x32(a, b, c); }
 // the legacy 16-deep form (conv.hip's multi-channel fused first conv)
 static __device__ __forceinline__ amtx_f32x4 amtx_mfma_16x16x16(uint2 a, uint2 b, amtx_f32x4 c) {
 #ifdef AMTX_F16
@@ -224,6 +227,20 @@ static __device__ __forceinline__ void glds16x4(const void* g0, const void* g1, 
                  : "memory");
 }
 
+// Two pieces with one m0 set-up: piece n reads gn and lands at lds_addr + n * 1024.
+static __device__ __forceinline__ void glds16x2(const void* g0, const void* g1, unsigned lds_addr) {
+    unsigned keep;
+    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
+    const char* p1 = static_cast<const char*>(g1) - 1024;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %1, off\n\t"
+                 "global_load_lds_dwordx4 %2, off offset:1024\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(g0), "v"(p1), "s"(lds_addr)
+                 : "memory");
+}
+
 template <int N>
 static __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -231,6 +248,22 @@ static __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt
 static __device__ __forceinline__ void lds_only_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
+}
+
+// Makes the compiler finish the loads that produced v before a persistent loop: otherwise the first use inside the
+// loop carries an s_waitcnt vmcnt(0) that also drains the next tile's prefetch loads every iteration.
+static __device__ __forceinline__ void settle(const uint4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
+static __device__ __forceinline__ void settle(const uint2& v) { asm volatile("" ::"v"(v.x), "v"(v.y)); }
+static __device__ __forceinline__ void settle(float v) { asm volatile("" ::"v"(v)); }
+
+// compile-time loop: the body sees its index as a constant expression (register arrays indexed through it stay in registers;
+// with a plain unrolled loop and computed indices hipcc left the weight arrays in scratch memory)
+template <int I, int N, class F>
+static __device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
 }
 
 // observed (speed only, never correctness): block b runs on XCD b % 8.  Remap so consecutive logical

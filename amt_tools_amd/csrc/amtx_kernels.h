@@ -151,6 +151,8 @@ void amtx_bilstm_pack_host_h(const float* whh_fwd, const float* whh_bwd, int hid
 size_t amtx_bce_loss_partials(int B, int T, int keys);
 int amtx_launch_bce_loss(const float* logits, int64_t ld, const float* labels, const float* weight, int B, int T, int keys, float* loss,
                          float* grad, float* partial, hipStream_t stream);
+// *loss = inv_bt * sum(partial[0 .. n)) in a fixed order (double accumulation): second level of the BCE and grouped-softmax loss reductions
+int amtx_launch_loss_reduce(const float* partial, int64_t n, float inv_bt, float* loss, hipStream_t stream);
 int amtx_launch_pianoroll(const float* logits, int64_t ld, int col0, int B, int T, int keys, float threshold, float* out,
                           hipStream_t stream);
 

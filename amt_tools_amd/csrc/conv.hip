@@ -36,11 +36,6 @@ constexpr int PLANE_BYTES = ROWS * PITCH * 64;
 constexpr int CM_PLANE = (ROWS * PITCH * 16 + 255) / 256 * 256;
 constexpr int CM_BYTES = 3 * CM_PLANE + ROWS * PITCH * 16;   // the last chunk plane needs no tail padding
 
-typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf16x8;
-__device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
-    return amtx_mfma_16x16x32(a, b, c);
-}
-
 // Byte offset of 16-byte chunk c of tile position (row i, column j).  A fragment read takes, per lane,
 // row = (lane & 15) + kh and chunk = lane >> 4.  With PITCH = 1 (mod 4) consecutive rows rotate through the four
 // 64-byte quarters of a 256-byte bank row; XOR-ing the chunk with 2*((i >> 2) & 1) then makes every
@@ -64,12 +59,6 @@ __device__ __forceinline__ void cvt8(const float (&f)[8], bool split, uint4& hi,
     hi = make_uint4(h[0], h[1], h[2], h[3]);
     lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
-
-// Makes the compiler finish the loads that produced v before the persistent loop: otherwise the first use inside the
-// loop carries an s_waitcnt vmcnt(0) that also drains the next tile's prefetch loads every iteration.
-__device__ __forceinline__ void settle(const uint4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
-__device__ __forceinline__ void settle(const uint2& v) { asm volatile("" ::"v"(v.x), "v"(v.y)); }
-__device__ __forceinline__ void settle(float v) { asm volatile("" ::"v"(v)); }
 
 #ifdef AMTX_CONV_TIMING
 // Debug build only (AMTX_EXTRA_FLAGS=-DAMTX_CONV_TIMING): cycles wave 0 of every block spends per phase of the persistent loop,

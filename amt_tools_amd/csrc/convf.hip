@@ -80,13 +80,6 @@ constexpr int XB = CS / 4;                                 // 4-column blocks pe
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 static_assert(CP == 4 && XB == 2, "wave roles below are written for 8 layer2 columns per step");
 
-typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf16x8;
-__device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
-    return amtx_mfma_16x16x32(a, b, c);
-}
-__device__ __forceinline__ void settle(const uint4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
-__device__ __forceinline__ void settle(float v) { asm volatile("" ::"v"(v)); }
-
 #ifdef AMTX_CONVF_TIMING
 // Debug build only (AMTX_EXTRA_FLAGS=-DAMTX_CONVF_TIMING): cycles wave 0 (producer) and wave 4 (consumer) of every block spend per
 // phase, summed over blocks: [0] layer2, [1] slab write + load issue + layer1 unit, [2] wait at the barrier, [3] steps;

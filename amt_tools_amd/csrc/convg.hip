@@ -39,20 +39,6 @@ namespace {
 constexpr int GTT = 16;             // frames per tile
 constexpr int GROWS = GTT + 2;
 
-typedef __attribute__((ext_vector_type(8))) __bf16 g_bf16x8;
-__device__ __forceinline__ f32x4_t gm32(uint4 a, uint4 b, f32x4_t c) {
-    return amtx_mfma_16x16x32(a, b, c);
-}
-
-// compile-time loop: the body sees its index as a constant expression, so register arrays indexed through it stay in registers
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 #ifdef AMTX_CONV_TIMING
 // Debug build only (AMTX_EXTRA_FLAGS=-DAMTX_CONV_TIMING): cycles wave 0 of every block spends per phase of the persistent loop, summed
 // over blocks: [0] tile store / feature store + barrier, [1] fused first conv, [2] weight store + barrier, [3] MFMA loop, [4] epilogue
@@ -492,10 +478,10 @@ __global__ __launch_bounds__(16 * FT, (FCL && CI16 == 2) ? CONVG_FCL_MINW : 1) v
                     f32x4_t dd = (f32x4_t){s4[nt].x, s4[nt].y, s4[nt].z, s4[nt].w};
                     static_for<0, KS1>([&](auto kc) {
                         constexpr int ks = decltype(kc)::value;
-                        dd = gm32(wf[nt][ks][0], ph[i_][ks], dd);
+                        dd = mfma16(wf[nt][ks][0], ph[i_][ks], dd);
                         if constexpr (NS == 2) {
-                            dd = gm32(wf[nt][ks][0], pl[i_][ks], dd);
-                            dd = gm32(wf[nt][ks][NS - 1], ph[i_][ks], dd);
+                            dd = mfma16(wf[nt][ks][0], pl[i_][ks], dd);
+                            dd = mfma16(wf[nt][ks][NS - 1], ph[i_][ks], dd);
                         }
                     });
                     d[i_][nt] = dd;
@@ -600,10 +586,10 @@ __global__ __launch_bounds__(16 * FT, (FCL && CI16 == 2) ? CONVG_FCL_MINW : 1) v
             if constexpr (v + WD < NITM) load_witem(std::integral_constant<int, v + WD>{});
             static_for<0, 4>([&](auto colc) {
                 constexpr int col = decltype(colc)::value;
-                acc[col][nt] = gm32(wq[v % (WD + 1)][0], xa[col + kw][st][0], acc[col][nt]);
+                acc[col][nt] = mfma16(wq[v % (WD + 1)][0], xa[col + kw][st][0], acc[col][nt]);
                 if constexpr (NS == 2) {
-                    acc[col][nt] = gm32(wq[v % (WD + 1)][0], xa[col + kw][st][NS - 1], acc[col][nt]);
-                    acc[col][nt] = gm32(wq[v % (WD + 1)][NS - 1], xa[col + kw][st][0], acc[col][nt]);
+                    acc[col][nt] = mfma16(wq[v % (WD + 1)][0], xa[col + kw][st][NS - 1], acc[col][nt]);
+                    acc[col][nt] = mfma16(wq[v % (WD + 1)][NS - 1], xa[col + kw][st][0], acc[col][nt]);
                 }
             });
             __builtin_amdgcn_sched_barrier(0);

@@ -33,8 +33,6 @@ constexpr int XQ = (2 * XPIECES + 7) / 8;      // pieces per wave and tile: 10 (
 // what the padding cells of a tile are copied from (a DMA cannot write a constant)
 __device__ uint4 g_convx_zero[4];
 
-__device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) { return amtx_mfma_16x16x32(a, b, c); }
-
 // Byte offset of 16-byte chunk c of tile position (row i, column j): conv.hip's tile_off with this tile's pitch.  PITCH = 1 (mod 4)
 // rotates consecutive rows through the four 64-byte quarters of a 256-byte bank row; XOR-ing the chunk with 2 ((i >> 2) & 1) puts every
 // ds_read_b128 lane group (rows r .. r + 3, r + 12 .. r + 15 of chunk g, rows r + 4 .. r + 11 of chunk g + 1) on 16 distinct slots.
@@ -58,8 +56,6 @@ __device__ __forceinline__ void xcvt8(const float (&f)[8], uint4& hi, uint4& lo)
     hi = make_uint4(h[0], h[1], h[2], h[3]);
     lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
-
-__device__ __forceinline__ void xsettle(const uint4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
 
 // C_in = 32 -> C_out = 16 NT; in [2 planes][B][T][F][32], out [2 planes][B][T][F / 2][C_out] (channels-last, planes in_split / out_split apart).
 // EIGHT waves: wave = (pair group pg = wave >> 1, channel half ch = wave & 1).  A wave holds the weights of ITS half of the output
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(512) void convx3_kernel(ConvArgs a, int ft, int ntf
 #pragma unroll
         for (int k = 0; k < NW; ++k)
 #pragma unroll
-            for (int p = 0; p < 2; ++p) xsettle(wf[tap][k][p]);
+            for (int p = 0; p < 2; ++p) settle(wf[tap][k][p]);
 
     const bf16_t* in_grp = reinterpret_cast<const bf16_t*>(a.in) + (int64_t)grp * a.in_gs;
     const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_void_t*)smem);
@@ -310,7 +306,7 @@ __global__ __launch_bounds__(512) void convx12_kernel(ConvArgs a, int ft, int nt
     }
     const int c0 = g * 8;                                         // this lane's first channel (of both layers)
 #pragma unroll
-    for (int i = 0; i < 36; ++i) xsettle(wreg[i]);
+    for (int i = 0; i < 36; ++i) settle(wreg[i]);
     // the folded BatchNorm shifts (the accumulators' initial values) live in LDS: 8 registers per lane are what this kernel does not have
     float* shtab = reinterpret_cast<float*>(smem + YLDS - 256);                 // [layer2's 32 | layer1's 32]
     if (tid < 64) shtab[tid] = tid < 32 ? a.shift[(int64_t)grp * a.shift_gs + tid] : a.shift1[(int64_t)grp * 32 + tid - 32];

@@ -54,10 +54,6 @@ __device__ __forceinline__ float row_max_f32(float v) {
     v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false)));   // row_mirror
     return v;
 }
-typedef __attribute__((ext_vector_type(8))) __bf16 cq_bf16x8;
-__device__ __forceinline__ f32x4_t cq_mfma(uint4 a, uint4 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cq_bf16x8, a), __builtin_bit_cast(cq_bf16x8, b), c, 0, 0, 0);
-}
 
 // level 0 of the pyramid: the clip copied between its centre paddings.  `zero_pads`: the paddings are written here too (zeros, librosa
 // >= 0.10; the reflecting pad of 0.9 keeps its own kernel); the per-(clip, harmonic) maxima the basis products accumulate are reset.
@@ -452,7 +448,7 @@ __global__ __launch_bounds__(256, 2) void cqt_basis_kernel(BasisArgs a, BasisLev
                     for (int u = 0; u < 2; ++u)
 #pragma unroll
                         for (int c = 0; c < 2; ++c)
-                            acc[u][c] = cq_mfma(pr == 2 ? wl[c][ks] : wh[c][ks], pr == 1 ? al[ks % NB][u] : ah[ks % NB][u], acc[u][c]);
+                            acc[u][c] = mfma16(pr == 2 ? wl[c][ks] : wh[c][ks], pr == 1 ? al[ks % NB][u] : ah[ks % NB][u], acc[u][c]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }

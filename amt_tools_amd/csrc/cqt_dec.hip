@@ -36,11 +36,6 @@ __device__ __forceinline__ void cqt_zero_pads(float* __restrict__ row, int64_t n
 constexpr int DEC_MCH = 4096;                     // outputs per block: 4 waves x 4 iterations x 256
 constexpr int DEC_MXS = 2 * DEC_MCH + DEC_KW;     // input samples per block
 
-typedef __attribute__((ext_vector_type(8))) __bf16 cq_bf16x8;
-__device__ __forceinline__ f32x4_t cq_mfma(uint4 a, uint4 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cq_bf16x8, a), __builtin_bit_cast(cq_bf16x8, b), c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(256) void cqt_decimate_mfma_kernel(const float* __restrict__ in, int64_t n_in, int64_t in_stride, int in_pad, float* __restrict__ out,
                                                                 int64_t n_out, int64_t out_stride, int pad, const uint4* __restrict__ tfrag, int zero_pads,
                                                                 float* __restrict__ maxbuf, int n_harm) {
@@ -94,12 +89,12 @@ __global__ __launch_bounds__(256) void cqt_decimate_mfma_kernel(const float* __r
         for (int ks = 0; ks < DEC_NKS; ++ks) {
             const uint4 bh = *reinterpret_cast<const uint4*>(xh + s0 + 32 * ks), bm = *reinterpret_cast<const uint4*>(xm + s0 + 32 * ks),
                         bl = *reinterpret_cast<const uint4*>(xl + s0 + 32 * ks);
-            acc = cq_mfma(tl[ks], bh, acc);                            // smallest terms first
-            acc = cq_mfma(th[ks], bl, acc);
-            acc = cq_mfma(tm[ks], bm, acc);
-            acc = cq_mfma(tm[ks], bh, acc);
-            acc = cq_mfma(th[ks], bm, acc);
-            acc = cq_mfma(th[ks], bh, acc);
+            acc = mfma16(tl[ks], bh, acc);                            // smallest terms first
+            acc = mfma16(th[ks], bl, acc);
+            acc = mfma16(tm[ks], bm, acc);
+            acc = mfma16(tm[ks], bh, acc);
+            acc = mfma16(th[ks], bm, acc);
+            acc = mfma16(th[ks], bh, acc);
         }
         const int64_t m = m0 + o0 + 16 * q + 4 * g;
         const float r2 = 1.41421356237309505f;
@@ -328,23 +323,23 @@ __global__ __launch_bounds__(512, 1) void cqt_decimate2_kernel(const float* __re
             for (int ks = 0; ks < DEC_NKS; ++ks) {
                 if (ks + DEC2_AHEAD <= DEC_NKS) fetch(ks + DEC2_AHEAD);
                 __builtin_amdgcn_sched_barrier(0);
-                acca = cq_mfma(tl[ks], fh[ks], acca);                 // smallest terms first (the order of cqt_decimate_mfma_kernel)
-                accb = cq_mfma(tl[ks], fh[ks + 1], accb);
+                acca = mfma16(tl[ks], fh[ks], acca);                 // smallest terms first (the order of cqt_decimate_mfma_kernel)
+                accb = mfma16(tl[ks], fh[ks + 1], accb);
                 __builtin_amdgcn_sched_barrier(0);
-                acca = cq_mfma(th[ks], fl[ks], acca);
-                accb = cq_mfma(th[ks], fl[ks + 1], accb);
+                acca = mfma16(th[ks], fl[ks], acca);
+                accb = mfma16(th[ks], fl[ks + 1], accb);
                 __builtin_amdgcn_sched_barrier(0);
-                acca = cq_mfma(tm[ks], fm[ks], acca);
-                accb = cq_mfma(tm[ks], fm[ks + 1], accb);
+                acca = mfma16(tm[ks], fm[ks], acca);
+                accb = mfma16(tm[ks], fm[ks + 1], accb);
                 __builtin_amdgcn_sched_barrier(0);
-                acca = cq_mfma(tm[ks], fh[ks], acca);
-                accb = cq_mfma(tm[ks], fh[ks + 1], accb);
+                acca = mfma16(tm[ks], fh[ks], acca);
+                accb = mfma16(tm[ks], fh[ks + 1], accb);
                 __builtin_amdgcn_sched_barrier(0);
-                acca = cq_mfma(th[ks], fm[ks], acca);
-                accb = cq_mfma(th[ks], fm[ks + 1], accb);
+                acca = mfma16(th[ks], fm[ks], acca);
+                accb = mfma16(th[ks], fm[ks + 1], accb);
                 __builtin_amdgcn_sched_barrier(0);
-                acca = cq_mfma(th[ks], fh[ks], acca);
-                accb = cq_mfma(th[ks], fh[ks + 1], accb);
+                acca = mfma16(th[ks], fh[ks], acca);
+                accb = mfma16(th[ks], fh[ks + 1], accb);
                 __builtin_amdgcn_sched_barrier(0);
             }
             const float r2 = 1.41421356237309505f;

@@ -28,12 +28,6 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {
     return (row * 4 + (chunk ^ ((0x78 >> (((row >> 2) & 3) * 2)) & 3))) * 16;
 }
 
-typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf16x8;
-
-__device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
-    return amtx_mfma_16x16x32(a, b, c);
-}
-
 template <int A_TYPE, int NS>
 struct AStage {
     // one 8-element K chunk of one A row.  load() only ISSUES the loads (fp32 A: the raw bits of elements 0-3 in `hi`, 4-7 in `lo`);
@@ -751,19 +745,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g, int ntiles) {
 // C_TYPE: AMTX_T_F32 or AMTX_T_SPLIT (the next GEMM's A).
 constexpr int SPL = 256 * RBK * 2;          // bytes per operand plane and stage (16 KiB)
 constexpr int SSTAGE = 4 * SPL;
-
-static __device__ __forceinline__ void glds16x2(const void* g0, const void* g1, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    const char* p1 = static_cast<const char*>(g1) - 1024;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\t"
-                 "global_load_lds_dwordx4 %2, off offset:1024\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(g0), "v"(p1), "s"(lds_addr)
-                 : "memory");
-}
 
 template <int C_TYPE>
 __global__ __launch_bounds__(512) void gemm_split_kernel(GemmArgs g, int ntiles) {

@@ -172,7 +172,8 @@ __global__ __launch_bounds__(256) void bce_loss_kernel(const float* __restrict__
         partial[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(64) void bce_loss_reduce_kernel(const float* __restrict__ partial, int64_t n, float inv_bt, float* __restrict__ loss) {
+// *loss = inv_bt * sum(partial[0 .. n)): the second level of the BCE and the grouped-softmax (tabtrain.hip) loss reductions
+__global__ __launch_bounds__(64) void partial_loss_reduce_kernel(const float* __restrict__ partial, int64_t n, float inv_bt, float* __restrict__ loss) {
     // fixed order: lane l sums partial[l], partial[l+64], ... in double, then a fixed butterfly
     double a = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 64) a += (double)partial[i];
@@ -182,6 +183,12 @@ __global__ __launch_bounds__(64) void bce_loss_reduce_kernel(const float* __rest
 }
 
 }  // namespace
+
+int amtx_launch_loss_reduce(const float* partial, int64_t n, float inv_bt, float* loss, hipStream_t stream) {
+    hipLaunchKernelGGL(partial_loss_reduce_kernel, dim3(1), dim3(64), 0, stream, partial, n, inv_bt, loss);
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
+}
 
 size_t amtx_bce_loss_partials(int B, int T, int keys) { return (size_t)B * ((T + 31) / 32) * ((keys + 31) / 32); }
 
@@ -193,9 +200,7 @@ int amtx_launch_bce_loss(const float* logits, int64_t ld, const float* labels, c
     dim3 grid((unsigned)((T + 31) / 32), (unsigned)((keys + 31) / 32), (unsigned)B);
     hipLaunchKernelGGL(bce_loss_kernel, grid, dim3(256), 0, stream, logits, ld, labels, weight, T, keys, inv_bt, grad, partial);
     AMTX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bce_loss_reduce_kernel, dim3(1), dim3(64), 0, stream, partial, (int64_t)amtx_bce_loss_partials(B, T, keys), inv_bt, loss);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+    return amtx_launch_loss_reduce(partial, (int64_t)amtx_bce_loss_partials(B, T, keys), inv_bt, loss, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -33,11 +33,6 @@ constexpr int LTHREADS = 64 * LWAVES;
 constexpr int HP = H + 8;                    // bf16 elements per LDS row
 constexpr int HBUF_BYTES = 16 * HP * 2;      // one plane of one buffer
 
-typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf16x8;
-__device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
-    return amtx_mfma_16x16x32(a, b, c);
-}
-
 // FAST (bf16 mode): v_exp_f32 + v_rcp_f32 (1 ulp each) -- far below the bf16 rounding of h.
 template <bool FAST>
 __device__ __forceinline__ float sigmoid_f(float x) {
@@ -576,16 +571,6 @@ __global__ void bilstm_pack_dev_kernel(const float* __restrict__ whh_fwd, const 
 // also the training forward (post-activation gates and cell states written per step).  Step time at HH = 256: 5.3 us bf16
 // (7.3 us all-streamed), 10 us two-plane: T dependent steps per launch, latency-bound like the register-stationary kernels,
 // only with a longer step.
-// compile-time loop: the body sees its index as a constant expression (register arrays indexed through it stay in registers;
-// with a plain unrolled loop and computed indices hipcc left the weight arrays in scratch memory)
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 template <int HH, int NS, int X_TYPE, int OUT_TYPE>
 __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
     constexpr int NU = HH / 16, UPW = NU / 8, KSN = HH / 32;

@@ -16,43 +16,61 @@
 
 #include "amtx_kernels.h"
 #include "amtx_kernels_f16.h"
+#include "amtx_model_common.h"
 
 #include <cmath>
 #include <cstdlib>
-#include <map>
-#include <string>
 #include <thread>
-#include <vector>
 
 namespace {
 
-struct Tensor { std::vector<float> v; };
+struct LinearPack { DevBuf w, b; int N = 0, K = 0, n_pad = 0, k_pad = 0; };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int upload(const void* host, size_t n) {
-        if (!p || bytes != n) {        // a weight re-sync (validate() inside train()) keeps its allocations: same model, same sizes
-            if (p) (void)hipFree(p);
-            p = nullptr; bytes = n;
-            AMTX_CHECK_HIP(hipMalloc(&p, n));
-        }
-        AMTX_CHECK_HIP(hipMemcpy(p, host, n, hipMemcpyHostToDevice));
-        return AMTX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
+// The kernels and packers that exist once per 16-bit operand format (the files compiled twice: amtx_f16_names.h).  A model picks its
+// table when it is created and calls through it.
+struct KernelSet {
+    void (*gemm_pack_host)(const float* W, int64_t ldw, int N, int K, int planes, bf16_t* out);
+    void (*bilstm_pack_host_h)(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);
+    void (*conv1_pack_host)(const float* w, const float* scale, int c_in, int planes, bf16_t* out);
+    void (*conv1g_pack_host)(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out);
+    void (*conv3x3_pack_host)(const float* w, const float* scale, int c_out, int planes, bf16_t* out);
+    void (*conv3x3_gen_pack_host)(const float* w, const float* scale, int c_in, int c_out, int planes, bf16_t* out);
+    int (*pack_conv1_dev)(const float* w, const float* scale, int planes, bf16_t* out, hipStream_t s);
+    int (*pack_conv1g_dev)(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out, hipStream_t s);
+    int (*pack_conv3x3_dev)(const float* w, const float* scale, int c_out, int planes, bf16_t* out, hipStream_t s);
+    int (*pack_conv_gen_dev)(const float* w, const float* scale, int c_in, int c_out, int ntc, int planes, bf16_t* out, hipStream_t s);
+    int (*pack_linear_dev)(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c,
+                           int perm_f, bf16_t* out, hipStream_t s);
+    int (*launch_bilstm_pack_dev_h)(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd,
+                                    hipStream_t stream);
+    int (*launch_conv1)(const Conv1Args& c, hipStream_t stream);
+    int (*launch_conv3x3)(const ConvArgs& c, hipStream_t stream);
+    int (*launch_conv3x3_gen)(const ConvArgs& c, int c_in, hipStream_t stream);
+    int (*launch_conv_stack)(const ConvArgs& c2, const bf16_t* w3frag, int64_t w3_gs, const float* shift3, void* out, int64_t out_gs,
+                             int64_t out_plane, hipStream_t stream);
+    int (*launch_gemm)(const GemmArgs& g, hipStream_t stream);
+    int (*launch_bilstm)(const LstmArgs& l, hipStream_t stream);
 };
 
-struct LinearPack { DevBuf w, b; int N = 0, K = 0, n_pad = 0, k_pad = 0; };
+const KernelSet kKernelsBf16 = {
+    amtx_gemm_pack_host, amtx_bilstm_pack_host_h, amtx_conv1_pack_host, amtx_conv1g_pack_host, amtx_conv3x3_pack_host, amtx_conv3x3_gen_pack_host,
+    amtx_pack_conv1_dev, amtx_pack_conv1g_dev, amtx_pack_conv3x3_dev, amtx_pack_conv_gen_dev, amtx_pack_linear_dev, amtx_launch_bilstm_pack_dev_h,
+    amtx_launch_conv1, amtx_launch_conv3x3, amtx_launch_conv3x3_gen, amtx_launch_conv_stack, amtx_launch_gemm, amtx_launch_bilstm};
+#ifdef AMTX_WITH_F16
+const KernelSet kKernelsF16 = {
+    amtx_gemm_pack_host_f16, amtx_bilstm_pack_host_h_f16, amtx_conv1_pack_host_f16, amtx_conv1g_pack_host_f16, amtx_conv3x3_pack_host_f16,
+    amtx_conv3x3_gen_pack_host_f16, amtx_pack_conv1_dev_f16, amtx_pack_conv1g_dev_f16, amtx_pack_conv3x3_dev_f16, amtx_pack_conv_gen_dev_f16,
+    amtx_pack_linear_dev_f16, amtx_launch_bilstm_pack_dev_h_f16, amtx_launch_conv1_f16, amtx_launch_conv3x3_f16, amtx_launch_conv3x3_gen_f16,
+    amtx_launch_conv_stack_f16, amtx_launch_gemm_f16, amtx_launch_bilstm_f16};
+#endif
 
 }  // namespace
 
 struct amtx_of_model {
     int dim_in, in_channels, mc, n_out, has_offsets, precision;
     int planes, act_type;
-    bool f16 = false;                          // AMTX_PREC_F16: the half-operand builds of the conv / GEMM / BiLSTM kernels, weights packed as half
+    bool f16 = false;                          // AMTX_PREC_F16: weights and 16-bit activations are IEEE half
+    const KernelSet* k = &kKernelsBf16;        // the kernels of this model's 16-bit operand format (f16: the half-operand twins)
     int nf1, nf2, nf3, dim_am, dim_lm, fq, kfc;
     int kfc_pad;                               // fc1's K rounded up to the DMA GEMM's 64-deep k-tile (rows of a3 are this long)
     int hid, xw;                               // LSTM hidden size per direction, width of an x-projection row (2 dirs x 4 gates x hid)
@@ -61,8 +79,7 @@ struct amtx_of_model {
     int n_heads;                               // acoustic heads: onset, (offset), pitch
     int n_rec;                                 // recurrent heads feeding the joint: onset, (offset)
     std::vector<std::string> head_names;       // state_dict prefixes of the acoustic models, group order
-    std::map<std::string, Tensor> tensors;
-    std::map<std::string, std::pair<const float*, int64_t>> dev_tensors;   // amtx_of_model_set_tensor_device: borrowed device pointers
+    TensorStore store{"of_model", "was not provided"};   // amtx_of_model_set_tensor / _set_tensor_device
     DevBuf pack_scratch;                       // device re-sync: BatchNorm scale / shift, the folded pitch head, the unused backward LSTM fragments
     bool finalized = false;
     bool packed_once = false;                  // the packed buffers hold a weight version that forwards may still be reading
@@ -95,23 +112,9 @@ static const char* kStageNames[ST_COUNT] = {"conv1", "conv2_pool", "conv3_pool",
 
 namespace {
 
-int need(const amtx_of_model* m, const std::string& name, size_t numel, const float** out) {
-    auto it = m->tensors.find(name);
-    if (it == m->tensors.end()) {
-        amtx_set_error("of_model: tensor '%s' was not provided", name.c_str());
-        return AMTX_ERR_ARG;
-    }
-    if (it->second.v.size() != numel) {
-        amtx_set_error("of_model: tensor '%s' has %zu elements, expected %zu", name.c_str(), it->second.v.size(), numel);
-        return AMTX_ERR_ARG;
-    }
-    *out = it->second.v.data();
-    return AMTX_OK;
-}
-
 #define NEED(name, numel, ptr)                                         \
     do {                                                               \
-        int _rc = need(m, name, numel, &(ptr));                        \
+        int _rc = m->store.need(name, numel, &(ptr));                  \
         if (_rc != AMTX_OK) return _rc;                                \
     } while (0)
 
@@ -141,7 +144,7 @@ int pack_linear_groups(amtx_of_model* m, LinearPack& lp, const std::vector<std::
     std::vector<bf16_t> packed(per * Ws.size());
     std::vector<float> bias((size_t)N * Ws.size());
     for (size_t g = 0; g < Ws.size(); ++g) {
-        (m->f16 ? amtx_gemm_pack_host_f16 : amtx_gemm_pack_host)(Ws[g].data(), K, N, K, m->planes, packed.data() + g * per);
+        m->k->gemm_pack_host(Ws[g].data(), K, N, K, m->planes, packed.data() + g * per);
         memcpy(bias.data() + g * N, bs[g].data(), sizeof(float) * N);
     }
     int rc = lp.w.upload(packed.data(), packed.size() * sizeof(bf16_t));
@@ -166,7 +169,7 @@ int pack_lstm(amtx_of_model* m, const std::string& prefix, int dim_in, std::vect
     b.resize(2 * G);
     for (int i = 0; i < G; ++i) { b[i] = bif[i] + bhf[i]; b[G + i] = bib[i] + bhb[i]; }
     hh.resize(amtx_bilstm_wfrag_elems_h(H, m->planes));
-    (m->f16 ? amtx_bilstm_pack_host_h_f16 : amtx_bilstm_pack_host_h)(whf, whb, H, m->planes, hh.data());
+    m->k->bilstm_pack_host_h(whf, whb, H, m->planes, hh.data());
     return AMTX_OK;
 }
 
@@ -180,21 +183,20 @@ Workspace carve(const amtx_of_model* m, int B, int T, char* base) {
     const size_t es = amtx_tsize(m->act_type);
     const size_t BT = (size_t)B * T;
     const int F = m->dim_in, F2 = F / 2;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    w.a1 = take(m->fuse_conv1 ? 256 : BT * F * m->nf1 * es * m->n_heads);
+    WorkspaceCarver ws{base};
+    w.a1 = ws.take(m->fuse_conv1 ? 256 : BT * F * m->nf1 * es * m->n_heads);
     // the 32-channel map behind layer2 only exists in HBM on the two-kernel path
-    w.a2 = take(m->fuse_stack && amtx_conv_stack_fused_ok(B, T, F, m->n_heads) ? 256 : BT * F2 * m->nf2 * es * m->n_heads);
-    w.a3 = take(BT * m->kfc_pad * es * m->n_heads);
-    w.e = take(BT * m->dim_am * es * m->n_heads);
-    w.xp = take(BT * m->xw * es * m->n_rec);
-    w.l1 = take(BT * m->dim_lm * es * m->n_rec);
-    w.joint = take(BT * m->dim_aj * sizeof(float));
-    w.joint16 = take(BT * (size_t)((m->dim_aj + 63) / 64 * 64) * 2 * (m->split_acts ? 2 : 1));   // bf16 copy (two planes with split_acts), K padded to the GEMM's 64-deep k-tile
-    w.xp2 = take(BT * m->xw * es);
-    w.l2 = take(BT * m->dim_lm * es);
-    w.mp = take(BT * m->n_out * sizeof(float));
-    w.total = off;
+    w.a2 = ws.take(m->fuse_stack && amtx_conv_stack_fused_ok(B, T, F, m->n_heads) ? 256 : BT * F2 * m->nf2 * es * m->n_heads);
+    w.a3 = ws.take(BT * m->kfc_pad * es * m->n_heads);
+    w.e = ws.take(BT * m->dim_am * es * m->n_heads);
+    w.xp = ws.take(BT * m->xw * es * m->n_rec);
+    w.l1 = ws.take(BT * m->dim_lm * es * m->n_rec);
+    w.joint = ws.take(BT * m->dim_aj * sizeof(float));
+    w.joint16 = ws.take(BT * (size_t)((m->dim_aj + 63) / 64 * 64) * 2 * (m->split_acts ? 2 : 1));   // bf16 copy (two planes with split_acts), K padded to the GEMM's 64-deep k-tile
+    w.xp2 = ws.take(BT * m->xw * es);
+    w.l2 = ws.take(BT * m->dim_lm * es);
+    w.mp = ws.take(BT * m->n_out * sizeof(float));
+    w.total = ws.off;
     return w;
 }
 
@@ -230,6 +232,9 @@ extern "C" int amtx_of_model_create(amtx_of_model** out, int dim_in, int in_chan
     m->planes = precision == AMTX_PREC_X3 ? 2 : 1;
     m->act_type = precision == AMTX_PREC_X3 ? AMTX_T_F32 : AMTX_T_BF16;      // AMTX_T_BF16 = "16-bit operand format": half in the f16 mode
     m->f16 = precision == AMTX_PREC_F16;
+#ifdef AMTX_WITH_F16
+    if (m->f16) m->k = &kKernelsF16;
+#endif
     m->nf1 = 16 * model_complexity; m->nf2 = m->nf1; m->nf3 = 32 * model_complexity;
     m->dim_am = 256 * model_complexity; m->dim_lm = 256 * (model_complexity - 1);
     m->fq = dim_in / 4;                      // two MaxPool(1,2): floor(floor(F/2)/2) == F//4
@@ -275,24 +280,15 @@ extern "C" int amtx_of_model_destroy(amtx_of_model* m) {
 
 extern "C" int amtx_of_model_set_tensor(amtx_of_model* m, const char* name, const float* host_data, int64_t numel) {
     AMTX_REQUIRE(m && name && host_data && numel > 0, "amtx_of_model_set_tensor: bad argument");
-    Tensor& t = m->tensors[name];
-    t.v.assign(host_data, host_data + numel);
+    m->store.set(name, host_data, numel);
     m->finalized = false;
-    return AMTX_OK;
-}
-
-// A RE-sync overwrites the packed buffers in place (DevBuf::upload keeps its allocation; the device packers write on the caller's
-// stream).  A forward pass of the previous weight version may still be in flight on ANOTHER stream (PyTorch side streams do not
-// synchronise with the null stream), so both re-sync entry points first wait for everything the device has been given.
-static int quiesce_before_resync(const amtx_of_model* m) {
-    if (m->packed_once) AMTX_CHECK_HIP(hipDeviceSynchronize());
     return AMTX_OK;
 }
 
 extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
     AMTX_REQUIRE(m, "amtx_of_model_finalize: null model");
     {
-        int qrc = quiesce_before_resync(m);
+        int qrc = amtx_quiesce_before_resync(m->packed_once);
         if (qrc != AMTX_OK) return qrc;
     }
     const int nh = m->n_heads;
@@ -323,22 +319,22 @@ extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
             for (int i = 0; i < m->in_channels * 9; ++i)
                 c1w[((size_t)h * m->nf1 + co) * m->in_channels * 9 + i] = w[(size_t)co * m->in_channels * 9 + i] * scale[co];
         memcpy(c1s.data() + (size_t)h * m->nf1, shift.data(), sizeof(float) * m->nf1);
-        if (m->fuse_conv1 && m->gen_conv2) (m->f16 ? amtx_conv1g_pack_host_f16 : amtx_conv1g_pack_host)(w, scale.data(), m->in_channels, m->nf1, m->planes, c1f.data() + c1f_per * h);
-        else if (m->fuse_conv1) (m->f16 ? amtx_conv1_pack_host_f16 : amtx_conv1_pack_host)(w, scale.data(), m->in_channels, m->planes, c1f.data() + c1f_per * h);
+        if (m->fuse_conv1 && m->gen_conv2) m->k->conv1g_pack_host(w, scale.data(), m->in_channels, m->nf1, m->planes, c1f.data() + c1f_per * h);
+        else if (m->fuse_conv1) m->k->conv1_pack_host(w, scale.data(), m->in_channels, m->planes, c1f.data() + c1f_per * h);
 
         rc = fold_bn(m, am + ".layer2.0", am + ".layer2.1", m->nf2, scale, shift);
         if (rc != AMTX_OK) return rc;
         NEED(am + ".layer2.0.weight", (size_t)m->nf2 * m->nf1 * 9, w);
-        if (m->gen_conv2) (m->f16 ? amtx_conv3x3_gen_pack_host_f16 : amtx_conv3x3_gen_pack_host)(w, scale.data(), m->nf1, m->nf2, m->planes, c2w.data() + c2w_per * h);
-        else (m->f16 ? amtx_conv3x3_pack_host_f16 : amtx_conv3x3_pack_host)(w, scale.data(), m->nf2, m->planes, c2w.data() + c2w_per * h);
+        if (m->gen_conv2) m->k->conv3x3_gen_pack_host(w, scale.data(), m->nf1, m->nf2, m->planes, c2w.data() + c2w_per * h);
+        else m->k->conv3x3_pack_host(w, scale.data(), m->nf2, m->planes, c2w.data() + c2w_per * h);
         if (m->x12m) amtx_conv3x3_pack_host(w, scale.data(), m->nf2, m->planes, c2x.data() + c2x_per * h);
         memcpy(c2s.data() + (size_t)h * m->nf2, shift.data(), sizeof(float) * m->nf2);
 
         rc = fold_bn(m, am + ".layer3.0", am + ".layer3.1", m->nf3, scale, shift);
         if (rc != AMTX_OK) return rc;
         NEED(am + ".layer3.0.weight", (size_t)m->nf3 * m->nf2 * 9, w);
-        if (m->gen_conv) (m->f16 ? amtx_conv3x3_gen_pack_host_f16 : amtx_conv3x3_gen_pack_host)(w, scale.data(), m->nf2, m->nf3, m->planes, c3w.data() + c3w_per * h);
-        else (m->f16 ? amtx_conv3x3_pack_host_f16 : amtx_conv3x3_pack_host)(w, scale.data(), m->nf3, m->planes, c3w.data() + c3w_per * h);
+        if (m->gen_conv) m->k->conv3x3_gen_pack_host(w, scale.data(), m->nf2, m->nf3, m->planes, c3w.data() + c3w_per * h);
+        else m->k->conv3x3_pack_host(w, scale.data(), m->nf3, m->planes, c3w.data() + c3w_per * h);
         memcpy(c3s.data() + (size_t)h * m->nf3, shift.data(), sizeof(float) * m->nf3);
 
         // fc1: reference column index c*fq + f  ->  ours f*nf3 + c
@@ -438,7 +434,7 @@ extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
         std::vector<std::vector<float>> W{std::vector<float>(w, w + (size_t)m->n_out * m->dim_lm)}, Bv{std::vector<float>(b, b + m->n_out)};
         if ((rc = pack_linear_groups(m, m->adj_out, W, Bv, m->n_out, m->dim_lm)) != AMTX_OK) return rc;
     }
-    m->tensors.clear();
+    m->store.host.clear();
     m->finalized = true;
     m->packed_once = true;
     return AMTX_OK;
@@ -453,27 +449,14 @@ extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
 // AMTX_ERR_UNSUPPORTED and keeps the host path.
 extern "C" int amtx_of_model_set_tensor_device(amtx_of_model* m, const char* name, const float* device_data, int64_t numel) {
     AMTX_REQUIRE(m && name && device_data && numel > 0, "amtx_of_model_set_tensor_device: bad argument");
-    m->dev_tensors[name] = std::make_pair(device_data, numel);
+    m->store.set_device(name, device_data, numel);
     return AMTX_OK;
 }
 
 namespace {
-int need_dev(const amtx_of_model* m, const std::string& name, size_t numel, const float** out) {
-    auto it = m->dev_tensors.find(name);
-    if (it == m->dev_tensors.end()) {
-        amtx_set_error("of_model: device tensor '%s' was not provided", name.c_str());
-        return AMTX_ERR_ARG;
-    }
-    if ((size_t)it->second.second != numel) {
-        amtx_set_error("of_model: device tensor '%s' has %lld elements, expected %zu", name.c_str(), (long long)it->second.second, numel);
-        return AMTX_ERR_ARG;
-    }
-    *out = it->second.first;
-    return AMTX_OK;
-}
 #define NEED_DEV(name, numel, ptr)                                     \
     do {                                                               \
-        int _rc = need_dev(m, name, numel, &(ptr));                    \
+        int _rc = m->store.need_device(name, numel, &(ptr));           \
         if (_rc != AMTX_OK) return _rc;                                \
     } while (0)
 #define PACK_TRY(expr)                                                 \
@@ -491,7 +474,7 @@ extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
     AMTX_REQUIRE(m, "amtx_of_model_finalize_device: null model");
     struct Clear {                             // the borrowed device pointers are dropped on EVERY exit: the caller may free them afterwards
         amtx_of_model* m;
-        ~Clear() { m->dev_tensors.clear(); }
+        ~Clear() { m->store.device.clear(); }
     } clear{m};
     AMTX_REQUIRE(m->finalized, "amtx_of_model_finalize_device: the first sync goes through amtx_of_model_finalize (it allocates the packed buffers)");
     if (!m->gen_conv2 && m->in_channels != 1) {
@@ -501,7 +484,7 @@ extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
     hipStream_t s = (hipStream_t)stream_;
     int rc = finalize_device_pass(m, s, true);
     if (rc != AMTX_OK) return rc;
-    if ((rc = quiesce_before_resync(m)) != AMTX_OK) return rc;
+    if ((rc = amtx_quiesce_before_resync(m->packed_once)) != AMTX_OK) return rc;
     rc = finalize_device_pass(m, s, false);
     if (rc != AMTX_OK) m->finalized = false;   // a launch failed half-way: the packed weights are no version at all, refuse to run on them
     return rc;
@@ -522,15 +505,7 @@ extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
 
 static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry) {
     const int nh = m->n_heads, pl = m->planes, H = m->hid, G = 4 * H;
-    const bool f16 = m->f16;
-    auto pack_conv = [f16](const float* w, const float* sc, int c_out, int planes, bf16_t* out, hipStream_t st) {
-        return f16 ? amtx_pack_conv3x3_dev_f16(w, sc, c_out, planes, out, st) : amtx_pack_conv3x3_dev(w, sc, c_out, planes, out, st);
-    };
-    auto pack_lin = [f16](const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows, int pc, int pf, bf16_t* out,
-                          hipStream_t st) {
-        return f16 ? amtx_pack_linear_dev_f16(W, ldw, N, K, planes, n_pad, k_pad, row0, rows, pc, pf, out, st)
-                   : amtx_pack_linear_dev(W, ldw, N, K, planes, n_pad, k_pad, row0, rows, pc, pf, out, st);
-    };
+    const KernelSet* k = m->k;
     // scratch: scale[256] | folded pitch head (n_out x kfc_pad) | folded bias | backward LSTM fragments (written by the shared pack
     // kernel, not used by inference)
     const size_t hh_elems = amtx_bilstm_wfrag_elems_h(H, pl);
@@ -550,9 +525,8 @@ static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry)
     const size_t c1f_per = m->gen_conv2 ? amtx_conv1g_wfrag_elems(ic, m->nf1, pl) : amtx_conv1_wfrag_elems(ic, pl);
     const size_t c2w_per = m->gen_conv2 ? amtx_conv3x3_gen_wfrag_elems(m->nf1, m->nf2, pl) : amtx_conv3x3_wfrag_elems(m->nf2, pl);
     const size_t c3w_per = m->gen_conv ? amtx_conv3x3_gen_wfrag_elems(m->nf2, m->nf3, pl) : amtx_conv3x3_wfrag_elems(m->nf3, pl);
-    auto pack_conv_gen = [f16](const float* w, const float* sc, int c_in, int c_out, int planes, bf16_t* out, hipStream_t st) {
-        const int ntc = amtx_conv3x3_gen_ntc(c_in, c_out);
-        return f16 ? amtx_pack_conv_gen_dev_f16(w, sc, c_in, c_out, ntc, planes, out, st) : amtx_pack_conv_gen_dev(w, sc, c_in, c_out, ntc, planes, out, st);
+    auto pack_conv_gen = [k](const float* w, const float* sc, int c_in, int c_out, int planes, bf16_t* out, hipStream_t st) {
+        return k->pack_conv_gen_dev(w, sc, c_in, c_out, amtx_conv3x3_gen_ntc(c_in, c_out), planes, out, st);
     };
     const size_t fc_per = (size_t)m->fc1.n_pad * m->fc1.k_pad * pl;
     for (int h = 0; h < nh; ++h) {
@@ -564,27 +538,27 @@ static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry)
         NEED_DEV(am + ".layer1.1.running_mean", (size_t)m->nf1, mu); NEED_DEV(am + ".layer1.1.running_var", (size_t)m->nf1, var);
         PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, m->nf1, scale, (float*)m->conv1_s.p + (size_t)h * m->nf1, s));
         PACK_TRY(amtx_pack_scale_rows_dev(w, scale, m->nf1, ic * 9, (float*)m->conv1_w.p + (size_t)h * m->nf1 * ic * 9, s));
-        if (m->fuse_conv1 && m->gen_conv2) PACK_TRY((f16 ? amtx_pack_conv1g_dev_f16 : amtx_pack_conv1g_dev)(w, scale, ic, m->nf1, pl, (bf16_t*)m->conv1_frag.p + c1f_per * h, s));
-        else if (m->fuse_conv1) PACK_TRY((f16 ? amtx_pack_conv1_dev_f16 : amtx_pack_conv1_dev)(w, scale, pl, (bf16_t*)m->conv1_frag.p + c1f_per * h, s));
+        if (m->fuse_conv1 && m->gen_conv2) PACK_TRY(k->pack_conv1g_dev(w, scale, ic, m->nf1, pl, (bf16_t*)m->conv1_frag.p + c1f_per * h, s));
+        else if (m->fuse_conv1) PACK_TRY(k->pack_conv1_dev(w, scale, pl, (bf16_t*)m->conv1_frag.p + c1f_per * h, s));
         NEED_DEV(am + ".layer2.0.weight", (size_t)m->nf2 * m->nf1 * 9, w);
         NEED_DEV(am + ".layer2.0.bias", (size_t)m->nf2, cb); NEED_DEV(am + ".layer2.1.weight", (size_t)m->nf2, g); NEED_DEV(am + ".layer2.1.bias", (size_t)m->nf2, be);
         NEED_DEV(am + ".layer2.1.running_mean", (size_t)m->nf2, mu); NEED_DEV(am + ".layer2.1.running_var", (size_t)m->nf2, var);
         PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, m->nf2, scale, (float*)m->conv2_s.p + (size_t)h * m->nf2, s));
         if (m->gen_conv2) PACK_TRY(pack_conv_gen(w, scale, m->nf1, m->nf2, pl, (bf16_t*)m->conv2_w.p + c2w_per * h, s));
-        else PACK_TRY(pack_conv(w, scale, m->nf2, pl, (bf16_t*)m->conv2_w.p + c2w_per * h, s));
-        if (m->x12m) PACK_TRY(pack_conv(w, scale, m->nf2, pl, (bf16_t*)m->conv2_wx.p + (size_t)amtx_conv3x3_wfrag_elems(m->nf2, pl) * h, s));
+        else PACK_TRY(k->pack_conv3x3_dev(w, scale, m->nf2, pl, (bf16_t*)m->conv2_w.p + c2w_per * h, s));
+        if (m->x12m) PACK_TRY(k->pack_conv3x3_dev(w, scale, m->nf2, pl, (bf16_t*)m->conv2_wx.p + (size_t)amtx_conv3x3_wfrag_elems(m->nf2, pl) * h, s));
         NEED_DEV(am + ".layer3.0.weight", (size_t)m->nf3 * m->nf2 * 9, w);
         NEED_DEV(am + ".layer3.0.bias", (size_t)m->nf3, cb); NEED_DEV(am + ".layer3.1.weight", (size_t)m->nf3, g); NEED_DEV(am + ".layer3.1.bias", (size_t)m->nf3, be);
         NEED_DEV(am + ".layer3.1.running_mean", (size_t)m->nf3, mu); NEED_DEV(am + ".layer3.1.running_var", (size_t)m->nf3, var);
         PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, m->nf3, scale, (float*)m->conv3_s.p + (size_t)h * m->nf3, s));
         if (m->gen_conv) PACK_TRY(pack_conv_gen(w, scale, m->nf2, m->nf3, pl, (bf16_t*)m->conv3_w.p + c3w_per * h, s));
-        else PACK_TRY(pack_conv(w, scale, m->nf3, pl, (bf16_t*)m->conv3_w.p + c3w_per * h, s));
+        else PACK_TRY(k->pack_conv3x3_dev(w, scale, m->nf3, pl, (bf16_t*)m->conv3_w.p + c3w_per * h, s));
         // fc1 of the recurrent heads, columns permuted (channel, freq) -> (freq, channel)
         if (h < m->n_rec) {
             const float* fb;
             NEED_DEV(am + ".fc1.0.weight", (size_t)m->dim_am * m->kfc, w);
             NEED_DEV(am + ".fc1.0.bias", (size_t)m->dim_am, fb);
-            PACK_TRY(pack_lin(w, m->kfc, m->dim_am, m->kfc, pl, m->fc1.n_pad, m->fc1.k_pad, 0, m->fc1.n_pad, m->nf3, m->fq, (bf16_t*)m->fc1.w.p + fc_per * h, s));
+            PACK_TRY(k->pack_linear_dev(w, m->kfc, m->dim_am, m->kfc, pl, m->fc1.n_pad, m->fc1.k_pad, 0, m->fc1.n_pad, m->nf3, m->fq, (bf16_t*)m->fc1.w.p + fc_per * h, s));
             PACK_COPY((float*)m->fc1.b.p + (size_t)h * m->dim_am, fb, sizeof(float) * m->dim_am);
         }
     }
@@ -597,15 +571,15 @@ static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry)
         NEED_DEV(p + "bias_ih_l0", (size_t)G, bif); NEED_DEV(p + "bias_ih_l0_reverse", (size_t)G, bib);
         NEED_DEV(p + "bias_hh_l0", (size_t)G, bhf); NEED_DEV(p + "bias_hh_l0_reverse", (size_t)G, bhb);
         bf16_t* ihw = (bf16_t*)ih.w.p + (size_t)ih.n_pad * ih.k_pad * pl * grp;
-        PACK_TRY(pack_lin(wif, dim_in, G, dim_in, pl, ih.n_pad, ih.k_pad, 0, G, 0, 0, ihw, s));
-        PACK_TRY(pack_lin(wib, dim_in, G, dim_in, pl, ih.n_pad, ih.k_pad, G, ih.n_pad - G, 0, 0, ihw, s));
+        PACK_TRY(k->pack_linear_dev(wif, dim_in, G, dim_in, pl, ih.n_pad, ih.k_pad, 0, G, 0, 0, ihw, s));
+        PACK_TRY(k->pack_linear_dev(wib, dim_in, G, dim_in, pl, ih.n_pad, ih.k_pad, G, ih.n_pad - G, 0, 0, ihw, s));
         float* ihb = (float*)ih.b.p + (size_t)ih.N * grp;
         PACK_TRY(amtx_pack_vec_add_dev(bif, bhf, G, ihb, s));
         PACK_TRY(amtx_pack_vec_add_dev(bib, bhb, G, ihb + G, s));
-        PACK_TRY((f16 ? amtx_launch_bilstm_pack_dev_h_f16 : amtx_launch_bilstm_pack_dev_h)(whf, whb, H, pl, (bf16_t*)hh.p + hh_elems * grp, hh_bwd, s));
+        PACK_TRY(k->launch_bilstm_pack_dev_h(whf, whb, H, pl, (bf16_t*)hh.p + hh_elems * grp, hh_bwd, s));
         NEED_DEV(bank + ".output_layer.weight", (size_t)m->n_out * m->dim_lm, wo);
         NEED_DEV(bank + ".output_layer.bias", (size_t)m->n_out, bo);
-        PACK_TRY(pack_lin(wo, m->dim_lm, m->n_out, m->dim_lm, pl, outp.n_pad, outp.k_pad, 0, outp.n_pad, 0, 0,
+        PACK_TRY(k->pack_linear_dev(wo, m->dim_lm, m->n_out, m->dim_lm, pl, outp.n_pad, outp.k_pad, 0, outp.n_pad, 0, 0,
                           (bf16_t*)outp.w.p + (size_t)outp.n_pad * outp.k_pad * pl * grp, s));
         PACK_COPY((float*)outp.b.p + (size_t)outp.N * grp, bo, sizeof(float) * m->n_out);
         return AMTX_OK;
@@ -626,7 +600,7 @@ static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry)
         NEED_DEV("pitch_head.0.fc1.0.weight", (size_t)m->dim_am * m->kfc, w1);
         NEED_DEV("pitch_head.0.fc1.0.bias", (size_t)m->dim_am, b1);
         PACK_TRY(amtx_pack_head_fold_dev(wo, w1, b1, bo, m->n_out, m->dim_am, m->kfc, m->kfc_pad, m->nf3, m->fq, wfold, bfold, s));
-        PACK_TRY(pack_lin(wfold, m->kfc_pad, m->n_out, m->kfc_pad, pl, m->pitch_out.n_pad, m->pitch_out.k_pad, 0, m->pitch_out.n_pad, 0, 0,
+        PACK_TRY(k->pack_linear_dev(wfold, m->kfc_pad, m->n_out, m->kfc_pad, pl, m->pitch_out.n_pad, m->pitch_out.k_pad, 0, m->pitch_out.n_pad, 0, 0,
                           (bf16_t*)m->pitch_out.w.p, s));
         PACK_COPY(m->pitch_out.b.p, bfold, sizeof(float) * m->n_out);
     }
@@ -673,12 +647,7 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
     const int64_t BT = (int64_t)B * T;
     const int F = m->dim_in, F2 = F / 2, at = m->act_type, pl = m->planes;
     int rc;
-    // the kernels of this model's 16-bit operand format (bf16, or IEEE half: the second build of conv / convf / gemm / lstm.hip)
-    const bool f16 = m->f16;
-    auto launch_gemm = [f16](const GemmArgs& ga, hipStream_t st) { return f16 ? amtx_launch_gemm_f16(ga, st) : amtx_launch_gemm(ga, st); };
-    auto launch_conv = [f16](const ConvArgs& ca, hipStream_t st) { return f16 ? amtx_launch_conv3x3_f16(ca, st) : amtx_launch_conv3x3(ca, st); };
-    auto launch_convg = [f16](const ConvArgs& ca, int ci, hipStream_t st) { return f16 ? amtx_launch_conv3x3_gen_f16(ca, ci, st) : amtx_launch_conv3x3_gen(ca, ci, st); };
-    auto launch_bilstm = [f16](const LstmArgs& la, hipStream_t st) { return f16 ? amtx_launch_bilstm_f16(la, st) : amtx_launch_bilstm(la, st); };
+    const KernelSet* k = m->k;
     std::vector<hipEvent_t>* evs = nullptr;
     if (m->prof) {
         m->prof_events.emplace_back();
@@ -696,7 +665,7 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
     c1.w = (const float*)m->conv1_w.p; c1.shift = (const float*)m->conv1_s.p; c1.out = w.a1; c1.out_type = at;
     c1.B = B; c1.T = T; c1.F = F; c1.c_in = m->in_channels; c1.c_out = m->nf1;
     c1.groups = m->n_heads; c1.w_gs = (int64_t)m->nf1 * m->in_channels * 9; c1.shift_gs = m->nf1; c1.out_gs = BT * F * m->nf1;
-    if (!m->fuse_conv1 && (rc = (f16 ? amtx_launch_conv1_f16 : amtx_launch_conv1)(c1, s)) != AMTX_OK) return rc;
+    if (!m->fuse_conv1 && (rc = k->launch_conv1(c1, s)) != AMTX_OK) return rc;
     mark();
 
     ConvArgs c2;
@@ -731,11 +700,11 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
     const int64_t a3_plane = (fused_stack && !rowmajor_a3 && m->nf3 == 64 && m->kfc_pad == m->kfc) ? BT * 64 : 0;
     if (fused_stack) {
         // layer1 -> layer2 -> layer3 in one kernel: neither intermediate map reaches HBM (stage timer: all of it under conv2_pool)
-        if ((rc = (f16 ? amtx_launch_conv_stack_f16 : amtx_launch_conv_stack)(c2, (const bf16_t*)m->conv3_w.p, (int64_t)amtx_conv3x3_wfrag_elems(m->nf3, pl), (const float*)m->conv3_s.p,
+        if ((rc = k->launch_conv_stack(c2, (const bf16_t*)m->conv3_w.p, (int64_t)amtx_conv3x3_wfrag_elems(m->nf3, pl), (const float*)m->conv3_s.p,
                                          w.a3, BT * m->kfc_pad, a3_plane, s)) != AMTX_OK) return rc;
     } else if (x12m_now) {
         if ((rc = amtx_launch_convx12(c2, s)) != AMTX_OK) return rc;
-    } else if ((rc = m->gen_conv2 ? launch_convg(c2, m->nf1, s) : launch_conv(c2, s)) != AMTX_OK) return rc;
+    } else if ((rc = m->gen_conv2 ? k->launch_conv3x3_gen(c2, m->nf1, s) : k->launch_conv3x3(c2, s)) != AMTX_OK) return rc;
     mark();
 
     ConvArgs c3 = c2;
@@ -753,26 +722,26 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
         if ((rc = amtx_launch_zero_cols(w.a3 + (size_t)m->kfc * es, (int64_t)m->kfc_pad * es, (int)((m->kfc_pad - m->kfc) * es),
                                         BT * m->n_heads, s)) != AMTX_OK) return rc;
     }
-    if (!fused_stack && (rc = m->gen_conv ? launch_convg(c3, m->nf2, s) : launch_conv(c3, s)) != AMTX_OK) return rc;
+    if (!fused_stack && (rc = m->gen_conv ? k->launch_conv3x3_gen(c3, m->nf2, s) : k->launch_conv3x3(c3, s)) != AMTX_OK) return rc;
     mark();
 
     // fc1 of the recurrent heads (heads 0..n_rec-1 of a3); the pitch head's fc1 is folded into its output layer below
     const int at_d = sp ? AMTX_T_SPLIT : at;   // element type of the dense layers' activations
     GemmArgs g = gemm_args(w.a3, m->kfc_pad, at_d, m->fc1, pl, w.e, m->dim_am, at_d, BT, m->n_rec, BT * m->kfc_pad, BT * m->dim_am);
     g.a_plane = a3_plane; g.a_split = a3_split; g.c_split = e_split;
-    if ((rc = launch_gemm(g, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
     mark();
 
     // recurrent heads: heads 0..n_rec-1 of `e`
     g = gemm_args(w.e, m->dim_am, at_d, m->rec_ih, pl, w.xp, m->xw, at, BT, m->n_rec, BT * m->dim_am, BT * m->xw);
     g.a_split = e_split;
-    if ((rc = launch_gemm(g, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
     mark();
     LstmArgs l;
     l.xproj = w.xp; l.x_type = at; l.whh = (const bf16_t*)m->rec_hh.p; l.planes = pl; l.out = w.l1; l.out_type = at;
     l.B = B; l.T = T; l.groups = m->n_rec; l.x_gs = BT * m->xw; l.w_gs = (int64_t)amtx_bilstm_wfrag_elems_h(m->hid, pl); l.out_gs = BT * m->dim_lm;
     l.hidden = m->hid;
-    if ((rc = launch_bilstm(l, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_bilstm(l, s)) != AMTX_OK) return rc;
     mark();
     // LogisticBank of each recurrent head -> joint[:, r*n_out : (r+1)*n_out]; group stride of C = n_out columns
     g = gemm_args(w.l1, m->dim_lm, at, m->rec_out, pl, w.joint, m->dim_aj, AMTX_T_F32, BT, m->n_rec, BT * m->dim_lm, m->n_out);
@@ -795,16 +764,16 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
         gp.copy16 = (bf16_t*)w.joint16; gp.copy16_ld = kp; gp.copy16_col0 = m->n_rec * m->n_out; gp.copy16_gs = 0; gp.copy16_pad = kp - m->dim_aj;
         if (roll_on && !logits_onsets && !logits_pitch_head && !m->has_offsets) { g.C = nullptr; gp.C = nullptr; }
     }
-    if ((rc = launch_gemm(g, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
     mark();
     // pitch head: (fc1 . LogisticBank) folded, straight from its conv3 map -> last n_out columns of joint
-    if ((rc = launch_gemm(gp, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_gemm(gp, s)) != AMTX_OK) return rc;
     mark();
 
     // adjoin
     if (pl == 1) {
         // bf16 mode: the joint logits rounded to bf16 (zero-padded to a 64-multiple K) feed the direct-to-LDS GEMM
-        if (!copy_on && (rc = amtx_launch_cvt_pad_bf16((const float*)w.joint, m->dim_aj, m->dim_aj, (bf16_t*)w.joint16, kp, BT, s, f16)) != AMTX_OK) return rc;
+        if (!copy_on && (rc = amtx_launch_cvt_pad_bf16((const float*)w.joint, m->dim_aj, m->dim_aj, (bf16_t*)w.joint16, kp, BT, s, m->f16)) != AMTX_OK) return rc;
         g = gemm_args(w.joint16, kp, AMTX_T_BF16, m->adj_ih, pl, w.xp2, m->xw, at, BT, 1, 0, 0);
         g.K = kp;
     } else if (sp) {
@@ -815,10 +784,10 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
     } else {
         g = gemm_args(w.joint, m->dim_aj, AMTX_T_F32, m->adj_ih, pl, w.xp2, m->xw, at, BT, 1, 0, 0);
     }
-    if ((rc = launch_gemm(g, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
     mark();
     l.xproj = w.xp2; l.whh = (const bf16_t*)m->adj_hh.p; l.out = w.l2; l.groups = 1;
-    if ((rc = launch_bilstm(l, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_bilstm(l, s)) != AMTX_OK) return rc;
     mark();
     g = gemm_args(w.l2, m->dim_lm, at, m->adj_out, pl, w.mp, m->n_out, AMTX_T_F32, BT, 1, 0, 0);
     const bool roll_mp = out_multi_pitch && !no_roll_epi && amtx_gemm_has_roll_epilogue(g);
@@ -826,7 +795,7 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
         g.roll_out = out_multi_pitch; g.roll_T = T; g.roll_thr = 0.5f; g.roll_group = 0;
         if (!logits_multi_pitch) g.C = nullptr;            // nobody reads the refined logits then: only the roll is written
     }
-    if ((rc = launch_gemm(g, s)) != AMTX_OK) return rc;
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
     mark();
 
     // piano rolls of the modes whose LogisticBank GEMM has no roll epilogue (x3)

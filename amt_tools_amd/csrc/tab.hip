@@ -12,11 +12,8 @@
 //   fc           amtx_launch_gemm (gemm.hip): [B*T][128] fp32 = rows . W^T + bias
 //   tab_head     ReLU -> output layer (fp32) -> logits [B*T][G*C] and the per-group argmax (first index on ties, last class -> -1) as
 //                tablature [B][G][T] int64
-#include <map>
-#include <string>
-#include <vector>
-
 #include "amtx_kernels.h"
+#include "amtx_model_common.h"
 
 namespace {
 
@@ -282,23 +279,6 @@ __global__ void __launch_bounds__(TAB_THREADS) tab_head_kernel(const float* __re
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int upload(const void* host, size_t n) {
-        if (!p || bytes != n) {
-            if (p) (void)hipFree(p);
-            p = nullptr; bytes = n;
-            AMTX_CHECK_HIP(hipMalloc(&p, n));
-        }
-        AMTX_CHECK_HIP(hipMemcpy(p, host, n, hipMemcpyHostToDevice));
-        return AMTX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
-
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
 size_t conv12_lds(int c_in, int planes) {
     return (size_t)(c_in * (TAB_TF + 4) * (TAB_TT + 4) + c_in * 9 * TAB_C1 + TAB_C1) * 4 + (size_t)planes * (TAB_TT + 2) * (TAB_TF + 2) * TAB_P1 * 2;
 }
@@ -309,7 +289,7 @@ size_t conv3_lds(int planes) { return (size_t)planes * (TAB_TT + 3) * (TAB_TF + 
 struct amtx_tab_model {
     int dim_in, in_channels, mc, G, C, precision, planes;
     int H, K;                                    // pooled rows, fc input width 64*H
-    std::map<std::string, std::vector<float>> tensors;
+    TensorStore store{"amtx_tab_model_finalize", "was never set"};
     std::map<std::string, int64_t> expected;     // state_dict key -> numel
     DevBuf w1, b1, w2, b2, w3, b3, fcw, fcb, hw, hb;
     int fc_npad = 0, fc_kpad = 0;
@@ -371,24 +351,27 @@ extern "C" int amtx_tab_model_set_tensor(amtx_tab_model* m, const char* name, co
     AMTX_REQUIRE(it != m->expected.end(), "amtx_tab_model_set_tensor: unknown tensor '%s' (the reference's TabCNN state_dict keys: conv.{0,2,4}.{weight,bias}, "
                                           "dense.0.{weight,bias}, dense.3.output_layer.{weight,bias})", name);
     AMTX_REQUIRE(numel == it->second, "amtx_tab_model_set_tensor: '%s' has %lld elements, this model needs %lld", name, (long long)numel, (long long)it->second);
-    m->tensors[name].assign(host_data, host_data + numel);
+    m->store.set(name, host_data, numel);
     m->finalized = false;
     return AMTX_OK;
 }
 
 extern "C" int amtx_tab_model_finalize(amtx_tab_model* m) {
     AMTX_REQUIRE(m, "amtx_tab_model_finalize: null model");
-    for (const auto& kv : m->expected)
-        AMTX_REQUIRE(m->tensors.count(kv.first), "amtx_tab_model_finalize: tensor '%s' was never set", kv.first.c_str());
-    // a re-sync overwrites buffers a forward pass on another stream may still read
-    if (m->w1.p) AMTX_CHECK_HIP(hipDeviceSynchronize());
+    int rc;
+    for (const auto& kv : m->expected) {
+        const float* unused;
+        if ((rc = m->store.need(kv.first, (size_t)kv.second, &unused)) != AMTX_OK) return rc;
+    }
+    if ((rc = amtx_quiesce_before_resync(m->w1.p != nullptr)) != AMTX_OK) return rc;
+    std::map<std::string, std::vector<float>>& tensors = m->store.host;
     const int P = m->planes, cin = m->in_channels;
     auto plane_of = [](float x, int p) -> bf16_t {
         const bf16_t hi = f32_to_bf16_rn(x);
         return p == 0 ? hi : f32_to_bf16_rn(x - bf16_to_f32(hi));
     };
     // conv1: [c*9 + kf*3 + kt][32] fp32
-    const std::vector<float>& c1 = m->tensors["conv.0.weight"];
+    const std::vector<float>& c1 = tensors["conv.0.weight"];
     std::vector<float> w1((size_t)cin * 9 * TAB_C1);
     for (int o = 0; o < TAB_C1; ++o)
         for (int k = 0; k < cin * 9; ++k) w1[(size_t)k * TAB_C1 + o] = c1[(size_t)o * cin * 9 + k];
@@ -407,10 +390,10 @@ extern "C" int amtx_tab_model_finalize(amtx_tab_model* m) {
                         }
     };
     std::vector<bf16_t> w2, w3;
-    pack_conv(m->tensors["conv.2.weight"], TAB_C1, 9, w2);
-    pack_conv(m->tensors["conv.4.weight"], TAB_C2, 18, w3);
+    pack_conv(tensors["conv.2.weight"], TAB_C1, 9, w2);
+    pack_conv(tensors["conv.4.weight"], TAB_C2, 18, w3);
     // fc: columns permuted from the reference's flatten order (c * H + h) to the engine's (h * 64 + c)
-    const std::vector<float>& fw = m->tensors["dense.0.weight"];
+    const std::vector<float>& fw = tensors["dense.0.weight"];
     std::vector<float> wp((size_t)TAB_FC * m->K);
     for (int n = 0; n < TAB_FC; ++n)
         for (int c = 0; c < TAB_C2; ++c)
@@ -418,41 +401,41 @@ extern "C" int amtx_tab_model_finalize(amtx_tab_model* m) {
     amtx_gemm_pack_dims(TAB_FC, m->K, &m->fc_npad, &m->fc_kpad);
     std::vector<bf16_t> fcp((size_t)P * m->fc_npad * m->fc_kpad);
     amtx_gemm_pack_host(wp.data(), m->K, TAB_FC, m->K, P, fcp.data());
-    int rc;
 #define TAB_UP(buf, vec) if ((rc = m->buf.upload((vec).data(), (vec).size() * sizeof((vec)[0]))) != AMTX_OK) return rc
     TAB_UP(w1, w1);
-    TAB_UP(b1, m->tensors["conv.0.bias"]);
+    TAB_UP(b1, tensors["conv.0.bias"]);
     TAB_UP(w2, w2);
-    TAB_UP(b2, m->tensors["conv.2.bias"]);
+    TAB_UP(b2, tensors["conv.2.bias"]);
     TAB_UP(w3, w3);
-    TAB_UP(b3, m->tensors["conv.4.bias"]);
+    TAB_UP(b3, tensors["conv.4.bias"]);
     TAB_UP(fcw, fcp);
-    TAB_UP(fcb, m->tensors["dense.0.bias"]);
-    TAB_UP(hw, m->tensors["dense.3.output_layer.weight"]);
-    TAB_UP(hb, m->tensors["dense.3.output_layer.bias"]);
+    TAB_UP(fcb, tensors["dense.0.bias"]);
+    TAB_UP(hw, tensors["dense.3.output_layer.weight"]);
+    TAB_UP(hb, tensors["dense.3.output_layer.bias"]);
 #undef TAB_UP
     m->finalized = true;
     return AMTX_OK;
 }
 
 namespace {
-struct TabLayout { size_t y2, e, h1, total; int64_t y2_elems, e_elems; };
-TabLayout tab_layout(const amtx_tab_model* m, int64_t batch, int64_t num_windows) {
+struct TabLayout { bf16_t *y2, *e; float* h1; size_t total; int64_t y2_elems, e_elems; };
+TabLayout tab_layout(const amtx_tab_model* m, int64_t batch, int64_t num_windows, void* base) {
     TabLayout L;
     const size_t es = m->planes == 2 ? 4 : 2;     // bf16, or the two planes of a split element
     L.y2_elems = batch * (num_windows + 4) * (m->dim_in - 4) * TAB_C2;
     L.e_elems = batch * num_windows * m->K;
-    L.y2 = 0;
-    L.e = L.y2 + align256(L.y2_elems * es);
-    L.h1 = L.e + align256(L.e_elems * es);
-    L.total = L.h1 + align256(batch * num_windows * TAB_FC * 4);
+    WorkspaceCarver ws{static_cast<char*>(base)};
+    L.y2 = reinterpret_cast<bf16_t*>(ws.take(L.y2_elems * es));
+    L.e = reinterpret_cast<bf16_t*>(ws.take(L.e_elems * es));
+    L.h1 = reinterpret_cast<float*>(ws.take(batch * num_windows * TAB_FC * 4));
+    L.total = ws.off;
     return L;
 }
 }  // namespace
 
 extern "C" size_t amtx_tab_workspace_bytes(const amtx_tab_model* m, int batch, int num_windows) {
     if (!m || batch <= 0 || num_windows <= 0) return 0;
-    return tab_layout(m, batch, num_windows).total;
+    return tab_layout(m, batch, num_windows, nullptr).total;
 }
 
 extern "C" int amtx_tab_forward(const amtx_tab_model* m, const float* feats, int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t,
@@ -463,13 +446,11 @@ extern "C" int amtx_tab_forward(const amtx_tab_model* m, const float* feats, int
     AMTX_REQUIRE(batch > 0 && batch <= 65535 && num_windows > 0, "amtx_tab_forward: bad batch / num_windows (%d, %d)", batch, num_windows);
     AMTX_REQUIRE((int64_t)batch * num_windows < (1ll << 31), "amtx_tab_forward: batch x num_windows must be below 2^31");
     AMTX_REQUIRE(((uintptr_t)workspace % 256) == 0, "amtx_tab_forward: workspace must be 256-byte aligned");
-    const TabLayout L = tab_layout(m, batch, num_windows);
+    const TabLayout L = tab_layout(m, batch, num_windows, workspace);
     AMTX_REQUIRE(workspace_bytes >= L.total, "amtx_tab_forward: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    bf16_t* y2 = reinterpret_cast<bf16_t*>(ws + L.y2);
-    bf16_t* e = reinterpret_cast<bf16_t*>(ws + L.e);
-    float* h1 = reinterpret_cast<float*>(ws + L.h1);
+    bf16_t *y2 = L.y2, *e = L.e;
+    float* h1 = L.h1;
     const int F = m->dim_in, F2 = F - 4, T = num_windows, T2 = T + 4;
     const bool x3 = m->planes == 2;
 

@@ -147,15 +147,6 @@ __global__ __launch_bounds__(256) void sm_loss_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(64) void sm_loss_reduce_kernel(const float* __restrict__ partial, int64_t n, float inv_bt, float* __restrict__ loss) {
-    // fixed order: lane l sums partial[l], partial[l+64], ... in double, then a fixed butterfly
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 64) a += (double)partial[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-    if (threadIdx.x == 0) *loss = (float)(a * (double)inv_bt);
-}
-
 int64_t sm_loss_blocks(int batch, int num_frames, int num_groups) { return ((int64_t)batch * num_frames * num_groups + 255) / 256; }
 
 }  // namespace
@@ -215,7 +206,5 @@ extern "C" int amtx_softmax_groups_loss(const float* logits, int64_t ld, const i
     hipLaunchKernelGGL(sm_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, s, logits, ld, targets, weight, num_frames, num_groups, num_classes,
                        pairs, inv_bt, grad, partial);
     AMTX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sm_loss_reduce_kernel, dim3(1), dim3(64), 0, s, (const float*)partial, blocks, inv_bt, loss);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+    return amtx_launch_loss_reduce(partial, blocks, inv_bt, loss, s);
 }

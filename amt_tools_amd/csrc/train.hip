@@ -44,11 +44,6 @@ constexpr int XBK = 32;
 constexpr int XBM = 128;
 constexpr int XPITCH = 80;   // bytes per LDS tile row: 32 bf16 + 16 bytes of padding
 
-typedef __attribute__((ext_vector_type(8))) __bf16 x_bf16x8;
-__device__ __forceinline__ f32x4_t xmfma(uint4 a, uint4 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(x_bf16x8, a), __builtin_bit_cast(x_bf16x8, b), c, 0, 0, 0);
-}
-
 __device__ __forceinline__ void tap_offsets(int tap, int& dy, int& dx) {
     dy = tap / 3 - 1;
     dx = tap - (tap / 3) * 3 - 1;
@@ -274,9 +269,9 @@ __global__ __launch_bounds__(256) void xgemm_kernel(XArgs g) {
             const uint4 bl = *reinterpret_cast<const uint4*>(b_lo + 16 * nt * XPITCH + frag);
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                acc[mt][nt] = xmfma(ah[mt], bh, acc[mt][nt]);
-                acc[mt][nt] = xmfma(ah[mt], bl, acc[mt][nt]);
-                acc[mt][nt] = xmfma(al[mt], bh, acc[mt][nt]);
+                acc[mt][nt] = mfma16(ah[mt], bh, acc[mt][nt]);
+                acc[mt][nt] = mfma16(ah[mt], bl, acc[mt][nt]);
+                acc[mt][nt] = mfma16(al[mt], bh, acc[mt][nt]);
             }
         }
         __syncthreads();
@@ -471,9 +466,9 @@ __global__ __launch_bounds__(256) void xconv_kernel(XConvArgs g) {
                     const uint4 bl = *reinterpret_cast<const uint4*>(w_lo + 16 * nt * WP + boff);
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) {
-                        acc[mt][nt] = xmfma(ah[mt], bh, acc[mt][nt]);
-                        acc[mt][nt] = xmfma(ah[mt], bl, acc[mt][nt]);
-                        acc[mt][nt] = xmfma(al[mt], bh, acc[mt][nt]);
+                        acc[mt][nt] = mfma16(ah[mt], bh, acc[mt][nt]);
+                        acc[mt][nt] = mfma16(ah[mt], bl, acc[mt][nt]);
+                        acc[mt][nt] = mfma16(al[mt], bh, acc[mt][nt]);
                     }
                 }
             }
@@ -706,9 +701,9 @@ __global__ __launch_bounds__(256) void xwgrad_kernel(XWgradArgs g) {
                 for (int n = 0; n < NT; ++n) {
                     const uint4 bh = *reinterpret_cast<const uint4*>(db + 16 * n * WG_DP);
                     const uint4 bl = *reinterpret_cast<const uint4*>(db + CO * WG_DP + 16 * n * WG_DP);
-                    acc[a][n] = xmfma(ah, bh, acc[a][n]);
-                    acc[a][n] = xmfma(ah, bl, acc[a][n]);
-                    acc[a][n] = xmfma(al, bh, acc[a][n]);
+                    acc[a][n] = mfma16(ah, bh, acc[a][n]);
+                    acc[a][n] = mfma16(ah, bl, acc[a][n]);
+                    acc[a][n] = mfma16(al, bh, acc[a][n]);
                 }
             }
         }

@@ -55,6 +55,24 @@ class TranscriptionModel(nn.Module):
         # hook for on-device front-ends (models/common.py:56-57); empty by default
         self.frontend = nn.Sequential()
 
+    # ---- engine management (device handles never enter state_dict / pickles, SURVEY finding F11) ----
+    _engine_class = None           # the subclass's _EngineBase
+    _transient = ('_engine',)      # __dict__ keys that live only between calls on one device: subclasses extend, __getstate__ drops them
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        for key in self._transient:
+            state.pop(key, None)
+        return state
+
+    def _get_engine(self, device):
+        eng = self.__dict__.get('_engine')
+        if eng is None or eng.device != device:
+            eng = self._engine_class(self, device)
+            self.__dict__['_engine'] = eng
+        eng.sync_weights(self)
+        return eng
+
     def change_device(self, device=None):
         if device is None:
             device = self.device
@@ -351,63 +369,90 @@ class PendingFeatures16(PendingFeatures):
         return self.module.process_batch(self.audio).transpose(-1, -2)
 
 
-class _OFEngine(object):
-    """ctypes handle of an amtx_of_model + its workspace, bound to one device."""
+class _EngineBase(object):
+    """ctypes handle of a native model (ABI functions `<ABI>_create / _set_tensor / _finalize / _destroy`) + its workspace, bound to one device."""
 
-    def __init__(self, model, device):
+    ABI = None
+
+    def __init__(self, device, *create_args):
         self.device = device
         self.handle = C.c_void_p()
-        prec = {'bf16': 0, 'x3': 1, 'f16': 2}[model.precision]
-        L = _lib.lib()
         with torch.cuda.device(device):
-            _lib.check(L.amtx_of_model_create(C.byref(self.handle), int(model.dim_in), int(model.in_channels),
-                                              int(model.model_complexity), int(model.profile.get_range_len()),
-                                              int(model.has_offsets), prec), 'amtx_of_model_create')
+            _lib.check(getattr(_lib.lib(), self.ABI + '_create')(C.byref(self.handle), *create_args), self.ABI + '_create')
         self.version = None
         self.workspace = None
+
+    def sync_weights(self, model):
+        items = [(k, v) for k, v in model.state_dict().items() if v.dtype.is_floating_point and not k.startswith('frontend.') and v.numel() > 0]
+        version = tuple((k, v._version, v.data_ptr()) for k, v in items)
+        if version == self.version:
+            return
+        if self.version is None or not self._resync_on_device(items):
+            # ONE device-to-host copy of all parameters and buffers (a copy per tensor is ~60 synchronisations per re-sync); the library
+            # packs from host memory
+            L = _lib.lib()
+            flat = torch.cat([v.detach().reshape(-1).to(torch.float32) for _, v in items]).cpu().numpy()
+            off = 0
+            for k, v in items:
+                n = v.numel()
+                _lib.check(getattr(L, self.ABI + '_set_tensor')(self.handle, k.encode(), _lib.ptr(flat[off:off + n]), n), self.ABI + '_set_tensor')
+                off += n
+            with torch.cuda.device(self.device):
+                _lib.check(getattr(L, self.ABI + '_finalize')(self.handle), self.ABI + '_finalize')
+        self.version = version
+
+    def _resync_on_device(self, items):
+        """A later weight version packed without leaving the GPU: True when done, False for the host path."""
+        return False
+
+    def _grow_workspace(self, need, device):
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = None
+            self.workspace = _lib.alloc_workspace(need, device)
+
+    def __del__(self):
+        try:
+            getattr(_lib.lib(), self.ABI + '_destroy')(self.handle)
+        except Exception:
+            pass
+
+
+class _OFEngine(_EngineBase):
+    """The Onsets & Frames engine (amtx_of_model)."""
+
+    ABI = 'amtx_of_model'
+
+    def __init__(self, model, device):
+        self.n_out = model.profile.get_range_len()
+        super().__init__(device, int(model.dim_in), int(model.in_channels), int(model.model_complexity), int(self.n_out),
+                         int(model.has_offsets), {'bf16': 0, 'x3': 1, 'f16': 2}[model.precision])
         self.device_sync = os.environ.get('AMTX_HOST_WEIGHT_SYNC') is None     # A/B switch: always pack on the host
         self.device_syncs = 0                            # re-syncs that stayed on the GPU (tests)
 
-    def sync_weights(self, model):
-        sd = model.state_dict()
-        version = tuple((k, v._version, v.data_ptr()) for k, v in sd.items() if v.dtype.is_floating_point)
-        if version == self.version:
-            return
-        L = _lib.lib()
-        items = [(k, v) for k, v in sd.items() if v.dtype.is_floating_point and not k.startswith('frontend.') and v.numel() > 0]
+    def _resync_on_device(self, items):
         # A RE-sync (validate() inside train() pays one at every checkpoint) stays on the GPU where the library can pack there: the
         # tensors are handed over as device pointers and folded / packed by kernels -- the same bits as the host path.
-        if self.version is not None and self.device_sync and all(v.is_cuda and v.device == torch.device(self.device) and v.dtype == torch.float32 for _, v in items):
-            keep = []                                   # channels-last convolution weights (the GPU training layout) go through a dense device copy
-            for k, v in items:
-                t = v.detach()
-                t = t if t.is_contiguous() else t.contiguous()
-                keep.append(t)
-                _lib.check(L.amtx_of_model_set_tensor_device(self.handle, k.encode(), _lib.ptr(t), t.numel()), 'amtx_of_model_set_tensor_device')
-            with torch.cuda.device(self.device):
-                rc = L.amtx_of_model_finalize_device(self.handle, _lib.current_stream(self.device))
-                if keep and rc == 0:
-                    torch.cuda.current_stream(self.device).synchronize()     # the borrowed copies may go once the pack kernels have read them
-            del keep
-            if rc == 0:
-                self.version = version
-                self.device_syncs += 1
-                return
-            if rc != _lib.ERR_UNSUPPORTED:
-                _lib.check(rc, 'amtx_of_model_finalize_device')
-            self.device_sync = False                    # this configuration packs on the host
-        # ONE device-to-host copy of all parameters and buffers (a copy per tensor is ~60 synchronisations per re-sync); the library packs
-        # from host memory
-        flat = torch.cat([v.detach().reshape(-1).to(torch.float32) for _, v in items]).cpu().numpy()
-        off = 0
+        if not (self.device_sync and all(v.is_cuda and v.device == torch.device(self.device) and v.dtype == torch.float32 for _, v in items)):
+            return False
+        L = _lib.lib()
+        keep = []                                   # channels-last convolution weights (the GPU training layout) go through a dense device copy
         for k, v in items:
-            n = v.numel()
-            arr = flat[off:off + n]
-            off += n
-            _lib.check(L.amtx_of_model_set_tensor(self.handle, k.encode(), _lib.ptr(arr), n), 'amtx_of_model_set_tensor')
+            t = v.detach()
+            t = t if t.is_contiguous() else t.contiguous()
+            keep.append(t)
+            _lib.check(L.amtx_of_model_set_tensor_device(self.handle, k.encode(), _lib.ptr(t), t.numel()), 'amtx_of_model_set_tensor_device')
         with torch.cuda.device(self.device):
-            _lib.check(L.amtx_of_model_finalize(self.handle), 'amtx_of_model_finalize')
-        self.version = version
+            rc = L.amtx_of_model_finalize_device(self.handle, _lib.current_stream(self.device))
+            if keep and rc == 0:
+                torch.cuda.current_stream(self.device).synchronize()     # the borrowed copies may go once the pack kernels have read them
+        del keep
+        if rc == 0:
+            self.device_syncs += 1
+            return True
+        if rc != _lib.ERR_UNSUPPORTED:
+            _lib.check(rc, 'amtx_of_model_finalize_device')
+        self.device_sync = False                    # this configuration packs on the host
+        return False
 
     def fuses_db_scale(self):
         return bool(_lib.lib().amtx_of_fuses_db_scale(self.handle))
@@ -432,10 +477,7 @@ class _OFEngine(object):
             feats = pending.power.unsqueeze(1)
         if not pending16:
             B, Cc, T, Fd = feats.shape
-        need = L.amtx_of_workspace_bytes(self.handle, B, T)
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = None
-            self.workspace = _lib.alloc_workspace(need, feats.device)
+        self._grow_workspace(L.amtx_of_workspace_bytes(self.handle, B, T), feats.device)
         n_out = self.n_out
         opts = dict(dtype=torch.float32, device=feats.device)
         onsets = torch.empty((B, n_out, T), **opts)
@@ -473,12 +515,6 @@ class _OFEngine(object):
                                          _lib.ptr(logits), _lib.current_stream(device)), 'amtx_of_offsets')
         return prob, logits
 
-    def __del__(self):
-        try:
-            _lib.lib().amtx_of_model_destroy(self.handle)
-        except Exception:
-            pass
-
 
 class OnsetsFrames(TranscriptionModel):
     """Onsets & Frames V1 (amt_tools/models/onsetsframes.py:17-196)."""
@@ -501,26 +537,9 @@ class OnsetsFrames(TranscriptionModel):
         self.dim_aj = 2 * dim_out
         self.adjoin = nn.Sequential(LanguageModel(self.dim_aj, self.dim_lm), LogisticBank(self.dim_lm, dim_out))
 
-    # ---- engine management (device handles never enter state_dict / pickles, SURVEY finding F11) ----
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_engine', None)
-        state.pop('_engine_out', None)
-        state.pop('_engine_offsets', None)
-        state.pop('_side_stream', None)
-        state.pop('_overlap_armed', None)
-        state.pop('_fb_last_forward', None)
-        state.pop('_overlap_latched_off', None)
-        return state
-
-    def _get_engine(self, device):
-        eng = self.__dict__.get('_engine')
-        if eng is None or eng.device != device:
-            eng = _OFEngine(self, device)
-            eng.n_out = self.profile.get_range_len()
-            self.__dict__['_engine'] = eng
-        eng.sync_weights(self)
-        return eng
+    _engine_class = _OFEngine
+    _transient = TranscriptionModel._transient + ('_engine_out', '_engine_offsets', '_side_stream', '_overlap_armed', '_fb_last_forward',
+                                                  '_overlap_latched_off')
 
     def pre_proc(self, batch):
         pending = self._deferred_scale(batch) if self.__dict__.get('_in_run_on_batch') else None
@@ -847,41 +866,18 @@ def tab_window_view(feats, frame_width=9):
     return dict(offset=off, num_windows=T, num_cols=ncols, strides=(sb, sc, sf, st))
 
 
-class _TabEngine(object):
-    """ctypes handle of an amtx_tab_model + its workspace, bound to one device."""
+class _TabEngine(_EngineBase):
+    """The TabCNN engine (amtx_tab_model)."""
 
+    ABI = 'amtx_tab_model'
     WORKSPACE_CAP = 1 << 30      # bytes: longer inputs run as several calls over independent chunks of windows (and of clips)
 
     def __init__(self, model, device):
-        self.device = device
-        self.handle = C.c_void_p()
-        L = _lib.lib()
-        with torch.cuda.device(device):
-            _lib.check(L.amtx_tab_model_create(C.byref(self.handle), int(model.dim_in), int(model.in_channels), int(model.model_complexity),
-                                               int(model.profile.get_num_dofs()), int(model.profile.num_pitches + 1),
-                                               {'bf16': 0, 'x3': 1}[model.precision]), 'amtx_tab_model_create')
         self.G = int(model.profile.get_num_dofs())
         self.C = int(model.profile.num_pitches + 1)
-        self.version = None
-        self.workspace = None
+        super().__init__(device, int(model.dim_in), int(model.in_channels), int(model.model_complexity), self.G, self.C,
+                         {'bf16': 0, 'x3': 1}[model.precision])
         self.forwards = 0                               # engine calls made (tests)
-
-    def sync_weights(self, model):
-        sd = model.state_dict()
-        items = [(k, v) for k, v in sd.items() if v.dtype.is_floating_point and not k.startswith('frontend.')]
-        version = tuple((k, v._version, v.data_ptr()) for k, v in items)
-        if version == self.version:
-            return
-        L = _lib.lib()
-        flat = torch.cat([v.detach().reshape(-1).to(torch.float32) for _, v in items]).cpu().numpy()   # one device-to-host copy
-        off = 0
-        for k, v in items:
-            n = v.numel()
-            _lib.check(L.amtx_tab_model_set_tensor(self.handle, k.encode(), _lib.ptr(flat[off:off + n]), n), 'amtx_tab_model_set_tensor')
-            off += n
-        with torch.cuda.device(self.device):
-            _lib.check(L.amtx_tab_model_finalize(self.handle), 'amtx_tab_model_finalize')
-        self.version = version
 
     def workspace_bytes(self, batch, num_windows):
         return int(_lib.lib().amtx_tab_workspace_bytes(self.handle, int(batch), int(num_windows)))
@@ -913,10 +909,7 @@ class _TabEngine(object):
         logits = torch.empty((B, T, G * Cn), dtype=torch.float32, device=feats.device)
         tab = torch.empty((B, G, T), dtype=torch.int64, device=feats.device)
         chunks = self._chunks(B, T)
-        need = max(self.workspace_bytes(b1 - b0, t1 - t0) for b0, b1, t0, t1 in chunks)
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = None
-            self.workspace = _lib.alloc_workspace(need, feats.device)
+        self._grow_workspace(max(self.workspace_bytes(b1 - b0, t1 - t0) for b0, b1, t0, t1 in chunks), feats.device)
         base = feats.data_ptr()                          # element (0, 0, 0, 0, 0): column 0 of clip 0's sequence
         esz = feats.element_size()
         with torch.cuda.device(feats.device):
@@ -933,12 +926,6 @@ class _TabEngine(object):
                     tab[b0:b1, :, t0:t1] = tb
         self.forwards += 1
         return logits, tab
-
-    def __del__(self):
-        try:
-            _lib.lib().amtx_tab_model_destroy(self.handle)
-        except Exception:
-            pass
 
 
 class TabCNN(TranscriptionModel):
@@ -981,12 +968,8 @@ class TabCNN(TranscriptionModel):
         self.dense = nn.Sequential(nn.Linear(self.conv_embedding_size, self.fc_embedding_size), nn.ReLU(), nn.Dropout(0.50),
                                    SoftmaxGroups(self.fc_embedding_size, self.profile.get_num_dofs(), self.profile.num_pitches + 1))
 
-    # ---- engine management (device handles never enter state_dict / pickles, SURVEY finding F11) ----
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_engine', None)
-        state.pop('_engine_tab', None)
-        return state
+    _engine_class = _TabEngine
+    _transient = TranscriptionModel._transient + ('_engine_tab',)
 
     def engine_unsupported(self):
         """Why the HIP engine does not build this configuration, or None when it does."""
@@ -1001,14 +984,6 @@ class TabCNN(TranscriptionModel):
         if C_ > 32 or G * C_ > 256:
             return f'num_classes={C_}, num_groups={G} (num_classes <= 32 and num_groups x num_classes <= 256 are built)'
         return None
-
-    def _get_engine(self, device):
-        eng = self.__dict__.get('_engine')
-        if eng is None or eng.device != device:
-            eng = _TabEngine(self, device)
-            self.__dict__['_engine'] = eng
-        eng.sync_weights(self)
-        return eng
 
     def _engine_view(self, feats):
         """The window view's geometry when this forward pass belongs to the HIP engine, else None."""

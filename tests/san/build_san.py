@@ -9,12 +9,13 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+from amt_tools_amd.build import F16_TWINS  # noqa: E402  (the files compiled a second time with -DAMTX_F16)
 CSRC = os.path.join(ROOT, 'amt_tools_amd', 'csrc')
 OUT = os.path.join(HERE, '_build')
 LIB = os.path.join(OUT, 'libamtx_san.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 SAN = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g', '-O1']
-F16_TWINS = ('conv.hip', 'convf.hip', 'convg.hip', 'gemm.hip', 'lstm.hip', 'pack.hip')
 
 
 def asan_runtime():
