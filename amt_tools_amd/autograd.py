@@ -375,7 +375,7 @@ class BCELogitsLossFunction(torch.autograd.Function):
         need_grad = logits.requires_grad
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         grad = torch.empty((B, T, K), dtype=torch.float32, device=x.device) if need_grad else None
-        ws = torch.empty(int(L.amtx_bce_logits_loss_workspace_bytes(B, T, K)), dtype=torch.uint8, device=x.device)
+        ws = _lib.alloc_workspace(int(L.amtx_bce_logits_loss_workspace_bytes(B, T, K)), x.device)
         with torch.cuda.device(x.device):
             _lib.check(L.amtx_bce_logits_loss(_lib.ptr(x), K, _lib.ptr(y), _lib.ptr(w), B, T, K, _lib.ptr(loss), _lib.ptr(grad),
                                               _lib.ptr(ws), ws.numel(), _lib.current_stream(x.device)), 'amtx_bce_logits_loss')
@@ -407,7 +407,7 @@ class BNReLUPoolFunction(torch.autograd.Function):
         Fo = F // 2 if pool else F
         y = torch.empty((B, Cc, T, Fo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         stats = torch.empty((4, Cc), dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(L.amtx_bn_train_workspace_bytes(Cc)), dtype=torch.uint8, device=x.device)
+        ws = _lib.alloc_workspace(int(L.amtx_bn_train_workspace_bytes(Cc)), x.device)
         with torch.cuda.device(x.device):
             _lib.check(L.amtx_bn_relu_pool_train_fwd(_lib.ptr(x), B * T, F, Cc, int(pool), _lib.ptr(weight), _lib.ptr(bias), float(eps),
                                                      float(momentum), _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(y),

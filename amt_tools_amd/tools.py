@@ -253,7 +253,7 @@ def rms_norm_batch(audio):
     audio = audio.contiguous()
     B, N = audio.shape
     L = _lib.lib()
-    ws = torch.empty(int(L.amtx_rms_norm_workspace_bytes(B, N)), dtype=torch.uint8, device=audio.device)
+    ws = _lib.alloc_workspace(int(L.amtx_rms_norm_workspace_bytes(B, N)), audio.device)
     out = torch.empty_like(audio)
     with torch.cuda.device(audio.device):
         # a one-clip batch may carry any stride in its size-1 dimension (numpy's x[None] has 0): the rows are N apart by definition then

@@ -18,6 +18,22 @@ def guards(monkeypatch):
     yield
 
 
+@pytest.fixture
+def handed_out(guards, monkeypatch):
+    """Every workspace _lib.alloc_workspace hands out during the test, kept alive: the per-call scratch buffers (BatchNorm partials, the
+    BCE loss partials, rms_norm's chunk sums) live only for one call and are reachable no other way."""
+    kept = []
+    real = _lib.alloc_workspace
+
+    def alloc_workspace(nbytes, device):
+        ws = real(nbytes, device)
+        kept.append(ws)
+        return ws
+
+    monkeypatch.setattr(_lib, 'alloc_workspace', alloc_workspace)
+    return kept
+
+
 @pytest.mark.parametrize('cls,mc,ch,dim_in,precision', [('OnsetsFrames', 2, 1, 229, 'bf16'), ('OnsetsFrames', 2, 1, 229, 'x3'), ('OnsetsFrames', 2, 1, 229, 'f16'),
                                                         ('OnsetsFrames2', 3, 1, 229, 'bf16'), ('OnsetsFrames2', 3, 1, 229, 'f16'), ('OnsetsFrames', 2, 6, 72, 'bf16'), ('OnsetsFrames', 2, 6, 72, 'f16'), ('OnsetsFrames', 2, 1, 54, 'bf16'),
                                                         ('OnsetsFrames', 2, 1, 8, 'x3'),
@@ -43,7 +59,7 @@ def test_engine_workspace_guard_bands_survive_ragged_forwards(guards, cls, mc, c
         assert _lib.guards_intact(eng.workspace), (cls, precision, B, T)
 
 
-def test_power_path_and_cqt_workspace_guard_bands(guards):
+def test_power_path_and_cqt_workspace_guard_bands(handed_out):
     from amt_tools_amd.features import MelSpec, HCQT
     import amt_tools_amd.models as M
     mod = MelSpec(sample_rate=22050, hop_length=512, n_mels=229, n_fft=2048)
@@ -67,10 +83,18 @@ def test_power_path_and_cqt_workspace_guard_bands(guards):
         torch.cuda.synchronize()
         ws = cq.__dict__.get('_workspace')
         assert ws is not None and ws._base is not None and _lib.guards_intact(ws), (B, n)
+    # rms_norm's per-call chunk sums (tools.rms_norm_batch)
+    for B, n in ((1, 1), (3, 22050), (2, 70001)):
+        before = len(handed_out)
+        tools.rms_norm_batch(torch.from_numpy(np.stack([synth_clip(i, num_samples=n) for i in range(B)])).cuda())
+        torch.cuda.synchronize()
+        assert len(handed_out) == before + 1 and handed_out[-1]._base is not None and _lib.guards_intact(handed_out[-1]), (B, n)
+    assert all(_lib.guards_intact(ws) for ws in handed_out)
 
 
-def test_training_scratch_guard_bands(guards):
-    """One training step (fwd + bwd) of both model families on the HIP autograd kernels with the per-stream scratch buffer guarded."""
+def test_training_scratch_guard_bands(handed_out):
+    """One training step (fwd + bwd) of both model families on the HIP autograd kernels with the per-stream scratch buffer guarded, and
+    the per-call scratch of the BatchNorm passes and of the BCE loss with it."""
     import amt_tools_amd.models as M
     from amt_tools_amd import autograd
     from amt_tools_amd.synth import synth_labels
@@ -90,5 +114,11 @@ def test_training_scratch_guard_bands(guards):
         torch.cuda.synchronize()
     assert autograd._WS, 'the HIP autograd path did not run'
     for ws in autograd._WS.values():
+        assert ws._base is not None and _lib.guards_intact(ws)
+    shared = {ws.data_ptr() for ws in autograd._WS.values()}
+    per_call = [ws for ws in handed_out if ws.data_ptr() not in shared]
+    # 3 BatchNorm stages per acoustic model (2 + 3 of them) and one loss per head (2 + 3), each with a buffer of its own
+    assert len(per_call) >= 3 * 5 + 5, len(per_call)
+    for ws in per_call:
         assert ws._base is not None and _lib.guards_intact(ws)
     autograd._WS.clear()
