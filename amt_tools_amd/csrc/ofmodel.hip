@@ -64,6 +64,61 @@ const KernelSet kKernelsF16 = {
     amtx_launch_conv_stack_f16, amtx_launch_gemm_f16, amtx_launch_bilstm_f16};
 #endif
 
+// Which convolution kernels a model runs.  make_conv_plan decides it once, when the model is created; resolve_conv adds what depends on
+// the call.  Packing, workspace carving, the forward pass and the query entry points only read the two (table: DESIGN.md).
+enum ConvFamily { K_CONV1,      // conv.hip's separate first conv (fp32 weights): only where the first conv cannot be fused into conv2
+                  K_CONV,       // conv.hip: 32 / 32 / 64 channels, weights stationary in registers (two planes: with convx.hip behind the same launcher)
+                  K_CONVG };    // convg.hip: the general kernel, weights in LDS
+struct ConvLayer { const char* name; int c_in, c_out; ConvFamily fam; size_t frag_per; };   // frag_per: packed 16-bit weight elements per head
+
+// the A/B switches of this file (switch table), all read here, once per model
+struct ConvSwitches { bool no_convg_mc2, no_conv_fuse, x3_no_split, no_convx12m, rowmajor_a3, no_roll_epilogue; };
+ConvSwitches switches_from_env() {
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    return {on("AMTX_NO_CONVG_MC2"), on("AMTX_NO_CONV_FUSE"), on("AMTX_X3_NO_SPLIT"), on("AMTX_NO_CONVX12M"), on("AMTX_OF_ROWMAJOR_A3"), on("AMTX_OF_NO_ROLL_EPILOGUE")};
+}
+
+struct ConvPlan {
+    ConvLayer layer[3];         // layer1 .. layer3 of every acoustic head
+    bool conv1_fused;           // the first conv runs inside the conv2 kernel (layer[0].fam == layer[1].fam), a1 never exists
+    bool stack;                 // eligible for layer1 -> layer2 -> layer3 in one kernel (convf.hip); batches that fill the chip with strips take it
+    bool two_plane_acts;        // x3 (round 5): activations in HBM as two 16-bit planes (AMTX_T_SPLIT) from conv2 on; the GEMMs DMA them straight into LDS
+    bool convx12; size_t c2x_per;   // round 6: conv1 + conv2 from two-plane 16-bit features on convx.hip; it reads a second copy of layer2's weights (conv2_wx, c2x_per per head)
+    bool rowmajor_a3, no_roll_epilogue;   // A/B: the fused stack's output row-major; piano rolls / refinement input from separate kernels
+    bool device_resync;         // amtx_of_model_finalize_device has a packer for every layer
+    int fuses_db_scale, takes_feats16;   // the answers of amtx_of_fuses_db_scale / amtx_of_takes_feats16 once the model is finalized (feats16 = 2:
+                                         // convx12's two planes [2][B][T][F][8], the lo plane B T F 8 elements behind the hi plane, amtx_cqt_forward16_split)
+};
+
+ConvPlan make_conv_plan(int in_channels, int model_complexity, int precision, const ConvSwitches& sw) {
+    const int ic = in_channels, nf1 = 16 * model_complexity, nf3 = 2 * nf1, pl = precision == AMTX_PREC_X3 ? 2 : 1;
+    ConvPlan p{};
+    // channel counts other than 32 / 32 / 64: convg.hip throughout.  32 / 32 / 64 with more than one input channel (HCQT): conv.hip's fused first
+    // conv runs its 9 c_in taps as four legacy 16-deep MFMA steps and stages c_in x 20 x (columns + 4) feature values per tile through a
+    // register-starved loop (3.6 ms per 512 HCQT clips); convg.hip's fused first conv (two 32-deep steps, weights in LDS) is the faster one there
+    // (2.7 ms).  With one input channel conv.hip stays far ahead: 5.6 vs 9.7 ms per 1024 mel clips (weights stationary in registers, 18 x 46 tiles).
+    const ConvFamily f3 = nf1 != 32 ? K_CONVG : K_CONV;
+    const bool g_fuse1 = amtx_conv3x3_gen_can_fuse1(ic, nf1, nf1, pl);
+    const ConvFamily f2 = f3 == K_CONVG || (ic > 1 && !sw.no_convg_mc2 && g_fuse1) ? K_CONVG : K_CONV;
+    p.conv1_fused = f2 == K_CONVG ? g_fuse1 : 9 * ic <= 64;
+    auto frag3x3 = [pl](ConvFamily f, int c_in, int c_out) { return f == K_CONVG ? amtx_conv3x3_gen_wfrag_elems(c_in, c_out, pl) : amtx_conv3x3_wfrag_elems(c_out, pl); };
+    p.layer[0] = {"layer1", ic, nf1, p.conv1_fused ? f2 : K_CONV1,
+                  !p.conv1_fused ? 0 : f2 == K_CONVG ? amtx_conv1g_wfrag_elems(ic, nf1, pl) : amtx_conv1_wfrag_elems(ic, pl)};
+    p.layer[1] = {"layer2", nf1, nf1, f2, frag3x3(f2, nf1, nf1)};
+    p.layer[2] = {"layer3", nf1, nf3, f3, frag3x3(f3, nf1, nf3)};
+    p.stack = f2 == K_CONV && p.conv1_fused && ic == 1 && pl == 1 && !sw.no_conv_fuse;
+    // one input channel: conv.hip / convx.hip write the planes; 2 .. 7 input channels at 32 / 32 / 64 channels -- HCQT --: convg.hip's
+    // two-plane kernel writes a2 as planes, convx.hip's conv3 and the GEMMs behind it are the same
+    p.two_plane_acts = pl == 2 && f3 == K_CONV && p.conv1_fused && !sw.x3_no_split && (f2 == K_CONV ? ic == 1 : ic > 1 && (9 * ic + 31) / 32 <= 2);
+    p.convx12 = p.two_plane_acts && f2 == K_CONVG && ic >= 2 && ic <= 8 && amtx_conv1g_tapk(ic, 2) && !sw.no_convx12m;
+    p.c2x_per = frag3x3(K_CONV, nf1, nf1);
+    p.rowmajor_a3 = sw.rowmajor_a3; p.no_roll_epilogue = sw.no_roll_epilogue;
+    p.device_resync = f2 == K_CONVG || ic == 1;          // no device packer for conv.hip's multi-channel first conv (AMTX_NO_CONVG_MC2, or 9 and more channels)
+    p.fuses_db_scale = p.conv1_fused && f2 == K_CONV && ic == 1;
+    p.takes_feats16 = !(p.conv1_fused && f2 == K_CONVG && precision != AMTX_PREC_F16) ? 0 : p.convx12 ? 2 : pl == 1 && nf1 == 32 && amtx_conv1g_tapk(ic, pl);
+    return p;
+}
+
 }  // namespace
 
 struct amtx_of_model {
@@ -74,8 +129,8 @@ struct amtx_of_model {
     int nf1, nf2, nf3, dim_am, dim_lm, fq, kfc;
     int kfc_pad;                               // fc1's K rounded up to the DMA GEMM's 64-deep k-tile (rows of a3 are this long)
     int hid, xw;                               // LSTM hidden size per direction, width of an x-projection row (2 dirs x 4 gates x hid)
-    bool gen_conv = false;                     // channel counts other than 32/32/64: convg.hip (weights in LDS) instead of conv.hip
-    bool gen_conv2 = false;                    // conv2 (+ fused first conv) through convg.hip: gen_conv, or 32 -> 32 with a multi-channel input
+    size_t hh_elems;                           // packed W_hh elements of one BiLSTM
+    ConvPlan plan;                             // which convolution kernels this model runs
     int n_heads;                               // acoustic heads: onset, (offset), pitch
     int n_rec;                                 // recurrent heads feeding the joint: onset, (offset)
     std::vector<std::string> head_names;       // state_dict prefixes of the acoustic models, group order
@@ -84,13 +139,9 @@ struct amtx_of_model {
     bool finalized = false;
     bool packed_once = false;                  // the packed buffers hold a weight version that forwards may still be reading
     // packed device weights (group-major)
-    DevBuf conv1_w, conv1_s, conv1_frag, conv2_w, conv2_s, conv3_w, conv3_s;
-    DevBuf conv2_wx;                           // x12m: layer2's weights a second time, in conv.hip's fragment order (convx12_kernel<true> reads them; conv2_w is convg.hip's)
-    bool x12m = false;                         // round 6: two planes, 2 .. 8 input channels, 32 / 32 channels: conv1 + conv2 from two-plane 16-bit features on convx.hip
-    bool fuse_conv1 = false;                   // first conv computed inside the conv2 kernel (9*C_in <= 64)
-    bool fuse_stack = false;                   // layer1 -> layer2 -> layer3 in one kernel (convf.hip) for batches that fill the chip with strips
-    bool split_acts = false;                   // x3 (round 5): the dense layers' activations live in HBM as two 16-bit planes (AMTX_T_SPLIT), written by
-                                               // the producing kernel's epilogue; the GEMMs DMA them straight into LDS (gemm_split_kernel)
+    DevBuf conv_w[3], conv_s[3];               // per conv layer: fragments (layer1: only when fused into conv2), fp32 shifts
+    DevBuf conv1_w;                            // layer1's weights in fp32, BatchNorm scale folded in: the separate first conv reads them
+    DevBuf conv2_wx;                           // convx12: layer2's weights a second time, in conv.hip's fragment order (convx12_kernel<true> reads them)
     LinearPack fc1;                            // groups = n_heads
     LinearPack rec_ih;                         // groups = n_rec, N = 1024
     DevBuf rec_hh;                             // groups = n_rec
@@ -168,7 +219,7 @@ int pack_lstm(amtx_of_model* m, const std::string& prefix, int dim_in, std::vect
     memcpy(w_ih.data() + (size_t)G * dim_in, wib, sizeof(float) * G * dim_in);
     b.resize(2 * G);
     for (int i = 0; i < G; ++i) { b[i] = bif[i] + bhf[i]; b[G + i] = bib[i] + bhb[i]; }
-    hh.resize(amtx_bilstm_wfrag_elems_h(H, m->planes));
+    hh.resize(m->hh_elems);
     m->k->bilstm_pack_host_h(whf, whb, H, m->planes, hh.data());
     return AMTX_OK;
 }
@@ -178,21 +229,36 @@ struct Workspace {
     size_t total;
 };
 
+// What one call launches for conv1 + conv2 (conv3 follows on layer3's family unless the fused stack has covered it).  carve and the
+// forward pass both ask here, so the workspace and the launches cannot disagree.
+enum ConvPath { PATH_STACK,                  // convf.hip: all three layers in one kernel, neither intermediate map reaches HBM
+                PATH_CONVX12,                   // convx.hip: conv1 + conv2 from two-plane 16-bit features
+                PATH_CONV12, PATH_CONVG12,   // conv1 inside the conv2 kernel of conv.hip / convg.hip
+                PATH_CONV1 };                // conv.hip's separate first conv, then conv2 on layer2's family
+struct ConvCall { ConvPath path; bool a2_in_hbm; int64_t a3_plane; };
+
+ConvCall resolve_conv(const amtx_of_model* m, int B, int T, bool feats16) {
+    const ConvPlan& p = m->plan;
+    if (p.stack && amtx_conv_stack_fused_ok(B, T, m->dim_in, m->n_heads))
+        // output in planes of 64 channels per pooled frequency column ([F / 4][B T][64]): a k-tile of the GEMMs that read it is contiguous memory
+        return {PATH_STACK, false, p.rowmajor_a3 ? 0 : (int64_t)B * T * 64};
+    return {feats16 && p.convx12 ? PATH_CONVX12 : !p.conv1_fused ? PATH_CONV1 : p.layer[1].fam == K_CONVG ? PATH_CONVG12 : PATH_CONV12, true, 0};
+}
+
 Workspace carve(const amtx_of_model* m, int B, int T, char* base) {
     Workspace w;
     const size_t es = amtx_tsize(m->act_type);
     const size_t BT = (size_t)B * T;
     const int F = m->dim_in, F2 = F / 2;
     WorkspaceCarver ws{base};
-    w.a1 = ws.take(m->fuse_conv1 ? 256 : BT * F * m->nf1 * es * m->n_heads);
-    // the 32-channel map behind layer2 only exists in HBM on the two-kernel path
-    w.a2 = ws.take(m->fuse_stack && amtx_conv_stack_fused_ok(B, T, F, m->n_heads) ? 256 : BT * F2 * m->nf2 * es * m->n_heads);
+    w.a1 = ws.take(m->plan.conv1_fused ? 256 : BT * F * m->nf1 * es * m->n_heads);
+    w.a2 = ws.take(resolve_conv(m, B, T, false).a2_in_hbm ? BT * F2 * m->nf2 * es * m->n_heads : 256);
     w.a3 = ws.take(BT * m->kfc_pad * es * m->n_heads);
     w.e = ws.take(BT * m->dim_am * es * m->n_heads);
     w.xp = ws.take(BT * m->xw * es * m->n_rec);
     w.l1 = ws.take(BT * m->dim_lm * es * m->n_rec);
     w.joint = ws.take(BT * m->dim_aj * sizeof(float));
-    w.joint16 = ws.take(BT * (size_t)((m->dim_aj + 63) / 64 * 64) * 2 * (m->split_acts ? 2 : 1));   // bf16 copy (two planes with split_acts), K padded to the GEMM's 64-deep k-tile
+    w.joint16 = ws.take(BT * (size_t)((m->dim_aj + 63) / 64 * 64) * 2 * (m->plan.two_plane_acts ? 2 : 1));   // bf16 copy (two planes with two_plane_acts), K padded to the GEMM's 64-deep k-tile
     w.xp2 = ws.take(BT * m->xw * es);
     w.l2 = ws.take(BT * m->dim_lm * es);
     w.mp = ws.take(BT * m->n_out * sizeof(float));
@@ -241,36 +307,21 @@ extern "C" int amtx_of_model_create(amtx_of_model** out, int dim_in, int in_chan
     m->kfc = m->nf3 * m->fq;
     m->kfc_pad = (m->kfc + 63) / 64 * 64;
     m->hid = m->dim_lm / 2; m->xw = 8 * m->hid;
-    m->gen_conv = m->nf1 != 32;
-    // 32/32/64 channels with more than one input channel (HCQT): conv.hip's fused first conv runs its 9 c_in taps as four legacy
-    // 16-deep MFMA steps and stages c_in x 20 x (columns + 4) feature values per tile through a register-starved loop (3.6 ms per
-    // 512 HCQT clips); convg.hip's fused first conv (two 32-deep steps, weights in LDS) is the faster one there (2.7 ms).  With one
-    // input channel conv.hip stays far ahead: 5.6 vs 9.7 ms per 1024 mel clips (weights stationary in registers, 18 x 46 tiles).
-    m->gen_conv2 = m->gen_conv || (in_channels > 1 && getenv("AMTX_NO_CONVG_MC2") == nullptr && amtx_conv3x3_gen_can_fuse1(in_channels, m->nf1, m->nf2, m->planes));
+    m->hh_elems = amtx_bilstm_wfrag_elems_h(m->hid, m->planes);
+    m->plan = make_conv_plan(in_channels, model_complexity, precision, switches_from_env());
     m->head_names = {"onset_head"};
     if (has_offsets) m->head_names.push_back("offset_head");
     m->n_rec = (int)m->head_names.size();
     m->head_names.push_back("pitch_head");
     m->n_heads = (int)m->head_names.size();
     m->dim_aj = (m->n_rec + 1) * n_out;
-    m->fuse_conv1 = m->gen_conv2 ? amtx_conv3x3_gen_can_fuse1(in_channels, m->nf1, m->nf2, m->planes) : (9 * in_channels <= 64);
-    // A/B switch: AMTX_NO_CONV_FUSE=1 keeps conv.hip's two kernels (conv1+conv2, conv3) at every batch size
-    m->fuse_stack = !m->gen_conv && !m->gen_conv2 && m->fuse_conv1 && in_channels == 1 && m->planes == 1 && getenv("AMTX_NO_CONV_FUSE") == nullptr;
-    // A/B switch: AMTX_X3_NO_SPLIT=1 keeps fp32 activations between the two-plane kernels (round 4's data path)
-    // (one input channel: conv.hip / convx.hip write the planes; 2 .. 7 input channels at 32 / 32 / 64 channels -- HCQT --: convg.hip's two-plane
-    // kernel writes a2 as planes, convx.hip's conv3 and the GEMMs behind it are the same)
-    m->split_acts = m->planes == 2 && !m->gen_conv && m->fuse_conv1 && getenv("AMTX_X3_NO_SPLIT") == nullptr &&
-                    ((!m->gen_conv2 && in_channels == 1) || (m->gen_conv2 && in_channels > 1 && (9 * in_channels + 31) / 32 <= 2));
-    // A/B switch: AMTX_NO_CONVX12M=1 keeps convg.hip's two-plane kernel (fp32 features) for the multi-channel first conv
-    m->x12m = m->split_acts && m->gen_conv2 && in_channels >= 2 && in_channels <= 8 && m->nf1 == 32 && m->nf2 == 32 && amtx_conv1g_tapk(in_channels, 2) &&
-              getenv("AMTX_NO_CONVX12M") == nullptr;
     *out = m;
     return AMTX_OK;
 }
 
 extern "C" int amtx_of_model_destroy(amtx_of_model* m) {
     if (!m) return AMTX_OK;
-    DevBuf* bufs[] = {&m->conv1_w, &m->conv1_s, &m->conv1_frag, &m->conv2_w, &m->conv2_wx, &m->conv2_s, &m->conv3_w, &m->conv3_s, &m->fc1.w, &m->fc1.b,
+    DevBuf* bufs[] = {&m->conv1_w, &m->conv_w[0], &m->conv_w[1], &m->conv_w[2], &m->conv_s[0], &m->conv_s[1], &m->conv_s[2], &m->conv2_wx, &m->fc1.w, &m->fc1.b,
                       &m->rec_ih.w, &m->rec_ih.b, &m->rec_hh, &m->rec_out.w, &m->rec_out.b, &m->pitch_out.w, &m->pitch_out.b,
                       &m->adj_ih.w, &m->adj_ih.b, &m->adj_hh, &m->adj_out.w, &m->adj_out.b, &m->pack_scratch};
     for (DevBuf* b : bufs) b->release();
@@ -291,52 +342,39 @@ extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
         int qrc = amtx_quiesce_before_resync(m->packed_once);
         if (qrc != AMTX_OK) return qrc;
     }
-    const int nh = m->n_heads;
-    // ---- acoustic heads
-    std::vector<float> c1w((size_t)nh * m->nf1 * m->in_channels * 9), c1s((size_t)nh * m->nf1);
-    m->fuse_conv1 = m->gen_conv2 ? amtx_conv3x3_gen_can_fuse1(m->in_channels, m->nf1, m->nf2, m->planes) : (9 * m->in_channels <= 64);
-    const size_t c1f_per = m->gen_conv2 ? amtx_conv1g_wfrag_elems(m->in_channels, m->nf1, m->planes) : amtx_conv1_wfrag_elems(m->in_channels, m->planes);
-    std::vector<bf16_t> c1f(m->fuse_conv1 ? c1f_per * nh : 0);
-    const size_t c2w_per = m->gen_conv2 ? amtx_conv3x3_gen_wfrag_elems(m->nf1, m->nf2, m->planes) : amtx_conv3x3_wfrag_elems(m->nf2, m->planes);
-    const size_t c3w_per = m->gen_conv ? amtx_conv3x3_gen_wfrag_elems(m->nf2, m->nf3, m->planes) : amtx_conv3x3_wfrag_elems(m->nf3, m->planes);
-    if (m->gen_conv && (!amtx_conv3x3_gen_ntc(m->nf1, m->nf2) || !amtx_conv3x3_gen_ntc(m->nf2, m->nf3))) {
+    const int nh = m->n_heads, ic = m->in_channels;
+    const ConvPlan& p = m->plan;
+    if (p.layer[2].fam == K_CONVG && (!amtx_conv3x3_gen_ntc(m->nf1, m->nf2) || !amtx_conv3x3_gen_ntc(m->nf2, m->nf3))) {
         amtx_set_error("of_model: no convolution kernel for %d -> %d -> %d channels", m->nf1, m->nf2, m->nf3);
         return AMTX_ERR_UNSUPPORTED;
     }
-    std::vector<bf16_t> c2w(c2w_per * nh), c3w(c3w_per * nh);
-    const size_t c2x_per = amtx_conv3x3_wfrag_elems(m->nf2, m->planes);
-    std::vector<bf16_t> c2x(m->x12m ? c2x_per * nh : 0);
-    std::vector<float> c2s((size_t)nh * m->nf2), c3s((size_t)nh * m->nf3);
+    // ---- acoustic heads
+    std::vector<float> c1w((size_t)nh * m->nf1 * ic * 9), cs[3];
+    std::vector<bf16_t> cw[3], c2x(p.convx12 ? p.c2x_per * nh : 0);
+    for (int l = 0; l < 3; ++l) { cw[l].resize(p.layer[l].frag_per * nh); cs[l].resize((size_t)nh * p.layer[l].c_out); }
     std::vector<std::vector<float>> fcw(nh), fcb(nh);
     for (int h = 0; h < nh; ++h) {
         const std::string am = m->head_names[h] + ".0";
-        std::vector<float> scale, shift;
         const float* w;
-        int rc = fold_bn(m, am + ".layer1.0", am + ".layer1.1", m->nf1, scale, shift);
-        if (rc != AMTX_OK) return rc;
-        NEED(am + ".layer1.0.weight", (size_t)m->nf1 * m->in_channels * 9, w);
-        for (int co = 0; co < m->nf1; ++co)
-            for (int i = 0; i < m->in_channels * 9; ++i)
-                c1w[((size_t)h * m->nf1 + co) * m->in_channels * 9 + i] = w[(size_t)co * m->in_channels * 9 + i] * scale[co];
-        memcpy(c1s.data() + (size_t)h * m->nf1, shift.data(), sizeof(float) * m->nf1);
-        if (m->fuse_conv1 && m->gen_conv2) m->k->conv1g_pack_host(w, scale.data(), m->in_channels, m->nf1, m->planes, c1f.data() + c1f_per * h);
-        else if (m->fuse_conv1) m->k->conv1_pack_host(w, scale.data(), m->in_channels, m->planes, c1f.data() + c1f_per * h);
-
-        rc = fold_bn(m, am + ".layer2.0", am + ".layer2.1", m->nf2, scale, shift);
-        if (rc != AMTX_OK) return rc;
-        NEED(am + ".layer2.0.weight", (size_t)m->nf2 * m->nf1 * 9, w);
-        if (m->gen_conv2) m->k->conv3x3_gen_pack_host(w, scale.data(), m->nf1, m->nf2, m->planes, c2w.data() + c2w_per * h);
-        else m->k->conv3x3_pack_host(w, scale.data(), m->nf2, m->planes, c2w.data() + c2w_per * h);
-        if (m->x12m) amtx_conv3x3_pack_host(w, scale.data(), m->nf2, m->planes, c2x.data() + c2x_per * h);
-        memcpy(c2s.data() + (size_t)h * m->nf2, shift.data(), sizeof(float) * m->nf2);
-
-        rc = fold_bn(m, am + ".layer3.0", am + ".layer3.1", m->nf3, scale, shift);
-        if (rc != AMTX_OK) return rc;
-        NEED(am + ".layer3.0.weight", (size_t)m->nf3 * m->nf2 * 9, w);
-        if (m->gen_conv) m->k->conv3x3_gen_pack_host(w, scale.data(), m->nf2, m->nf3, m->planes, c3w.data() + c3w_per * h);
-        else m->k->conv3x3_pack_host(w, scale.data(), m->nf3, m->planes, c3w.data() + c3w_per * h);
-        memcpy(c3s.data() + (size_t)h * m->nf3, shift.data(), sizeof(float) * m->nf3);
-
+        for (int l = 0; l < 3; ++l) {
+            // Conv + eval-mode BatchNorm: the scale goes into the packed weights, the shift stays fp32
+            const ConvLayer& y = p.layer[l];
+            const std::string conv = am + "." + y.name + ".0";
+            std::vector<float> scale, shift;
+            int rc = fold_bn(m, conv, am + "." + y.name + ".1", y.c_out, scale, shift);
+            if (rc != AMTX_OK) return rc;
+            NEED(conv + ".weight", (size_t)y.c_out * y.c_in * 9, w);
+            memcpy(cs[l].data() + (size_t)h * y.c_out, shift.data(), sizeof(float) * y.c_out);
+            bf16_t* frag = cw[l].data() + y.frag_per * h;
+            if (l == 0) {     // the fp32 copy feeds only the separate first conv
+                for (int co = 0; co < y.c_out; ++co)
+                    for (int i = 0; i < ic * 9; ++i) c1w[((size_t)h * y.c_out + co) * ic * 9 + i] = w[(size_t)co * ic * 9 + i] * scale[co];
+                if (y.fam == K_CONVG) m->k->conv1g_pack_host(w, scale.data(), ic, y.c_out, m->planes, frag);
+                else if (y.fam == K_CONV) m->k->conv1_pack_host(w, scale.data(), ic, m->planes, frag);
+            } else if (y.fam == K_CONVG) m->k->conv3x3_gen_pack_host(w, scale.data(), y.c_in, y.c_out, m->planes, frag);
+            else m->k->conv3x3_pack_host(w, scale.data(), y.c_out, m->planes, frag);
+            if (l == 1 && p.convx12) m->k->conv3x3_pack_host(w, scale.data(), y.c_out, m->planes, c2x.data() + p.c2x_per * h);
+        }
         // fc1: reference column index c*fq + f  ->  ours f*nf3 + c
         const float* fb;
         NEED(am + ".fc1.0.weight", (size_t)m->dim_am * m->kfc, w);
@@ -349,14 +387,13 @@ extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
         fcb[h].assign(fb, fb + m->dim_am);
     }
     int rc;
-    if ((rc = m->conv1_w.upload(c1w.data(), c1w.size() * 4)) != AMTX_OK) return rc;
-    if ((rc = m->conv1_s.upload(c1s.data(), c1s.size() * 4)) != AMTX_OK) return rc;
-    if (m->fuse_conv1 && (rc = m->conv1_frag.upload(c1f.data(), c1f.size() * 2)) != AMTX_OK) return rc;
-    if ((rc = m->conv2_w.upload(c2w.data(), c2w.size() * 2)) != AMTX_OK) return rc;
-    if (m->x12m && (rc = m->conv2_wx.upload(c2x.data(), c2x.size() * 2)) != AMTX_OK) return rc;
-    if ((rc = m->conv2_s.upload(c2s.data(), c2s.size() * 4)) != AMTX_OK) return rc;
-    if ((rc = m->conv3_w.upload(c3w.data(), c3w.size() * 2)) != AMTX_OK) return rc;
-    if ((rc = m->conv3_s.upload(c3s.data(), c3s.size() * 4)) != AMTX_OK) return rc;
+    if ((rc = m->conv1_w.upload(c1w.data(), c1w.size() * 4)) != AMTX_OK || (rc = m->conv_s[0].upload(cs[0].data(), cs[0].size() * 4)) != AMTX_OK) return rc;
+    if (p.conv1_fused && (rc = m->conv_w[0].upload(cw[0].data(), cw[0].size() * 2)) != AMTX_OK) return rc;
+    for (int l = 1; l < 3; ++l) {
+        if ((rc = m->conv_w[l].upload(cw[l].data(), cw[l].size() * 2)) != AMTX_OK) return rc;
+        if (l == 1 && p.convx12 && (rc = m->conv2_wx.upload(c2x.data(), c2x.size() * 2)) != AMTX_OK) return rc;
+        if ((rc = m->conv_s[l].upload(cs[l].data(), cs[l].size() * 4)) != AMTX_OK) return rc;
+    }
     {
         // fc1 of the RECURRENT heads only.  The pitch head's fc1 feeds its LogisticBank directly (AcousticModel.fc1 is Linear +
         // Dropout, no activation: onsetsframes.py:422-427, then models/common.py:539), so in eval mode the two Linear layers are one:
@@ -444,27 +481,20 @@ extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
 // Weight RE-SYNC without leaving the GPU.  After one host-side amtx_of_model_finalize (which sizes and allocates every packed
 // buffer), later weight versions can be handed over as device pointers under the same state_dict names and packed by the kernels of
 // pack.hip -- the host packers' arithmetic and layouts, bit for bit.  Built for every configuration the engine runs (the engine
-// validates at every checkpoint of train.py, amt_tools/train.py:183-189): model_complexity 2, 3 and 4, one or several input channels,
-// any precision -- except a multi-channel first conv on conv.hip's kernel (only reachable with AMTX_NO_CONVG_MC2), which answers
-// AMTX_ERR_UNSUPPORTED and keeps the host path.
+// validates at every checkpoint of train.py, amt_tools/train.py:183-189): model_complexity 2 .. 5, one or several input channels,
+// any precision -- except a multi-channel first conv on conv.hip's kernel (AMTX_NO_CONVG_MC2, or 9 and more input channels at 32 / 32 / 64; ConvPlan::device_resync),
+// which answers AMTX_ERR_UNSUPPORTED and keeps the host path.
 extern "C" int amtx_of_model_set_tensor_device(amtx_of_model* m, const char* name, const float* device_data, int64_t numel) {
     AMTX_REQUIRE(m && name && device_data && numel > 0, "amtx_of_model_set_tensor_device: bad argument");
     m->store.set_device(name, device_data, numel);
     return AMTX_OK;
 }
 
-namespace {
 #define NEED_DEV(name, numel, ptr)                                     \
     do {                                                               \
         int _rc = m->store.need_device(name, numel, &(ptr));           \
         if (_rc != AMTX_OK) return _rc;                                \
     } while (0)
-#define PACK_TRY(expr)                                                 \
-    do {                                                               \
-        int _rc = (expr);                                              \
-        if (_rc != AMTX_OK) return _rc;                                \
-    } while (0)
-}  // namespace
 
 // `dry`: look up and size-check every tensor, launch nothing -- amtx_of_model_finalize_device runs this pass first, so a missing or
 // mis-sized tensor is reported before a single packed buffer has been touched (the buffers never end up half new, half old).
@@ -477,7 +507,7 @@ extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
         ~Clear() { m->store.device.clear(); }
     } clear{m};
     AMTX_REQUIRE(m->finalized, "amtx_of_model_finalize_device: the first sync goes through amtx_of_model_finalize (it allocates the packed buffers)");
-    if (!m->gen_conv2 && m->in_channels != 1) {
+    if (!m->plan.device_resync) {
         amtx_set_error("amtx_of_model_finalize_device: no device packer for conv.hip's multi-channel first conv; use amtx_of_model_finalize");
         return AMTX_ERR_UNSUPPORTED;
     }
@@ -490,7 +520,6 @@ extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
     return rc;
 }
 
-#undef PACK_TRY
 #define PACK_TRY(expr)                                                 \
     do {                                                               \
         if (!dry) {                                                    \
@@ -504,11 +533,11 @@ extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
     } while (0)
 
 static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry) {
-    const int nh = m->n_heads, pl = m->planes, H = m->hid, G = 4 * H;
+    const int nh = m->n_heads, pl = m->planes, H = m->hid, G = 4 * H, ic = m->in_channels;
     const KernelSet* k = m->k;
     // scratch: scale[256] | folded pitch head (n_out x kfc_pad) | folded bias | backward LSTM fragments (written by the shared pack
     // kernel, not used by inference)
-    const size_t hh_elems = amtx_bilstm_wfrag_elems_h(H, pl);
+    const size_t hh_elems = m->hh_elems;
     const size_t sc_bytes = (size_t)(256 + (size_t)m->n_out * m->kfc_pad + m->n_out) * sizeof(float) + hh_elems * sizeof(bf16_t) + 256;
     AMTX_REQUIRE(m->nf3 <= 256, "amtx_of_model_finalize_device: internal: scale scratch");
     if (!m->pack_scratch.p || m->pack_scratch.bytes < sc_bytes) {
@@ -521,38 +550,28 @@ static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry)
     float* bfold = wfold + (size_t)m->n_out * m->kfc_pad;
     bf16_t* hh_bwd = (bf16_t*)(((uintptr_t)(bfold + m->n_out) + 255) & ~(uintptr_t)255);
 
-    const int ic = m->in_channels;
-    const size_t c1f_per = m->gen_conv2 ? amtx_conv1g_wfrag_elems(ic, m->nf1, pl) : amtx_conv1_wfrag_elems(ic, pl);
-    const size_t c2w_per = m->gen_conv2 ? amtx_conv3x3_gen_wfrag_elems(m->nf1, m->nf2, pl) : amtx_conv3x3_wfrag_elems(m->nf2, pl);
-    const size_t c3w_per = m->gen_conv ? amtx_conv3x3_gen_wfrag_elems(m->nf2, m->nf3, pl) : amtx_conv3x3_wfrag_elems(m->nf3, pl);
-    auto pack_conv_gen = [k](const float* w, const float* sc, int c_in, int c_out, int planes, bf16_t* out, hipStream_t st) {
-        return k->pack_conv_gen_dev(w, sc, c_in, c_out, amtx_conv3x3_gen_ntc(c_in, c_out), planes, out, st);
-    };
+    const ConvPlan& p = m->plan;
     const size_t fc_per = (size_t)m->fc1.n_pad * m->fc1.k_pad * pl;
     for (int h = 0; h < nh; ++h) {
         const std::string am = m->head_names[h] + ".0";
         const float *w, *cb, *g, *be, *mu, *var;
-        // layer1: scale folded into the Toeplitz fragments, shift kept fp32 (conv1_s); the fp32 copy conv1_w feeds only the unfused first conv
-        NEED_DEV(am + ".layer1.0.weight", (size_t)m->nf1 * ic * 9, w);
-        NEED_DEV(am + ".layer1.0.bias", (size_t)m->nf1, cb); NEED_DEV(am + ".layer1.1.weight", (size_t)m->nf1, g); NEED_DEV(am + ".layer1.1.bias", (size_t)m->nf1, be);
-        NEED_DEV(am + ".layer1.1.running_mean", (size_t)m->nf1, mu); NEED_DEV(am + ".layer1.1.running_var", (size_t)m->nf1, var);
-        PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, m->nf1, scale, (float*)m->conv1_s.p + (size_t)h * m->nf1, s));
-        PACK_TRY(amtx_pack_scale_rows_dev(w, scale, m->nf1, ic * 9, (float*)m->conv1_w.p + (size_t)h * m->nf1 * ic * 9, s));
-        if (m->fuse_conv1 && m->gen_conv2) PACK_TRY(k->pack_conv1g_dev(w, scale, ic, m->nf1, pl, (bf16_t*)m->conv1_frag.p + c1f_per * h, s));
-        else if (m->fuse_conv1) PACK_TRY(k->pack_conv1_dev(w, scale, pl, (bf16_t*)m->conv1_frag.p + c1f_per * h, s));
-        NEED_DEV(am + ".layer2.0.weight", (size_t)m->nf2 * m->nf1 * 9, w);
-        NEED_DEV(am + ".layer2.0.bias", (size_t)m->nf2, cb); NEED_DEV(am + ".layer2.1.weight", (size_t)m->nf2, g); NEED_DEV(am + ".layer2.1.bias", (size_t)m->nf2, be);
-        NEED_DEV(am + ".layer2.1.running_mean", (size_t)m->nf2, mu); NEED_DEV(am + ".layer2.1.running_var", (size_t)m->nf2, var);
-        PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, m->nf2, scale, (float*)m->conv2_s.p + (size_t)h * m->nf2, s));
-        if (m->gen_conv2) PACK_TRY(pack_conv_gen(w, scale, m->nf1, m->nf2, pl, (bf16_t*)m->conv2_w.p + c2w_per * h, s));
-        else PACK_TRY(k->pack_conv3x3_dev(w, scale, m->nf2, pl, (bf16_t*)m->conv2_w.p + c2w_per * h, s));
-        if (m->x12m) PACK_TRY(k->pack_conv3x3_dev(w, scale, m->nf2, pl, (bf16_t*)m->conv2_wx.p + (size_t)amtx_conv3x3_wfrag_elems(m->nf2, pl) * h, s));
-        NEED_DEV(am + ".layer3.0.weight", (size_t)m->nf3 * m->nf2 * 9, w);
-        NEED_DEV(am + ".layer3.0.bias", (size_t)m->nf3, cb); NEED_DEV(am + ".layer3.1.weight", (size_t)m->nf3, g); NEED_DEV(am + ".layer3.1.bias", (size_t)m->nf3, be);
-        NEED_DEV(am + ".layer3.1.running_mean", (size_t)m->nf3, mu); NEED_DEV(am + ".layer3.1.running_var", (size_t)m->nf3, var);
-        PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, m->nf3, scale, (float*)m->conv3_s.p + (size_t)h * m->nf3, s));
-        if (m->gen_conv) PACK_TRY(pack_conv_gen(w, scale, m->nf2, m->nf3, pl, (bf16_t*)m->conv3_w.p + c3w_per * h, s));
-        else PACK_TRY(k->pack_conv3x3_dev(w, scale, m->nf3, pl, (bf16_t*)m->conv3_w.p + c3w_per * h, s));
+        for (int l = 0; l < 3; ++l) {
+            // scale folded into the packed weights, shift kept fp32; layer1's fp32 copy conv1_w feeds only the separate first conv
+            const ConvLayer& y = p.layer[l];
+            const std::string conv = am + "." + y.name + ".0", bn = am + "." + y.name + ".1";
+            NEED_DEV(conv + ".weight", (size_t)y.c_out * y.c_in * 9, w);
+            NEED_DEV(conv + ".bias", (size_t)y.c_out, cb); NEED_DEV(bn + ".weight", (size_t)y.c_out, g); NEED_DEV(bn + ".bias", (size_t)y.c_out, be);
+            NEED_DEV(bn + ".running_mean", (size_t)y.c_out, mu); NEED_DEV(bn + ".running_var", (size_t)y.c_out, var);
+            PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, y.c_out, scale, (float*)m->conv_s[l].p + (size_t)h * y.c_out, s));
+            bf16_t* frag = (bf16_t*)m->conv_w[l].p + y.frag_per * h;
+            if (l == 0) {
+                PACK_TRY(amtx_pack_scale_rows_dev(w, scale, y.c_out, ic * 9, (float*)m->conv1_w.p + (size_t)h * y.c_out * ic * 9, s));
+                if (y.fam == K_CONVG) PACK_TRY(k->pack_conv1g_dev(w, scale, ic, y.c_out, pl, frag, s));
+                else if (y.fam == K_CONV) PACK_TRY(k->pack_conv1_dev(w, scale, pl, frag, s));
+            } else if (y.fam == K_CONVG) PACK_TRY(k->pack_conv_gen_dev(w, scale, y.c_in, y.c_out, amtx_conv3x3_gen_ntc(y.c_in, y.c_out), pl, frag, s));
+            else PACK_TRY(k->pack_conv3x3_dev(w, scale, y.c_out, pl, frag, s));
+            if (l == 1 && p.convx12) PACK_TRY(k->pack_conv3x3_dev(w, scale, y.c_out, pl, (bf16_t*)m->conv2_wx.p + p.c2x_per * h, s));
+        }
         // fc1 of the recurrent heads, columns permuted (channel, freq) -> (freq, channel)
         if (h < m->n_rec) {
             const float* fb;
@@ -624,30 +643,81 @@ static GemmArgs gemm_args(const void* A, int64_t lda, int a_type, const LinearPa
     return g;
 }
 
-extern "C" int amtx_of_fuses_db_scale(const amtx_of_model* m);
+// The features of one forward call.  clip_max != null: `feats` are raw power values, dB-scaled by the conv kernel while it stages them
+// (amtx_of_forward_power); feats16 != null: the features as [B][T][F][8] 16-bit channels-last instead of `feats` (amtx_of_forward_feats16)
+struct FeatsIn { const float* feats; const void* feats16; int64_t stride_b, stride_c, stride_t, stride_f; const float *clip_max, *ref; };
 
-extern "C" int amtx_of_takes_feats16(const amtx_of_model* m);
+// conv1 -> conv2 + pool -> conv3 + pool of every acoustic head on the path `call` names: features -> w.a3.  `mark` closes the stages
+// conv1, conv2_pool (the fused stack: all of it) and conv3_pool.
+template <class Mark>
+static int run_convs(const amtx_of_model* m, const ConvCall& call, const FeatsIn& in, const Workspace& w, int B, int T, hipStream_t s, Mark&& mark) {
+    const ConvPlan& p = m->plan;
+    const KernelSet* k = m->k;
+    const int64_t BT = (int64_t)B * T;
+    const int F = m->dim_in, F2 = F / 2, at = m->act_type, pl = m->planes, nh = m->n_heads;
+    int rc;
+    if (call.path == PATH_CONV1) {
+        Conv1Args c1;
+        c1.in = in.feats; c1.stride_b = in.stride_b; c1.stride_c = in.stride_c; c1.stride_t = in.stride_t; c1.stride_f = in.stride_f;
+        c1.w = (const float*)m->conv1_w.p; c1.shift = (const float*)m->conv_s[0].p; c1.out = w.a1; c1.out_type = at;
+        c1.B = B; c1.T = T; c1.F = F; c1.c_in = m->in_channels; c1.c_out = m->nf1;
+        c1.groups = nh; c1.w_gs = (int64_t)m->nf1 * m->in_channels * 9; c1.shift_gs = m->nf1; c1.out_gs = BT * F * m->nf1;
+        if ((rc = k->launch_conv1(c1, s)) != AMTX_OK) return rc;
+    }
+    mark();
+    ConvArgs c2;
+    c2.in = w.a1; c2.in_type = at; c2.wfrag = (const bf16_t*)m->conv_w[1].p; c2.planes = pl; c2.shift = (const float*)m->conv_s[1].p;
+    c2.out = w.a2; c2.out_type = at; c2.B = B; c2.T = T; c2.F = F; c2.c_out = m->nf2;
+    c2.groups = nh; c2.in_gs = BT * F * m->nf1; c2.shift_gs = m->nf2; c2.w_gs = (int64_t)p.layer[1].frag_per; c2.out_gs = BT * F2 * m->nf2;
+    const int64_t a2_split = BT * F2 * m->nf2 * nh, a3_split = BT * m->kfc_pad * nh;   // two-plane maps: plane stride = all groups of one plane
+    if (p.two_plane_acts) { c2.out_type = AMTX_T_SPLIT; c2.out_split = a2_split; }
+    if (p.conv1_fused) {   // Conv(c_in->32)+BN+ReLU computed inside the conv2 kernel; a1 is never materialised
+        c2.in = nullptr;
+        c2.feats = in.feats; c2.f_stride_b = in.stride_b; c2.f_stride_c = in.stride_c; c2.f_stride_t = in.stride_t; c2.f_stride_f = in.stride_f;
+        c2.c_in = m->in_channels; c2.w1frag = (const bf16_t*)m->conv_w[0].p; c2.shift1 = (const float*)m->conv_s[0].p; c2.w1_gs = (int64_t)p.layer[0].frag_per;
+        c2.f_clip_max = in.clip_max; c2.f_ref = in.ref;
+        if (in.feats16) { c2.feats = nullptr; c2.feats16 = in.feats16; }
+    }
+    // convx12: layer2's weights in conv.hip's order; the lo plane of the features lies right behind the hi plane
+    if (call.path == PATH_CONVX12) { c2.in_split = BT * F * 8; c2.wfrag = (const bf16_t*)m->conv2_wx.p; c2.w_gs = (int64_t)p.c2x_per; }
+    if (call.path == PATH_STACK)
+        rc = k->launch_conv_stack(c2, (const bf16_t*)m->conv_w[2].p, (int64_t)p.layer[2].frag_per, (const float*)m->conv_s[2].p, w.a3, BT * m->kfc_pad, call.a3_plane, s);
+    else if (call.path == PATH_CONVX12) rc = amtx_launch_convx12(c2, s);
+    else rc = p.layer[1].fam == K_CONVG ? k->launch_conv3x3_gen(c2, m->nf1, s) : k->launch_conv3x3(c2, s);
+    if (rc != AMTX_OK) return rc;
+    mark();
+    ConvArgs c3 = c2;
+    c3.feats = nullptr; c3.feats16 = nullptr; c3.w1frag = nullptr; c3.shift1 = nullptr; c3.c_in = 0;
+    c3.in = w.a2; c3.wfrag = (const bf16_t*)m->conv_w[2].p; c3.shift = (const float*)m->conv_s[2].p; c3.out = w.a3;
+    c3.F = F2; c3.c_out = m->nf3; c3.in_gs = BT * F2 * m->nf2; c3.w_gs = (int64_t)p.layer[2].frag_per; c3.shift_gs = m->nf3; c3.out_gs = BT * m->kfc_pad;
+    if (p.two_plane_acts) { c3.in_type = AMTX_T_SPLIT; c3.in_split = a2_split; c3.out_type = AMTX_T_SPLIT; c3.out_split = a3_split; }
+    if (m->kfc_pad != m->kfc) {
+        // rows of a3 are padded to the DMA GEMM's k-tile: the pad columns meet zero weights, they only have to be finite
+        AMTX_REQUIRE(p.layer[2].fam == K_CONVG, "amtx_of_forward: internal: padded fc1 rows need the general conv kernel");
+        c3.out_ts = m->kfc_pad;
+        const size_t es = amtx_tsize(at);
+        if ((rc = amtx_launch_zero_cols(w.a3 + (size_t)m->kfc * es, (int64_t)m->kfc_pad * es, (int)((m->kfc_pad - m->kfc) * es), BT * nh, s)) != AMTX_OK) return rc;
+    }
+    if (call.path != PATH_STACK && (rc = p.layer[2].fam == K_CONVG ? k->launch_conv3x3_gen(c3, m->nf2, s) : k->launch_conv3x3(c3, s)) != AMTX_OK) return rc;
+    mark();
+    return AMTX_OK;
+}
 
-// clip_max != null: `feats` are raw power values, dB-scaled by the conv kernel while it stages them (amtx_of_forward_power)
-// feats16 != null: the features as [B][T][F][8] 16-bit channels-last instead of `feats` (amtx_of_forward_feats16)
-static int of_forward_impl(const amtx_of_model* m, const float* feats, const void* feats16, int64_t stride_b, int64_t stride_c, int64_t stride_t,
-                           int64_t stride_f, const float* clip_max, const float* ref, int batch, int num_frames, void* workspace,
-                           size_t workspace_bytes, float* out_onsets, float* out_multi_pitch, float* logits_onsets,
-                           float* logits_multi_pitch, float* logits_pitch_head, void* stream_) {
+static int of_forward_impl(const amtx_of_model* m, const FeatsIn& in, int B, int T, void* workspace, size_t workspace_bytes, float* out_onsets,
+                           float* out_multi_pitch, float* logits_onsets, float* logits_multi_pitch, float* logits_pitch_head, void* stream_) {
     AMTX_REQUIRE(m && m->finalized, "amtx_of_forward: model not finalized");
-    AMTX_REQUIRE(!clip_max || amtx_of_fuses_db_scale(m), "amtx_of_forward_power: this model does not stage its features in the conv kernel");
-    AMTX_REQUIRE(!feats16 || amtx_of_takes_feats16(m), "amtx_of_forward_feats16: this model does not stage 16-bit channels-last features");
-    AMTX_REQUIRE((feats || feats16) && workspace, "amtx_of_forward: null pointer");
-    AMTX_REQUIRE(batch > 0 && num_frames > 0, "amtx_of_forward: bad batch/num_frames");
-    const int B = batch, T = num_frames;
+    AMTX_REQUIRE(!in.clip_max || m->plan.fuses_db_scale, "amtx_of_forward_power: this model does not stage its features in the conv kernel");
+    AMTX_REQUIRE(!in.feats16 || m->plan.takes_feats16, "amtx_of_forward_feats16: this model does not stage 16-bit channels-last features");
+    AMTX_REQUIRE((in.feats || in.feats16) && workspace, "amtx_of_forward: null pointer");
+    AMTX_REQUIRE(B > 0 && T > 0, "amtx_of_forward: bad batch/num_frames");
     Workspace w = carve(m, B, T, (char*)workspace);
     AMTX_REQUIRE(workspace_bytes >= w.total, "amtx_of_forward: workspace too small (%zu < %zu)", workspace_bytes, w.total);
     AMTX_REQUIRE(((uintptr_t)workspace % 256) == 0, "amtx_of_forward: workspace must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream_;
     const int64_t BT = (int64_t)B * T;
-    const int F = m->dim_in, F2 = F / 2, at = m->act_type, pl = m->planes;
-    int rc;
+    const int at = m->act_type, pl = m->planes;
     const KernelSet* k = m->k;
+    int rc;
     std::vector<hipEvent_t>* evs = nullptr;
     if (m->prof) {
         m->prof_events.emplace_back();
@@ -660,70 +730,10 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
     };
     mark();
 
-    Conv1Args c1;
-    c1.in = feats; c1.stride_b = stride_b; c1.stride_c = stride_c; c1.stride_t = stride_t; c1.stride_f = stride_f;
-    c1.w = (const float*)m->conv1_w.p; c1.shift = (const float*)m->conv1_s.p; c1.out = w.a1; c1.out_type = at;
-    c1.B = B; c1.T = T; c1.F = F; c1.c_in = m->in_channels; c1.c_out = m->nf1;
-    c1.groups = m->n_heads; c1.w_gs = (int64_t)m->nf1 * m->in_channels * 9; c1.shift_gs = m->nf1; c1.out_gs = BT * F * m->nf1;
-    if (!m->fuse_conv1 && (rc = k->launch_conv1(c1, s)) != AMTX_OK) return rc;
-    mark();
-
-    ConvArgs c2;
-    c2.in = w.a1; c2.in_type = at; c2.wfrag = (const bf16_t*)m->conv2_w.p; c2.planes = pl; c2.shift = (const float*)m->conv2_s.p;
-    c2.out = w.a2; c2.out_type = at; c2.B = B; c2.T = T; c2.F = F; c2.c_out = m->nf2;
-    c2.groups = m->n_heads; c2.in_gs = BT * F * m->nf1; c2.shift_gs = m->nf2;
-    c2.w_gs = (int64_t)(m->gen_conv2 ? amtx_conv3x3_gen_wfrag_elems(m->nf1, m->nf2, pl) : amtx_conv3x3_wfrag_elems(m->nf2, pl));
-    c2.out_gs = BT * F2 * m->nf2;
-    const bool sp = m->split_acts;
-    // two-plane maps: plane stride = all groups of one plane
-    const int64_t a2_split = BT * F2 * m->nf2 * m->n_heads, a3_split = BT * m->kfc_pad * m->n_heads, e_split = BT * m->dim_am * m->n_heads;
-    if (sp) { c2.out_type = AMTX_T_SPLIT; c2.out_split = a2_split; }
-    if (m->fuse_conv1) {   // Conv(c_in->32)+BN+ReLU computed inside the conv2 kernel; a1 is never materialised
-        c2.in = nullptr;
-        c2.feats = feats; c2.f_stride_b = stride_b; c2.f_stride_c = stride_c; c2.f_stride_t = stride_t; c2.f_stride_f = stride_f;
-        c2.c_in = m->in_channels; c2.w1frag = (const bf16_t*)m->conv1_frag.p; c2.shift1 = (const float*)m->conv1_s.p;
-        c2.w1_gs = (int64_t)(m->gen_conv2 ? amtx_conv1g_wfrag_elems(m->in_channels, m->nf1, pl) : amtx_conv1_wfrag_elems(m->in_channels, pl));
-        c2.f_clip_max = clip_max; c2.f_ref = ref;
-        if (feats16) { c2.feats = nullptr; c2.feats16 = feats16; }
-    }
-    // two-plane 16-bit features into a two-plane model: conv1 + conv2 on convx.hip's layer-specialised kernel (layer2's weights in conv.hip's order)
-    const bool x12m_now = feats16 && m->x12m;
-    if (x12m_now) {
-        c2.in_split = BT * F * 8;                              // the lo plane of the features: right behind the hi plane
-        c2.wfrag = (const bf16_t*)m->conv2_wx.p;
-        c2.w_gs = (int64_t)amtx_conv3x3_wfrag_elems(m->nf2, pl);
-    }
-    const bool fused_stack = m->fuse_stack && amtx_conv_stack_fused_ok(B, T, F, m->n_heads);
-    // the fused stack writes its output in planes of 64 channels per pooled frequency column ([F / 4][B T][64]): a k-tile of the two GEMMs
-    // that read it (fc1, the folded pitch head) is then contiguous memory.  A/B switch: AMTX_OF_ROWMAJOR_A3=1
-    static const bool rowmajor_a3 = getenv("AMTX_OF_ROWMAJOR_A3") != nullptr;
-    const int64_t a3_plane = (fused_stack && !rowmajor_a3 && m->nf3 == 64 && m->kfc_pad == m->kfc) ? BT * 64 : 0;
-    if (fused_stack) {
-        // layer1 -> layer2 -> layer3 in one kernel: neither intermediate map reaches HBM (stage timer: all of it under conv2_pool)
-        if ((rc = k->launch_conv_stack(c2, (const bf16_t*)m->conv3_w.p, (int64_t)amtx_conv3x3_wfrag_elems(m->nf3, pl), (const float*)m->conv3_s.p,
-                                         w.a3, BT * m->kfc_pad, a3_plane, s)) != AMTX_OK) return rc;
-    } else if (x12m_now) {
-        if ((rc = amtx_launch_convx12(c2, s)) != AMTX_OK) return rc;
-    } else if ((rc = m->gen_conv2 ? k->launch_conv3x3_gen(c2, m->nf1, s) : k->launch_conv3x3(c2, s)) != AMTX_OK) return rc;
-    mark();
-
-    ConvArgs c3 = c2;
-    c3.feats = nullptr; c3.feats16 = nullptr; c3.w1frag = nullptr; c3.shift1 = nullptr; c3.c_in = 0;
-    c3.in = w.a2; c3.wfrag = (const bf16_t*)m->conv3_w.p; c3.shift = (const float*)m->conv3_s.p; c3.out = w.a3;
-    c3.F = F2; c3.c_out = m->nf3; c3.in_gs = BT * F2 * m->nf2;
-    c3.w_gs = (int64_t)(m->gen_conv ? amtx_conv3x3_gen_wfrag_elems(m->nf2, m->nf3, pl) : amtx_conv3x3_wfrag_elems(m->nf3, pl));
-    c3.shift_gs = m->nf3; c3.out_gs = BT * m->kfc_pad;
-    if (sp) { c3.in_type = AMTX_T_SPLIT; c3.in_split = a2_split; c3.out_type = AMTX_T_SPLIT; c3.out_split = a3_split; }
-    if (m->kfc_pad != m->kfc) {
-        // rows of a3 are padded to the DMA GEMM's k-tile: the pad columns meet zero weights, they only have to be finite
-        AMTX_REQUIRE(m->gen_conv, "amtx_of_forward: internal: padded fc1 rows need the general conv kernel");
-        c3.out_ts = m->kfc_pad;
-        const size_t es = amtx_tsize(at);
-        if ((rc = amtx_launch_zero_cols(w.a3 + (size_t)m->kfc * es, (int64_t)m->kfc_pad * es, (int)((m->kfc_pad - m->kfc) * es),
-                                        BT * m->n_heads, s)) != AMTX_OK) return rc;
-    }
-    if (!fused_stack && (rc = m->gen_conv ? k->launch_conv3x3_gen(c3, m->nf2, s) : k->launch_conv3x3(c3, s)) != AMTX_OK) return rc;
-    mark();
+    const ConvCall call = resolve_conv(m, B, T, in.feats16 != nullptr);
+    if ((rc = run_convs(m, call, in, w, B, T, s, mark)) != AMTX_OK) return rc;
+    const bool sp = m->plan.two_plane_acts, no_roll_epi = m->plan.no_roll_epilogue;
+    const int64_t a3_plane = call.a3_plane, a3_split = BT * m->kfc_pad * m->n_heads, e_split = BT * m->dim_am * m->n_heads;   // two-plane maps: plane stride = all groups of one plane
 
     // fc1 of the recurrent heads (heads 0..n_rec-1 of a3); the pitch head's fc1 is folded into its output layer below
     const int at_d = sp ? AMTX_T_SPLIT : at;   // element type of the dense layers' activations
@@ -739,7 +749,7 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
     mark();
     LstmArgs l;
     l.xproj = w.xp; l.x_type = at; l.whh = (const bf16_t*)m->rec_hh.p; l.planes = pl; l.out = w.l1; l.out_type = at;
-    l.B = B; l.T = T; l.groups = m->n_rec; l.x_gs = BT * m->xw; l.w_gs = (int64_t)amtx_bilstm_wfrag_elems_h(m->hid, pl); l.out_gs = BT * m->dim_lm;
+    l.B = B; l.T = T; l.groups = m->n_rec; l.x_gs = BT * m->xw; l.w_gs = (int64_t)m->hh_elems; l.out_gs = BT * m->dim_lm;
     l.hidden = m->hid;
     if ((rc = k->launch_bilstm(l, s)) != AMTX_OK) return rc;
     mark();
@@ -747,7 +757,6 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
     g = gemm_args(w.l1, m->dim_lm, at, m->rec_out, pl, w.joint, m->dim_aj, AMTX_T_F32, BT, m->n_rec, BT * m->dim_lm, m->n_out);
     // piano rolls (LogisticBank.finalize_output with threshold 0.5) come out of the LogisticBank GEMMs' epilogues where that kernel has
     // one (bf16 mode); otherwise amtx_launch_pianoroll below reads the logits back
-    static const bool no_roll_epi = getenv("AMTX_OF_NO_ROLL_EPILOGUE") != nullptr;     // A/B switch: separate pianoroll launches
     const bool roll_on = out_onsets && !no_roll_epi && amtx_gemm_has_roll_epilogue(g);
     if (roll_on) { g.roll_out = out_onsets; g.roll_T = T; g.roll_thr = 0.5f; g.roll_group = 0; }
     // bf16 mode: the refinement stage's input (the joint logits rounded to bf16, K zero-padded to the DMA GEMM's 64-deep k-tile) is
@@ -816,19 +825,14 @@ static int of_forward_impl(const amtx_of_model* m, const float* feats, const voi
 }
 
 // 1 when amtx_of_forward_power applies: one input channel and the first conv fused into the C_out = 32 conv kernel (conv.hip, KS = 1)
-extern "C" int amtx_of_fuses_db_scale(const amtx_of_model* m) {
-    return m && m->finalized && m->fuse_conv1 && !m->gen_conv2 && m->in_channels == 1;
-}
-
-extern "C" int amtx_of_conv_stack_fused(const amtx_of_model* m, int batch, int num_frames) {
-    return m && m->fuse_stack && amtx_conv_stack_fused_ok(batch, num_frames, m->dim_in, m->n_heads);
-}
+extern "C" int amtx_of_fuses_db_scale(const amtx_of_model* m) { return m && m->finalized && m->plan.fuses_db_scale; }
+extern "C" int amtx_of_conv_stack_fused(const amtx_of_model* m, int batch, int num_frames) { return m && resolve_conv(m, batch, num_frames, false).path == PATH_STACK; }
 
 extern "C" int amtx_of_forward(const amtx_of_model* m, const float* feats, int64_t stride_b, int64_t stride_c, int64_t stride_t,
                                int64_t stride_f, int batch, int num_frames, void* workspace, size_t workspace_bytes,
                                float* out_onsets, float* out_multi_pitch, float* logits_onsets, float* logits_multi_pitch,
                                float* logits_pitch_head, void* stream_) {
-    return of_forward_impl(m, feats, nullptr, stride_b, stride_c, stride_t, stride_f, nullptr, nullptr, batch, num_frames, workspace, workspace_bytes,
+    return of_forward_impl(m, {feats, nullptr, stride_b, stride_c, stride_t, stride_f, nullptr, nullptr}, batch, num_frames, workspace, workspace_bytes,
                            out_onsets, out_multi_pitch, logits_onsets, logits_multi_pitch, logits_pitch_head, stream_);
 }
 
@@ -837,23 +841,19 @@ extern "C" int amtx_of_forward_power(const amtx_of_model* m, const float* power,
                                      size_t workspace_bytes, float* out_onsets, float* out_multi_pitch, float* logits_onsets,
                                      float* logits_multi_pitch, float* logits_pitch_head, void* stream_) {
     AMTX_REQUIRE(clip_max, "amtx_of_forward_power: clip_max is null");
-    return of_forward_impl(m, power, nullptr, stride_b, 0, stride_t, stride_f, clip_max, ref, batch, num_frames, workspace, workspace_bytes,
+    return of_forward_impl(m, {power, nullptr, stride_b, 0, stride_t, stride_f, clip_max, ref}, batch, num_frames, workspace, workspace_bytes,
                            out_onsets, out_multi_pitch, logits_onsets, logits_multi_pitch, logits_pitch_head, stream_);
 }
 
 // 1 when amtx_of_forward_feats16 applies: 2 .. 8 input channels and the first conv fused tap-major into the general conv kernel's 32-channel
 // pipelined variant (convg.hip: one-plane bf16 mode, model_complexity 2) -- the HCQT configuration (BASELINE config 3)
-extern "C" int amtx_of_takes_feats16(const amtx_of_model* m) {
-    if (!(m && m->finalized && m->fuse_conv1 && m->gen_conv2 && !m->f16)) return 0;
-    if (m->x12m) return 2;     // two planes: [2][B][T][F][8], the lo plane B T F 8 elements behind the hi plane (amtx_cqt_forward16_split)
-    return m->planes == 1 && m->nf1 == 32 && amtx_conv1g_tapk(m->in_channels, m->planes) && m->act_type == AMTX_T_BF16;
-}
+extern "C" int amtx_of_takes_feats16(const amtx_of_model* m) { return m && m->finalized ? m->plan.takes_feats16 : 0; }
 
 extern "C" int amtx_of_forward_feats16(const amtx_of_model* m, const void* feats16, int batch, int num_frames, void* workspace, size_t workspace_bytes,
                                        float* out_onsets, float* out_multi_pitch, float* logits_onsets, float* logits_multi_pitch,
                                        float* logits_pitch_head, void* stream_) {
     AMTX_REQUIRE(feats16, "amtx_of_forward_feats16: feats16 is null");
-    return of_forward_impl(m, nullptr, feats16, 0, 0, 0, 0, nullptr, nullptr, batch, num_frames, workspace, workspace_bytes, out_onsets, out_multi_pitch,
+    return of_forward_impl(m, {nullptr, feats16, 0, 0, 0, 0, nullptr, nullptr}, batch, num_frames, workspace, workspace_bytes, out_onsets, out_multi_pitch,
                            logits_onsets, logits_multi_pitch, logits_pitch_head, stream_);
 }
 

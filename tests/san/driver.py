@@ -2,9 +2,16 @@
 of the C ABI through tests/san/_build/libamtx_san.so -- weight packers at ragged sizes, amtx_of_model_create / set_tensor / finalize for
 every engine configuration (their BatchNorm folding, fc1 permutation, fp64 head folding, fragment packing), the argument checks and
 workspace carving of the forward entry points (the first kernel launch then reports "no device" through the shim: that is the expected
-error), spectrogram and CQT plan builders.  numpy + ctypes only; any ASan / UBSan report aborts the process."""
+error), spectrogram and CQT plan builders.  numpy + ctypes only; any ASan / UBSan report aborts the process.
+
+With a second argument it also writes, as JSON, what the engine DECIDES and PACKS: for each of the engine configurations below the hash of
+the bytes amtx_of_model_finalize uploads (the shim's hipMemcpy sees them), and for those plus a grid of small models -- model_complexity
+2 .. 5 x input channels x precision x offset head x each create-time A/B switch (thinned at model_complexity 4 and 5) -- the answers of the query entry points, the workspace
+sizes and the device re-sync's support check.  tests/golden/of_conv_plan.json is that file as the commit before the ConvPlan refactor
+wrote it; tests/test_sanitized_host.py requires every row of it back."""
 import ctypes as C
 import importlib.util
+import json
 import os
 import sys
 
@@ -30,6 +37,24 @@ missing = [s for s in _lib.declared_symbols() if not hasattr(L, s)]
 assert not missing, missing
 rng = np.random.default_rng(0)
 n_calls = 0
+L.amtx_san_upload_hash_take.restype = C.c_uint64
+L.amtx_san_upload_hash_take.argtypes = []
+PLAN_BT = ((1, 1), (3, 17), (130, 47), (43, 140), (1024, 625))
+PLAN_COLUMNS = ['dim_in', 'in_channels', 'model_complexity', 'offsets', 'precision', 'switch', 'fuses_db_scale', 'takes_feats16'] + \
+               [f'conv_stack_fused_{B}x{T}' for B, T in PLAN_BT] + [f'workspace_bytes_{B}x{T}' for B, T in PLAN_BT] + ['finalize_device_rc', 'finalize_device_error']
+PLAN_SWITCHES = ('', 'AMTX_NO_CONVG_MC2', 'AMTX_NO_CONV_FUSE', 'AMTX_X3_NO_SPLIT', 'AMTX_NO_CONVX12M')
+
+
+def plan_row(h, cfg, switch):
+    """What a finalized model decides, through the C ABI only.  The device re-sync is called with no device tensor set: it answers its support
+    check, or the first missing tensor."""
+    rc = L.amtx_of_model_finalize_device(h, None)
+    err = L.amtx_last_error().decode()
+    return [cfg['dim_in'], cfg['ch'], cfg['mc'], cfg['off'], cfg['prec'], switch, L.amtx_of_fuses_db_scale(h), L.amtx_of_takes_feats16(h)] + \
+           [L.amtx_of_conv_stack_fused(h, B, T) for B, T in PLAN_BT] + [L.amtx_of_workspace_bytes(h, B, T) for B, T in PLAN_BT] + [rc, err]
+
+
+plan_rows, upload_hashes = [], []
 
 # ---------------------------------------------------------------- weight packers (op-level C ABI)
 for planes in (1, 2):
@@ -80,7 +105,10 @@ for cfg in configs:
             continue
         keep.append(a)
         _lib.check(L.amtx_of_model_set_tensor(h, k.encode(), P(a), a.size), 'set_tensor')
+    L.amtx_san_upload_hash_take()
     _lib.check(L.amtx_of_model_finalize(h), 'finalize')
+    upload_hashes.append([cfg['dim_in'], cfg['ch'], cfg['mc'], cfg['off'], cfg['prec'], '%016x' % L.amtx_san_upload_hash_take()])
+    plan_rows.append(plan_row(h, cfg, ''))
     for B, T in ((1, 1), (3, 17), (130, 47), (1024, 625)):
         need = L.amtx_of_workspace_bytes(h, B, T)
         assert need > 0
@@ -105,6 +133,36 @@ h = C.c_void_p()
 _lib.check(L.amtx_of_model_create(C.byref(h), 229, 1, 2, 88, 0, 0))
 assert L.amtx_of_model_finalize(h) != 0
 _lib.check(L.amtx_of_model_destroy(h))
+
+# ---------------------------------------------------------------- engine: the decision grid (small models: 20 bins, 4 keys; the weights do not matter)
+if len(sys.argv) > 2:
+    for mc in (2, 3, 4, 5):
+        for ch in (1, 2, 3, 6, 8, 9):
+            for off in (0, 1):
+                sd = {k: np.full(shape, 0.5, np.float32) for k, shape in
+                      synth.of_state_dict_shapes(dim_in=20, in_channels=ch, model_complexity=mc, dim_out=4, offsets=bool(off)).items() if 'num_batches_tracked' not in k}
+                for prec in (0, 1, 2):
+                    for switch in PLAN_SWITCHES:
+                        # model_complexity 4 and 5 cost 0.2 .. 0.8 s each under ASan (their LSTMs) and decide alike whatever the switch: every
+                        # channel count and precision without a switch and without offsets; offsets, and the switches (bf16, x3), at 1, 6, 9 channels
+                        if mc >= 4 and (off or switch) and not (ch in (1, 6, 9) and (not switch or (not off and prec in (0, 1)))):
+                            continue
+                        cfg = dict(dim_in=20, ch=ch, mc=mc, off=off, prec=prec)
+                        if switch:
+                            os.environ[switch] = '1'
+                        h = C.c_void_p()
+                        _lib.check(L.amtx_of_model_create(C.byref(h), 20, ch, mc, 4, off, prec), 'create')
+                        os.environ.pop(switch, None)
+                        assert L.amtx_of_fuses_db_scale(h) == 0 and L.amtx_of_takes_feats16(h) == 0           # not finalized yet
+                        for k, a in sd.items():
+                            _lib.check(L.amtx_of_model_set_tensor(h, k.encode(), P(a), a.size), 'set_tensor')
+                        _lib.check(L.amtx_of_model_finalize(h), 'finalize')
+                        plan_rows.append(plan_row(h, cfg, switch))
+                        _lib.check(L.amtx_of_model_destroy(h))
+                        n_calls += 1
+    with open(sys.argv[2], 'w') as f:
+        f.write('{"plan_columns": %s,\n"plan_rows": [\n%s\n],\n"upload_hash_columns": ["dim_in", "in_channels", "model_complexity", "offsets", "precision", "fnv1a64"],\n'
+                '"upload_hashes": [\n%s\n]}\n' % (json.dumps(PLAN_COLUMNS), ',\n'.join(json.dumps(r) for r in plan_rows), ',\n'.join(json.dumps(r) for r in upload_hashes)))
 
 # ---------------------------------------------------------------- spectrogram and CQT plans (host-built tables, uploaded through the shim)
 for sr, n_fft, hop, win, n_mels, htk, center, pad in ((22050, 2048, 512, 2048, 229, 0, 1, 0), (22050, 2048, 512, 2048, 229, 1, 1, 1), (16000, 1024, 160, 800, 80, 0, 0, 0),

@@ -4,6 +4,7 @@
 // builders and amtx_of_model_finalize upload is written through instrumented code into instrumented memory -- and a kernel launch
 // reports hipErrorNoDevice, which the library turns into its ordinary error return.
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -11,7 +12,18 @@ extern "C" {
 static hipError_t g_last = hipSuccess;
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
+// every host -> "device" upload (its length, then its bytes) goes into one FNV-1a hash: tests/san/driver.py pins the packed weights with it
+static uint64_t g_up_hash = 0xcbf29ce484222325ull;
+static void up_hash(const void* s, size_t n) {
+    for (size_t i = 0; i < 8; ++i) g_up_hash = (g_up_hash ^ ((n >> (8 * i)) & 0xff)) * 0x100000001b3ull;
+    for (size_t i = 0; i < n; ++i) g_up_hash = (g_up_hash ^ ((const unsigned char*)s)[i]) * 0x100000001b3ull;
+}
+uint64_t amtx_san_upload_hash_take(void) { const uint64_t h = g_up_hash; g_up_hash = 0xcbf29ce484222325ull; return h; }   // reads and restarts the hash
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) {
+    if (k == hipMemcpyHostToDevice) up_hash(s, n);
+    memcpy(d, s, n);
+    return hipSuccess;
+}
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpy2DAsync(void* d, size_t dp, const void* s, size_t sp, size_t w, size_t h, hipMemcpyKind, hipStream_t) {
     for (size_t i = 0; i < h; ++i) memcpy((char*)d + i * dp, (const char*)s + i * sp, w);
