@@ -827,6 +827,9 @@ int launch_conv(const ConvArgs& a, hipStream_t stream) {
     return AMTX_OK;
 }
 
+// A/B switch: AMTX_NO_CONVX=1 keeps this file's register-staged kernel on the two-plane maps
+static bool no_convx() { static const bool v = getenv("AMTX_NO_CONVX") != nullptr; return v; }
+
 template <int NT, int NS>
 int dispatch_types(const ConvArgs& a, hipStream_t s) {
     if (a.feats) {
@@ -839,8 +842,7 @@ int dispatch_types(const ConvArgs& a, hipStream_t s) {
             if (a.out_type == AMTX_T_SPLIT) {
                 if constexpr (NS == 2) {
                     AMTX_REQUIRE(a.out_split > 0 && a.out_split % 8 == 0, "conv3x3: two-plane output needs a plane stride");
-                    static const bool no_convx = getenv("AMTX_NO_CONVX") != nullptr;      // A/B switch, as below
-                    if (!no_convx && a.c_in == 1) return amtx_launch_convx12(a, s);
+                    if (!no_convx() && a.c_in == 1) return amtx_launch_convx12(a, s);
                     return launch_conv<2, NS, AMTX_T_F32, AMTX_T_SPLIT, true, 1>(a, s);
                 }
                 amtx_set_error("conv3x3: two-plane maps exist in the two-plane mode only");
@@ -860,9 +862,7 @@ int dispatch_types(const ConvArgs& a, hipStream_t s) {
     if (a.in_type == AMTX_T_SPLIT && a.out_type == AMTX_T_SPLIT) {
         if constexpr (NS == 2) {
             AMTX_REQUIRE(a.in_split > 0 && a.in_split % 8 == 0 && a.out_split > 0 && a.out_split % 8 == 0, "conv3x3: two-plane maps need plane strides");
-            // A/B switch: AMTX_NO_CONVX=1 keeps this file's register-staged kernel on the two-plane maps
-            static const bool no_convx = getenv("AMTX_NO_CONVX") != nullptr;
-            if (!no_convx) return amtx_launch_convx3(a, s);
+            if (!no_convx()) return amtx_launch_convx3(a, s);
             return launch_conv<NT, NS, AMTX_T_SPLIT, AMTX_T_SPLIT, false>(a, s);
         }
     }

@@ -831,21 +831,25 @@ int launch_gen(const ConvArgs& a, hipStream_t stream, int f_base = 0, int ntf_on
     return AMTX_OK;
 }
 
+// A map whose last column tile would hold 8 columns or fewer (72 = 2 x 32 + 8; 229 mel bins = 7 x 32 + 4 columns that reach a pooled
+// output): those columns as strip tiles, in a launch of their own behind `main_launch` over the whole tiles.  Both take (f_base, ntf_only).
+// AMTX_CONVG_NO_STRIP=1: one launch of 32-column tiles, the A/B switch.
+static bool no_strip() { static const bool v = getenv("AMTX_CONVG_NO_STRIP") != nullptr; return v; }
+template <class Main, class Strip>
+int launch_with_strip(const ConvArgs& a, Main&& main_launch, Strip&& strip_launch) {
+    const int fe = a.F & ~1, rem = fe % 32;
+    if (no_strip() || fe <= 32 || rem == 0 || rem > 8) return main_launch(0, 0);
+    const int rc = main_launch(0, fe / 32);
+    return rc != AMTX_OK ? rc : strip_launch(fe - rem, 0);
+}
+
 template <int CI16, int NTC>
 int dispatch_gen(const ConvArgs& a, hipStream_t s) {
     if (a.feats16) {                                            // fused first conv from 16-bit channels-last features (amtx_cqt_forward16)
         if constexpr (CI16 == 2) {
             if (amtx_conv1g_tapk(a.c_in, a.planes) && a.out_type == AMTX_T_BF16) {
-                // a map whose last column tile would hold 8 columns or fewer (72 = 2 x 32 + 8): those columns as strip tiles, in a launch of
-                // their own (AMTX_CONVG_NO_STRIP=1: one launch of 32-column tiles, the A/B switch)
-                static const bool no_strip = getenv("AMTX_CONVG_NO_STRIP") != nullptr;
-                const int fe = a.F & ~1, rem = fe % 32;
-                if (!no_strip && fe > 32 && rem > 0 && rem <= 8) {
-                    int rc = launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true>(a, s, 0, fe / 32);
-                    if (rc != AMTX_OK) return rc;
-                    return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true, true>(a, s, fe - rem, 0);
-                }
-                return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true>(a, s);
+                return launch_with_strip(a, [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true>(a, s, f_base, ntf); },
+                                         [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true, true>(a, s, f_base, ntf); });
             }
         }
         amtx_set_error("conv3x3 (general): 16-bit channels-last features: 2 .. 8 input channels, 32 first-layer channels, one-plane modes only");
@@ -860,16 +864,10 @@ int dispatch_gen(const ConvArgs& a, hipStream_t s) {
             return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true>(a, s);
         }
         if (a.planes == 1 && a.out_type == AMTX_T_BF16 && a.c_in == 1) {   // one input channel (2 .. 8 channels: the tap-major variant above)
-            if constexpr (CI16 == 3) {       // OnsetsFrames2 as shipped (model_complexity 3, 229 mel bins = 7 x 32 + 4 columns that reach a pooled output)
-                static const bool no_strip = getenv("AMTX_CONVG_NO_STRIP") != nullptr;
-                const int fe = a.F & ~1, rem = fe % 32;
-                if (!no_strip && fe > 32 && rem > 0 && rem <= 8) {
-                    int rc = launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1>(a, s, 0, fe / 32);
-                    if (rc != AMTX_OK) return rc;
-                    return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1, false, true>(a, s, fe - rem, 0);
-                }
-            }
-            return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1>(a, s);
+            auto whole = [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1>(a, s, f_base, ntf); };
+            if constexpr (CI16 == 3)         // OnsetsFrames2 as shipped (model_complexity 3, 229 mel bins): the strip kernel exists for this shape only
+                return launch_with_strip(a, whole, [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1, false, true>(a, s, f_base, ntf); });
+            return whole(0, 0);
         }
         // two-plane modes.  2 .. 8 input channels: tap-major as well (round 5: the K-major form gathered and split 8 fp32 values per lane, k-step
         // and 16 positions -- 52 % of the HCQT model's x3 conv2; the packed weights follow amtx_conv1g_tapk, so there is no run-time switch back)

@@ -894,6 +894,12 @@ __global__ __launch_bounds__(512) void gemm_split_kernel(GemmArgs g, int ntiles)
 #undef SP_SYNC
 }
 
+// persistent grid: `blocks` resident blocks on the chip for all groups together, a multiple of 8 per group so that a block's tiles stay
+// on its XCD (tile ids advance by gridDim.x)
+static unsigned persistent_gx(int blocks, int groups, int64_t ntiles) {
+    return (unsigned)std::min(std::max<int64_t>(8, blocks / std::max(1, groups) / 8 * 8), ntiles);
+}
+
 template <int C_TYPE>
 int launch_split(const GemmArgs& g, hipStream_t stream) {
     const int64_t ntiles = ((g.M + RTB - 1) / RTB) * (g.n_pad / RTB);
@@ -901,10 +907,7 @@ int launch_split(const GemmArgs& g, hipStream_t stream) {
     const size_t lds = 2 * (size_t)SSTAGE;
     auto kern = gemm_split_kernel<C_TYPE>;
     AMTX_GRANT_LDS(kern, lds);
-    int64_t gx = 256 / std::max(1, g.groups);
-    gx = std::max<int64_t>(8, gx / 8 * 8);
-    if (gx > ntiles) gx = ntiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, 1, (unsigned)g.groups), dim3(512), lds, stream, g, (int)ntiles);
+    hipLaunchKernelGGL(kern, dim3(persistent_gx(256, g.groups, ntiles), 1, (unsigned)g.groups), dim3(512), lds, stream, g, (int)ntiles);
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
@@ -916,10 +919,7 @@ int launch_pp(const GemmArgs& g, hipStream_t stream) {
     const size_t lds = (size_t)RST * RSTAGE + (size_t)g.n_pad * sizeof(float);
     auto kern = gemm_pp_kernel<C_TYPE>;
     AMTX_GRANT_LDS(kern, RST * RSTAGE + RING_MAX_NPAD * sizeof(float));
-    int64_t gx = 256 / std::max(1, g.groups);
-    gx = std::max<int64_t>(8, gx / 8 * 8);
-    if (gx > ntiles) gx = ntiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, 1, (unsigned)g.groups), dim3(512), lds, stream, g, (int)ntiles);
+    hipLaunchKernelGGL(kern, dim3(persistent_gx(256, g.groups, ntiles), 1, (unsigned)g.groups), dim3(512), lds, stream, g, (int)ntiles);
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
@@ -1278,14 +1278,10 @@ int launch_glds(const GemmArgs& g, hipStream_t stream) {
     const int64_t ntiles = ((g.M + TB - 1) / TB) * (g.n_pad / TB);
     AMTX_REQUIRE(ntiles < (1ll << 31), "gemm: too many output tiles");
     const size_t lds = 4 * (size_t)TB * GBK * 2;
-    // persistent grid: every CU full (two 64 KiB blocks or one 128 KiB block), a multiple of 8 so that a block's tiles stay
-    // on its XCD (tile ids advance by gridDim.x)
-    int64_t gx = (TB == 128 ? 512 : 256) / std::max(1, g.groups);
-    gx = std::max<int64_t>(8, gx / 8 * 8);
-    if (gx > ntiles) gx = ntiles;
     auto kern = gemm_glds_kernel<C_TYPE, TB>;
     AMTX_GRANT_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, 1, (unsigned)g.groups), dim3(TB * 2), lds, stream, g, (int)ntiles);
+    // every CU full: two 64 KiB blocks or one 128 KiB block
+    hipLaunchKernelGGL(kern, dim3(persistent_gx(TB == 128 ? 512 : 256, g.groups, ntiles), 1, (unsigned)g.groups), dim3(TB * 2), lds, stream, g, (int)ntiles);
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
@@ -1329,14 +1325,25 @@ void amtx_gemm_pack_host(const float* W, int64_t ldw, int N, int K, int planes, 
         }
 }
 
-static int check_generic(const GemmArgs& g) {
-    AMTX_REQUIRE(g.A && g.W && (g.C || g.pair_map), "gemm: null pointer");
+// ---- kernel selection: amtx_launch_gemm is gemm_validate -> gemm_route -> one switch that launches (the table: DESIGN.md 5.9) ----
+
+// The A/B switches of this file, read once per process.  AMTX_GEMM_NO_SKINNY: skinny N on the kernels it had before
+// gemm_skinny_kernel and its two-plane variant; AMTX_GEMM_PP: the two-group ring for any K (tools/bench_gemm.py, tools/check_gemm_pp.py);
+// AMTX_GEMM_NO_PP: never the ring; AMTX_GEMM_NO_SPLIT_DMA: two-plane A on the generic kernel, on the same planes
+struct GemmSwitches { bool no_skinny, force_pp, no_pp, no_split_dma; };
+static const GemmSwitches& gemm_switches() {
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    static const GemmSwitches sw = {on("AMTX_GEMM_NO_SKINNY"), on("AMTX_GEMM_PP"), on("AMTX_GEMM_NO_PP"), on("AMTX_GEMM_NO_SPLIT_DMA")};
+    return sw;
+}
+
+// the argument checks common to amtx_launch_gemm and amtx_launch_gemm_multi
+static int gemm_validate(const GemmArgs& g) {
+    AMTX_REQUIRE(g.A && g.W, "gemm: null pointer");
     AMTX_REQUIRE(!g.pair_map || (g.a_type == AMTX_T_F32 && g.c_type == AMTX_T_F32 && g.pair_out && g.N % 2 == 0), "gemm: the magnitude epilogue needs fp32 A / C, an output and an even N");
     AMTX_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.groups > 0, "gemm: bad sizes");
     AMTX_REQUIRE(g.K % 8 == 0 && g.N % 4 == 0, "gemm: K must be a multiple of 8 and N of 4 (K=%d N=%d)", g.K, g.N);
     AMTX_REQUIRE(g.n_pad % BN == 0 && g.k_pad % BK == 0 && g.n_pad >= g.N && g.k_pad >= g.K, "gemm: bad packed dims");
-    // bf16 A: 16-byte fragments straight from memory.  fp32 A goes through registers with dword-aligned wide loads: rows may start at any
-    // 4-byte boundary (clips of an odd length in one buffer, strided rows of the CQT products)
     // bf16 / two-plane A: 16-byte fragments straight from memory.  fp32 A goes through registers; rows that start at ANY 4-byte boundary
     // (dword-aligned wide loads) are for the bounded strided-row problems only (a_valid_hi > 0: the CQT products straight from a caller's
     // audio) -- a plain fp32 A keeps 16-byte aligned rows (the relaxation had reached every caller)
@@ -1355,8 +1362,8 @@ int amtx_launch_gemm_multi(const GemmArgs* gs, int n, hipStream_t stream) {
     unsigned gx = 0, gy = 0;
     for (int i = 0; i < n; ++i) {
         const GemmArgs& g = gs[i];
-        int rc = check_generic(g);
-        if (rc != AMTX_OK) return rc;
+        AMTX_REQUIRE(g.C || g.pair_map, "gemm: null pointer");
+        if (const int rc = gemm_validate(g); rc != AMTX_OK) return rc;
         AMTX_REQUIRE(g.a_type == AMTX_T_F32 && g.c_type == AMTX_T_F32 && g.planes == 2 && g.groups == gs[0].groups,
                      "gemm_multi: fp32 A / C, two weight planes and one group count for all problems");
         mm.p[i] = g;
@@ -1370,81 +1377,75 @@ int amtx_launch_gemm_multi(const GemmArgs* gs, int n, hipStream_t stream) {
     return AMTX_OK;
 }
 
-// the shapes amtx_launch_gemm sends to gemm_glds_kernel<fp32 C> (not the two-group ring, whose epilogue has no roll code)
-bool amtx_gemm_has_roll_epilogue(const GemmArgs& g) {
-    return g.a_type == AMTX_T_BF16 && g.c_type == AMTX_T_F32 && g.planes == 1 && g.K % GBK == 0 && g.k_pad == g.K && (g.lda % 8) == 0 &&
-           !(g.n_pad % 256 == 0 && g.N % 256 == 0 && g.M >= 256);
+// The kernel a problem runs on.  GENERIC is gemm_kernel in one of its type combinations; ROUTE_ERROR carries the argument error of a
+// problem that no kernel takes.
+enum GemmRoute { ROUTE_SKINNY, ROUTE_SKINNY_SPLIT, ROUTE_GLDS256, ROUTE_GLDS128, ROUTE_PP, ROUTE_SPLIT, ROUTE_GENERIC, ROUTE_ERROR };
+struct GemmRouted { GemmRoute route; const char* error; };
+
+// Pure: sizes, types, strides and (for the plain-epilogue rule of two-plane A) which outputs are asked for; no pointer is dereferenced,
+// nothing is launched, no environment is read.  Also answers for arguments that gemm_validate has not seen (amtx_gemm_has_roll_epilogue).
+static GemmRouted gemm_route(const GemmArgs& g, const GemmSwitches& sw) {
+#define ROUTE_REQUIRE(cond, msg) if (!(cond)) return {ROUTE_ERROR, msg}
+    const bool tiles256 = g.n_pad % 256 == 0 && g.N % 256 == 0 && g.M >= 256;     // whole 256-column tiles, one full row tile at least
+    if (g.a_type == AMTX_T_BF16 && g.planes == 1 && g.K % GBK == 0 && g.k_pad == g.K && (g.lda % 8) == 0) {   // the direct-to-LDS kernels
+        // skinny N: one 128-column tile, fp32 C -- the LogisticBanks and the pitch head
+        if (!sw.no_skinny && g.n_pad == 128 && g.c_type == AMTX_T_F32 && g.M >= 1024 && g.K >= 2 * GBK && g.M < (1ll << 31) * 256) return {ROUTE_SKINNY, nullptr};
+        if (!tiles256) return {ROUTE_GLDS128, nullptr};
+        // the two-group ring for the short K (never a planar A: the two-buffer kernel only).  Measured on MI355X (tools/bench_gemm.py,
+        // M = 320000, N = 1024): K = 512: 0.49 ms vs 0.53 (two 64-deep buffers); K = 192: 0.255 vs 0.271 ms; K = 3648 (N = 512): 1.21 vs
+        // 1.20 ms.  (Round 5: 128 x 128 tiles, two blocks per CU, for the short K: 0.356 / 0.611 ms -- worse.)
+        if (!g.a_plane && !sw.no_pp && (sw.force_pp || g.K <= 1024) && g.n_pad <= RING_MAX_NPAD && g.K >= 4 * RBK && (g.ldc * amtx_tsize(g.c_type)) % 16 == 0)
+            return {ROUTE_PP, nullptr};
+        return {ROUTE_GLDS256, nullptr};
+    }
+    ROUTE_REQUIRE(!g.a_plane, "gemm: planar A exists on the bf16 direct-to-LDS path only");
+    if (g.a_type == AMTX_T_SPLIT) {
+        ROUTE_REQUIRE(g.planes == 2 && g.a_split > 0 && (g.a_split % 8) == 0, "gemm: two-plane A needs two-plane weights and a plane stride that keeps 16-byte alignment");
+        ROUTE_REQUIRE(g.c_type != AMTX_T_SPLIT || (g.c_split > 0 && (g.c_split % 8) == 0), "gemm: two-plane C needs a plane stride");
+        ROUTE_REQUIRE(!g.pair_map && !g.roll_out && !g.copy16 && g.C, "gemm: two-plane A has the plain epilogues only");
+        // the direct-to-LDS two-plane kernel: whole 256-column tiles, whole 32-deep stages of real A columns.  C rows are stored 16 bytes at
+        // a time: fp32 C needs ldc % 4 == 0, the 2-byte planes of a two-plane C need ldc % 8 == 0 and a plane stride that keeps the second
+        // plane 16-byte aligned; anything else takes the generic kernel (8-byte stores)
+        const bool c_aligned = g.c_type == AMTX_T_SPLIT ? ((g.ldc * 2) % 16 == 0 && (g.c_split % 8) == 0) : ((g.ldc * 4) % 16 == 0);
+        if (!sw.no_split_dma && tiles256 && g.K == g.k_pad && (g.lda % 8) == 0 && g.c_type != AMTX_T_BF16 && c_aligned) return {ROUTE_SPLIT, nullptr};
+        ROUTE_REQUIRE(g.c_type != AMTX_T_BF16, "gemm: two-plane A writes fp32 or two-plane C");
+        // skinny N (the x3 LogisticBanks and pitch head): the two-plane variant of gemm_skinny_kernel
+        if (!sw.no_skinny && !sw.no_split_dma && g.n_pad == 128 && g.c_type == AMTX_T_F32 && g.M >= 1024 && g.K == g.k_pad && g.K >= 2 * RBK && (g.lda % 8) == 0 &&
+            g.M < (1ll << 31) * 256)
+            return {ROUTE_SKINNY_SPLIT, nullptr};
+        return {ROUTE_GENERIC, nullptr};
+    }
+    ROUTE_REQUIRE(g.c_type != AMTX_T_SPLIT, "gemm: two-plane C needs two-plane A");
+    return {ROUTE_GENERIC, nullptr};
+#undef ROUTE_REQUIRE
 }
 
+// the piano-roll and bf16-copy epilogues: gemm_skinny_kernel and gemm_glds_kernel<fp32 C, 128> (the 256-column kernels have no such code)
+static bool route_has_roll_epilogue(GemmRoute r, const GemmArgs& g) { return (r == ROUTE_SKINNY || r == ROUTE_GLDS128) && g.c_type == AMTX_T_F32; }
+bool amtx_gemm_has_roll_epilogue(const GemmArgs& g) { return route_has_roll_epilogue(gemm_route(g, gemm_switches()).route, g); }
+
 int amtx_launch_gemm(const GemmArgs& g, hipStream_t stream) {
-    AMTX_REQUIRE(g.A && g.W, "gemm: null pointer");
-    AMTX_REQUIRE(!g.pair_map || (g.a_type == AMTX_T_F32 && g.c_type == AMTX_T_F32 && g.pair_out && g.N % 2 == 0), "gemm: the magnitude epilogue needs fp32 A / C, an output and an even N");
-    AMTX_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.groups > 0, "gemm: bad sizes");
-    AMTX_REQUIRE(g.K % 8 == 0 && g.N % 4 == 0, "gemm: K must be a multiple of 8 and N of 4 (K=%d N=%d)", g.K, g.N);
-    AMTX_REQUIRE(g.n_pad % BN == 0 && g.k_pad % BK == 0 && g.n_pad >= g.N && g.k_pad >= g.K, "gemm: bad packed dims");
-    // bf16 A: 16-byte fragments straight from memory.  fp32 A goes through registers with dword-aligned wide loads: rows may start at any
-    // 4-byte boundary (clips of an odd length in one buffer, strided rows of the CQT products)
-    // bf16 / two-plane A: 16-byte fragments straight from memory.  fp32 A goes through registers; rows that start at ANY 4-byte boundary
-    // (dword-aligned wide loads) are for the bounded strided-row problems only (a_valid_hi > 0: the CQT products straight from a caller's
-    // audio) -- a plain fp32 A keeps 16-byte aligned rows (the relaxation had reached every caller)
-    AMTX_REQUIRE(g.a_type == AMTX_T_F32 ? (g.a_valid_hi > 0 ? ((uintptr_t)g.A % 4) == 0 : (g.lda % 4 == 0 && ((uintptr_t)g.A % 16) == 0))
-                                        : ((g.lda * 2) % 16 == 0 && ((uintptr_t)g.A % 16) == 0),
-                 "gemm: A rows must be 16-byte aligned (4-byte aligned for a bounded fp32 A)");
-    AMTX_REQUIRE(g.a_valid_hi == 0 || (g.a_type == AMTX_T_F32 && g.a_valid_lo >= 0 && g.a_valid_hi > g.a_valid_lo), "gemm: bad valid range of A");
-    AMTX_REQUIRE(g.ldc % 4 == 0 && ((uintptr_t)g.C % 16) == 0, "gemm: C rows must be 16-byte aligned");
-    AMTX_REQUIRE(g.planes == 1 || g.planes == 2, "gemm: planes must be 1 or 2");
+    if (const int rc = gemm_validate(g); rc != AMTX_OK) return rc;
+    const GemmRouted r = gemm_route(g, gemm_switches());
+    const bool roll_epilogue = route_has_roll_epilogue(r.route, g);
     AMTX_REQUIRE(g.a_type == AMTX_T_BF16 || g.a_type == AMTX_T_F32 || g.a_type == AMTX_T_SPLIT, "gemm: bad A type");
-    AMTX_REQUIRE(!g.copy16 || (amtx_gemm_has_roll_epilogue(g) && g.copy16_pad % 4 == 0 && g.N + g.copy16_pad <= g.n_pad &&
+    AMTX_REQUIRE(!g.copy16 || (roll_epilogue && g.copy16_pad % 4 == 0 && g.N + g.copy16_pad <= g.n_pad &&
                                (g.copy16_ld % 4) == 0 && ((g.copy16_col0 | g.copy16_gs) % 4) == 0 && ((uintptr_t)g.copy16 % 8) == 0),
                  "gemm: bad bf16-copy epilogue arguments");
     AMTX_REQUIRE(g.C || g.pair_map || g.roll_out || g.copy16, "gemm: no output");
-    AMTX_REQUIRE(!g.roll_out || amtx_gemm_has_roll_epilogue(g), "gemm: the piano-roll epilogue exists on the bf16 direct-to-LDS path with fp32 C only");
+    AMTX_REQUIRE(!g.roll_out || roll_epilogue, "gemm: the piano-roll epilogue exists on the bf16 direct-to-LDS path with fp32 C only");
     AMTX_REQUIRE(!g.roll_out || (g.roll_T > 0 && g.M % g.roll_T == 0 && g.M < (1ll << 31)), "gemm: piano-roll epilogue: M must be clips x frames");
-    if (g.a_type == AMTX_T_BF16 && g.planes == 1 && g.K % GBK == 0 && g.k_pad == g.K && (g.lda % 8) == 0) {
-        // skinny N: one 128-column tile, fp32 C -- the LogisticBanks and the pitch head (AMTX_GEMM_NO_SKINNY=1: the A/B switch)
-        static const bool no_skinny = getenv("AMTX_GEMM_NO_SKINNY") != nullptr;
-        if (!no_skinny && g.n_pad == 128 && g.c_type == AMTX_T_F32 && g.M >= 1024 && g.K >= 2 * GBK && g.M < (1ll << 31) * 256)
-            return launch_skinny(g, stream, false);
-        if (g.a_plane) {      // planar A: the two-buffer direct-to-LDS kernel only
-            if (g.n_pad % 256 == 0 && g.N % 256 == 0 && g.M >= 256)
-                return g.c_type == AMTX_T_BF16 ? launch_glds<AMTX_T_BF16, 256>(g, stream) : launch_glds<AMTX_T_F32, 256>(g, stream);
-            return g.c_type == AMTX_T_BF16 ? launch_glds<AMTX_T_BF16, 128>(g, stream) : launch_glds<AMTX_T_F32, 128>(g, stream);
-        }
-        // A/B switches for tools/bench_gemm.py / tools/check_gemm_pp.py: AMTX_GEMM_PP=1 forces the two-group ring for any K,
-        // AMTX_GEMM_NO_PP=1 disables it
-        static const bool force_pp = getenv("AMTX_GEMM_PP") != nullptr, no_pp = getenv("AMTX_GEMM_NO_PP") != nullptr;
-        // measured on MI355X (tools/bench_gemm.py, M = 320000, N = 1024): K = 512: 0.49 ms vs 0.53 (two 64-deep buffers);
-        // K = 192: 0.255 vs 0.271 ms; K = 3648 (N = 512): 1.21 vs 1.20 ms.  (Round 5: 128 x 128 tiles, two blocks per CU, for the short K: 0.356 /
-        // 0.611 ms -- worse.)
-        if (!no_pp && (force_pp || g.K <= 1024) && g.n_pad % 256 == 0 && g.N % 256 == 0 && g.M >= 256 && g.n_pad <= RING_MAX_NPAD &&
-            g.K >= 4 * RBK && (g.ldc * amtx_tsize(g.c_type)) % 16 == 0)
-            return g.c_type == AMTX_T_BF16 ? launch_pp<AMTX_T_BF16>(g, stream) : launch_pp<AMTX_T_F32>(g, stream);
-        if (g.n_pad % 256 == 0 && g.N % 256 == 0 && g.M >= 256)
-            return g.c_type == AMTX_T_BF16 ? launch_glds<AMTX_T_BF16, 256>(g, stream) : launch_glds<AMTX_T_F32, 256>(g, stream);
-        return g.c_type == AMTX_T_BF16 ? launch_glds<AMTX_T_BF16, 128>(g, stream) : launch_glds<AMTX_T_F32, 128>(g, stream);
+    const bool c16 = g.c_type == AMTX_T_BF16;
+    switch (r.route) {
+        case ROUTE_ERROR: amtx_set_error("%s", r.error); return AMTX_ERR_ARG;
+        case ROUTE_SKINNY: case ROUTE_SKINNY_SPLIT: return launch_skinny(g, stream, r.route == ROUTE_SKINNY_SPLIT);
+        case ROUTE_GLDS256: return c16 ? launch_glds<AMTX_T_BF16, 256>(g, stream) : launch_glds<AMTX_T_F32, 256>(g, stream);
+        case ROUTE_GLDS128: return c16 ? launch_glds<AMTX_T_BF16, 128>(g, stream) : launch_glds<AMTX_T_F32, 128>(g, stream);
+        case ROUTE_PP: return c16 ? launch_pp<AMTX_T_BF16>(g, stream) : launch_pp<AMTX_T_F32>(g, stream);
+        case ROUTE_SPLIT: return g.c_type == AMTX_T_SPLIT ? launch_split<AMTX_T_SPLIT>(g, stream) : launch_split<AMTX_T_F32>(g, stream);
+        case ROUTE_GENERIC: break;
     }
-    AMTX_REQUIRE(!g.a_plane, "gemm: planar A exists on the bf16 direct-to-LDS path only");
-    if (g.a_type == AMTX_T_SPLIT) {
-        AMTX_REQUIRE(g.planes == 2 && g.a_split > 0 && (g.a_split % 8) == 0, "gemm: two-plane A needs two-plane weights and a plane stride that keeps 16-byte alignment");
-        AMTX_REQUIRE(g.c_type != AMTX_T_SPLIT || (g.c_split > 0 && (g.c_split % 8) == 0), "gemm: two-plane C needs a plane stride");
-        AMTX_REQUIRE(!g.pair_map && !g.roll_out && !g.copy16 && g.C, "gemm: two-plane A has the plain epilogues only");
-        // the direct-to-LDS two-plane kernel: whole 256-column tiles, whole 32-deep stages of real A columns
-        static const bool no_split_dma = getenv("AMTX_GEMM_NO_SPLIT_DMA") != nullptr;   // A/B switch: the generic kernel on the same planes
-        // C rows are stored 16 bytes at a time: fp32 C needs ldc % 4 == 0, the 2-byte planes of a two-plane C need ldc % 8 == 0 and a plane
-        // stride that keeps the second plane 16-byte aligned; anything else takes the generic kernel (8-byte stores)
-        const bool c_aligned = g.c_type == AMTX_T_SPLIT ? ((g.ldc * 2) % 16 == 0 && (g.c_split % 8) == 0) : ((g.ldc * 4) % 16 == 0);
-        if (!no_split_dma && g.n_pad % 256 == 0 && g.N % 256 == 0 && g.M >= 256 && g.K == g.k_pad && (g.lda % 8) == 0 && g.c_type != AMTX_T_BF16 &&
-            c_aligned)
-            return g.c_type == AMTX_T_SPLIT ? launch_split<AMTX_T_SPLIT>(g, stream) : launch_split<AMTX_T_F32>(g, stream);
-        AMTX_REQUIRE(g.c_type != AMTX_T_BF16, "gemm: two-plane A writes fp32 or two-plane C");
-        // skinny N (the x3 LogisticBanks and pitch head): the two-plane variant of gemm_skinny_kernel
-        static const bool no_skinny2 = getenv("AMTX_GEMM_NO_SKINNY") != nullptr;
-        if (!no_skinny2 && !no_split_dma && g.n_pad == 128 && g.c_type == AMTX_T_F32 && g.M >= 1024 && g.K == g.k_pad && g.K >= 2 * RBK && (g.lda % 8) == 0 &&
-            g.M < (1ll << 31) * 256)
-            return launch_skinny(g, stream, true);
-        return g.c_type == AMTX_T_SPLIT ? launch<AMTX_T_SPLIT, AMTX_T_SPLIT, 2>(g, stream) : launch<AMTX_T_SPLIT, AMTX_T_F32, 2>(g, stream);
-    }
-    AMTX_REQUIRE(g.c_type != AMTX_T_SPLIT, "gemm: two-plane C needs two-plane A");
+    if (g.a_type == AMTX_T_SPLIT) return g.c_type == AMTX_T_SPLIT ? launch<AMTX_T_SPLIT, AMTX_T_SPLIT, 2>(g, stream) : launch<AMTX_T_SPLIT, AMTX_T_F32, 2>(g, stream);
     const int key = (g.a_type << 2) | (g.c_type << 1) | (g.planes - 1);
     switch (key) {
         case 0: return launch<AMTX_T_BF16, AMTX_T_BF16, 1>(g, stream);

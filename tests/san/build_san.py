@@ -15,7 +15,10 @@ CSRC = os.path.join(ROOT, 'amt_tools_amd', 'csrc')
 OUT = os.path.join(HERE, '_build')
 LIB = os.path.join(OUT, 'libamtx_san.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-SAN = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g', '-O1']
+# -fno-sanitize=function: a kernel launched through a variable (`auto kern = some_kernel<...>; hipLaunchKernelGGL(kern, ...)`) is a call through
+# the kernel's HANDLE, a constant that is no function; the function-type check reads in front of it, and the optimizer then drops the whole
+# launch -- the host code behind it would run as if the kernel had been launched, with neither the shim's "no device" nor a trace record
+SAN = ['-fsanitize=address,undefined', '-fno-sanitize=function', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g', '-O1']
 
 
 def asan_runtime():

@@ -8,7 +8,13 @@ With a second argument it also writes, as JSON, what the engine DECIDES and PACK
 the bytes amtx_of_model_finalize uploads (the shim's hipMemcpy sees them), and for those plus a grid of small models -- model_complexity
 2 .. 5 x input channels x precision x offset head x each create-time A/B switch (thinned at model_complexity 4 and 5) -- the answers of the query entry points, the workspace
 sizes and the device re-sync's support check.  tests/golden/of_conv_plan.json is that file as the commit before the ConvPlan refactor
-wrote it; tests/test_sanitized_host.py requires every row of it back."""
+wrote it; tests/test_sanitized_host.py requires every row of it back.
+
+With a third argument it does none of that: it writes, as JSON, the LAUNCH TRACE -- the shim records every kernel launch (name, grid,
+block, dynamic LDS bytes) instead of refusing it -- of a grid of GEMM problems through amtx_linear_fwd / amtx_linear_fwd_split and of whole
+forward passes of the engine configurations.  The A/B switches of the launchers are sampled once per process: tests/san/launch_trace.py
+runs this mode once per switch and tests/golden/launch_trace.json is what it recorded on the commit before gemm.hip's routing became
+one function."""
 import ctypes as C
 import importlib.util
 import json
@@ -54,6 +60,106 @@ def plan_row(h, cfg, switch):
            [L.amtx_of_conv_stack_fused(h, B, T) for B, T in PLAN_BT] + [L.amtx_of_workspace_bytes(h, B, T) for B, T in PLAN_BT] + [rc, err]
 
 
+# the engine configurations: (input bins, input channels, model_complexity, offset head, precision bf16 / x3 / f16)
+configs = [dict(dim_in=229, ch=1, mc=2, off=0, prec=0), dict(dim_in=229, ch=1, mc=2, off=0, prec=1), dict(dim_in=229, ch=1, mc=2, off=0, prec=2),
+           dict(dim_in=229, ch=1, mc=3, off=1, prec=0), dict(dim_in=229, ch=1, mc=3, off=0, prec=1), dict(dim_in=72, ch=6, mc=2, off=0, prec=0),
+           dict(dim_in=72, ch=6, mc=3, off=1, prec=1), dict(dim_in=72, ch=6, mc=2, off=0, prec=2), dict(dim_in=229, ch=1, mc=3, off=1, prec=2), dict(dim_in=8, ch=1, mc=2, off=1, prec=0), dict(dim_in=40, ch=1, mc=2, off=0, prec=2),
+           dict(dim_in=5, ch=1, mc=2, off=0, prec=0), dict(dim_in=192, ch=2, mc=2, off=0, prec=0)]
+
+
+def make_model(cfg):
+    """amtx_of_model_create + set_tensor with synthetic weights; the caller finalizes and destroys."""
+    h = C.c_void_p()
+    _lib.check(L.amtx_of_model_create(C.byref(h), cfg['dim_in'], cfg['ch'], cfg['mc'], 88, cfg['off'], cfg['prec']), 'create')
+    sd = synth.synth_state_dict(3, dim_in=cfg['dim_in'], in_channels=cfg['ch'], model_complexity=cfg['mc'], offsets=bool(cfg['off']))
+    for k, v in sd.items():
+        a = np.ascontiguousarray(np.asarray(v), dtype=np.float32)
+        if a.dtype.kind != 'f' or a.size == 0 or 'num_batches_tracked' in k:
+            continue
+        _lib.check(L.amtx_of_model_set_tensor(h, k.encode(), P(a), a.size), 'set_tensor')
+    return h
+
+
+# ---------------------------------------------------------------- launch trace (a third argument: instead of everything below)
+GEMM_M = (1, 255, 256, 1023, 1024, 4096)
+GEMM_N = (4, 88, 128, 256, 512, 1024, 2048)
+GEMM_K = (8, 64, 128, 176, 192, 512, 1024, 1088, 3648)
+TRACE_BT = ((2, 9), (3, 17), (130, 47), (43, 140))
+TRACE_BIG = (1024, 625)          # configs[0] only: the fused stack, the 256-tile, ring and skinny GEMMs, planar A
+
+
+def traced(call):
+    """[return code, error text, launches] of one library call with the shim recording: nothing runs, every launch "succeeds"."""
+    L.amtx_san_trace_begin()
+    rc = call()
+    return [rc, L.amtx_last_error().decode() if rc else '', L.amtx_san_trace_take().decode().splitlines()]
+
+
+def reserve(nbytes):
+    """Address space nothing may touch (the launches do not run): untouched pages of an anonymous mapping cost no memory."""
+    import mmap
+    mm = mmap.mmap(-1, nbytes + 256, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS | getattr(mmap, 'MAP_NORESERVE', 0x4000))
+    return mm, (C.addressof(C.c_char.from_buffer(mm)) + 255) // 256 * 256
+
+
+def trace_gemm():
+    """amtx_linear_fwd / amtx_linear_fwd_split over the whole M x N x K x lda x type grid (one call is microseconds: no thinning).  The
+    pointers are one 16-byte aligned address: routing looks at alignment only."""
+    buf = np.empty(64, np.uint8)
+    p = C.c_void_p((buf.ctypes.data + 15) // 16 * 16)
+    rows = []
+    for m in GEMM_M:
+        for n in GEMM_N:
+            for k in GEMM_K:
+                for lda in (k, k + 8):
+                    for a_type in (0, 1, 2):
+                        for c_type in (0, 1, 2):
+                            for planes in (1, 2):
+                                rows.append(traced(lambda: L.amtx_linear_fwd(p, lda, a_type, p, planes, p, p, n, c_type, m, n, k, None)))
+                    for c_type in (0, 1, 2):
+                        rows.append(traced(lambda: L.amtx_linear_fwd_split(p, lda, m * lda, p, p, p, n, c_type, m * n, m, n, k, None)))
+    return rows
+
+
+def trace_engine():
+    """Every launch of amtx_of_forward (and _power / _feats16 where the model takes them), with all outputs and with the rolls only."""
+    seqs = {}
+    for cfg in configs:
+        h = make_model(cfg)
+        _lib.check(L.amtx_of_model_finalize(h), 'finalize')
+        F, ch = cfg['dim_in'], cfg['ch']
+        for B, T in TRACE_BT + ((TRACE_BIG,) if cfg is configs[0] else ()):
+            need = L.amtx_of_workspace_bytes(h, B, T)
+            fbytes, obytes = max(B * ch * T * F * 4, 2 * B * T * F * 8 * 2), B * 88 * T * 4
+            big = (B, T) == TRACE_BIG
+            if big:         # never touched: no output copies are asked for at this size
+                keep, base = reserve(need + fbytes + 2 * obytes + 1024)
+                ws, feats, outs = base, base + (need + 255) // 256 * 256, [base + (need + fbytes + 511) // 256 * 256 + i * obytes for i in range(2)]
+            else:           # zeroed host memory: the logit copies of the shim are real, and instrumented
+                keep = [np.zeros(need + 256, np.uint8), np.zeros(fbytes, np.uint8)] + [np.zeros(obytes, np.uint8) for _ in range(5)]
+                ws, feats, outs = (keep[0].ctypes.data + 255) // 256 * 256, keep[1].ctypes.data, [a.ctypes.data for a in keep[2:]]
+            ws, feats = C.c_void_p(ws), C.c_void_p(feats)
+            for what in ('rolls',) if big else ('all', 'rolls'):
+                o = [C.c_void_p(x) for x in outs] if what == 'all' else [C.c_void_p(x) for x in outs[:2]] + [None] * 3
+                name = '%d/%d/%d/%d/%d %dx%d %s ' % (F, ch, cfg['mc'], cfg['off'], cfg['prec'], B, T, what)
+                seqs[name + 'forward'] = traced(lambda: L.amtx_of_forward(h, feats, ch * T * F, T * F, F, 1, B, T, ws, need, *o, None))
+                if L.amtx_of_fuses_db_scale(h):
+                    seqs[name + 'power'] = traced(lambda: L.amtx_of_forward_power(h, feats, T * F, F, 1, feats, None, B, T, ws, need, *o, None))
+                if L.amtx_of_takes_feats16(h):
+                    seqs[name + 'feats16'] = traced(lambda: L.amtx_of_forward_feats16(h, feats, B, T, ws, need, *o, None))
+            del keep
+        _lib.check(L.amtx_of_model_destroy(h))
+    return seqs
+
+
+if len(sys.argv) > 3:
+    L.amtx_san_trace_begin.restype, L.amtx_san_trace_begin.argtypes = None, []
+    L.amtx_san_trace_take.restype, L.amtx_san_trace_take.argtypes = C.c_char_p, []
+    with open(sys.argv[3], 'w') as f:
+        json.dump({'gemm': trace_gemm(), 'engine': trace_engine()}, f)
+    print('launch trace written')
+    sys.exit(0)
+
 plan_rows, upload_hashes = [], []
 
 # ---------------------------------------------------------------- weight packers (op-level C ABI)
@@ -90,21 +196,8 @@ for planes in (1, 2):
     n_calls += 1
 
 # ---------------------------------------------------------------- engine: create / set_tensor / finalize / workspace / argument checks
-configs = [dict(dim_in=229, ch=1, mc=2, off=0, prec=0), dict(dim_in=229, ch=1, mc=2, off=0, prec=1), dict(dim_in=229, ch=1, mc=2, off=0, prec=2),
-           dict(dim_in=229, ch=1, mc=3, off=1, prec=0), dict(dim_in=229, ch=1, mc=3, off=0, prec=1), dict(dim_in=72, ch=6, mc=2, off=0, prec=0),
-           dict(dim_in=72, ch=6, mc=3, off=1, prec=1), dict(dim_in=72, ch=6, mc=2, off=0, prec=2), dict(dim_in=229, ch=1, mc=3, off=1, prec=2), dict(dim_in=8, ch=1, mc=2, off=1, prec=0), dict(dim_in=40, ch=1, mc=2, off=0, prec=2),
-           dict(dim_in=5, ch=1, mc=2, off=0, prec=0), dict(dim_in=192, ch=2, mc=2, off=0, prec=0)]
 for cfg in configs:
-    h = C.c_void_p()
-    _lib.check(L.amtx_of_model_create(C.byref(h), cfg['dim_in'], cfg['ch'], cfg['mc'], 88, cfg['off'], cfg['prec']), 'create')
-    sd = synth.synth_state_dict(3, dim_in=cfg['dim_in'], in_channels=cfg['ch'], model_complexity=cfg['mc'], offsets=bool(cfg['off']))
-    keep = []
-    for k, v in sd.items():
-        a = np.ascontiguousarray(np.asarray(v), dtype=np.float32)
-        if a.dtype.kind != 'f' or a.size == 0 or 'num_batches_tracked' in k:
-            continue
-        keep.append(a)
-        _lib.check(L.amtx_of_model_set_tensor(h, k.encode(), P(a), a.size), 'set_tensor')
+    h = make_model(cfg)
     L.amtx_san_upload_hash_take()
     _lib.check(L.amtx_of_model_finalize(h), 'finalize')
     upload_hashes.append([cfg['dim_in'], cfg['ch'], cfg['mc'], cfg['off'], cfg['prec'], '%016x' % L.amtx_san_upload_hash_take()])

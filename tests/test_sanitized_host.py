@@ -56,3 +56,32 @@ def test_engine_decisions_and_packed_weights_are_those_of_the_recorded_table(dri
         assert len(got[key]) == len(want[key])
         wrong = [(g, w) for g, w in zip(got[key], want[key]) if g != w]
         assert not wrong, (key, len(wrong), wrong[:5])
+
+
+def test_kernel_launches_are_those_of_the_recorded_trace():
+    """tests/golden/launch_trace.json was recorded by tests/san/launch_trace.py on the commit BEFORE the GEMM launcher's routing became one
+    function (gemm.hip: gemm_validate, gemm_route) and the doubled switches of conv.hip and convg.hip one accessor each.  With the shim
+    recording launches (kernel name, grid, block, dynamic LDS bytes) instead of refusing them, once per A/B switch of those three files in
+    a child process of its own: the return code, error text and launch of amtx_linear_fwd / amtx_linear_fwd_split over
+    M {1, 255, 256, 1023, 1024, 4096} x N {4, 88, 128, 256, 512, 1024, 2048} x K {8, 64, 128, 176, 192, 512, 1024, 1088, 3648} x
+    lda {K, K + 8} x (A type x C type x weight planes | two-plane A x C type), and every launch of amtx_of_forward, _power and _feats16 for
+    the driver's thirteen engine configurations at (batch, frames) (2, 9), (3, 17), (130, 47), (43, 140), all outputs and rolls only, plus
+    the bf16 model_complexity 2 configuration at (1024, 625), rolls only.  Every row and every sequence has to come back."""
+    import build_san
+    import launch_trace
+    if not os.path.exists(build_san.HIPCC):
+        pytest.skip('no hipcc: the sanitizer build needs the ROCm clang')
+    env = dict(os.environ, LD_PRELOAD=build_san.asan_runtime(), ASAN_OPTIONS='detect_leaks=0:abort_on_error=1:halt_on_error=1',
+               UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
+    got = launch_trace.record(build_san.build(), env)
+    with open(os.path.join(ROOT, 'tests', 'golden', 'launch_trace.json')) as f:
+        want = launch_trace.expand(json.load(f))
+    assert tuple(want) == launch_trace.SWITCHES == tuple(got)
+    for switch in launch_trace.SWITCHES:
+        g, w = got[switch], want[switch]
+        assert len(w['gemm']) == 15876 and len(w['engine']) == 170
+        assert len(g['gemm']) == len(w['gemm']) and list(g['engine']) == list(w['engine'])
+        wrong = [(i, a, b) for i, (a, b) in enumerate(zip(g['gemm'], w['gemm'])) if a != b]
+        assert not wrong, (switch, 'gemm rows (index, got, want)', len(wrong), wrong[:5])
+        wrong = [(k, g['engine'][k], b) for k, b in w['engine'].items() if g['engine'][k] != b]
+        assert not wrong, (switch, 'engine sequences (name, got, want)', len(wrong), wrong[:2])
