@@ -107,6 +107,8 @@ _SIGNATURES = {
     'amtx_spec_mel_layout': (_I, [_I, _I, _I, _I, _P, _P, _P]),
     'amtx_notes_decode': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     'amtx_notes_rows': (_I, [_P, _P, _I, _I, _I, _P, _L, _I, _P, _P, _L, _P, _P]),
+    'amtx_tab_expand': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    'amtx_tab_notes': (_I, [_P, _I, _I, _I, _P, _I, _P, _L, _P, _L, _I, C.c_double, _P, _L, _P, _P]),
     'amtx_pianoroll_fwd': (_I, [_P, _L, _I, _I, _I, _I, _F, _P, _P]),
     'amtx_matmul_workspace_bytes': (C.c_size_t, [_L, _L, _L]),
     'amtx_matmul_f32': (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _L, _L, _L, _L, _P, C.c_size_t, _P]),

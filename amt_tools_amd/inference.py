@@ -41,7 +41,9 @@ def _frame_times(model, num_frames):
 def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=1, decode_notes=False, keep=None):
     """clips: (num_clips, N) float32 -- or int16 PCM -- array / CPU tensor of equally long clips (the model needs a front-end in
     `model.frontend`) or (num_clips, C, F, T) features.  Returns {clip index: predictions dict} for the clips
-    this rank owns.  With decode_notes=True the note lists are decoded on the device (amtx_notes_decode).
+    this rank owns.  With decode_notes=True the note lists are decoded on the device (amtx_notes_decode; a model whose output is a
+    tablature, TabCNN: stacked notes {string: (pitches, intervals)} from amtx_tab_notes, and `keep` may name KEY_MULTIPITCH for the
+    collapsed pitch map of the tablature).
     `keep`: keys of the model output to bring back to the host (default: every array; () = notes only).
 
     On a GPU model the loop is a three-stage pipeline: batch i+1 is uploaded on a copy stream (from pinned memory) while batch
@@ -119,7 +121,19 @@ def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=
             nxt = stage(mine[starts[n + 1]:starts[n + 1] + batch_size])
         preds = model.run_on_batch({key: data})
         handle = None
-        if decode_notes:
+        if decode_notes and tools.KEY_MULTIPITCH not in preds and tools.KEY_TABLATURE in preds:
+            # tablature models (TabCNN): stacked notes per string straight from the tablature (amtx_tab_notes), the collapsed multi-pitch
+            # map only on request (amtx_tab_expand: 44 pitch rows per 6 tablature rows); CPU tablatures take the host estimators
+            from . import transcribe
+            tab = preds[tools.KEY_TABLATURE]
+            t = times if times is not None else _frame_times(model, tab.shape[-1])
+            handle = transcribe.decode_tab_notes_batch_async(tab, t, model.profile)
+            if keep is not None and tools.KEY_MULTIPITCH in keep:
+                if tab.is_cuda:
+                    preds[tools.KEY_MULTIPITCH] = tools.tab_expand(tab, model.profile, stacked=False, collapsed=True)[1]
+                else:
+                    preds[tools.KEY_MULTIPITCH] = tools.stacked_multi_pitch_to_multi_pitch(tools.tablature_to_stacked_multi_pitch(tab, model.profile))
+        elif decode_notes:
             T = preds[tools.KEY_MULTIPITCH].shape[-1]
             t = times if times is not None else _frame_times(model, T)
             if preds[tools.KEY_MULTIPITCH].is_cuda:

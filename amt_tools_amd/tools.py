@@ -238,6 +238,69 @@ def multi_pitch_to_offsets(multi_pitch):
     return offsets
 
 
+# ---- tablature -> pitch maps / stacked notes (the guitar estimators' arithmetic) --------------------
+def _tab_geometry(profile):
+    """(dof_start (S,), classes per string, pitch rows of the map) of a TablatureProfile (tools/utils.py:2013-2025)."""
+    dof_start = np.asarray(profile.get_midi_tuning(), dtype=np.int64) - profile.low
+    return dof_start, int(profile.num_pitches), int(profile.get_range_len())
+
+
+def tab_expand(tablature, profile, stacked=True, collapsed=False):
+    """Device path of the two functions below in ONE pass (amtx_tab_expand, csrc/tabnotes.hip): (..., S, T) int64 CUDA tablature ->
+    (stacked (..., S, P, T) or None, collapsed (..., P, T) or None), fp32 like every other map the engines hand out.  Raises AmtxError
+    when a class of the profile would land outside the map (or for more strings than the kernel is built for: no fallback here)."""
+    from . import _lib
+    assert tablature.is_cuda and tablature.dtype == torch.int64 and tablature.dim() >= 2 and (stacked or collapsed)
+    dof_start, num_classes, P = _tab_geometry(profile)
+    lead, (S, T) = tuple(tablature.shape[:-2]), tablature.shape[-2:]
+    assert S == len(dof_start), (S, len(dof_start))
+    B = int(np.prod(lead)) if lead else 1
+    tab = tablature.contiguous()
+    dev = tab.device
+    st = torch.empty(lead + (S, P, T), dtype=torch.float32, device=dev) if stacked else None
+    co = torch.empty(lead + (P, T), dtype=torch.float32, device=dev) if collapsed else None
+    if B * S * T > 0:
+        start = np.ascontiguousarray(dof_start, dtype=np.int32)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().amtx_tab_expand(_lib.ptr(tab), B, S, T, _lib.ptr(start), num_classes, P, _lib.ptr(st), _lib.ptr(co),
+                                                  _lib.current_stream(dev)), 'amtx_tab_expand')
+    return st, co
+
+
+def tablature_to_stacked_multi_pitch(tablature, profile):
+    """(..., S, T) classes per string and frame, -1 = silent -> (..., S, P, T) one-hot pitch maps over the profile's whole range
+    (amt_tools/tools/utils.py:1988-2059).  ndarray -> float64 ndarray, tensor -> tensor of the tablature's dtype, as in the reference;
+    an int64 CUDA tablature (what TabCNN's engine returns) goes through the HIP kernel and comes back as fp32."""
+    dof_start, _, P = _tab_geometry(profile)
+    if torch is not None and isinstance(tablature, torch.Tensor):
+        if tablature.is_cuda and tablature.dtype == torch.int64:
+            return tab_expand(tablature, profile, stacked=True)[0]
+        start = torch.as_tensor(dof_start, device=tablature.device).unsqueeze(-1)
+        rows = torch.where(tablature >= 0, tablature.long() + start, torch.full_like(tablature, -1, dtype=torch.int64))
+        hit = rows.unsqueeze(-2) == torch.arange(P, device=tablature.device).unsqueeze(-1)
+        return hit.to(tablature.dtype)
+    tablature = np.asarray(tablature)
+    rows = np.where(tablature >= 0, tablature.astype(np.int64) + dof_start[:, None], -1)
+    return (rows[..., None, :] == np.arange(P)[:, None]).astype(np.float64)
+
+
+def stacked_multi_pitch_to_multi_pitch(stacked_multi_pitch):
+    """(..., S, P, T) -> (..., P, T): the maximum over the strings (amt_tools/tools/utils.py:1787-1815)."""
+    if torch is not None and isinstance(stacked_multi_pitch, torch.Tensor):
+        return torch.max(stacked_multi_pitch, dim=-3)[0]
+    return np.max(stacked_multi_pitch, axis=-3)
+
+
+def notes_to_stacked_notes(pitches, intervals, key=0):
+    """{key: (pitches (N,), intervals (N, 2))} sorted by onset the reference's way: through an (N, 3) float64 array and NumPy's default
+    argsort (amt_tools/tools/utils.py:719-746, sort_notes :2713-2746); no notes -> shapes (0,) and (0, 2)."""
+    batched = np.empty([0, 3])
+    if len(pitches) > 0:
+        batched = np.concatenate((intervals, np.expand_dims(pitches, axis=-1)), axis=-1)
+    batched = batched[np.argsort(batched[..., 0])]
+    return {key: (batched[..., 2], batched[:, :2])}
+
+
 def rms_norm(audio):
     """Root-mean-square normalisation (amt_tools/tools/utils.py:2789-2814)."""
     rms = np.sqrt(np.mean(audio ** 2))

@@ -9,6 +9,10 @@ that the paper scripts attach to Onsets & Frames (examples/papers/of_1.py:150-15
   The per-event Python `while` walk is replaced by a vectorised next-stop scan (host arrays) or by the HIP kernel
   behind `amtx_notes_decode` (device tensors, whole batches: `decode_notes_batch`).
 * `PitchListWrapper.estimate` -- amt_tools/transcribe.py:1038-1071, tools.multi_pitch_to_pitch_list utils.py:1023-1062.
+* The guitar pipeline of examples/papers/tabcnn.py:90-91 -- `ComboEstimator` (transcribe.py:88-128), `TablatureWrapper` (:1097-1145),
+  `StackedMultiPitchCollapser` (:1173-1201) -- and `StackedNoteTranscriber` (:373-481) for note lists per string.  On TabCNN's
+  device output the maps come from `amtx_tab_expand` and the notes straight from the tablature (`decode_tab_notes_batch_async`,
+  `amtx_tab_notes`: on one string a note is a run of one class), bit-exact with the host classes.
 
 The reference's own estimators keep working on this package's model output unchanged; these classes exist so a
 batched offline driver (BASELINE config 5) does not spend its time in per-note Python loops.
@@ -18,7 +22,9 @@ import numpy as np
 
 from . import _lib, tools
 
-__all__ = ['NoteTranscriber', 'PitchListWrapper', 'multi_pitch_to_notes', 'decode_notes_batch', 'estimate_hop_length', 'inhibit_activations']
+__all__ = ['NoteTranscriber', 'PitchListWrapper', 'multi_pitch_to_notes', 'decode_notes_batch', 'estimate_hop_length', 'inhibit_activations',
+           'ComboEstimator', 'TablatureWrapper', 'StackedMultiPitchCollapser', 'StackedNoteTranscriber', 'decode_tab_notes_batch_async',
+           'decode_tab_notes_batch']
 
 
 def estimate_hop_length(times):
@@ -52,11 +58,13 @@ def _extend_times(times):
     return np.append(times, times[-1] + estimate_hop_length(times))
 
 
-def _events_to_notes(pitch_idcs, on_frames, off_frames, times, low, times_ext=None, min_duration=None):
+def _events_to_notes(pitch_idcs, on_frames, off_frames, times, low, times_ext=None, min_duration=None, sorts=3):
     """(key, onset frame, offset frame) events in np.nonzero order -> (K,3) rows ordered like the reference.
     `times_ext` = _extend_times(times) when the caller already has it (one grid shared by a whole batch).
     `min_duration`: the reference's duration filter (transcribe.py:36-80), which sits between its first and second sort:
-    notes shorter than the threshold go (threshold 0: zero-length notes go)."""
+    notes shorter than the threshold go (threshold 0: zero-length notes go).
+    `sorts`: how many of the reference's argsorts the caller's pipeline runs -- three for NoteTranscriber, two for
+    StackedNoteTranscriber (multi_pitch_to_notes and notes_to_stacked_notes; no stacked_notes_to_notes)."""
     if times_ext is None:
         times_ext = _extend_times(times)
     if len(pitch_idcs) == 0:
@@ -74,7 +82,7 @@ def _events_to_notes(pitch_idcs, on_frames, off_frames, times, low, times_ext=No
         perm = perm[dur >= min_duration] if min_duration else perm[dur > min_duration]
         if len(perm) == 0:
             return np.empty([0, 3])
-    for _ in range(2):
+    for _ in range(sorts - 1):
         perm = perm[np.argsort(onset_t[perm])]
     batched = np.empty((len(perm), 3))
     batched[:, 0] = onset_t[perm]
@@ -103,7 +111,7 @@ def inhibit_activations(activations, times, window_length):
     return out
 
 
-def multi_pitch_to_notes(multi_pitch, times, low=tools.DEFAULT_PIANO_LOWEST_PITCH, onsets=None, min_duration=None):
+def multi_pitch_to_notes(multi_pitch, times, low=tools.DEFAULT_PIANO_LOWEST_PITCH, onsets=None, min_duration=None, sorts=3):
     """Vectorised tools.multi_pitch_to_notes for host arrays: returns (K,3) batched notes."""
     multi_pitch = np.asarray(multi_pitch)
     if onsets is None:
@@ -119,7 +127,8 @@ def multi_pitch_to_notes(multi_pitch, times, low=tools.DEFAULT_PIANO_LOWEST_PITC
     nearest = np.minimum.accumulate(idx[..., ::-1], axis=-1)[..., ::-1]          # nearest stop at >= t
     after = np.concatenate([nearest[..., 1:], np.full(nearest.shape[:-1] + (1,), T)], axis=-1)   # strictly after t
     pitch_idcs, frame_idcs = imp.nonzero()
-    return _events_to_notes(pitch_idcs, frame_idcs, after[pitch_idcs, frame_idcs], np.asarray(times), low, min_duration=min_duration)
+    return _events_to_notes(pitch_idcs, frame_idcs, after[pitch_idcs, frame_idcs], np.asarray(times), low, min_duration=min_duration,
+                            sorts=sorts)
 
 
 from ._order_pool import order_batch, reference_order as _reference_order     # noqa: E402  (the reference's three unstable argsorts)
@@ -286,3 +295,215 @@ class PitchListWrapper(object):
 
     def process_track(self, raw_output, track=None):
         return {self.get_key(): self.estimate(raw_output)}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Guitar: tablature -> stacked multi-pitch -> multi-pitch / stacked notes
+# ------------------------------------------------------------------------------------------------------------------------------
+class ComboEstimator(object):
+    """Several estimators in succession, each fed the dict updated by the ones before it (amt_tools/transcribe.py:88-128)."""
+
+    def __init__(self, estimators):
+        self.estimators = estimators
+
+    def process_track(self, raw_output, track=None):
+        output = dict(raw_output)              # the caller's dict is not touched (the reference deep-copies; nothing here mutates an entry)
+        for estimator in self.estimators:
+            output.update(estimator.process_track(output, track))
+        return output
+
+
+class _Estimator(object):
+    """What the estimators below share (amt_tools/transcribe.py:170-308).  `save_dir` is accepted; nothing is written."""
+
+    def __init__(self, profile, estimates_key=None, save_dir=None):
+        self.profile = profile
+        self.estimates_key = self.get_default_key() if estimates_key is None else estimates_key
+        self.save_dir = save_dir
+
+    @staticmethod
+    def get_default_key():
+        return tools.KEY_MULTIPITCH
+
+    def get_key(self):
+        return self.estimates_key
+
+    def process_track(self, raw_output, track=None):
+        return {self.estimates_key: self.estimate(raw_output)}
+
+
+class TablatureWrapper(_Estimator):
+    """Tablature (S, T) -> stacked multi-pitch (S, P, T) (amt_tools/transcribe.py:1097-1145)."""
+
+    def __init__(self, profile, tablature_key=None, estimates_key=None, save_dir=None):
+        super().__init__(profile, estimates_key, save_dir)
+        self.tablature_key = tools.KEY_TABLATURE if tablature_key is None else tablature_key
+
+    def estimate(self, raw_output):
+        return tools.tablature_to_stacked_multi_pitch(tools.unpack_dict(raw_output, self.tablature_key), self.profile)
+
+
+class StackedMultiPitchCollapser(_Estimator):
+    """Stacked multi-pitch (S, P, T) -> multi-pitch (P, T).  `stacked_key` defaults to the estimates key, so behind a TablatureWrapper the
+    stacked map is replaced by its collapse (amt_tools/transcribe.py:1148-1201)."""
+
+    def __init__(self, profile, stacked_key=None, estimates_key=None, save_dir=None):
+        super().__init__(profile, estimates_key, save_dir)
+        self.stacked_key = self.estimates_key if stacked_key is None else stacked_key
+
+    def estimate(self, raw_output):
+        return tools.stacked_multi_pitch_to_multi_pitch(tools.unpack_dict(raw_output, self.stacked_key))
+
+
+class StackedNoteTranscriber(_Estimator):
+    """Stacked multi-pitch (S, P, T) + times -> {slice: (pitches (N,), intervals (N, 2))} in float64 (amt_tools/transcribe.py:373-481):
+    per slice NoteTranscriber's decoding with two of its three sorts by onset.  Options as in NoteTranscriber above."""
+
+    def __init__(self, profile, inhibition_window=None, minimum_duration=None, multi_pitch_key=None, onsets_key=None,
+                 offsets_key=None, estimates_key=None, save_dir=None):
+        super().__init__(profile, estimates_key, save_dir)
+        self.inhibition_window = inhibition_window
+        self.minimum_duration = minimum_duration
+        self.multi_pitch_key = tools.KEY_MULTIPITCH if multi_pitch_key is None else multi_pitch_key
+        self.onsets_key = tools.KEY_ONSETS if onsets_key is None else onsets_key
+        self.offsets_key = tools.KEY_OFFSETS if offsets_key is None else offsets_key
+
+    @staticmethod
+    def get_default_key():
+        return tools.KEY_NOTES
+
+    def estimate(self, raw_output):
+        stacked = tools.tensor_to_array(tools.unpack_dict(raw_output, self.multi_pitch_key))
+        stacked_onsets = tools.tensor_to_array(tools.unpack_dict(raw_output, self.onsets_key))
+        times = tools.tensor_to_array(tools.unpack_dict(raw_output, tools.KEY_TIMES))
+        stacked_notes = dict()
+        for slc in range(stacked.shape[-3]):
+            multi_pitch = np.asarray(stacked[slc])
+            onsets = None if stacked_onsets is None else stacked_onsets[slc]
+            if self.inhibition_window is not None and onsets is None:
+                onsets = inhibit_activations(_impulses(multi_pitch).astype(multi_pitch.dtype), times, self.inhibition_window)
+            rows = multi_pitch_to_notes(multi_pitch, times, self.profile.low, onsets, self.minimum_duration, sorts=2)
+            stacked_notes[slc] = (rows[..., 2], rows[:, :2])
+        return stacked_notes
+
+
+def _tab_to_stacked_notes_host(tablature, times, profile, inhibition_window=None, minimum_duration=None):
+    """One track on the host: (S, T) tablature -> stacked notes through the classes above."""
+    raw = {tools.KEY_MULTIPITCH: tools.tablature_to_stacked_multi_pitch(np.asarray(tablature), profile), tools.KEY_TIMES: np.asarray(times)}
+    return StackedNoteTranscriber(profile, inhibition_window, minimum_duration).estimate(raw)
+
+
+_RELEASE = {}      # (grid dtype, grid digest, window) -> int32 release table of amtx_tab_notes
+
+
+def _release_table(times, window):
+    """release[t] = first frame after t outside the inhibition window of an onset at frame t: the expression of inhibit_activations above,
+    evaluated once per frame of the grid (NumPy scalars and all: the grid's dtype decides how `time + window` rounds), then the same
+    max(release, t + 1).  Computed once per distinct (grid, window)."""
+    import hashlib
+    times = np.ascontiguousarray(times)
+    key = (times.dtype.str, times.shape, hashlib.blake2b(times.view(np.uint8).reshape(-1), digest_size=16).digest(), repr(window))
+    table = _RELEASE.get(key)
+    if table is None:
+        if len(_RELEASE) >= 16:
+            _RELEASE.pop(next(iter(_RELEASE)))
+        one = lambda g: np.array([max(int(np.searchsorted(g, g[t] + window, side='left')), t + 1) for t in range(len(g))], dtype=np.int32)   # noqa: E731
+        table = _RELEASE[key] = one(times) if times.ndim == 1 else np.stack([one(g) for g in times])
+    return table
+
+
+class _PendingTabNotes(object):
+    """Device half of the tablature decoder already enqueued (amtx_tab_notes: one dense (E, 3) float64 array of note rows, dense over
+    (clip, string), and its offsets table); `result()` copies both to the host -- on the side stream of _PendingNotes -- and slices them
+    into B stacked-notes dicts.  No sort: onsets of one string are distinct and already ascending."""
+
+    def __init__(self, rows, offsets, B, S, retry):
+        self._rows, self._offsets, self._B, self._S, self._retry = rows, offsets, B, S, retry
+        import torch
+        self._done = torch.cuda.Event()
+        self._done.record(torch.cuda.current_stream(rows.device))
+
+    def result(self):
+        import torch
+        dev = self._rows.device
+        side = _D2H_STREAMS.get(str(dev))
+        if side is None:
+            side = _D2H_STREAMS[str(dev)] = torch.cuda.Stream(dev)
+        side.wait_event(self._done)
+        with torch.cuda.stream(side):
+            off = self._offsets.cpu().numpy()
+            total = int(off[-1])
+            if total > self._rows.shape[0]:             # more notes than the first buffer held: once more with the exact size
+                again = self._retry(total)              # enqueued on this side stream, behind the decoder's event
+                self._rows, off = again._rows, again._offsets.cpu().numpy()
+            rows = self._rows[:total].cpu().numpy()
+        S = self._S
+        return [{s: (rows[off[b * S + s]:off[b * S + s + 1], 2], rows[off[b * S + s]:off[b * S + s + 1], :2]) for s in range(S)}
+                for b in range(self._B)]
+
+
+class _HostTabNotes(object):
+    """The same handle for what the kernel does not build (more than 64 classes under an inhibition window, more than 16 strings) and for
+    CPU tablatures: the host classes, track by track."""
+
+    def __init__(self, tablature, times, profile, inhibition_window, minimum_duration):
+        self._args = (tablature, times, profile, inhibition_window, minimum_duration)
+
+    def result(self):
+        tablature, times, profile, window, min_dur = self._args
+        tab = tools.tensor_to_array(tablature)
+        times = np.asarray(times)
+        return [_tab_to_stacked_notes_host(tab[b], times if times.ndim == 1 else times[b], profile, window, min_dur) for b in range(tab.shape[0])]
+
+
+TAB_NOTES_MAX_CLASSES = 64     # amtx_tab_notes keeps the inhibition state of class k in lane k of a wave
+TAB_MAX_STRINGS = 16
+
+
+def decode_tab_notes_batch_async(tablature, times, profile, inhibition_window=None, minimum_duration=None, rows_capacity=None):
+    """Enqueue the tablature decoder and return a handle; `handle.result()` -> list of B stacked-notes dicts {string: (pitches (N,),
+    intervals (N, 2))}, float64, equal to StackedNoteTranscriber(profile, inhibition_window, minimum_duration) on the
+    TablatureWrapper's map of each clip.  `tablature`: (B, S, T) int64 CUDA tensor, -1 = silent; `times`: one (T,) grid or (B, T)."""
+    import torch
+    assert tablature.dim() == 3
+    B, S, T = tablature.shape
+    num_classes = int(profile.num_pitches)
+    tuning = np.ascontiguousarray(profile.get_midi_tuning(), dtype=np.int32)
+    assert len(tuning) == S, (len(tuning), S)
+    times = np.asarray(times)
+    assert times.shape[-1] == T
+    if times.ndim == 1:
+        ext = _extend_times(times).astype(np.float64)                  # float32 grids convert exactly, as in the reference's float64 rows
+        stride = 0
+    else:
+        ext = np.stack([_extend_times(t) for t in times]).astype(np.float64)
+        stride = ext.shape[1]
+    if not tablature.is_cuda or S > TAB_MAX_STRINGS or (inhibition_window is not None and num_classes > TAB_NOTES_MAX_CLASSES):
+        return _HostTabNotes(tablature, times, profile, inhibition_window, minimum_duration)
+    assert tablature.dtype == torch.int64
+    dev = tablature.device
+    tablature = tablature.contiguous()
+    ext_d = _grid_on_device(np.ascontiguousarray(ext), dev)
+    rel_d, rel_stride = None, 0
+    if inhibition_window is not None:
+        rel_d = _grid_on_device(_release_table(times, inhibition_window), dev)
+        rel_stride = 0 if times.ndim == 1 else T
+    has_min = minimum_duration is not None
+    L = _lib.lib()
+
+    def rows_pass(capacity):
+        rows = torch.empty((capacity, 3), dtype=torch.float64, device=dev)
+        offsets = torch.empty((B * S + 1,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.amtx_tab_notes(_lib.ptr(tablature), B, S, T, _lib.ptr(tuning), num_classes, _lib.ptr(ext_d), stride, _lib.ptr(rel_d),
+                                        rel_stride, int(has_min), float(minimum_duration) if has_min else 0.0, _lib.ptr(rows), capacity,
+                                        _lib.ptr(offsets), _lib.current_stream(dev)), 'amtx_tab_notes')
+        return _PendingTabNotes(rows, offsets, B, S, rows_pass)
+
+    # a string holds at most one note per frame; 128 notes per string on average is far above any real tablature (a denser batch is caught
+    # in result() through the total the device reports and decoded again into a buffer of the exact size)
+    return rows_pass(int(rows_capacity) if rows_capacity else max(1, min(B * S * T, max(B * S * 128, 1 << 14))))
+
+
+def decode_tab_notes_batch(tablature, times, profile, inhibition_window=None, minimum_duration=None):
+    return decode_tab_notes_batch_async(tablature, times, profile, inhibition_window, minimum_duration).result()

@@ -341,6 +341,38 @@ int amtx_notes_rows(const int32_t* pairs, const int32_t* counts, int batch, int 
                     int64_t times_stride, int low_pitch, double* rows, double* onset_col, int64_t rows_capacity, int32_t* clip_offsets,
                     void* stream);
 
+/* Tablature decoding (csrc/tabnotes.hip): what the reference's guitar experiment runs on TabCNN's output (examples/papers/tabcnn.py:90-91).
+ * tablature = [batch][strings][num_frames] int64 on the device, class -1 = silent (SoftmaxGroups.finalize_output); strings <= 16
+ * (AMTX_ERR_UNSUPPORTED beyond).
+ *
+ * amtx_tab_expand: tools.tablature_to_stacked_multi_pitch (tools/utils.py:1988-2059) and / or its collapse over the strings
+ * (stacked_multi_pitch_to_multi_pitch, :1787-1815: the maximum).
+ *   dof_start   HOST array [strings]: midi tuning - profile.low, the map row of each string's class 0
+ *   num_classes classes per string (profile.num_pitches); every string must satisfy 0 <= dof_start and dof_start + num_classes - 1 <
+ *               num_pitches, else AMTX_ERR_ARG -- a class outside the map is an error, never a store (a stray class VALUE in the device
+ *               data matches no row and reads as silence)
+ *   stacked     [batch][strings][num_pitches][num_frames] fp32 or NULL;  collapsed [batch][num_pitches][num_frames] fp32 or NULL (not both
+ *               NULL).  Every element of a requested output is written, zeros included: no memset, no dependence on old contents. */
+int amtx_tab_expand(const int64_t* tablature, int batch, int strings, int num_frames, const int32_t* dof_start, int num_classes,
+                    int num_pitches, float* stacked, float* collapsed, void* stream);
+
+/* amtx_tab_notes: transcribe.StackedNoteTranscriber (transcribe.py:420-481) on the stacked map of the tablature without building the map:
+ * per string a note is a run of one class (start: tab[t] >= 0 and (t == 0 or tab[t-1] != tab[t]); end: the next frame whose class differs,
+ * or num_frames).  Rows [onset_s, offset_s, midi_pitch = tuning[string] + class] in float64, ascending onset within a (clip, string) and dense
+ * over (clip, string) in that order -- the reference's order: onsets of one string are distinct.
+ *   tuning      HOST array [strings]: midi pitch of each string's class 0
+ *   times_ext   as for amtx_notes_rows: [num_frames + 1] float64 (times_stride 0) or [batch][times_stride]
+ *   release     NULL (no inhibition window) or int32 [num_frames] (release_stride 0) / [batch][release_stride] on the device: release[t] =
+ *               the first frame > t outside the inhibition window of an onset at frame t (the caller evaluates the reference's expression,
+ *               utils.py:3026, on its own grid).  A run whose onset lies before the release frame of the last KEPT onset of the same class
+ *               on the same string yields no note.  With release, num_classes <= 64 (AMTX_ERR_UNSUPPORTED beyond).
+ *   has_minimum_duration / minimum_duration   transcribe.py:39-80: keep offset_s - onset_s >= minimum_duration, or > 0 when it is 0
+ *   row_offsets [batch * strings + 1] int32: row r = clip * strings + string owns rows [row_offsets[r], row_offsets[r + 1]); the last entry is
+ *               the total, which may EXCEED rows_capacity -- rows past the capacity are not written, the caller retries with a larger buffer. */
+int amtx_tab_notes(const int64_t* tablature, int batch, int strings, int num_frames, const int32_t* tuning, int num_classes,
+                   const double* times_ext, int64_t times_stride, const int32_t* release, int64_t release_stride, int has_minimum_duration,
+                   double minimum_duration, double* rows, int64_t rows_capacity, int32_t* row_offsets, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * TabCNN inference engine (amt_tools/models/tabcnn.py:17-221; TabCNN.forward + SoftmaxGroups.finalize_output,
  * models/common.py:305-483).  The reference convolves each frame's 9-frame context window separately; the three unpadded 3x3
