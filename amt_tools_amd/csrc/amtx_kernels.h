@@ -162,8 +162,8 @@ int amtx_launch_cvt_pad_bf16(const float* src, int64_t ld_src, int n_src, bf16_t
 int amtx_launch_cvt_split(const float* src, int64_t ld_src, int n_src, bf16_t* dst, int ld_dst, int64_t split, int64_t rows, hipStream_t stream);
 int amtx_launch_zero_cols(void* base, int64_t pitch_bytes, int width_bytes, int64_t rows, hipStream_t stream);
 
-// ---------------------------------------------------------------- device-side weight packing (pack.hip): the host packers' layouts and
-// arithmetic as kernels, for a weight re-sync that does not leave the GPU (amtx_of_model_finalize_device)
+// ---------------------------------------------------------------- device-side weight packing (pack.hip): kernels over the layouts of
+// amtx_pack_layouts.h, which the host packers loop over too, for a weight re-sync that does not leave the GPU (amtx_of_model_finalize_device)
 int amtx_pack_bn_fold_dev(const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var, int c_out, float* scale,
                           float* shift, hipStream_t s);
 int amtx_pack_conv3x3_dev(const float* w, const float* scale, int c_out, int planes, bf16_t* out, hipStream_t s);
@@ -173,6 +173,8 @@ int amtx_pack_conv1g_dev(const float* w, const float* scale, int c_in, int c_mid
 int amtx_pack_scale_rows_dev(const float* w, const float* scale, int rows, int cols, float* out, hipStream_t s);
 int amtx_pack_linear_dev(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c, int perm_f,
                          bf16_t* out, hipStream_t s);
+void amtx_pack_linear_host(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c, int perm_f,
+                           bf16_t* out);      // the same rows on the host (amtx_gemm_pack_host: all of them)
 int amtx_pack_head_fold_dev(const float* w_out, const float* w_fc1, const float* b_fc1, const float* b_out, int n_out, int dim_am, int kfc, int kfc_pad,
                             int nf3, int fq, float* wfold, float* bfold, hipStream_t s);
 int amtx_pack_vec_add_dev(const float* a, const float* b, int n, float* out, hipStream_t s);

@@ -15,7 +15,8 @@ int amtx_launch_conv_stack_f16(const ConvArgs& c2, const bf16_t* w3frag, int64_t
 void amtx_conv3x3_gen_pack_host_f16(const float* w, const float* scale, int c_in, int c_out, int planes, bf16_t* out);
 void amtx_conv1g_pack_host_f16(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out);
 int amtx_launch_conv3x3_gen_f16(const ConvArgs& c, int c_in, hipStream_t stream);
-void amtx_gemm_pack_host_f16(const float* W, int64_t ldw, int N, int K, int planes, bf16_t* out);
+void amtx_pack_linear_host_f16(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c, int perm_f,
+                               bf16_t* out);
 int amtx_launch_gemm_f16(const GemmArgs& g, hipStream_t stream);
 void amtx_bilstm_pack_host_h_f16(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);
 int amtx_launch_bilstm_f16(const LstmArgs& l, hipStream_t stream);

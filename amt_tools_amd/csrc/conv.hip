@@ -14,6 +14,7 @@
 
 #include "amtx_f16_names.h"
 #include "amtx_kernels.h"
+#include "amtx_pack_layouts.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -933,71 +934,24 @@ __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args a) {
 
 }  // namespace
 
-size_t amtx_conv3x3_wfrag_elems(int c_out, int planes) { return (size_t)9 * (c_out / 16) * planes * 64 * 8; }
+static_assert(CIN == AMTX_CONV_CIN, "the 3x3 fragments of amtx_pack_layouts.h are laid out for this kernel's input channels");
+
+size_t amtx_conv3x3_wfrag_elems(int c_out, int planes) { return (size_t)amtx_layout_conv3x3_items(c_out) * planes; }
 
 void amtx_conv3x3_pack_host(const float* w, const float* scale, int c_out, int planes, bf16_t* out) {
-    const int NT = c_out / 16;
-    for (int tap = 0; tap < 9; ++tap)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int l = 0; l < 64; ++l) {
-                const int row = l & 15;
-                const int co = (row >> 2) * (4 * NT) + 4 * nt + (row & 3);
-                for (int j = 0; j < 8; ++j) {
-                    const int ci = (l >> 4) * 8 + j;
-                    const float v = w[((size_t)co * CIN + ci) * 9 + tap] * (scale ? scale[co] : 1.0f);
-                    const bf16_t hi = f32_to_bf16_rn(v);
-                    const size_t base = ((size_t)(tap * NT + nt) * planes) * 64 * 8 + (size_t)l * 8 + j;
-                    out[base] = hi;
-                    if (planes == 2) out[base + 64 * 8] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-                }
-            }
+    const AmtxFragPut put{out, planes};
+    for (int item = 0, n = amtx_layout_conv3x3_items(c_out); item < n; ++item) amtx_layout_conv3x3(item, w, scale, c_out, put);
 }
 
 size_t amtx_conv1_wfrag_elems(int c_in, int planes) {
-    if (c_in == 1) return (size_t)4 * 2 * planes * 64 * 8;    // Toeplitz fragments: 4 output columns x 2 channel halves, 32-deep
+    if (c_in == 1) return (size_t)AMTX_LAYOUT_CONV1_ITEMS * planes;    // Toeplitz fragments: 4 output columns x 2 channel halves, 32-deep
     return (size_t)((9 * c_in + 15) / 16) * 2 * planes * 64 * 4;
 }
 
 void amtx_conv1_pack_host(const float* w, const float* scale, int c_in, int planes, bf16_t* out) {
-    if (c_in == 1) {
-        // Toeplitz A fragments of the fused first conv (conv3x3_kernel, KS == 1): fragment (q, nt), lane l = (row, k-group g):
-        // row -> channel co = 8 (row >> 2) + 4 nt + (row & 3) (a lane of the D tile then holds 8 consecutive channels over nt = 0, 1),
-        // k = 8 g + e -> tap (dy = g, kw = e - q) of output column q within a 4-column unit; everything else is zero
-        for (int q = 0; q < 4; ++q)
-            for (int nt = 0; nt < 2; ++nt)
-                for (int l = 0; l < 64; ++l) {
-                    const int row = l & 15, g = l >> 4;
-                    const int co = (row >> 2) * 8 + 4 * nt + (row & 3);
-                    for (int e = 0; e < 8; ++e) {
-                        const int kw = e - q;
-                        const float v = (g < 3 && kw >= 0 && kw <= 2) ? w[(size_t)co * 9 + g * 3 + kw] * (scale ? scale[co] : 1.0f) : 0.0f;
-                        const bf16_t hi = f32_to_bf16_rn(v);
-                        const size_t base = ((size_t)(q * 2 + nt) * planes) * 64 * 8 + (size_t)l * 8 + e;
-                        out[base] = hi;
-                        if (planes == 2) out[base + 64 * 8] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-                    }
-                }
-        return;
-    }
-    const int kvalid = 9 * c_in, ksteps = (kvalid + 15) / 16;
-    for (int ks = 0; ks < ksteps; ++ks)
-        for (int nt = 0; nt < 2; ++nt)
-            for (int l = 0; l < 64; ++l) {
-                const int row = l & 15;
-                const int co = (row >> 2) * 8 + 4 * nt + (row & 3);
-                for (int j = 0; j < 4; ++j) {
-                    // c_in = 1: K slot (g, j) of the single 16-deep step is tap (kh = g, kw = j), g, j < 3 (the other 7 slots are
-                    // zero), so a lane's four im2col values are one LDS row segment: one address, immediate offsets.
-                    // Otherwise k runs over (ci, kh, kw) in the weight tensor's own order.
-                    int k = 16 * ks + 4 * (l >> 4) + j;
-                    if (c_in == 1) k = ((l >> 4) < 3 && j < 3) ? 3 * (l >> 4) + j : kvalid;
-                    const float v = k < kvalid ? w[(size_t)co * kvalid + k] * (scale ? scale[co] : 1.0f) : 0.0f;
-                    const bf16_t hi = f32_to_bf16_rn(v);
-                    const size_t base = ((size_t)(ks * 2 + nt) * planes) * 64 * 4 + (size_t)l * 4 + j;
-                    out[base] = hi;
-                    if (planes == 2) out[base + 64 * 4] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-                }
-            }
+    if (c_in != 1) return amtx_layout_conv1_multi(w, scale, c_in, planes, out);
+    const AmtxFragPut put{out, planes};
+    for (int item = 0; item < AMTX_LAYOUT_CONV1_ITEMS; ++item) amtx_layout_conv1(item, w, scale, put);
 }
 
 int amtx_launch_conv3x3(const ConvArgs& a, hipStream_t stream) {

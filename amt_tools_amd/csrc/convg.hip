@@ -20,6 +20,7 @@
 
 #include "amtx_f16_names.h"
 #include "amtx_kernels.h"
+#include "amtx_pack_layouts.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -66,7 +67,6 @@ constexpr int g_cplane(int ft) {
 // 16-channel tail, 5 PAIRED tail steps: the two 16-channel tails of two taps share one 32-deep MFMA (lane groups 0, 1 = first tap,
 // 2, 3 = second tap): (kh 0, kh 1) for each kw, then (2,0)+(2,1), then (2,2) alone (upper half zero).  14 MFMAs per output column
 // and channel tile at C_in = 48 instead of 18 with one half-empty tail step per tap.
-constexpr int g_wfrags_per_tile(int ci16) { return 9 * (ci16 / 2) + 5 * (ci16 % 2); }
 
 // KS1 > 0: the first convolution (Conv2d(c_in -> C_in of this layer) + BN + ReLU, models/onsetsframes.py:375-384) is computed
 // inside this kernel, from the fp32 features, straight into the LDS input tile (the C_in-channel map never exists in HBM):
@@ -901,78 +901,24 @@ int amtx_conv3x3_gen_ntc(int c_in, int c_out) {
     return 0;
 }
 
-size_t amtx_conv3x3_gen_wfrag_elems(int c_in, int c_out, int planes) { return (size_t)(c_out / 16) * planes * g_wfrags_per_tile(c_in / 16) * 512; }
+size_t amtx_conv3x3_gen_wfrag_elems(int c_in, int c_out, int planes) { return (size_t)(c_out / 16) * planes * g_wfrags_per_tile(c_in / 16) * AMTX_FRAG; }
 
-// host packing: weight (c_out, c_in, 3, 3) fp32 * scale[c_out] -> [chunk][fragment][plane][lane][8]; fragments of a chunk: the full
-// steps in (tap, tile, step) order, then the paired tails A (kw, tile): taps (0,kw) | (1,kw); B (tile): (2,0) | (2,1); C (tile): (2,2) | 0
+// host packing: weight (c_out, c_in, 3, 3) fp32 * scale[c_out] -> amtx_layout_conv_gen
 void amtx_conv3x3_gen_pack_host(const float* w, const float* scale, int c_in, int c_out, int planes, bf16_t* out) {
     const int ntc = amtx_conv3x3_gen_ntc(c_in, c_out);
-    const int ci16 = c_in / 16, n32 = ci16 / 2, n16 = ci16 % 2;
-    const int nmain = 9 * ntc * n32, nfrag = nmain + 5 * ntc * n16;
-    const int nchunks = c_out / (16 * ntc);
-    auto put = [&](bf16_t* frag, int l, int j, float v) {
-        const bf16_t hi = f32_to_bf16_rn(v);
-        frag[l * 8 + j] = hi;
-        if (planes == 2) frag[512 + l * 8 + j] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-    };
-    for (int ch = 0; ch < nchunks; ++ch) {
-        bf16_t* cbase = out + (size_t)ch * nfrag * planes * 512;
-        for (int nt = 0; nt < ntc; ++nt)
-            for (int l = 0; l < 64; ++l) {
-                const int row = l & 15, gq = l >> 4;
-                const int co = ch * 16 * ntc + (row >> 2) * (4 * ntc) + 4 * nt + (row & 3);
-                const float sc = scale ? scale[co] : 1.0f;
-                auto wv = [&](int ci, int tap) { return w[((size_t)co * c_in + ci) * 9 + tap] * sc; };
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int ks = 0; ks < n32; ++ks)
-                        for (int j = 0; j < 8; ++j)
-                            put(cbase + (size_t)(((tap * ntc + nt) * n32) + ks) * planes * 512, l, j, wv(32 * ks + 8 * gq + j, tap));
-                if (!n16) continue;
-                const int ct = 32 * n32 + 8 * (gq & 1);                // tail channels of this lane group: ct .. ct + 7
-                for (int j = 0; j < 8; ++j) {
-                    for (int kw = 0; kw < 3; ++kw)                   // A: tap rows 0 | 1 at column shift kw
-                        put(cbase + (size_t)(nmain + kw * ntc + nt) * planes * 512, l, j, wv(ct + j, (gq < 2 ? 0 : 3) + kw));
-                    put(cbase + (size_t)(nmain + 3 * ntc + nt) * planes * 512, l, j, wv(ct + j, gq < 2 ? 6 : 7));      // B: (2,0) | (2,1)
-                    put(cbase + (size_t)(nmain + 4 * ntc + nt) * planes * 512, l, j, gq < 2 ? wv(ct + j, 8) : 0.0f);  // C: (2,2) | zero
-                }
-            }
-    }
+    const AmtxFragPut put{out, planes};
+    for (int item = 0, n = amtx_layout_conv_gen_items(c_out); item < n; ++item) amtx_layout_conv_gen(item, w, scale, c_in, ntc, put);
 }
 
-// fused first conv (c_in -> c_mid channels, c_mid = this layer's C_in): fragments [tile of 16 channels][k-step][plane][lane][8],
-// k = 32 ks + 8 (lane >> 4) + j over (ci, kh, kw) in the weight tensor's order, zero past 9 c_in
-// (amtx_conv1g_tapk: k = 8 tap + ci instead, three steps)
+// fused first conv (c_in -> c_mid channels, c_mid = this layer's C_in): amtx_layout_conv1g, in the K order amtx_conv1g_tapk picks
 size_t amtx_conv1g_wfrag_elems(int c_in, int c_mid, int planes) {
-    return (size_t)(c_mid / 16) * (amtx_conv1g_tapk(c_in, planes) ? 3 : (9 * c_in + 31) / 32) * planes * 512;
+    return (size_t)amtx_layout_conv1g_items(c_in, c_mid, amtx_conv1g_tapk(c_in, planes)) * planes;
 }
 
 void amtx_conv1g_pack_host(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out) {
-    if (amtx_conv1g_tapk(c_in, planes)) {
-        for (int nt = 0; nt < c_mid / 16; ++nt)
-            for (int ks = 0; ks < 3; ++ks)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = 16 * nt + (l & 15), tap = 4 * ks + (l >> 4);
-                        const float v = (tap < 9 && j < c_in) ? w[((size_t)co * c_in + j) * 9 + tap] * (scale ? scale[co] : 1.0f) : 0.0f;
-                        const bf16_t hi = f32_to_bf16_rn(v);
-                        const size_t base = ((size_t)(nt * 3 + ks) * planes) * 512 + (size_t)l * 8 + j;
-                        out[base] = hi;
-                        if (planes == 2) out[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-                    }
-        return;
-    }
-    const int kvalid = 9 * c_in, ks1 = (kvalid + 31) / 32;
-    for (int nt = 0; nt < c_mid / 16; ++nt)
-        for (int ks = 0; ks < ks1; ++ks)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int co = 16 * nt + (l & 15), k = 32 * ks + 8 * (l >> 4) + j;
-                    const float v = k < kvalid ? w[(size_t)co * kvalid + k] * (scale ? scale[co] : 1.0f) : 0.0f;
-                    const bf16_t hi = f32_to_bf16_rn(v);
-                    const size_t base = ((size_t)(nt * ks1 + ks) * planes) * 512 + (size_t)l * 8 + j;
-                    out[base] = hi;
-                    if (planes == 2) out[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-                }
+    const bool tapk = amtx_conv1g_tapk(c_in, planes);
+    const AmtxFragPut put{out, planes};
+    for (int item = 0, n = amtx_layout_conv1g_items(c_in, c_mid, tapk); item < n; ++item) amtx_layout_conv1g(item, w, scale, c_in, tapk, put);
 }
 
 // does the fused-first-conv variant fit the LDS for this layer?
@@ -983,7 +929,7 @@ bool amtx_conv3x3_gen_can_fuse1(int c_in, int c_mid, int c_out, int planes) {
     const bool pipe = tapk && c_mid == 32 && planes == 1;      // two input tiles and two feature tiles (conv3x3_gen_kernel PIPE)
     const size_t feat = tapk ? (size_t)(pipe ? 2 : 1) * planes * ((GROWS + 2) * (ft + 4) * 16 + 128) : (size_t)c_in * (GROWS + 2) * (ft + 5) * sizeof(float);
     const size_t lds = (size_t)(pipe ? 2 : 1) * planes * (c_mid / 8) * g_cplane(ft) + (size_t)ntc * planes * g_wfrags_per_tile(c_mid / 16) * 1024 + feat +
-                       (size_t)(c_mid / 16) * (tapk ? 3 : (9 * c_in + 31) / 32) * planes * 1024 + c_mid * 4 + 16 + (size_t)c_out * 4;   // + this layer's shift
+                       (size_t)(c_mid / 16) * amtx_conv1g_ksteps(c_in, tapk) * planes * 1024 + c_mid * 4 + 16 + (size_t)c_out * 4;   // + this layer's shift
     return lds <= 160 * 1024;
 }
 

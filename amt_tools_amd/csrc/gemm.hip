@@ -1314,15 +1314,7 @@ void amtx_gemm_pack_dims(int N, int K, int* n_pad, int* k_pad) {
 void amtx_gemm_pack_host(const float* W, int64_t ldw, int N, int K, int planes, bf16_t* out) {
     int n_pad, k_pad;
     amtx_gemm_pack_dims(N, K, &n_pad, &k_pad);
-    const size_t plane = (size_t)n_pad * k_pad;
-    memset(out, 0, plane * planes * sizeof(bf16_t));
-    for (int n = 0; n < N; ++n)
-        for (int k = 0; k < K; ++k) {
-            const float w = W[(int64_t)n * ldw + k];
-            const bf16_t hi = f32_to_bf16_rn(w);
-            out[(size_t)n * k_pad + k] = hi;
-            if (planes == 2) out[plane + (size_t)n * k_pad + k] = f32_to_bf16_rn(w - bf16_to_f32(hi));
-        }
+    amtx_pack_linear_host(W, ldw, N, K, planes, n_pad, k_pad, 0, n_pad, 0, 0, out);
 }
 
 // ---- kernel selection: amtx_launch_gemm is gemm_validate -> gemm_route -> one switch that launches (the table: DESIGN.md 5.9) ----

@@ -21,6 +21,7 @@
 
 #include "amtx_f16_names.h"
 #include "amtx_kernels.h"
+#include "amtx_pack_layouts.h"
 
 #include <type_traits>
 
@@ -519,43 +520,15 @@ extern "C" int amtxdbg_lstm_prof(unsigned long long* out4, int reset) {
 }
 #endif
 
-// fp32 W_hh (512 x 128, both directions) on the DEVICE -> forward fragments (amtx_bilstm_pack_host's layout) and transposed
-// fragments for the backward kernel, hi/lo planes: training repacks after every optimizer step without a host round trip.
-__global__ void bilstm_pack_dev_kernel(const float* __restrict__ whh_fwd, const float* __restrict__ whh_bwd, int planes,
-                                       bf16_t* __restrict__ frag_fwd, bf16_t* __restrict__ frag_bwd) {
-    const int n = 2 * 4 * H * H;                                   // elements per plane set (both directions)
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
-        // forward fragment element: [dir][w][q][ks][l][j]
-        {
-            int r = idx;
-            const int j = r & 7; r >>= 3;
-            const int l = r & 63; r >>= 6;
-            const int ks = r & 3; r >>= 2;
-            const int q = r & 3; r >>= 2;
-            const int w = r & 7; r >>= 3;
-            const int dir = r;
-            const float* W = dir == 0 ? whh_fwd : whh_bwd;
-            const float v = W[(q * H + 16 * w + (l & 15)) * H + 32 * ks + 8 * (l >> 4) + j];
-            const bf16_t hi = f32_to_bf16_rn(v);
-            const size_t base = ((size_t)((((dir * LWAVES + w) * 4 + q) * 4 + ks) * planes)) * 512 + (size_t)l * 8 + j;
-            frag_fwd[base] = hi;
-            if (planes == 2) frag_fwd[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-        }
-        // transposed fragment element: [dir][w][ks(16)][l][j]: W[row k = 32 ks + 8 (l >> 4) + j][unit 16 w + (l & 15)]
-        {
-            int r = idx;
-            const int j = r & 7; r >>= 3;
-            const int l = r & 63; r >>= 6;
-            const int ks = r & 15; r >>= 4;
-            const int w = r & 7; r >>= 3;
-            const int dir = r;
-            const float* W = dir == 0 ? whh_fwd : whh_bwd;
-            const float v = W[(32 * ks + 8 * (l >> 4) + j) * H + 16 * w + (l & 15)];
-            const bf16_t hi = f32_to_bf16_rn(v);
-            const size_t base = ((size_t)(((dir * LWAVES + w) * 16 + ks) * planes)) * 512 + (size_t)l * 8 + j;
-            frag_bwd[base] = hi;
-            if (planes == 2) frag_bwd[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-        }
+// fp32 W_hh (4 hidden x hidden, both directions) on the DEVICE -> forward fragments (the host packers' amtx_layout_bilstm) and transposed
+// fragments for the backward kernels, hi/lo planes: training repacks after every optimizer step without a host round trip.
+// HC: the hidden size at compile time (the hidden-128 kernel runs in every training step), 0: `hidden`
+template <int HC>
+__global__ void bilstm_pack_dev_kernel(const float* __restrict__ whh_fwd, const float* __restrict__ whh_bwd, int hidden, AmtxFragPut fwd, AmtxFragPut bwd) {
+    if (HC) hidden = HC;
+    for (int item = blockIdx.x * blockDim.x + threadIdx.x, n = amtx_layout_bilstm_items(hidden); item < n; item += gridDim.x * blockDim.x) {
+        amtx_layout_bilstm(item, whh_fwd, whh_bwd, hidden, fwd);
+        amtx_layout_bilstm_transposed(item, whh_fwd, whh_bwd, hidden, bwd);
     }
 }
 
@@ -946,46 +919,6 @@ __global__ __launch_bounds__(512) void bilstm_stream_bwd_kernel(LstmBwdHArgs a) 
     }
 }
 
-// fp32 W_hh (4 hidden x hidden, both directions) on the DEVICE -> forward fragments of bilstm_stream_kernel and transposed
-// fragments of bilstm_stream_bwd_kernel, hi/lo planes
-__global__ void bilstm_pack_dev_h_kernel(const float* __restrict__ whh_fwd, const float* __restrict__ whh_bwd, int hidden, int planes,
-                                         bf16_t* __restrict__ frag_fwd, bf16_t* __restrict__ frag_bwd) {
-    const int HHr = hidden, nu = HHr / 16, ksn = HHr / 32, ut_n = HHr / 128, ksn_b = 4 * HHr / 32;
-    const int n = 2 * 4 * HHr * HHr;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
-        {   // forward: [dir][u][q][ks][p][l][j]
-            int r = idx;
-            const int j = r & 7; r >>= 3;
-            const int l = r & 63; r >>= 6;
-            const int ks = r % ksn; r /= ksn;
-            const int q = r & 3; r >>= 2;
-            const int u = r % nu; r /= nu;
-            const int dir = r;
-            const float* W = dir == 0 ? whh_fwd : whh_bwd;
-            const float v = W[(size_t)(q * HHr + 16 * u + (l & 15)) * HHr + 32 * ks + 8 * (l >> 4) + j];
-            const bf16_t hi = f32_to_bf16_rn(v);
-            const size_t base = ((((size_t)(dir * nu + u) * 4 + q) * ksn + ks) * planes) * 512 + (size_t)l * 8 + j;
-            frag_fwd[base] = hi;
-            if (planes == 2) frag_fwd[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-        }
-        {   // transposed: [dir][wave][ut][ks][p][l][j] = W[row 32 ks + 8 (l >> 4) + j][unit 16 ut_n wave + 16 ut + (l & 15)]
-            int r = idx;
-            const int j = r & 7; r >>= 3;
-            const int l = r & 63; r >>= 6;
-            const int ks = r % ksn_b; r /= ksn_b;
-            const int ut = r % ut_n; r /= ut_n;
-            const int wv = r & 7; r >>= 3;
-            const int dir = r;
-            const float* W = dir == 0 ? whh_fwd : whh_bwd;
-            const float v = W[(size_t)(32 * ks + 8 * (l >> 4) + j) * HHr + 16 * ut_n * wv + 16 * ut + (l & 15)];
-            const bf16_t hi = f32_to_bf16_rn(v);
-            const size_t base = ((((size_t)(dir * 8 + wv) * ut_n + ut) * ksn_b + ks) * planes) * 512 + (size_t)l * 8 + j;
-            frag_bwd[base] = hi;
-            if (planes == 2) frag_bwd[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-        }
-    }
-}
-
 template <int HH, int NS, int X_TYPE, int OUT_TYPE>
 int launch_stream(const LstmArgs& a, hipStream_t stream) {
     // h tiles + (bf16 mode) the LDS-resident quarter of W_hh: 8 waves x (groups / 4) x 4 KiB
@@ -1040,47 +973,17 @@ size_t amtx_bilstm_wfrag_elems(int planes) { return (size_t)2 * 512 * 128 * plan
 
 size_t amtx_bilstm_wfrag_elems_h(int hidden, int planes) { return (size_t)2 * 4 * hidden * hidden * planes; }
 
-// hidden != 128: fragment order of bilstm_stream_kernel, [dir][unit tile][gate][k-step][plane][lane][8]
+// wave w of the hidden-128 kernels owns unit tiles UB w .. UB w + UB - 1 and the backward kernels run AMTX_LSTM_BWD_WAVES waves: what
+// amtx_layout_bilstm / _transposed (amtx_pack_layouts.h) lay the fragments out for
+static_assert(16 * UB * LWAVES == H && LWAVES == AMTX_LSTM_BWD_WAVES, "W_hh fragment layouts");
+
+// fragment order of every forward kernel: [dir][unit tile][gate][k-step][plane][lane][8]
 void amtx_bilstm_pack_host_h(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out) {
-    if (hidden == H) { amtx_bilstm_pack_host(whh_fwd, whh_bwd, planes, out); return; }
-    const int nu = hidden / 16, ksn = hidden / 32;
-    for (int dir = 0; dir < 2; ++dir) {
-        const float* W = dir == 0 ? whh_fwd : whh_bwd;   // (4 hidden, hidden) row-major, gate-major rows i,f,g,o
-        for (int u = 0; u < nu; ++u)
-            for (int q = 0; q < 4; ++q)
-                for (int ks = 0; ks < ksn; ++ks)
-                    for (int l = 0; l < 64; ++l)
-                        for (int j = 0; j < 8; ++j) {
-                            const int row = q * hidden + 16 * u + (l & 15);
-                            const int k = 32 * ks + 8 * (l >> 4) + j;
-                            const float v = W[(size_t)row * hidden + k];
-                            const bf16_t hi = f32_to_bf16_rn(v);
-                            const size_t base = (((((size_t)dir * nu + u) * 4 + q) * ksn + ks) * planes) * 512 + (size_t)l * 8 + j;
-                            out[base] = hi;
-                            if (planes == 2) out[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-                        }
-    }
+    const AmtxFragPut put{out, planes};
+    for (int item = 0, n = amtx_layout_bilstm_items(hidden); item < n; ++item) amtx_layout_bilstm(item, whh_fwd, whh_bwd, hidden, put);
 }
 
-void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* out) {
-    for (int dir = 0; dir < 2; ++dir) {
-        const float* W = dir == 0 ? whh_fwd : whh_bwd;   // (512, 128) row-major, gate-major rows i,f,g,o
-        for (int w = 0; w < LWAVES; ++w)
-            for (int ub = 0; ub < UB; ++ub)
-                for (int q = 0; q < 4; ++q)
-                    for (int ks = 0; ks < 4; ++ks)
-                        for (int l = 0; l < 64; ++l)
-                            for (int j = 0; j < 8; ++j) {
-                                const int row = q * 128 + 16 * UB * w + 16 * ub + (l & 15);
-                                const int k = 32 * ks + 8 * (l >> 4) + j;
-                                const float v = W[(size_t)row * H + k];
-                                const bf16_t hi = f32_to_bf16_rn(v);
-                                const size_t base = ((((((size_t)dir * LWAVES + w) * UB + ub) * 4 + q) * 4 + ks) * planes) * 512 + (size_t)l * 8 + j;
-                                out[base] = hi;
-                                if (planes == 2) out[base + 512] = f32_to_bf16_rn(v - bf16_to_f32(hi));
-                            }
-    }
-}
+void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* out) { amtx_bilstm_pack_host_h(whh_fwd, whh_bwd, H, planes, out); }
 
 int amtx_launch_bilstm(const LstmArgs& a, hipStream_t stream) {
     AMTX_REQUIRE(a.xproj && a.whh && a.out, "bilstm: null pointer");
@@ -1103,7 +1006,7 @@ int amtx_launch_bilstm(const LstmArgs& a, hipStream_t stream) {
 
 int amtx_launch_bilstm_pack_dev(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream) {
     AMTX_REQUIRE(whh_fwd && whh_bwd && frag_fwd && frag_bwd && (planes == 1 || planes == 2), "bilstm pack: bad argument");
-    hipLaunchKernelGGL(bilstm_pack_dev_kernel, dim3(128), dim3(256), 0, stream, whh_fwd, whh_bwd, planes, frag_fwd, frag_bwd);
+    hipLaunchKernelGGL(bilstm_pack_dev_kernel<H>, dim3(64), dim3(256), 0, stream, whh_fwd, whh_bwd, H, AmtxFragPut{frag_fwd, planes}, AmtxFragPut{frag_bwd, planes});
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
@@ -1129,7 +1032,7 @@ int amtx_launch_bilstm_pack_dev_h(const float* whh_fwd, const float* whh_bwd, in
     AMTX_REQUIRE(whh_fwd && whh_bwd && frag_fwd && frag_bwd && (planes == 1 || planes == 2), "bilstm pack: bad argument");
     if (hidden == H) return amtx_launch_bilstm_pack_dev(whh_fwd, whh_bwd, planes, frag_fwd, frag_bwd, stream);
     AMTX_REQUIRE(hidden == 256 || hidden == 384 || hidden == 512, "bilstm pack: hidden size %d is not built (128, 256, 384, 512)", hidden);
-    hipLaunchKernelGGL(bilstm_pack_dev_h_kernel, dim3(256), dim3(256), 0, stream, whh_fwd, whh_bwd, hidden, planes, frag_fwd, frag_bwd);
+    hipLaunchKernelGGL(bilstm_pack_dev_kernel<0>, dim3(256), dim3(256), 0, stream, whh_fwd, whh_bwd, hidden, AmtxFragPut{frag_fwd, planes}, AmtxFragPut{frag_bwd, planes});
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }

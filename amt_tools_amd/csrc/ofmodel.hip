@@ -17,6 +17,7 @@
 #include "amtx_kernels.h"
 #include "amtx_kernels_f16.h"
 #include "amtx_model_common.h"
+#include "amtx_pack_layouts.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -24,12 +25,13 @@
 
 namespace {
 
-struct LinearPack { DevBuf w, b; int N = 0, K = 0, n_pad = 0, k_pad = 0; };
+struct LinearPack { DevBuf w, b; int N = 0, K = 0, n_pad = 0, k_pad = 0, groups = 0; };     // w: [groups][planes][n_pad][k_pad], b: [groups][N]
 
 // The kernels and packers that exist once per 16-bit operand format (the files compiled twice: amtx_f16_names.h).  A model picks its
 // table when it is created and calls through it.
 struct KernelSet {
-    void (*gemm_pack_host)(const float* W, int64_t ldw, int N, int K, int planes, bf16_t* out);
+    void (*pack_linear_host)(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c,
+                             int perm_f, bf16_t* out);
     void (*bilstm_pack_host_h)(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);
     void (*conv1_pack_host)(const float* w, const float* scale, int c_in, int planes, bf16_t* out);
     void (*conv1g_pack_host)(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out);
@@ -53,12 +55,12 @@ struct KernelSet {
 };
 
 const KernelSet kKernelsBf16 = {
-    amtx_gemm_pack_host, amtx_bilstm_pack_host_h, amtx_conv1_pack_host, amtx_conv1g_pack_host, amtx_conv3x3_pack_host, amtx_conv3x3_gen_pack_host,
+    amtx_pack_linear_host, amtx_bilstm_pack_host_h, amtx_conv1_pack_host, amtx_conv1g_pack_host, amtx_conv3x3_pack_host, amtx_conv3x3_gen_pack_host,
     amtx_pack_conv1_dev, amtx_pack_conv1g_dev, amtx_pack_conv3x3_dev, amtx_pack_conv_gen_dev, amtx_pack_linear_dev, amtx_launch_bilstm_pack_dev_h,
     amtx_launch_conv1, amtx_launch_conv3x3, amtx_launch_conv3x3_gen, amtx_launch_conv_stack, amtx_launch_gemm, amtx_launch_bilstm};
 #ifdef AMTX_WITH_F16
 const KernelSet kKernelsF16 = {
-    amtx_gemm_pack_host_f16, amtx_bilstm_pack_host_h_f16, amtx_conv1_pack_host_f16, amtx_conv1g_pack_host_f16, amtx_conv3x3_pack_host_f16,
+    amtx_pack_linear_host_f16, amtx_bilstm_pack_host_h_f16, amtx_conv1_pack_host_f16, amtx_conv1g_pack_host_f16, amtx_conv3x3_pack_host_f16,
     amtx_conv3x3_gen_pack_host_f16, amtx_pack_conv1_dev_f16, amtx_pack_conv1g_dev_f16, amtx_pack_conv3x3_dev_f16, amtx_pack_conv_gen_dev_f16,
     amtx_pack_linear_dev_f16, amtx_launch_bilstm_pack_dev_h_f16, amtx_launch_conv1_f16, amtx_launch_conv3x3_f16, amtx_launch_conv3x3_gen_f16,
     amtx_launch_conv_stack_f16, amtx_launch_gemm_f16, amtx_launch_bilstm_f16};
@@ -162,67 +164,6 @@ static const char* kStageNames[ST_COUNT] = {"conv1", "conv2_pool", "conv3_pool",
                                             "pitch_head_gemm", "adj_xproj_gemm", "adj_bilstm", "adj_head_gemm", "pianoroll"};
 
 namespace {
-
-#define NEED(name, numel, ptr)                                         \
-    do {                                                               \
-        int _rc = m->store.need(name, numel, &(ptr));                  \
-        if (_rc != AMTX_OK) return _rc;                                \
-    } while (0)
-
-// fold eval-mode BatchNorm2d behind a conv: scale[c] and shift[c]
-int fold_bn(const amtx_of_model* m, const std::string& conv, const std::string& bn, int c_out, std::vector<float>& scale,
-            std::vector<float>& shift) {
-    const float *cb, *g, *be, *mu, *var;
-    NEED(conv + ".bias", (size_t)c_out, cb);
-    NEED(bn + ".weight", (size_t)c_out, g);
-    NEED(bn + ".bias", (size_t)c_out, be);
-    NEED(bn + ".running_mean", (size_t)c_out, mu);
-    NEED(bn + ".running_var", (size_t)c_out, var);
-    scale.resize(c_out); shift.resize(c_out);
-    for (int c = 0; c < c_out; ++c) {
-        const double s = (double)g[c] / std::sqrt((double)var[c] + 1e-5);
-        scale[c] = (float)s;
-        shift[c] = (float)((double)be[c] + ((double)cb[c] - (double)mu[c]) * s);
-    }
-    return AMTX_OK;
-}
-
-int pack_linear_groups(amtx_of_model* m, LinearPack& lp, const std::vector<std::vector<float>>& Ws, const std::vector<std::vector<float>>& bs,
-                       int N, int K) {
-    lp.N = N; lp.K = K;
-    amtx_gemm_pack_dims(N, K, &lp.n_pad, &lp.k_pad);
-    const size_t per = (size_t)lp.n_pad * lp.k_pad * m->planes;
-    std::vector<bf16_t> packed(per * Ws.size());
-    std::vector<float> bias((size_t)N * Ws.size());
-    for (size_t g = 0; g < Ws.size(); ++g) {
-        m->k->gemm_pack_host(Ws[g].data(), K, N, K, m->planes, packed.data() + g * per);
-        memcpy(bias.data() + g * N, bs[g].data(), sizeof(float) * N);
-    }
-    int rc = lp.w.upload(packed.data(), packed.size() * sizeof(bf16_t));
-    if (rc != AMTX_OK) return rc;
-    return lp.b.upload(bias.data(), bias.size() * sizeof(float));
-}
-
-int pack_lstm(amtx_of_model* m, const std::string& prefix, int dim_in, std::vector<float>& w_ih, std::vector<float>& b, std::vector<bf16_t>& hh) {
-    const int H = m->dim_lm / 2, G = 4 * H;
-    const float *wif, *wib, *whf, *whb, *bif, *bib, *bhf, *bhb;
-    NEED(prefix + ".mlm.weight_ih_l0", (size_t)G * dim_in, wif);
-    NEED(prefix + ".mlm.weight_ih_l0_reverse", (size_t)G * dim_in, wib);
-    NEED(prefix + ".mlm.weight_hh_l0", (size_t)G * H, whf);
-    NEED(prefix + ".mlm.weight_hh_l0_reverse", (size_t)G * H, whb);
-    NEED(prefix + ".mlm.bias_ih_l0", (size_t)G, bif);
-    NEED(prefix + ".mlm.bias_ih_l0_reverse", (size_t)G, bib);
-    NEED(prefix + ".mlm.bias_hh_l0", (size_t)G, bhf);
-    NEED(prefix + ".mlm.bias_hh_l0_reverse", (size_t)G, bhb);
-    w_ih.resize((size_t)2 * G * dim_in);
-    memcpy(w_ih.data(), wif, sizeof(float) * G * dim_in);
-    memcpy(w_ih.data() + (size_t)G * dim_in, wib, sizeof(float) * G * dim_in);
-    b.resize(2 * G);
-    for (int i = 0; i < G; ++i) { b[i] = bif[i] + bhf[i]; b[G + i] = bib[i] + bhb[i]; }
-    hh.resize(m->hh_elems);
-    m->k->bilstm_pack_host_h(whf, whb, H, m->planes, hh.data());
-    return AMTX_OK;
-}
 
 struct Workspace {
     char *a1, *a2, *a3, *e, *xp, *l1, *joint, *joint16, *xp2, *l2, *mp;
@@ -336,140 +277,262 @@ extern "C" int amtx_of_model_set_tensor(amtx_of_model* m, const char* name, cons
     return AMTX_OK;
 }
 
-extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
-    AMTX_REQUIRE(m, "amtx_of_model_finalize: null model");
-    {
-        int qrc = amtx_quiesce_before_resync(m->packed_once);
-        if (qrc != AMTX_OK) return qrc;
-    }
-    const int nh = m->n_heads, ic = m->in_channels;
-    const ConvPlan& p = m->plan;
-    if (p.layer[2].fam == K_CONVG && (!amtx_conv3x3_gen_ntc(m->nf1, m->nf2) || !amtx_conv3x3_gen_ntc(m->nf2, m->nf3))) {
-        amtx_set_error("of_model: no convolution kernel for %d -> %d -> %d channels", m->nf1, m->nf2, m->nf3);
-        return AMTX_ERR_UNSUPPORTED;
-    }
-    // ---- acoustic heads
-    std::vector<float> c1w((size_t)nh * m->nf1 * ic * 9), cs[3];
-    std::vector<bf16_t> cw[3], c2x(p.convx12 ? p.c2x_per * nh : 0);
-    for (int l = 0; l < 3; ++l) { cw[l].resize(p.layer[l].frag_per * nh); cs[l].resize((size_t)nh * p.layer[l].c_out); }
-    std::vector<std::vector<float>> fcw(nh), fcb(nh);
-    for (int h = 0; h < nh; ++h) {
-        const std::string am = m->head_names[h] + ".0";
-        const float* w;
-        for (int l = 0; l < 3; ++l) {
-            // Conv + eval-mode BatchNorm: the scale goes into the packed weights, the shift stays fp32
-            const ConvLayer& y = p.layer[l];
-            const std::string conv = am + "." + y.name + ".0";
-            std::vector<float> scale, shift;
-            int rc = fold_bn(m, conv, am + "." + y.name + ".1", y.c_out, scale, shift);
-            if (rc != AMTX_OK) return rc;
-            NEED(conv + ".weight", (size_t)y.c_out * y.c_in * 9, w);
-            memcpy(cs[l].data() + (size_t)h * y.c_out, shift.data(), sizeof(float) * y.c_out);
-            bf16_t* frag = cw[l].data() + y.frag_per * h;
-            if (l == 0) {     // the fp32 copy feeds only the separate first conv
-                for (int co = 0; co < y.c_out; ++co)
-                    for (int i = 0; i < ic * 9; ++i) c1w[((size_t)h * y.c_out + co) * ic * 9 + i] = w[(size_t)co * ic * 9 + i] * scale[co];
-                if (y.fam == K_CONVG) m->k->conv1g_pack_host(w, scale.data(), ic, y.c_out, m->planes, frag);
-                else if (y.fam == K_CONV) m->k->conv1_pack_host(w, scale.data(), ic, m->planes, frag);
-            } else if (y.fam == K_CONVG) m->k->conv3x3_gen_pack_host(w, scale.data(), y.c_in, y.c_out, m->planes, frag);
-            else m->k->conv3x3_pack_host(w, scale.data(), y.c_out, m->planes, frag);
-            if (l == 1 && p.convx12) m->k->conv3x3_pack_host(w, scale.data(), y.c_out, m->planes, c2x.data() + p.c2x_per * h);
-        }
-        // fc1: reference column index c*fq + f  ->  ours f*nf3 + c
-        const float* fb;
-        NEED(am + ".fc1.0.weight", (size_t)m->dim_am * m->kfc, w);
-        NEED(am + ".fc1.0.bias", (size_t)m->dim_am, fb);
-        fcw[h].assign((size_t)m->dim_am * m->kfc_pad, 0.0f);     // columns kfc .. kfc_pad stay zero
-        for (int n = 0; n < m->dim_am; ++n)
-            for (int c = 0; c < m->nf3; ++c)
-                for (int f = 0; f < m->fq; ++f)
-                    fcw[h][(size_t)n * m->kfc_pad + (size_t)f * m->nf3 + c] = w[(size_t)n * m->kfc + (size_t)c * m->fq + f];
-        fcb[h].assign(fb, fb + m->dim_am);
-    }
-    int rc;
-    if ((rc = m->conv1_w.upload(c1w.data(), c1w.size() * 4)) != AMTX_OK || (rc = m->conv_s[0].upload(cs[0].data(), cs[0].size() * 4)) != AMTX_OK) return rc;
-    if (p.conv1_fused && (rc = m->conv_w[0].upload(cw[0].data(), cw[0].size() * 2)) != AMTX_OK) return rc;
-    for (int l = 1; l < 3; ++l) {
-        if ((rc = m->conv_w[l].upload(cw[l].data(), cw[l].size() * 2)) != AMTX_OK) return rc;
-        if (l == 1 && p.convx12 && (rc = m->conv2_wx.upload(c2x.data(), c2x.size() * 2)) != AMTX_OK) return rc;
-        if ((rc = m->conv_s[l].upload(cs[l].data(), cs[l].size() * 4)) != AMTX_OK) return rc;
-    }
-    {
-        // fc1 of the RECURRENT heads only.  The pitch head's fc1 feeds its LogisticBank directly (AcousticModel.fc1 is Linear +
-        // Dropout, no activation: onsetsframes.py:422-427, then models/common.py:539), so in eval mode the two Linear layers are one:
-        //     logits = W_out (W_fc1 a + b_fc1) + b_out = (W_out W_fc1) a + (W_out b_fc1 + b_out)
-        // folded here in double precision (the same kind of weight folding as the BatchNorms above): a K = kfc, N = n_out GEMM
-        // replaces a K = kfc, N = dim_am one plus a K = dim_am, N = n_out one, and the dim_am-wide activation never exists.
-        std::vector<std::vector<float>> fcw_rec(fcw.begin(), fcw.begin() + m->n_rec), fcb_rec(fcb.begin(), fcb.begin() + m->n_rec);
-        if (m->n_rec > 0 && (rc = pack_linear_groups(m, m->fc1, fcw_rec, fcb_rec, m->dim_am, m->kfc_pad)) != AMTX_OK) return rc;
-    }
+// ---------------------------------------------------------------------------------------------------------------------------
+// Weight sync.  pack_model is the ONE walk over the state_dict: per head and stage, which tensors are needed (name, element count),
+// which layout or fold applies, and where in which packed buffer the result goes.  An executor does the steps.  HostPack
+// (amtx_of_model_finalize; the first sync, it sizes and allocates the buffers) runs the host packers on the host copies into staging
+// images of the buffers, which are then uploaded.  DevicePack (amtx_of_model_finalize_device) launches the kernels of pack.hip on
+// borrowed device tensors into the buffers themselves.  Both loop over the layouts of amtx_pack_layouts.h: the same bits.
+namespace {
 
-    // ---- recurrent heads (onset, offset): LSTM + LogisticBank
-    {
-        std::vector<std::vector<float>> wih(m->n_rec), bih(m->n_rec), wo(m->n_rec), bo(m->n_rec);
-        std::vector<bf16_t> hh_all;
-        for (int r = 0; r < m->n_rec; ++r) {
-            std::vector<bf16_t> hh;
-            if ((rc = pack_lstm(m, m->head_names[r] + ".1", m->dim_am, wih[r], bih[r], hh)) != AMTX_OK) return rc;
-            hh_all.insert(hh_all.end(), hh.begin(), hh.end());
-            const float *w, *b;
-            NEED(m->head_names[r] + ".2.output_layer.weight", (size_t)m->n_out * m->dim_lm, w);
-            NEED(m->head_names[r] + ".2.output_layer.bias", (size_t)m->n_out, b);
-            wo[r].assign(w, w + (size_t)m->n_out * m->dim_lm);
-            bo[r].assign(b, b + m->n_out);
-        }
-        if ((rc = pack_linear_groups(m, m->rec_ih, wih, bih, m->xw, m->dim_am)) != AMTX_OK) return rc;
-        if ((rc = m->rec_hh.upload(hh_all.data(), hh_all.size() * 2)) != AMTX_OK) return rc;
-        if ((rc = pack_linear_groups(m, m->rec_out, wo, bo, m->n_out, m->dim_lm)) != AMTX_OK) return rc;
+struct HostPack {
+    amtx_of_model* m;
+    std::map<DevBuf*, std::vector<char>> image;        // staging images of the packed buffers
+    std::vector<float> scratch_;
+
+    int need(const std::string& name, size_t numel, const float** p) { return m->store.need(name, numel, p); }
+    template <class T> T* dst(DevBuf& b, size_t elems) {
+        std::vector<char>& v = image[&b];
+        v.resize(elems * sizeof(T));
+        return (T*)v.data();
     }
-    // ---- pitch head LogisticBank
-    {
-        const float *w, *b;
-        NEED("pitch_head.1.output_layer.weight", (size_t)m->n_out * m->dim_am, w);
-        NEED("pitch_head.1.output_layer.bias", (size_t)m->n_out, b);
-        const std::vector<float>& fw = fcw[nh - 1];   // (dim_am, kfc_pad), columns already in the engine's (freq, channel) order
-        const std::vector<float>& fb1 = fcb[nh - 1];
-        std::vector<std::vector<float>> W(1), Bv(1);
-        W[0].assign((size_t)m->n_out * m->kfc_pad, 0.0f);
-        Bv[0].assign(m->n_out, 0.0f);
-        // n_out x dim_am x kfc double-precision multiply-adds (164 M at model_complexity 2): output rows dealt to a few host threads, each
-        // row summed in the same order as before (the result does not depend on the thread count)
-        auto fold_rows = [&](int o0, int o1) {
-            std::vector<double> rowacc(m->kfc_pad);
+    int scratch(size_t floats, float** p) { scratch_.resize(floats); *p = scratch_.data(); return AMTX_OK; }
+    int bn_fold(const float* cb, const float* g, const float* be, const float* mu, const float* var, int c_out, float* scale, float* shift) {
+        for (int c = 0; c < c_out; ++c) amtx_bn_fold(cb, g, be, mu, var, c, scale, shift);
+        return AMTX_OK;
+    }
+    int scale_rows(const float* w, const float* scale, int rows, int cols, float* out) {
+        for (int item = 0; item < rows * cols; ++item) amtx_layout_scale_rows(item, w, scale, cols, out);
+        return AMTX_OK;
+    }
+    int conv1(const float* w, const float* scale, int c_in, bf16_t* out) { m->k->conv1_pack_host(w, scale, c_in, m->planes, out); return AMTX_OK; }
+    int conv1g(const float* w, const float* scale, int c_in, int c_mid, bf16_t* out) { m->k->conv1g_pack_host(w, scale, c_in, c_mid, m->planes, out); return AMTX_OK; }
+    int conv3x3(const float* w, const float* scale, int c_out, bf16_t* out) { m->k->conv3x3_pack_host(w, scale, c_out, m->planes, out); return AMTX_OK; }
+    int conv_gen(const float* w, const float* scale, int c_in, int c_out, bf16_t* out) { m->k->conv3x3_gen_pack_host(w, scale, c_in, c_out, m->planes, out); return AMTX_OK; }
+    int linear(const float* W, int64_t ldw, int N, int K, const LinearPack& lp, int row0, int rows, int perm_c, int perm_f, bf16_t* out) {
+        m->k->pack_linear_host(W, ldw, N, K, m->planes, lp.n_pad, lp.k_pad, row0, rows, perm_c, perm_f, out);
+        return AMTX_OK;
+    }
+    int vec_add(const float* a, const float* b, int n, float* out) { for (int i = 0; i < n; ++i) out[i] = a[i] + b[i]; return AMTX_OK; }
+    int copy(float* out, const float* src, size_t n) { memcpy(out, src, n * sizeof(float)); return AMTX_OK; }
+    int bilstm(const float* whh_fwd, const float* whh_bwd, bf16_t* out) { m->k->bilstm_pack_host_h(whh_fwd, whh_bwd, m->hid, m->planes, out); return AMTX_OK; }
+    // The ONE step with a loop structure of its own: n_out x dim_am x kfc double multiply-adds (164 M at model_complexity 2) would be
+    // many times slower on a CPU one output element at a time, as head_fold_kernel (pack.hip) does them.  Output rows are dealt to a few
+    // host threads; a row is accumulated over W_fc1's rows in W_fc1's own, contiguous column order and permuted when it is written.
+    // What the two share: the column map amtx_fc1_col and the summation order, j ascending per element (the result does not depend on
+    // the thread count).
+    int head_fold(const float* w_out, const float* w_fc1, const float* b_fc1, const float* b_out, float* wfold, float* bfold) {
+        const int n_out = m->n_out, dim_am = m->dim_am, kfc = m->kfc, kfc_pad = m->kfc_pad, nf3 = m->nf3, fq = m->fq;
+        auto fold_rows = [=](int o0, int o1) {
+            std::vector<double> rowacc(kfc);
             for (int o = o0; o < o1; ++o) {
                 std::fill(rowacc.begin(), rowacc.end(), 0.0);
-                double bacc = b[o];
-                for (int j = 0; j < m->dim_am; ++j) {
-                    const double wo = w[(size_t)o * m->dim_am + j];
-                    const float* frow = fw.data() + (size_t)j * m->kfc_pad;
-                    for (int k = 0; k < m->kfc_pad; ++k) rowacc[k] += wo * frow[k];
-                    bacc += wo * fb1[j];
+                double bacc = b_out[o];
+                for (int j = 0; j < dim_am; ++j) {
+                    const double wo = w_out[(size_t)o * dim_am + j];
+                    const float* frow = w_fc1 + (size_t)j * kfc;
+                    for (int ks = 0; ks < kfc; ++ks) rowacc[ks] += wo * frow[ks];
+                    bacc += wo * b_fc1[j];
                 }
-                for (int k = 0; k < m->kfc_pad; ++k) W[0][(size_t)o * m->kfc_pad + k] = (float)rowacc[k];
-                Bv[0][o] = (float)bacc;
+                for (int k = 0; k < kfc_pad; ++k) wfold[(size_t)o * kfc_pad + k] = k < kfc ? (float)rowacc[amtx_fc1_col(k, nf3, fq)] : 0.0f;
+                bfold[o] = (float)bacc;
             }
         };
         const int nthreads = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
         std::vector<std::thread> pool;
-        const int per = (m->n_out + nthreads - 1) / nthreads;
+        const int per = (n_out + nthreads - 1) / nthreads;
         for (int t = 1; t < nthreads; ++t)
-            if (t * per < m->n_out) pool.emplace_back(fold_rows, t * per, std::min(m->n_out, (t + 1) * per));
-        fold_rows(0, std::min(m->n_out, per));
+            if (t * per < n_out) pool.emplace_back(fold_rows, t * per, std::min(n_out, (t + 1) * per));
+        fold_rows(0, std::min(n_out, per));
         for (auto& th : pool) th.join();
-        if ((rc = pack_linear_groups(m, m->pitch_out, W, Bv, m->n_out, m->kfc_pad)) != AMTX_OK) return rc;
+        return AMTX_OK;
+    }
+};
+
+// `dry`: look up and size-check every tensor, launch nothing -- amtx_of_model_finalize_device runs this pass first, so a missing or
+// mis-sized tensor is reported before a single packed buffer has been touched (the buffers never end up half new, half old).
+struct DevicePack {
+    amtx_of_model* m;
+    hipStream_t s;
+    bool dry;
+
+    int need(const std::string& name, size_t numel, const float** p) { return m->store.need_device(name, numel, p); }
+    template <class T> T* dst(DevBuf& b, size_t) { return (T*)b.p; }
+    // behind the walk's floats: the backward LSTM fragments (written by the shared pack kernel, not used by inference)
+    bf16_t* hh_bwd = nullptr;
+    int scratch(size_t floats, float** p) {
+        const size_t bytes = floats * sizeof(float) + m->hh_elems * sizeof(bf16_t) + 256;
+        if (!m->pack_scratch.p || m->pack_scratch.bytes < bytes) {
+            m->pack_scratch.release();
+            AMTX_CHECK_HIP(hipMalloc(&m->pack_scratch.p, bytes));
+            m->pack_scratch.bytes = bytes;
+        }
+        *p = (float*)m->pack_scratch.p;
+        hh_bwd = (bf16_t*)(((uintptr_t)(*p + floats) + 255) & ~(uintptr_t)255);
+        return AMTX_OK;
+    }
+    int bn_fold(const float* cb, const float* g, const float* be, const float* mu, const float* var, int c_out, float* scale, float* shift) {
+        return dry ? AMTX_OK : amtx_pack_bn_fold_dev(cb, g, be, mu, var, c_out, scale, shift, s);
+    }
+    int scale_rows(const float* w, const float* scale, int rows, int cols, float* out) { return dry ? AMTX_OK : amtx_pack_scale_rows_dev(w, scale, rows, cols, out, s); }
+    int conv1(const float* w, const float* scale, int c_in, bf16_t* out) {
+        AMTX_REQUIRE(c_in == 1, "amtx_of_model_finalize_device: internal: no device packer for a multi-channel first conv on conv.hip");
+        return dry ? AMTX_OK : m->k->pack_conv1_dev(w, scale, m->planes, out, s);
+    }
+    int conv1g(const float* w, const float* scale, int c_in, int c_mid, bf16_t* out) { return dry ? AMTX_OK : m->k->pack_conv1g_dev(w, scale, c_in, c_mid, m->planes, out, s); }
+    int conv3x3(const float* w, const float* scale, int c_out, bf16_t* out) { return dry ? AMTX_OK : m->k->pack_conv3x3_dev(w, scale, c_out, m->planes, out, s); }
+    int conv_gen(const float* w, const float* scale, int c_in, int c_out, bf16_t* out) {
+        return dry ? AMTX_OK : m->k->pack_conv_gen_dev(w, scale, c_in, c_out, amtx_conv3x3_gen_ntc(c_in, c_out), m->planes, out, s);
+    }
+    int linear(const float* W, int64_t ldw, int N, int K, const LinearPack& lp, int row0, int rows, int perm_c, int perm_f, bf16_t* out) {
+        return dry ? AMTX_OK : m->k->pack_linear_dev(W, ldw, N, K, m->planes, lp.n_pad, lp.k_pad, row0, rows, perm_c, perm_f, out, s);
+    }
+    int vec_add(const float* a, const float* b, int n, float* out) { return dry ? AMTX_OK : amtx_pack_vec_add_dev(a, b, n, out, s); }
+    int copy(float* out, const float* src, size_t n) {
+        if (!dry) AMTX_CHECK_HIP(hipMemcpyAsync(out, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return AMTX_OK;
+    }
+    int bilstm(const float* whh_fwd, const float* whh_bwd, bf16_t* out) {
+        return dry ? AMTX_OK : m->k->launch_bilstm_pack_dev_h(whh_fwd, whh_bwd, m->hid, m->planes, out, hh_bwd, s);
+    }
+    int head_fold(const float* w_out, const float* w_fc1, const float* b_fc1, const float* b_out, float* wfold, float* bfold) {
+        return dry ? AMTX_OK : amtx_pack_head_fold_dev(w_out, w_fc1, b_fc1, b_out, m->n_out, m->dim_am, m->kfc, m->kfc_pad, m->nf3, m->fq, wfold, bfold, s);
+    }
+};
+
+#define NEED(name, numel, ptr)                                         \
+    do {                                                               \
+        int _rc = x.need(name, numel, &(ptr));                         \
+        if (_rc != AMTX_OK) return _rc;                                \
+    } while (0)
+#define STEP(expr)                                                     \
+    do {                                                               \
+        int _rc = (expr);                                              \
+        if (_rc != AMTX_OK) return _rc;                                \
+    } while (0)
+
+template <class X>
+int pack_model(amtx_of_model* m, X& x) {
+    const int nh = m->n_heads, pl = m->planes, G = 4 * m->hid, ic = m->in_channels;
+    const ConvPlan& p = m->plan;
+    auto size_linear = [](LinearPack& lp, int N, int K, int groups) {
+        lp.N = N; lp.K = K; lp.groups = groups;
+        amtx_gemm_pack_dims(N, K, &lp.n_pad, &lp.k_pad);
+    };
+    size_linear(m->fc1, m->dim_am, m->kfc_pad, m->n_rec);
+    size_linear(m->rec_ih, m->xw, m->dim_am, m->n_rec);
+    size_linear(m->rec_out, m->n_out, m->dim_lm, m->n_rec);
+    size_linear(m->pitch_out, m->n_out, m->kfc_pad, 1);
+    size_linear(m->adj_ih, m->xw, m->dim_aj, 1);
+    size_linear(m->adj_out, m->n_out, m->dim_lm, 1);
+    // rows [row0, row0 + rows) of group grp of a Linear layer's packed weights, from W (N x K); its bias
+    auto linear = [&](LinearPack& lp, int grp, const float* W, int N, int K, int row0, int rows, int perm_c, int perm_f) {
+        const size_t per = (size_t)lp.n_pad * lp.k_pad * pl;
+        return x.linear(W, K, N, K, lp, row0, rows, perm_c, perm_f, x.template dst<bf16_t>(lp.w, per * lp.groups) + per * grp);
+    };
+    auto bias = [&](LinearPack& lp, int grp) { return x.template dst<float>(lp.b, (size_t)lp.N * lp.groups) + (size_t)lp.N * grp; };
+    auto need_fc1 = [&](int h, const float*& w, const float*& b) {
+        NEED(m->head_names[h] + ".0.fc1.0.weight", (size_t)m->dim_am * m->kfc, w);
+        NEED(m->head_names[h] + ".0.fc1.0.bias", (size_t)m->dim_am, b);
+        return (int)AMTX_OK;
+    };
+    auto need_bank = [&](const std::string& bank, int K, const float*& w, const float*& b) {
+        NEED(bank + ".output_layer.weight", (size_t)m->n_out * K, w);
+        NEED(bank + ".output_layer.bias", (size_t)m->n_out, b);
+        return (int)AMTX_OK;
+    };
+    // scratch: BatchNorm scale[256] | folded pitch head (n_out x kfc_pad) | folded bias
+    AMTX_REQUIRE(m->nf3 <= 256, "of_model: internal: scale scratch");
+    float* scale;
+    STEP(x.scratch(256 + (size_t)m->n_out * m->kfc_pad + m->n_out, &scale));
+    float* wfold = scale + 256;
+    float* bfold = wfold + (size_t)m->n_out * m->kfc_pad;
+
+    // ---- acoustic heads
+    for (int h = 0; h < nh; ++h) {
+        const std::string am = m->head_names[h] + ".0";
+        const float *w, *cb, *g, *be, *mu, *var;
+        for (int l = 0; l < 3; ++l) {
+            // Conv + eval-mode BatchNorm: the scale goes into the packed weights, the shift stays fp32
+            const ConvLayer& y = p.layer[l];
+            const std::string conv = am + "." + y.name + ".0", bn = am + "." + y.name + ".1";
+            NEED(conv + ".weight", (size_t)y.c_out * y.c_in * 9, w);
+            NEED(conv + ".bias", (size_t)y.c_out, cb); NEED(bn + ".weight", (size_t)y.c_out, g); NEED(bn + ".bias", (size_t)y.c_out, be);
+            NEED(bn + ".running_mean", (size_t)y.c_out, mu); NEED(bn + ".running_var", (size_t)y.c_out, var);
+            STEP(x.bn_fold(cb, g, be, mu, var, y.c_out, scale, x.template dst<float>(m->conv_s[l], (size_t)nh * y.c_out) + (size_t)h * y.c_out));
+            bf16_t* frag = x.template dst<bf16_t>(m->conv_w[l], y.frag_per * nh) + y.frag_per * h;
+            if (l == 0) {     // the fp32 copy feeds only the separate first conv
+                const size_t per = (size_t)y.c_out * ic * 9;
+                STEP(x.scale_rows(w, scale, y.c_out, ic * 9, x.template dst<float>(m->conv1_w, per * nh) + per * h));
+                if (y.fam == K_CONVG) STEP(x.conv1g(w, scale, ic, y.c_out, frag));
+                else if (y.fam == K_CONV) STEP(x.conv1(w, scale, ic, frag));
+            } else if (y.fam == K_CONVG) STEP(x.conv_gen(w, scale, y.c_in, y.c_out, frag));
+            else STEP(x.conv3x3(w, scale, y.c_out, frag));
+            if (l == 1 && p.convx12) STEP(x.conv3x3(w, scale, y.c_out, x.template dst<bf16_t>(m->conv2_wx, p.c2x_per * nh) + p.c2x_per * h));
+        }
+        // fc1 of the RECURRENT heads only (the pitch head's is folded into its LogisticBank below), columns permuted from the reference's
+        // (channel, freq) to the conv kernels' (freq, channel) order; columns kfc .. kfc_pad are zero
+        if (h < m->n_rec) {
+            const float* fb;
+            STEP(need_fc1(h, w, fb));
+            STEP(linear(m->fc1, h, w, m->dim_am, m->kfc, 0, m->fc1.n_pad, m->nf3, m->fq));
+            STEP(x.copy(bias(m->fc1, h), fb, m->dim_am));
+        }
+    }
+    // ---- LSTM + LogisticBank of a recurrent stage: input projection rows [fwd | reverse], merged biases b_ih + b_hh, W_hh fragments, output layer
+    auto pack_rec = [&](const std::string& lstm, const std::string& bank, int dim_in, LinearPack& ih, DevBuf& hh, LinearPack& outp, int grp) {
+        const float *wif, *wib, *whf, *whb, *bif, *bib, *bhf, *bhb, *wo, *bo;
+        const std::string q = lstm + ".mlm.";
+        NEED(q + "weight_ih_l0", (size_t)G * dim_in, wif); NEED(q + "weight_ih_l0_reverse", (size_t)G * dim_in, wib);
+        NEED(q + "weight_hh_l0", (size_t)G * m->hid, whf); NEED(q + "weight_hh_l0_reverse", (size_t)G * m->hid, whb);
+        NEED(q + "bias_ih_l0", (size_t)G, bif); NEED(q + "bias_ih_l0_reverse", (size_t)G, bib);
+        NEED(q + "bias_hh_l0", (size_t)G, bhf); NEED(q + "bias_hh_l0_reverse", (size_t)G, bhb);
+        STEP(linear(ih, grp, wif, G, dim_in, 0, G, 0, 0));
+        STEP(linear(ih, grp, wib, G, dim_in, G, ih.n_pad - G, 0, 0));
+        STEP(x.vec_add(bif, bhf, G, bias(ih, grp)));
+        STEP(x.vec_add(bib, bhb, G, bias(ih, grp) + G));
+        STEP(x.bilstm(whf, whb, x.template dst<bf16_t>(hh, m->hh_elems * ih.groups) + m->hh_elems * grp));
+        STEP(need_bank(bank, m->dim_lm, wo, bo));
+        STEP(linear(outp, grp, wo, m->n_out, m->dim_lm, 0, outp.n_pad, 0, 0));
+        STEP(x.copy(bias(outp, grp), bo, m->n_out));
+        return (int)AMTX_OK;
+    };
+    for (int r = 0; r < m->n_rec; ++r) STEP(pack_rec(m->head_names[r] + ".1", m->head_names[r] + ".2", m->dim_am, m->rec_ih, m->rec_hh, m->rec_out, r));
+    // ---- pitch head.  Its fc1 feeds its LogisticBank directly (AcousticModel.fc1 is Linear + Dropout, no activation:
+    // onsetsframes.py:422-427, then models/common.py:539), so in eval mode the two Linear layers are one:
+    //     logits = W_out (W_fc1 a + b_fc1) + b_out = (W_out W_fc1) a + (W_out b_fc1 + b_out)
+    // folded in double precision (the same kind of weight folding as the BatchNorms above): a K = kfc, N = n_out GEMM replaces a
+    // K = kfc, N = dim_am one plus a K = dim_am, N = n_out one, and the dim_am-wide activation never exists.
+    {
+        const float *wo, *bo, *w1, *b1;
+        STEP(need_bank("pitch_head.1", m->dim_am, wo, bo));
+        STEP(need_fc1(nh - 1, w1, b1));
+        STEP(x.head_fold(wo, w1, b1, bo, wfold, bfold));
+        STEP(linear(m->pitch_out, 0, wfold, m->n_out, m->kfc_pad, 0, m->pitch_out.n_pad, 0, 0));
+        STEP(x.copy(bias(m->pitch_out, 0), bfold, m->n_out));
     }
     // ---- adjoin: LSTM over the joint logits + LogisticBank
-    {
-        std::vector<std::vector<float>> wih(1), bih(1);
-        std::vector<bf16_t> hh;
-        if ((rc = pack_lstm(m, "adjoin.0", m->dim_aj, wih[0], bih[0], hh)) != AMTX_OK) return rc;
-        if ((rc = pack_linear_groups(m, m->adj_ih, wih, bih, m->xw, m->dim_aj)) != AMTX_OK) return rc;
-        if ((rc = m->adj_hh.upload(hh.data(), hh.size() * 2)) != AMTX_OK) return rc;
-        const float *w, *b;
-        NEED("adjoin.1.output_layer.weight", (size_t)m->n_out * m->dim_lm, w);
-        NEED("adjoin.1.output_layer.bias", (size_t)m->n_out, b);
-        std::vector<std::vector<float>> W{std::vector<float>(w, w + (size_t)m->n_out * m->dim_lm)}, Bv{std::vector<float>(b, b + m->n_out)};
-        if ((rc = pack_linear_groups(m, m->adj_out, W, Bv, m->n_out, m->dim_lm)) != AMTX_OK) return rc;
+    return pack_rec("adjoin.0", "adjoin.1", m->dim_aj, m->adj_ih, m->adj_hh, m->adj_out, 0);
+}
+
+}  // namespace
+
+extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
+    AMTX_REQUIRE(m, "amtx_of_model_finalize: null model");
+    STEP(amtx_quiesce_before_resync(m->packed_once));
+    if (m->plan.layer[2].fam == K_CONVG && (!amtx_conv3x3_gen_ntc(m->nf1, m->nf2) || !amtx_conv3x3_gen_ntc(m->nf2, m->nf3))) {
+        amtx_set_error("of_model: no convolution kernel for %d -> %d -> %d channels", m->nf1, m->nf2, m->nf3);
+        return AMTX_ERR_UNSUPPORTED;
+    }
+    HostPack x{m};
+    STEP(pack_model(m, x));
+    // the upload order is part of the recorded table (tests/golden/of_conv_plan.json); a buffer this model does not have has no image
+    DevBuf* order[] = {&m->conv1_w, &m->conv_s[0], &m->conv_w[0], &m->conv_w[1], &m->conv2_wx, &m->conv_s[1], &m->conv_w[2], &m->conv_s[2],
+                       &m->fc1.w, &m->fc1.b, &m->rec_ih.w, &m->rec_ih.b, &m->rec_hh, &m->rec_out.w, &m->rec_out.b, &m->pitch_out.w, &m->pitch_out.b,
+                       &m->adj_ih.w, &m->adj_ih.b, &m->adj_hh, &m->adj_out.w, &m->adj_out.b};
+    for (DevBuf* b : order) {
+        const std::vector<char>& v = x.image[b];
+        if (!v.empty()) STEP(b->upload(v.data(), v.size()));
     }
     m->store.host.clear();
     m->finalized = true;
@@ -477,28 +540,16 @@ extern "C" int amtx_of_model_finalize(amtx_of_model* m) {
     return AMTX_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// Weight RE-SYNC without leaving the GPU.  After one host-side amtx_of_model_finalize (which sizes and allocates every packed
-// buffer), later weight versions can be handed over as device pointers under the same state_dict names and packed by the kernels of
-// pack.hip -- the host packers' arithmetic and layouts, bit for bit.  Built for every configuration the engine runs (the engine
-// validates at every checkpoint of train.py, amt_tools/train.py:183-189): model_complexity 2 .. 5, one or several input channels,
-// any precision -- except a multi-channel first conv on conv.hip's kernel (AMTX_NO_CONVG_MC2, or 9 and more input channels at 32 / 32 / 64; ConvPlan::device_resync),
+// Weight RE-SYNC without leaving the GPU.  After one host-side amtx_of_model_finalize, later weight versions can be handed over as
+// device pointers under the same state_dict names.  Built for every configuration the engine runs (the engine validates at every
+// checkpoint of train.py, amt_tools/train.py:183-189): model_complexity 2 .. 5, one or several input channels, any precision -- except a
+// multi-channel first conv on conv.hip's kernel (AMTX_NO_CONVG_MC2, or 9 and more input channels at 32 / 32 / 64; ConvPlan::device_resync),
 // which answers AMTX_ERR_UNSUPPORTED and keeps the host path.
 extern "C" int amtx_of_model_set_tensor_device(amtx_of_model* m, const char* name, const float* device_data, int64_t numel) {
     AMTX_REQUIRE(m && name && device_data && numel > 0, "amtx_of_model_set_tensor_device: bad argument");
     m->store.set_device(name, device_data, numel);
     return AMTX_OK;
 }
-
-#define NEED_DEV(name, numel, ptr)                                     \
-    do {                                                               \
-        int _rc = m->store.need_device(name, numel, &(ptr));           \
-        if (_rc != AMTX_OK) return _rc;                                \
-    } while (0)
-
-// `dry`: look up and size-check every tensor, launch nothing -- amtx_of_model_finalize_device runs this pass first, so a missing or
-// mis-sized tensor is reported before a single packed buffer has been touched (the buffers never end up half new, half old).
-static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry);
 
 extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
     AMTX_REQUIRE(m, "amtx_of_model_finalize_device: null model");
@@ -511,119 +562,13 @@ extern "C" int amtx_of_model_finalize_device(amtx_of_model* m, void* stream_) {
         amtx_set_error("amtx_of_model_finalize_device: no device packer for conv.hip's multi-channel first conv; use amtx_of_model_finalize");
         return AMTX_ERR_UNSUPPORTED;
     }
-    hipStream_t s = (hipStream_t)stream_;
-    int rc = finalize_device_pass(m, s, true);
-    if (rc != AMTX_OK) return rc;
-    if ((rc = amtx_quiesce_before_resync(m->packed_once)) != AMTX_OK) return rc;
-    rc = finalize_device_pass(m, s, false);
+    DevicePack x{m, (hipStream_t)stream_, true};
+    STEP(pack_model(m, x));
+    STEP(amtx_quiesce_before_resync(m->packed_once));
+    x.dry = false;
+    const int rc = pack_model(m, x);
     if (rc != AMTX_OK) m->finalized = false;   // a launch failed half-way: the packed weights are no version at all, refuse to run on them
     return rc;
-}
-
-#define PACK_TRY(expr)                                                 \
-    do {                                                               \
-        if (!dry) {                                                    \
-            int _rc = (expr);                                          \
-            if (_rc != AMTX_OK) return _rc;                            \
-        }                                                              \
-    } while (0)
-#define PACK_COPY(dst, src, bytes)                                                                         \
-    do {                                                                                                   \
-        if (!dry) AMTX_CHECK_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, s));       \
-    } while (0)
-
-static int finalize_device_pass(amtx_of_model* m, hipStream_t s, const bool dry) {
-    const int nh = m->n_heads, pl = m->planes, H = m->hid, G = 4 * H, ic = m->in_channels;
-    const KernelSet* k = m->k;
-    // scratch: scale[256] | folded pitch head (n_out x kfc_pad) | folded bias | backward LSTM fragments (written by the shared pack
-    // kernel, not used by inference)
-    const size_t hh_elems = m->hh_elems;
-    const size_t sc_bytes = (size_t)(256 + (size_t)m->n_out * m->kfc_pad + m->n_out) * sizeof(float) + hh_elems * sizeof(bf16_t) + 256;
-    AMTX_REQUIRE(m->nf3 <= 256, "amtx_of_model_finalize_device: internal: scale scratch");
-    if (!m->pack_scratch.p || m->pack_scratch.bytes < sc_bytes) {
-        m->pack_scratch.release();
-        AMTX_CHECK_HIP(hipMalloc(&m->pack_scratch.p, sc_bytes));
-        m->pack_scratch.bytes = sc_bytes;
-    }
-    float* scale = (float*)m->pack_scratch.p;
-    float* wfold = scale + 256;
-    float* bfold = wfold + (size_t)m->n_out * m->kfc_pad;
-    bf16_t* hh_bwd = (bf16_t*)(((uintptr_t)(bfold + m->n_out) + 255) & ~(uintptr_t)255);
-
-    const ConvPlan& p = m->plan;
-    const size_t fc_per = (size_t)m->fc1.n_pad * m->fc1.k_pad * pl;
-    for (int h = 0; h < nh; ++h) {
-        const std::string am = m->head_names[h] + ".0";
-        const float *w, *cb, *g, *be, *mu, *var;
-        for (int l = 0; l < 3; ++l) {
-            // scale folded into the packed weights, shift kept fp32; layer1's fp32 copy conv1_w feeds only the separate first conv
-            const ConvLayer& y = p.layer[l];
-            const std::string conv = am + "." + y.name + ".0", bn = am + "." + y.name + ".1";
-            NEED_DEV(conv + ".weight", (size_t)y.c_out * y.c_in * 9, w);
-            NEED_DEV(conv + ".bias", (size_t)y.c_out, cb); NEED_DEV(bn + ".weight", (size_t)y.c_out, g); NEED_DEV(bn + ".bias", (size_t)y.c_out, be);
-            NEED_DEV(bn + ".running_mean", (size_t)y.c_out, mu); NEED_DEV(bn + ".running_var", (size_t)y.c_out, var);
-            PACK_TRY(amtx_pack_bn_fold_dev(cb, g, be, mu, var, y.c_out, scale, (float*)m->conv_s[l].p + (size_t)h * y.c_out, s));
-            bf16_t* frag = (bf16_t*)m->conv_w[l].p + y.frag_per * h;
-            if (l == 0) {
-                PACK_TRY(amtx_pack_scale_rows_dev(w, scale, y.c_out, ic * 9, (float*)m->conv1_w.p + (size_t)h * y.c_out * ic * 9, s));
-                if (y.fam == K_CONVG) PACK_TRY(k->pack_conv1g_dev(w, scale, ic, y.c_out, pl, frag, s));
-                else if (y.fam == K_CONV) PACK_TRY(k->pack_conv1_dev(w, scale, pl, frag, s));
-            } else if (y.fam == K_CONVG) PACK_TRY(k->pack_conv_gen_dev(w, scale, y.c_in, y.c_out, amtx_conv3x3_gen_ntc(y.c_in, y.c_out), pl, frag, s));
-            else PACK_TRY(k->pack_conv3x3_dev(w, scale, y.c_out, pl, frag, s));
-            if (l == 1 && p.convx12) PACK_TRY(k->pack_conv3x3_dev(w, scale, y.c_out, pl, (bf16_t*)m->conv2_wx.p + p.c2x_per * h, s));
-        }
-        // fc1 of the recurrent heads, columns permuted (channel, freq) -> (freq, channel)
-        if (h < m->n_rec) {
-            const float* fb;
-            NEED_DEV(am + ".fc1.0.weight", (size_t)m->dim_am * m->kfc, w);
-            NEED_DEV(am + ".fc1.0.bias", (size_t)m->dim_am, fb);
-            PACK_TRY(k->pack_linear_dev(w, m->kfc, m->dim_am, m->kfc, pl, m->fc1.n_pad, m->fc1.k_pad, 0, m->fc1.n_pad, m->nf3, m->fq, (bf16_t*)m->fc1.w.p + fc_per * h, s));
-            PACK_COPY((float*)m->fc1.b.p + (size_t)h * m->dim_am, fb, sizeof(float) * m->dim_am);
-        }
-    }
-    // LSTM + LogisticBank of a recurrent stage: input projection rows [fwd | reverse], merged biases, W_hh fragments, output layer
-    auto pack_rec = [&](const std::string& lstm, const std::string& bank, int dim_in, LinearPack& ih, DevBuf& hh, LinearPack& outp, int grp) -> int {
-        const float *wif, *wib, *whf, *whb, *bif, *bib, *bhf, *bhb, *wo, *bo;
-        const std::string p = lstm + ".mlm.";
-        NEED_DEV(p + "weight_ih_l0", (size_t)G * dim_in, wif); NEED_DEV(p + "weight_ih_l0_reverse", (size_t)G * dim_in, wib);
-        NEED_DEV(p + "weight_hh_l0", (size_t)G * H, whf); NEED_DEV(p + "weight_hh_l0_reverse", (size_t)G * H, whb);
-        NEED_DEV(p + "bias_ih_l0", (size_t)G, bif); NEED_DEV(p + "bias_ih_l0_reverse", (size_t)G, bib);
-        NEED_DEV(p + "bias_hh_l0", (size_t)G, bhf); NEED_DEV(p + "bias_hh_l0_reverse", (size_t)G, bhb);
-        bf16_t* ihw = (bf16_t*)ih.w.p + (size_t)ih.n_pad * ih.k_pad * pl * grp;
-        PACK_TRY(k->pack_linear_dev(wif, dim_in, G, dim_in, pl, ih.n_pad, ih.k_pad, 0, G, 0, 0, ihw, s));
-        PACK_TRY(k->pack_linear_dev(wib, dim_in, G, dim_in, pl, ih.n_pad, ih.k_pad, G, ih.n_pad - G, 0, 0, ihw, s));
-        float* ihb = (float*)ih.b.p + (size_t)ih.N * grp;
-        PACK_TRY(amtx_pack_vec_add_dev(bif, bhf, G, ihb, s));
-        PACK_TRY(amtx_pack_vec_add_dev(bib, bhb, G, ihb + G, s));
-        PACK_TRY(k->launch_bilstm_pack_dev_h(whf, whb, H, pl, (bf16_t*)hh.p + hh_elems * grp, hh_bwd, s));
-        NEED_DEV(bank + ".output_layer.weight", (size_t)m->n_out * m->dim_lm, wo);
-        NEED_DEV(bank + ".output_layer.bias", (size_t)m->n_out, bo);
-        PACK_TRY(k->pack_linear_dev(wo, m->dim_lm, m->n_out, m->dim_lm, pl, outp.n_pad, outp.k_pad, 0, outp.n_pad, 0, 0,
-                          (bf16_t*)outp.w.p + (size_t)outp.n_pad * outp.k_pad * pl * grp, s));
-        PACK_COPY((float*)outp.b.p + (size_t)outp.N * grp, bo, sizeof(float) * m->n_out);
-        return AMTX_OK;
-    };
-    for (int r = 0; r < m->n_rec; ++r) {
-        const int prc = pack_rec(m->head_names[r] + ".1", m->head_names[r] + ".2", m->dim_am, m->rec_ih, m->rec_hh, m->rec_out, r);
-        if (prc != AMTX_OK) return prc;
-    }
-    {
-        const int prc = pack_rec("adjoin.0", "adjoin.1", m->dim_aj, m->adj_ih, m->adj_hh, m->adj_out, 0);
-        if (prc != AMTX_OK) return prc;
-    }
-    // pitch head: LogisticBank folded into fc1 in double precision, then packed like any Linear layer
-    {
-        const float *wo, *bo, *w1, *b1;
-        NEED_DEV("pitch_head.1.output_layer.weight", (size_t)m->n_out * m->dim_am, wo);
-        NEED_DEV("pitch_head.1.output_layer.bias", (size_t)m->n_out, bo);
-        NEED_DEV("pitch_head.0.fc1.0.weight", (size_t)m->dim_am * m->kfc, w1);
-        NEED_DEV("pitch_head.0.fc1.0.bias", (size_t)m->dim_am, b1);
-        PACK_TRY(amtx_pack_head_fold_dev(wo, w1, b1, bo, m->n_out, m->dim_am, m->kfc, m->kfc_pad, m->nf3, m->fq, wfold, bfold, s));
-        PACK_TRY(k->pack_linear_dev(wfold, m->kfc_pad, m->n_out, m->kfc_pad, pl, m->pitch_out.n_pad, m->pitch_out.k_pad, 0, m->pitch_out.n_pad, 0, 0,
-                          (bf16_t*)m->pitch_out.w.p, s));
-        PACK_COPY(m->pitch_out.b.p, bfold, sizeof(float) * m->n_out);
-    }
-    return AMTX_OK;
 }
 
 extern "C" size_t amtx_of_workspace_bytes(const amtx_of_model* m, int batch, int num_frames) {
