@@ -109,6 +109,10 @@ _SIGNATURES = {
     'amtx_notes_rows': (_I, [_P, _P, _I, _I, _I, _P, _L, _I, _P, _P, _L, _P, _P]),
     'amtx_tab_expand': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
     'amtx_tab_notes': (_I, [_P, _I, _I, _I, _P, _I, _P, _L, _P, _L, _I, C.c_double, _P, _L, _P, _P]),
+    'amtx_eval_multipitch_counts': (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    'amtx_eval_tab_counts': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    'amtx_eval_notes_match_workspace_bytes': (C.c_size_t, [_L, _L]),
+    'amtx_eval_notes_match': (_I, [_P, _P, _L, _P, _P, _L, _I, C.c_double, C.c_double, C.c_double, _I, _P, C.c_size_t, _P, _P, _I, _P]),
     'amtx_pianoroll_fwd': (_I, [_P, _L, _I, _I, _I, _I, _F, _P, _P]),
     'amtx_matmul_workspace_bytes': (C.c_size_t, [_L, _L, _L]),
     'amtx_matmul_f32': (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _L, _L, _L, _L, _P, C.c_size_t, _P]),

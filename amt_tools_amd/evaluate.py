@@ -1,0 +1,796 @@
+"""
+Evaluation: the evaluator classes of amt_tools/evaluate.py (constructor arguments, result-dictionary layout and keys; `train()` takes them
+unchanged: process_track / average_results / reset_results / finalize(writer, step) / set_save_dir / set_patterns / set_verbose), and a
+batched validation loop that scores a partition on the device.
+
+Every evaluator is split in two:
+
+* counting -- `counts(estimated, reference)` on host arrays (the reference's own float64 expressions, evaluate.py:815-829, :1246-1281,
+  :1331-1334) or `counts_batch(estimated, reference)` on device tensors (ONE C-ABI call into csrc/eval.hip, a whole batch), and
+* `results_from_counts(counts)` -- the arithmetic from those few numbers to precision / recall / f-measure / tdr / accuracy.  Both paths end
+  in it, so they cannot disagree on the arithmetic.
+
+Note matching restates mir_eval.transcription.match_notes (mir_eval is not required): see `note_edges`.  UNPINNED: the rules -- non-strict
+comparisons, 0.05 s onset tolerance, 50 cents, 0.05 s minimum offset tolerance, distances rounded to N_DECIMALS before they are compared --
+are written down from the published behaviour, not checked against mir_eval's source; N_DECIMALS in particular.
+
+Not here: PitchListEvaluator / StackedPitchListEvaluator (they rest on mir_eval.multipitch's resampling) and run_online.
+"""
+import json
+import os
+import sys
+import warnings
+from copy import deepcopy
+
+import numpy as np
+
+from . import tools
+from .inference import run_offline
+
+__all__ = ['validate', 'validate_batched', 'average_results', 'append_results', 'log_results', 'write_results', 'pattern_match', 'Evaluator',
+           'ComboEvaluator', 'LossWrapper', 'StackedMultipitchEvaluator', 'MultipitchEvaluator', 'StackedNoteEvaluator', 'NoteEvaluator',
+           'TablatureEvaluator', 'SoftmaxAccuracy', 'note_edges', 'match_notes_count', 'N_DECIMALS']
+
+EPSILON = sys.float_info.epsilon
+N_DECIMALS = 4                 # decimals the note distances are rounded to before they meet a tolerance (UNPINNED, see above); the kernel takes it
+ONSET_TOLERANCE = 0.05         # seconds
+PITCH_TOLERANCE = 50.0         # cents
+OFFSET_MIN_TOLERANCE = 0.05    # seconds
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the loops
+# ------------------------------------------------------------------------------------------------------------------------------
+def validate(model, dataset, evaluator, estimator=None, online=False):
+    """One track at a time (amt_tools/evaluate.py:52-101): run_offline, then evaluator.process_track.  Returns the averaged results."""
+    import torch
+    if online:
+        raise NotImplementedError('run_online is not part of this package')
+    with torch.no_grad():
+        for track_id in dataset.tracks:
+            track_data = dataset.get_track_data(track_id)
+            model.eval()                       # per track, as in the reference: a model may reset state there
+            predictions = run_offline(track_data, model, estimator)
+            evaluator.process_track(predictions, track_data, track_id)
+    return evaluator.average_results()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# results dictionaries
+# ------------------------------------------------------------------------------------------------------------------------------
+def average_results(results):
+    """A copy in which every ndarray / list leaf is its mean as a float (nested dictionaries walked, other leaves kept)."""
+    out = deepcopy(results)
+    for key, entry in out.items():
+        if isinstance(entry, dict):
+            out[key] = average_results(entry)
+        elif isinstance(entry, (np.ndarray, list)):
+            out[key] = float(np.mean(entry))
+    return out
+
+
+def append_results(tracked_results, new_results):
+    """A copy of `tracked_results` with the leaves of `new_results` appended (np.append) under their keys; unknown keys are taken over."""
+    out = deepcopy(tracked_results)
+    for key, entry in new_results.items():
+        if key not in out:
+            out[key] = entry
+        elif isinstance(entry, dict):
+            out[key] = append_results(out[key], entry)
+        else:
+            out[key] = np.append(out[key], entry)
+    return out
+
+
+def pattern_match(query, patterns=None):
+    """Whether some pattern is a substring of `query` (no patterns: False)."""
+    return patterns is not None and any(p in query for p in patterns)
+
+
+def log_results(results, writer, step=0, patterns=None, tag='', prnt=False):
+    """writer.add_scalar(f'{tag}/{key}', value, global_step=step) for every leaf whose key matches (all when patterns is None); nested
+    dictionaries extend the tag.  As in the reference, `prnt` is not handed down to nested dictionaries."""
+    for key, entry in results.items():
+        if isinstance(entry, dict):
+            log_results(entry, writer, step, patterns, f'{tag}/{key}')
+        elif patterns is None or pattern_match(key, patterns):
+            writer.add_scalar(f'{tag}/{key}', entry, global_step=step)
+            if prnt:
+                print(json.dumps({'iter': step, f'{tag}/{key}': entry}))
+
+
+def _write_line(file, text, verbose):
+    file.write(text + '\n')
+    if verbose:
+        print(text)
+
+
+def write_results(results, file, patterns=None, verbose=False):
+    """Text form: '-----key-----' headers for nested dictionaries, ' key : value' lines, blank lines between blocks."""
+    for key, entry in results.items():
+        if isinstance(entry, dict):
+            _write_line(file, f'-----{key}-----', verbose)
+            write_results(entry, file, patterns, verbose)
+            _write_line(file, '', verbose)
+        elif patterns is None or pattern_match(key, patterns):
+            _write_line(file, f' {key} : {entry}', verbose)
+    _write_line(file, '', verbose)
+
+
+def _f_measure(precision, recall):
+    """mir_eval.util.f_measure with beta = 1: 2 p r / (p + r), 0 when both are 0."""
+    if precision == 0 and recall == 0:
+        return 0.0
+    return 2 * precision * recall / (precision + recall)
+
+
+def _hmean_f1(precision, recall):
+    """hmean([p + EPSILON, r + EPSILON]) - EPSILON (evaluate.py:836): the harmonic mean of two numbers is 2 / (1 / a + 1 / b)."""
+    return 2.0 / (1.0 / (precision + EPSILON) + 1.0 / (recall + EPSILON)) - EPSILON
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# note matching (host)
+# ------------------------------------------------------------------------------------------------------------------------------
+def _midi_to_hz(pitches):
+    return 440.0 * 2.0 ** ((np.asarray(pitches, dtype=np.float64) - 69.0) / 12.0)
+
+
+def note_edges(est_pitches, est_intervals, ref_pitches, ref_intervals, offset_ratio=None, onset_tolerance=ONSET_TOLERANCE,
+               pitch_tolerance=PITCH_TOLERANCE, offset_min_tolerance=OFFSET_MIN_TOLERANCE):
+    """(num_ref, num_est) boolean matrix: which reference note may be matched with which estimated note.  In float64, every distance rounded
+    with np.around(., N_DECIMALS) before the non-strict comparison:
+      onsets   |on_ref - on_est| <= onset_tolerance
+      pitches  |1200 (log2 f_ref - log2 f_est)| <= pitch_tolerance (MIDI pitches, converted to Hertz; integral pitches: equal pitch)
+      offsets  (offset_ratio given) |off_ref - off_est| <= max(offset_min_tolerance, offset_ratio * (off_ref - on_ref))"""
+    est_intervals = np.asarray(est_intervals, dtype=np.float64).reshape(-1, 2)
+    ref_intervals = np.asarray(ref_intervals, dtype=np.float64).reshape(-1, 2)
+    onset = np.around(np.abs(ref_intervals[:, None, 0] - est_intervals[None, :, 0]), N_DECIMALS) <= onset_tolerance
+    cents = np.abs(1200.0 * (np.log2(_midi_to_hz(ref_pitches))[:, None] - np.log2(_midi_to_hz(est_pitches))[None, :]))
+    edges = onset & (np.around(cents, N_DECIMALS) <= pitch_tolerance)
+    if offset_ratio is not None:
+        tol = np.maximum(offset_min_tolerance, offset_ratio * (ref_intervals[:, 1] - ref_intervals[:, 0]))
+        edges &= np.around(np.abs(ref_intervals[:, None, 1] - est_intervals[None, :, 1]), N_DECIMALS) <= tol[:, None]
+    return edges
+
+
+def _max_matching(edges):
+    """Size of a maximum matching of a boolean biadjacency matrix."""
+    if edges.size == 0 or not edges.any():
+        return 0
+    try:
+        from scipy.sparse import csr_matrix
+        from scipy.sparse.csgraph import maximum_bipartite_matching
+        return int((maximum_bipartite_matching(csr_matrix(edges), perm_type='column') >= 0).sum())
+    except ImportError:
+        pass
+    adj = [np.flatnonzero(row) for row in edges]
+    owner = [-1] * edges.shape[1]                 # column -> row
+    size = 0
+    for root in range(len(adj)):
+        seen, stack, cursor, via = set(), [root], {root: 0}, {}
+        while stack:
+            u = stack[-1]
+            if cursor[u] == len(adj[u]):
+                stack.pop()
+                continue
+            j = int(adj[u][cursor[u]])
+            cursor[u] += 1
+            if j in seen:
+                continue
+            seen.add(j)
+            via[u] = j
+            if owner[j] < 0:
+                for w in stack:
+                    owner[via[w]] = w
+                size += 1
+                break
+            stack.append(owner[j])
+            cursor[owner[j]] = 0
+    return size
+
+
+def match_notes_count(est_pitches, est_intervals, ref_pitches, ref_intervals, offset_ratio=None):
+    """Size of a maximum matching of estimated to reference notes under note_edges' rules."""
+    if len(est_pitches) == 0 or len(ref_pitches) == 0:
+        return 0
+    return _max_matching(note_edges(est_pitches, est_intervals, ref_pitches, ref_intervals, offset_ratio))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# evaluators
+# ------------------------------------------------------------------------------------------------------------------------------
+class Evaluator(object):
+    """What all evaluators share (amt_tools/evaluate.py:288-533)."""
+
+    def __init__(self, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
+        self.unpack_key = self.get_default_key() if unpack_key is None else unpack_key
+        self.results_key = self.get_default_key() if results_key is None else results_key
+        self.save_dir = None
+        self.set_save_dir(save_dir)
+        self.patterns = None
+        self.set_patterns(patterns)
+        self.verbose = None
+        self.set_verbose(verbose)
+        self.results = None
+        self.reset_results()
+
+    def set_save_dir(self, save_dir):
+        self.save_dir = save_dir
+        if save_dir is not None:
+            os.makedirs(save_dir, exist_ok=True)
+
+    def set_patterns(self, patterns):
+        self.patterns = patterns
+
+    def set_verbose(self, verbose):
+        self.verbose = verbose
+
+    def reset_results(self):
+        self.results = dict()
+
+    def average_results(self):
+        return average_results(self.results)
+
+    @staticmethod
+    def get_default_key():
+        return NotImplementedError
+
+    def unpack(self, estimated, reference):
+        estimated = tools.unpack_dict(estimated, self.unpack_key)
+        reference = tools.unpack_dict(reference, self.unpack_key)
+        if estimated is None:
+            warnings.warn(f'Entry for key \'{self.unpack_key}\' not found in estimates.', category=RuntimeWarning)
+        if reference is None:
+            warnings.warn(f'Entry for key \'{self.unpack_key}\' not found in ground-truth.', category=RuntimeWarning)
+        return estimated, reference
+
+    def evaluate(self, estimated, reference):
+        return NotImplementedError
+
+    def write(self, results, track=None):
+        if self.save_dir is None:
+            return
+        tag = tools.get_tag(track)
+        if self.verbose:
+            print(f'Evaluating track: {tag}')
+        path = os.path.join(self.save_dir, f'{tag}.{tools.TXT_EXT}')
+        os.makedirs(os.path.dirname(path), exist_ok=True)       # a track name may contain directories
+        with open(path, 'w') as f:
+            write_results(results, f, self.patterns, self.verbose)
+
+    def track_results(self, results, track=None):
+        """Second half of process_track: append one track's results and write them.  validate_batched enters here."""
+        self.results = append_results(self.results, results)
+        self.write(results, track)
+        return results
+
+    def process_track(self, estimated, reference, track=None):
+        return self.track_results(self.evaluate(*self.unpack(estimated, reference)), track)
+
+    def finalize(self, writer, step=0):
+        log_results(self.average_results(), writer, step, patterns=self.patterns, tag=tools.VAL)
+        self.reset_results()
+
+
+class ComboEvaluator(Evaluator):
+    """Several evaluators as one (amt_tools/evaluate.py:535-662): each keeps its own results; one file per track for all of them."""
+
+    def __init__(self, evaluators, save_dir=None, patterns=None, verbose=False):
+        self.evaluators = evaluators
+        super().__init__(None, None, save_dir, patterns, verbose)
+
+    def reset_results(self):
+        for evaluator in self.evaluators:
+            evaluator.reset_results()
+
+    @staticmethod
+    def _merge(into, key, results):
+        if tools.query_dict(into, key):
+            into[key].update(results)
+        else:
+            into[key] = results
+
+    def average_results(self):
+        average = dict()
+        for evaluator in self.evaluators:
+            self._merge(average, evaluator.results_key, average_results(evaluator.results))
+        return average
+
+    def unpack(self, estimated, reference):
+        return NotImplementedError
+
+    def track_results(self, results, track=None):
+        """`results`: one results dictionary per evaluator, in order."""
+        merged = dict()
+        for evaluator, new in zip(self.evaluators, results):
+            self._merge(merged, evaluator.results_key, new)
+            evaluator.results = append_results(evaluator.results, new)
+        self.write(merged, track)
+        return merged
+
+    def process_track(self, estimated, reference, track=None):
+        return self.track_results([e.evaluate(*e.unpack(estimated, reference)) for e in self.evaluators], track)
+
+
+class LossWrapper(Evaluator):
+    """Tracks the loss dictionary of the predictions (amt_tools/evaluate.py:665-725)."""
+
+    @staticmethod
+    def get_default_key():
+        return tools.KEY_LOSS
+
+    def unpack(self, estimated, reference=None):
+        loss = tools.unpack_dict(estimated, self.unpack_key)
+        if loss is None:
+            warnings.warn(f'Entry for key \'{self.unpack_key}\' not found in estimates.', category=RuntimeWarning)
+        return loss, None
+
+    def evaluate(self, estimated, reference=None):
+        return estimated
+
+
+class StackedEvaluator(Evaluator):
+    def __init__(self, average_slices=False, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
+        super().__init__(unpack_key, results_key, save_dir, patterns, verbose)
+        self.average_slices = average_slices
+
+    @staticmethod
+    def average_slice_results(_results):
+        results = dict()
+        for key in _results.keys():
+            results = append_results(results, _results[key])
+        return average_results(results)
+
+    def _per_slice(self, keys, rows):
+        results = dict(zip(keys, rows))
+        return self.average_slice_results(results) if self.average_slices else results
+
+
+class StackedMultipitchEvaluator(StackedEvaluator):
+    """Frame-level precision / recall / f-measure per slice of a stacked multi-pitch map (amt_tools/evaluate.py:780-855)."""
+
+    @staticmethod
+    def get_default_key():
+        return tools.KEY_MULTIPITCH
+
+    @staticmethod
+    def counts(estimated, reference):
+        """(S, K, T) host maps -> (S, 3) float64: sum(est * ref), sum(est), sum(ref) over each slice."""
+        shape = estimated.shape[:-2] + (-1,)
+        est, ref = np.reshape(estimated, shape), np.reshape(reference, shape)
+        return np.stack([np.sum(est * ref, axis=-1), np.sum(est, axis=-1), np.sum(ref, axis=-1)], axis=-1)
+
+    def counts_batch(self, estimated, reference):
+        """(B, S, K, T) or (B, K, T) fp32 device tensors holding 0 / 1 -> (B, S, 3) int64 device tensor (amtx_eval_multipitch_counts)."""
+        import torch
+        from . import _lib
+        assert estimated.is_cuda and reference.is_cuda and estimated.shape == reference.shape and estimated.dim() in (3, 4)
+        est, ref = estimated.contiguous().float(), reference.contiguous().float()
+        B, S = est.shape[0], (est.shape[1] if est.dim() == 4 else 1)
+        K, T = est.shape[-2:]
+        counts = torch.empty((B, S, 3), dtype=torch.int64, device=est.device)
+        with torch.cuda.device(est.device):
+            _lib.check(_lib.lib().amtx_eval_multipitch_counts(_lib.ptr(est), _lib.ptr(ref), B, S, K, T, _lib.ptr(counts), _lib.current_stream(est.device)),
+                       'amtx_eval_multipitch_counts')
+        return counts
+
+    def results_from_counts(self, counts):
+        """(S, 3) counts of one clip -> its results dictionary."""
+        counts = np.asarray(counts, dtype=np.float64)
+        num_correct, num_predicted, num_ground_truth = counts[..., 0], counts[..., 1], counts[..., 2]
+        precision = num_correct / (num_predicted + EPSILON)
+        recall = num_correct / (num_ground_truth + EPSILON)
+        f_measure = _hmean_f1(precision, recall)
+        keys = list(range(len(f_measure)))
+        return self._per_slice(keys, [{tools.KEY_PRECISION: precision[s], tools.KEY_RECALL: recall[s], tools.KEY_F1: f_measure[s]} for s in keys])
+
+    def evaluate(self, estimated, reference):
+        return self.results_from_counts(self.counts(np.asarray(estimated), np.asarray(reference)))
+
+
+class MultipitchEvaluator(StackedMultipitchEvaluator):
+    """The same for one (K, T) map: a stack of one slice, averaged away (amt_tools/evaluate.py:858-903)."""
+
+    def __init__(self, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
+        super().__init__(True, unpack_key, results_key, save_dir, patterns, verbose)
+
+    def evaluate(self, estimated, reference):
+        return super().evaluate(np.expand_dims(estimated, axis=-3), np.expand_dims(reference, axis=-3))
+
+
+def _sort_rows(rows):
+    """Note rows in (pitch, onset) order."""
+    return rows[np.lexsort((rows[:, 0], rows[:, 2]))] if len(rows) else rows.reshape(0, 3)
+
+
+def _stacked_rows(stacked_notes):
+    """{slice: (pitches, intervals)} -> list of (N, 3) float64 row arrays, one per slice in the dictionary's order."""
+    return [np.concatenate([np.asarray(iv, dtype=np.float64).reshape(-1, 2), np.asarray(p, dtype=np.float64).reshape(-1, 1)], axis=-1)
+            for p, iv in stacked_notes.values()]
+
+
+class StackedNoteEvaluator(StackedEvaluator):
+    """Note-level precision / recall / f-measure per slice of stacked notes (amt_tools/evaluate.py:906-987): a maximum matching under
+    note_edges' rules; offset_ratio None = onsets only."""
+
+    def __init__(self, offset_ratio=None, average_slices=False, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
+        super().__init__(average_slices, unpack_key, results_key, save_dir, patterns, verbose)
+        self.offset_ratio = offset_ratio
+
+    @staticmethod
+    def get_default_key():
+        return tools.KEY_NOTES
+
+    def counts(self, estimated, reference):
+        """Stacked notes -> (S, 3) int64: matched, estimated, reference notes per slice (slices paired by position, as in the reference)."""
+        est, ref = list(estimated.values()), list(reference.values())
+        out = np.zeros((len(ref), 3), dtype=np.int64)
+        for k in range(len(ref)):
+            (pe, ie), (pr, ir) = est[k], ref[k]
+            out[k] = match_notes_count(pe, ie, pr, ir, self.offset_ratio), len(pe), len(pr)
+        return out
+
+    def counts_batch(self, estimated, reference):
+        """estimated, reference: (rows (N, 3) float64 device tensor, offsets (G + 1,) int32 device tensor), rows of one pitch in ascending
+        onset order within a group -> (G, 3) int32 device tensor: matched, estimated, reference notes per group (amtx_eval_notes_match).
+        matched < 0: the kernel refused the group (_lib.ERR_UNSUPPORTED: beyond its candidate window; -1: a fractional pitch)."""
+        return self.match_batch(estimated, reference)[0]
+
+    def match_batch(self, estimated, reference):
+        """counts_batch with the call's status word: ((G, 3) counts, (1,) int32 device tensor: 0, or the first of -1 (a fractional pitch)
+        and _lib.ERR_UNSUPPORTED that any group answered).  One int tells a caller whether any count has to be looked at."""
+        import torch
+        from . import _lib
+        (er, eo), (rr, ro) = estimated, reference
+        assert er.is_cuda and er.dtype == rr.dtype == torch.float64 and eo.dtype == ro.dtype == torch.int32 and eo.shape == ro.shape
+        er, rr, eo, ro = er.contiguous(), rr.contiguous(), eo.contiguous(), ro.contiguous()
+        dev, G = er.device, eo.shape[0] - 1
+        L = _lib.lib()
+        ws = _lib.alloc_workspace(int(L.amtx_eval_notes_match_workspace_bytes(er.shape[0], rr.shape[0])), dev)
+        counts = torch.empty((G, 3), dtype=torch.int32, device=dev)
+        matched = torch.empty((G + 1,), dtype=torch.int32, device=dev)       # the last word: the call's status
+        ratio = -1.0 if self.offset_ratio is None else float(self.offset_ratio)
+        with torch.cuda.device(dev):
+            _lib.check(L.amtx_eval_notes_match(_lib.ptr(er), _lib.ptr(eo), er.shape[0], _lib.ptr(rr), _lib.ptr(ro), rr.shape[0], G, ONSET_TOLERANCE, ratio,
+                                               OFFSET_MIN_TOLERANCE, N_DECIMALS, _lib.ptr(ws), ws.numel(), _lib.ptr(matched), _lib.ptr(matched[G:]), 0,
+                                               _lib.current_stream(dev)), 'amtx_eval_notes_match')
+        counts[:, 0] = matched[:G]
+        counts[:, 1] = eo[1:] - eo[:-1]
+        counts[:, 2] = ro[1:] - ro[:-1]
+        return counts, matched[G:]
+
+    def results_from_counts(self, counts, keys=None):
+        """(S, 3) counts of one clip -> its results dictionary.  Either side empty: all zero, as mir_eval answers."""
+        rows = []
+        for matched, num_est, num_ref in np.asarray(counts).reshape(-1, 3).tolist():
+            if num_est == 0 or num_ref == 0:
+                p = r = f = 0.0
+            else:
+                p, r = float(matched) / num_est, float(matched) / num_ref
+                f = _f_measure(p, r)
+            rows.append({tools.KEY_PRECISION: p, tools.KEY_RECALL: r, tools.KEY_F1: f})
+        return self._per_slice(list(range(len(rows))) if keys is None else keys, rows)
+
+    def evaluate(self, estimated, reference):
+        return self.results_from_counts(self.counts(estimated, reference), list(estimated.keys())[:len(reference)])
+
+
+class NoteEvaluator(StackedNoteEvaluator):
+    """The same for one list of batched notes (N, 3) (amt_tools/evaluate.py:990-1037)."""
+
+    def __init__(self, offset_ratio=None, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
+        super().__init__(offset_ratio, True, unpack_key, results_key, save_dir, patterns, verbose)
+
+    def evaluate(self, estimated, reference):
+        estimated, reference = np.asarray(estimated), np.asarray(reference)
+        return super().evaluate(tools.notes_to_stacked_notes(estimated[..., 2], estimated[:, :2]),
+                                tools.notes_to_stacked_notes(reference[..., 2], reference[:, :2]))
+
+
+class _TabCounts(object):
+    """Counting shared by the two tablature evaluators: [0] sounding cells of the estimate, [1] of the reference, [2] cells where both sound
+    the same class, [3] (pitch, frame) cells sounding in both collapsed maps, [4] cells with equal class (silence included), [5] cells."""
+
+    @staticmethod
+    def counts(estimated, reference, profile):
+        estimated, reference = np.asarray(estimated), np.asarray(reference)
+        out = np.zeros(6, dtype=np.float64)
+        if profile is not None:
+            st_est = tools.tablature_to_stacked_multi_pitch(estimated, profile)
+            st_ref = tools.tablature_to_stacked_multi_pitch(reference, profile)
+            out[0], out[1], out[2] = np.sum(st_est.flatten()), np.sum(st_ref.flatten()), np.sum(st_est.flatten() * st_ref.flatten())
+            mp_est, mp_ref = tools.stacked_multi_pitch_to_multi_pitch(st_est), tools.stacked_multi_pitch_to_multi_pitch(st_ref)
+            out[3] = np.sum(mp_est.flatten() * mp_ref.flatten())
+        out[4], out[5] = np.sum(estimated == reference), reference.size
+        return out
+
+    @staticmethod
+    def counts_batch(estimated, reference, profile):
+        """(B, S, T) int64 device tablatures -> (B, 6) int64 device tensor (amtx_eval_tab_counts)."""
+        import torch
+        from . import _lib
+        assert estimated.is_cuda and estimated.dtype == reference.dtype == torch.int64 and estimated.shape == reference.shape and estimated.dim() == 3
+        est, ref = estimated.contiguous(), reference.contiguous()
+        B, S, T = est.shape
+        if profile is not None:
+            tuning, classes = np.ascontiguousarray(profile.get_midi_tuning(), dtype=np.int32), int(profile.num_pitches)
+            assert len(tuning) == S, (len(tuning), S)
+        else:
+            tuning, classes = np.zeros(S, dtype=np.int32), 1           # only count [4] is read then
+        counts = torch.empty((B, 6), dtype=torch.int64, device=est.device)
+        five = torch.empty((B, 5), dtype=torch.int64, device=est.device)
+        with torch.cuda.device(est.device):
+            _lib.check(_lib.lib().amtx_eval_tab_counts(_lib.ptr(est), _lib.ptr(ref), B, S, T, _lib.ptr(tuning), classes, _lib.ptr(five),
+                                                       _lib.current_stream(est.device)), 'amtx_eval_tab_counts')
+        counts[:, :5] = five
+        counts[:, 5] = S * T
+        return counts
+
+
+class TablatureEvaluator(Evaluator):
+    """Precision / recall / f-measure of (string, fret) activations and the tablature disambiguation rate (amt_tools/evaluate.py:1195-1294)."""
+
+    def __init__(self, profile, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
+        super().__init__(unpack_key, results_key, save_dir, patterns, verbose)
+        self.profile = profile
+
+    @staticmethod
+    def get_default_key():
+        return tools.KEY_TABLATURE
+
+    def counts(self, estimated, reference):
+        return _TabCounts.counts(estimated, reference, self.profile)
+
+    def counts_batch(self, estimated, reference):
+        return _TabCounts.counts_batch(estimated, reference, self.profile)
+
+    def results_from_counts(self, counts):
+        counts = np.asarray(counts, dtype=np.float64)
+        num_predicted, num_ground_truth, num_correct_tablature, num_correct_multi_pitch = counts[0], counts[1], counts[2], counts[3]
+        precision = num_correct_tablature / (num_predicted + EPSILON)
+        recall = num_correct_tablature / (num_ground_truth + EPSILON)
+        return {tools.KEY_PRECISION: precision, tools.KEY_RECALL: recall, tools.KEY_F1: _f_measure(precision, recall),
+                tools.KEY_TDR: num_correct_tablature / (num_correct_multi_pitch + EPSILON)}
+
+    def evaluate(self, estimated, reference):
+        return self.results_from_counts(self.counts(estimated, reference))
+
+
+class SoftmaxAccuracy(Evaluator):
+    """Share of (group, frame) cells whose class is right (amt_tools/evaluate.py:1297-1345)."""
+
+    @staticmethod
+    def get_default_key():
+        return tools.KEY_TABLATURE
+
+    def counts(self, estimated, reference):
+        return _TabCounts.counts(estimated, reference, None)
+
+    def counts_batch(self, estimated, reference):
+        return _TabCounts.counts_batch(estimated, reference, None)
+
+    def results_from_counts(self, counts):
+        counts = np.asarray(counts)
+        return {tools.KEY_ACCURACY: np.float64(counts[4]) / np.float64(counts[5])}
+
+    def evaluate(self, estimated, reference):
+        return self.results_from_counts(self.counts(estimated, reference))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# batched validation
+# ------------------------------------------------------------------------------------------------------------------------------
+def _leaves(evaluator):
+    if isinstance(evaluator, ComboEvaluator):
+        assert not any(isinstance(e, ComboEvaluator) for e in evaluator.evaluators), 'a ComboEvaluator inside a ComboEvaluator'
+        return list(evaluator.evaluators)
+    return [evaluator]
+
+
+def _pack_groups(groups):
+    """List of (N, 3) row arrays -> (rows (max(total, 1), 3) float64 in (pitch, onset) order per group, offsets (G + 1,) int32, whether
+    every pitch is an integer the kernel takes)."""
+    groups = [_sort_rows(np.asarray(g, dtype=np.float64).reshape(-1, 3)) for g in groups]
+    offsets = np.zeros(len(groups) + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(g) for g in groups])
+    rows = np.concatenate(groups + [np.zeros((0, 3))], axis=0)
+    ok = bool(np.all((rows[:, 2] == np.floor(rows[:, 2])) & (rows[:, 2] >= 0) & (rows[:, 2] < 128)))
+    if len(rows) == 0:
+        rows = np.zeros((1, 3))
+    return np.ascontiguousarray(rows), offsets, ok
+
+
+class _Staged(object):
+    """One batch's references on their way to the device, per evaluator."""
+
+    def __init__(self, leaves, references, idx, device, on_gpu):
+        import torch
+        self.items = []
+        for e in leaves:
+            refs = [tools.unpack_dict(references[i], e.unpack_key) for i in idx]
+            if isinstance(e, LossWrapper):
+                self.items.append(None)
+            elif isinstance(e, StackedNoteEvaluator):
+                stacked = not isinstance(e, NoteEvaluator)
+                groups = [g for r in refs for g in (_stacked_rows(r) if stacked else [r])]
+                per_clip = len(groups) // max(len(refs), 1)
+                rows, offsets, ok = _pack_groups(groups)
+                dev = None
+                if on_gpu and ok:
+                    dev = (torch.from_numpy(rows).pin_memory().to(device, non_blocking=True), torch.from_numpy(offsets).pin_memory().to(device, non_blocking=True))
+                self.items.append(dict(kind='notes', rows=rows, offsets=offsets, dev=dev, per_clip=per_clip, keys=[list(r.keys()) for r in refs] if stacked else None))
+            elif isinstance(e, (TablatureEvaluator, SoftmaxAccuracy)):
+                host = np.stack([np.asarray(r) for r in refs]).astype(np.int64)
+                self.items.append(dict(kind='tab', host=host, dev=torch.from_numpy(host).pin_memory().to(device, non_blocking=True) if on_gpu else None))
+            else:
+                host = np.stack([np.asarray(r) for r in refs]).astype(np.float32)
+                self.items.append(dict(kind='map', host=host, dev=torch.from_numpy(host).pin_memory().to(device, non_blocking=True) if on_gpu else None))
+
+
+def _host_note_counts(e, est_rows, est_off, ref_rows, ref_off):
+    """The host matcher on packed groups: (G, 3) counts."""
+    G = len(ref_off) - 1
+    out = np.zeros((G, 3), dtype=np.int64)
+    for g in range(G):
+        a, b = est_rows[est_off[g]:est_off[g + 1]], ref_rows[ref_off[g]:ref_off[g + 1]]
+        out[g] = match_notes_count(a[:, 2], a[:, :2], b[:, 2], b[:, :2], e.offset_ratio), len(a), len(b)
+    return out
+
+
+def validate_batched(clips, references, model, evaluator, times=None, batch_size=256, rank=0, world=1):
+    """Score a partition without bringing a map to the host.  `clips` as for run_offline_batched; `references`: one ground-truth dictionary
+    per clip with the keys the evaluators unpack (KEY_MULTIPITCH / KEY_ONSETS / KEY_OFFSETS maps, KEY_NOTES as batched notes -- stacked
+    notes for tablature models --, KEY_TABLATURE).  Per batch: audio and references are uploaded on a copy stream under the previous batch's
+    kernels, the model runs, notes are decoded on the device when the evaluator tree holds a note evaluator and the decoder's row arrays go
+    straight to amtx_eval_notes_match, every evaluator's counts_batch is enqueued, and only the count tensors (and the decoder's offsets
+    table) come back, on the side stream of transcribe._D2H_STREAMS, while the next batch runs.  Every clip's results are appended to the
+    evaluator in clip order, exactly as process_track would have.  Returns evaluator.average_results() for the clips this rank owns."""
+    import torch
+    from . import _lib, transcribe
+    from .dp import shard_indices
+    from .inference import _frame_times, run_offline_batched
+    clips = torch.as_tensor(np.asarray(clips) if not torch.is_tensor(clips) else clips)
+    assert len(references) == clips.shape[0], (len(references), clips.shape[0])
+    mine = [int(i) for i in shard_indices(clips.shape[0], rank, world)]
+    leaves = _leaves(evaluator)
+    need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
+    device = torch.device(f'cuda:{model.device}' if isinstance(model.device, int) else model.device)
+    on_gpu = device.type == 'cuda' and torch.cuda.is_available()
+
+    def track(results, i):
+        evaluator.track_results(results if isinstance(evaluator, ComboEvaluator) else results[0], i)
+
+    if not on_gpu:
+        # a CPU model: the host evaluators on run_offline_batched's output, clip by clip
+        out = run_offline_batched(clips, model, times=times, batch_size=batch_size, rank=rank, world=world, decode_notes=need_notes)
+        for i in mine:
+            track([e.evaluate(*e.unpack(out[i], references[i])) for e in leaves], i)
+        return evaluator.average_results()
+
+    key = tools.KEY_AUDIO if clips.dim() == 2 else tools.KEY_FEATS
+    pcm16 = key == tools.KEY_AUDIO and clips.dtype == torch.int16
+    copy_stream = torch.cuda.Stream(device)
+    side = transcribe._D2H_STREAMS.get(str(device))
+    if side is None:
+        side = transcribe._D2H_STREAMS[str(device)] = torch.cuda.Stream(device)
+
+    def stage(idx):
+        with torch.cuda.stream(copy_stream):
+            sel = clips[torch.as_tensor(idx)]
+            if not pcm16:
+                sel = sel.float()
+            data = sel.pin_memory().to(device, non_blocking=True)
+            if pcm16:
+                data = data.to(torch.float32).mul_(1.0 / 32768.0)
+            staged = _Staged(leaves, references, idx, device, True)
+            ev = torch.cuda.Event()
+            ev.record(copy_stream)
+        return data, staged, ev
+
+    def est_maps(e, preds, stacked):
+        est = preds.get(e.unpack_key)
+        if est is None and e.unpack_key == tools.KEY_MULTIPITCH and tools.KEY_TABLATURE in preds:
+            st, co = tools.tab_expand(preds[tools.KEY_TABLATURE], model.profile, stacked=stacked, collapsed=not stacked)
+            est = st if stacked else co
+        if est is None:
+            raise KeyError(f'the model output has no entry \'{e.unpack_key}\'')
+        return est
+
+    def enqueue(idx, preds, staged):
+        """Everything of one batch that runs on the device; returns what finish() needs."""
+        main = torch.cuda.current_stream(device)
+        handle, tab_model = None, tools.KEY_MULTIPITCH not in preds and tools.KEY_TABLATURE in preds
+        if need_notes:
+            T = preds[tools.KEY_TABLATURE if tab_model else tools.KEY_MULTIPITCH].shape[-1]
+            t = times if times is not None else _frame_times(model, T)
+            if tab_model:
+                handle = transcribe.decode_tab_notes_batch_async(preds[tools.KEY_TABLATURE], t, model.profile)
+            else:
+                handle = transcribe.decode_notes_batch_async(preds[tools.KEY_ONSETS], preds[tools.KEY_MULTIPITCH], t, model.profile.low)
+        dev_rows = handle.device_rows() if handle is not None else None      # None: the CPU tablature decoder
+        work = []
+        for e, item in zip(leaves, staged.items):
+            if item is None:
+                work.append(None)
+                continue
+            for v in (item['dev'] if isinstance(item['dev'], tuple) else (item['dev'],)):
+                if v is not None:
+                    v.record_stream(main)
+            if item['kind'] == 'notes':
+                stacked = not isinstance(e, NoteEvaluator)
+                assert stacked == tab_model, 'NoteEvaluator scores batched notes, StackedNoteEvaluator the stacked notes of a tablature model'
+                assert item['per_clip'] == (preds[tools.KEY_TABLATURE].shape[1] if tab_model else 1), 'one reference note group per string'
+                work.append(e.match_batch(dev_rows[:2], item['dev']) if item['dev'] is not None and dev_rows is not None else None)
+            elif item['kind'] == 'tab':
+                work.append(e.counts_batch(preds[tools.KEY_TABLATURE].long(), item['dev']))
+            else:
+                work.append(e.counts_batch(est_maps(e, preds, item['host'].ndim == 4), item['dev']))
+        done = torch.cuda.Event()
+        done.record(main)
+        return idx, staged, handle, dev_rows, work, done
+
+    def finish(pending):
+        idx, staged, handle, dev_rows, work, done = pending
+        side.wait_event(done)
+        with torch.cuda.stream(side):
+            # a note evaluator's work is (counts, status word); everything else one count tensor
+            host = [None if w is None else tuple(v.cpu().numpy() for v in w) if isinstance(w, tuple) else w.cpu().numpy() for w in work]
+            est_off = dev_rows[1].cpu().numpy() if dev_rows is not None else None
+        overflow = est_off is not None and int(est_off[-1]) > dev_rows[0].shape[0]      # the decoder's first buffer was too small
+        est_host = None                 # the estimated notes on the host: only when a batch has to take the host matcher
+
+        def est_rows_host():
+            nonlocal est_host
+            if est_host is None:
+                if dev_rows is not None:
+                    with torch.cuda.stream(side):
+                        total = int(est_off[-1])
+                        rows, offsets = dev_rows[2](total) if overflow else dev_rows[:2]
+                        est_host = (rows[:total].cpu().numpy(), offsets.cpu().numpy())
+                else:                    # CPU tablature decoder
+                    groups = [g for clip in handle.result() for g in _stacked_rows(clip)]
+                    est_host = _pack_groups(groups)[:2]
+            return est_host
+
+        per_eval = []
+        for e, item, counts in zip(leaves, staged.items, host):
+            if item is None:
+                warnings.warn(f'Entry for key \'{e.unpack_key}\' not found in estimates.', category=RuntimeWarning)
+                per_eval.append([dict() for _ in idx])
+            elif item['kind'] == 'notes':
+                counts, status = counts if counts is not None else (None, None)
+                if counts is not None and not overflow and int(status[0]) == -1:
+                    raise _lib.AmtxError('amtx_eval_notes_match: an estimated note with a fractional pitch')
+                # the host matcher takes the whole batch when the references' pitches are fractional, when the decoder overflowed (the
+                # matcher ran on a truncated buffer; the batch is decoded again for the host) or when a group is beyond the window bound
+                if counts is None or overflow or int(status[0]) != 0:
+                    rows, off = est_rows_host()
+                    counts = _host_note_counts(e, rows, off, item['rows'], item['offsets'])
+                n = item['per_clip']
+                per_eval.append([e.results_from_counts(counts[j * n:(j + 1) * n], item['keys'][j] if item['keys'] else None) for j in range(len(idx))])
+            else:
+                per_eval.append([e.results_from_counts(counts[j]) for j in range(len(idx))])
+        for j, i in enumerate(idx):
+            track([r[j] for r in per_eval], i)
+
+    with torch.no_grad():
+        starts = list(range(0, len(mine), batch_size))
+        nxt = stage(mine[starts[0]:starts[0] + batch_size]) if starts else None
+        pending = None
+        for n, s in enumerate(starts):
+            idx = mine[s:s + batch_size]
+            data, staged, ev = nxt
+            main = torch.cuda.current_stream(device)
+            main.wait_event(ev)
+            data.record_stream(main)
+            if n + 1 < len(starts):
+                nxt = stage(mine[starts[n + 1]:starts[n + 1] + batch_size])
+            preds = model.run_on_batch({key: data})
+            now = enqueue(idx, preds, staged)
+            if pending is not None:
+                finish(pending)
+            pending = now
+        if pending is not None:
+            finish(pending)
+    return evaluator.average_results()

@@ -31,6 +31,13 @@ KEY_LOSS_TOTAL = 'loss_total'
 KEY_LOSS_ONSETS = 'loss_onsets'
 KEY_LOSS_OFFSETS = 'loss_offsets'
 KEY_LOSS_PITCH = 'loss_pitch'
+KEY_ACCURACY = 'accuracy'
+KEY_PRECISION = 'precision'
+KEY_RECALL = 'recall'
+KEY_F1 = 'f1-score'
+KEY_TDR = 'tdr'
+VAL = 'validation'
+TXT_EXT = 'txt'
 DEFAULT_PIANO_LOWEST_PITCH = 21
 DEFAULT_PIANO_HIGHEST_PITCH = 108
 DEFAULT_GUITAR_LABELS = ['E', 'A', 'D', 'G', 'B', 'e']
@@ -128,6 +135,14 @@ def unpack_dict(data, key):
 
 def query_dict(dictionary, key):
     return isinstance(dictionary, dict) and key in dictionary.keys()
+
+
+def get_tag(tag=None):
+    """Name for a file that belongs to a track: the track's own name, or date and time when it has none (amt_tools/tools/utils.py:3881-3905)."""
+    if tag is None:
+        from datetime import datetime
+        tag = datetime.now().strftime('%m_%d_%Y_%H_%M_%S')
+    return tag
 
 
 def _map_dict(track, fn):

@@ -169,6 +169,15 @@ class _PendingNotes(object):
         self._done = torch.cuda.Event()
         self._done.record(torch.cuda.current_stream(rows.device))
 
+    def device_rows(self):
+        """(rows (E, 3) float64, offsets int32, retry): the dense note rows and the offsets table as the decoder left them on the device,
+        before result()'s host work.  offsets[-1] > len(rows) means the first buffer was too small; retry(total) then decodes once more
+        into a buffer of `total` rows and returns the new (rows, offsets)."""
+        def retry(total):
+            again = self._retry(total)
+            return again._rows, again._offsets
+        return self._rows, self._offsets, retry
+
     def result(self):
         import torch
         # The copies to the host run on their own stream behind this batch's event: on the caller's stream they would queue behind
@@ -423,6 +432,15 @@ class _PendingTabNotes(object):
         self._done = torch.cuda.Event()
         self._done.record(torch.cuda.current_stream(rows.device))
 
+    def device_rows(self):
+        """(rows (E, 3) float64, offsets int32, retry): the dense note rows and the offsets table as the decoder left them on the device,
+        before result()'s host work.  offsets[-1] > len(rows) means the first buffer was too small; retry(total) then decodes once more
+        into a buffer of `total` rows and returns the new (rows, offsets)."""
+        def retry(total):
+            again = self._retry(total)
+            return again._rows, again._offsets
+        return self._rows, self._offsets, retry
+
     def result(self):
         import torch
         dev = self._rows.device
@@ -448,6 +466,10 @@ class _HostTabNotes(object):
 
     def __init__(self, tablature, times, profile, inhibition_window, minimum_duration):
         self._args = (tablature, times, profile, inhibition_window, minimum_duration)
+
+    def device_rows(self):
+        """None: this handle has no rows on the device."""
+        return None
 
     def result(self):
         tablature, times, profile, window, min_dur = self._args

@@ -373,6 +373,52 @@ int amtx_tab_notes(const int64_t* tablature, int batch, int strings, int num_fra
                    const double* times_ext, int64_t times_stride, const int32_t* release, int64_t release_stride, int has_minimum_duration,
                    double minimum_duration, double* rows, int64_t rows_capacity, int32_t* row_offsets, void* stream);
 
+/* Evaluation on the device (csrc/eval.hip): the integers amt_tools/evaluate.py's evaluators are made of, counted where the maps already
+ * are.  No entry allocates; every element of every output is written (no memset, no dependence on old contents); integer sums only.
+ *
+ * amtx_eval_multipitch_counts: StackedMultipitchEvaluator.evaluate (evaluate.py:794-855).  est, ref [batch][slices][keys][num_frames] fp32
+ * maps holding 0 and 1 (slices = 1: a plain multi-pitch map) -> counts [batch][slices][3] int64: cells non-zero in both maps, in est, in ref.
+ * 4-byte aligned maps are enough: a slice starts keys * num_frames floats behind the last one, which leaves the 16-byte grid when that
+ * product is no multiple of 4 (never with 88 keys) or when the maps are views that start inside a buffer; keys * num_frames < 2^31. */
+int amtx_eval_multipitch_counts(const float* est, const float* ref, int batch, int slices, int keys, int num_frames, int64_t* counts,
+                                void* stream);
+
+/* amtx_eval_tab_counts: TablatureEvaluator.evaluate (evaluate.py:1225-1294) and SoftmaxAccuracy.evaluate (:1310-1344).  est, ref
+ * [batch][strings][num_frames] int64 tablatures, class -1 = silent; tuning HOST [strings] (midi pitch of class 0); strings <= 16
+ * (AMTX_ERR_UNSUPPORTED beyond) -> counts [batch][5] int64:
+ *   [0] (string, frame) cells with est >= 0          [1] cells with ref >= 0          [2] cells with est == ref >= 0
+ *   [3] (pitch, frame) cells sounding in BOTH collapsed multi-pitch maps: the pitches of a frame are tuning[s] + class over its sounding
+ *       strings as a SET (two strings on one pitch count once, like the maximum of stacked_multi_pitch_to_multi_pitch)
+ *   [4] cells with est == ref, silence included.
+ * A class outside [-1, num_classes) is silent for [0] .. [3] (as in amtx_tab_expand) and the plain integer it is for [4]. */
+int amtx_eval_tab_counts(const int64_t* est, const int64_t* ref, int batch, int strings, int num_frames, const int32_t* tuning, int num_classes,
+                         int64_t* counts, void* stream);
+
+/* amtx_eval_notes_match: the size of a MAXIMUM matching between estimated and reference notes, per group (a clip, or a (clip, string) of
+ * stacked notes), under the rules of mir_eval.transcription.match_notes for integral pitches (50 cents = equal pitch):
+ *   est, ref          dense note rows [onset_s, offset_s, midi_pitch] float64, est_rows / ref_rows of them in the arrays
+ *   *_offsets         [groups + 1] int32 on the device: group g owns rows [offsets[g], offsets[g + 1]) (clamped to the array: a decoder's
+ *                     total may exceed its buffer, and nothing outside the arrays is read).  Offsets must be NON-DECREASING: groups
+ *                     share the workspace by row position, so overlapping groups stay inside the arrays but race on it, and their
+ *                     counts mean nothing
+ *   order             within a group the rows of ONE pitch are in ascending onset order -- what amtx_notes_rows (pitch, onset) and
+ *                     amtx_tab_notes (onset) write; pitches may interleave
+ *   an estimated and a reference note of equal pitch are joined when around(|on_ref - on_est|, decimals) <= onset_tolerance and, if
+ *   offset_ratio >= 0, around(|off_ref - off_est|, decimals) <= max(offset_min_tolerance, offset_ratio * (off_ref - on_ref)), in float64
+ *   with numpy's around(x, d) = rint(x 10^d) / 10^d.  offset_ratio < 0: onsets only.
+ *   matched           [groups] int32: the matching's size; AMTX_ERR_ARG for a group holding a pitch that is no integer in [0, 128);
+ *                     AMTX_ERR_UNSUPPORTED for a group beyond the bound below
+ *   status            [1] int32 on the device: AMTX_ERR_ARG if any group answered it, else AMTX_ERR_UNSUPPORTED if any did, else AMTX_OK
+ *   wait              0: return after the launches (the caller reads `status` with the counts); else wait for `stream` and return status
+ *   workspace         256-byte aligned, amtx_eval_notes_match_workspace_bytes(est_rows, ref_rows) bytes
+ * BOUND: at most AMTX_EVAL_MATCH_MAX_WINDOW reference notes of one pitch within the onset tolerance of one estimated note; lists
+ * themselves are as long as the group. */
+#define AMTX_EVAL_MATCH_MAX_WINDOW 128
+size_t amtx_eval_notes_match_workspace_bytes(int64_t est_rows, int64_t ref_rows);
+int amtx_eval_notes_match(const double* est, const int32_t* est_offsets, int64_t est_rows, const double* ref, const int32_t* ref_offsets,
+                          int64_t ref_rows, int groups, double onset_tolerance, double offset_ratio, double offset_min_tolerance, int decimals,
+                          void* workspace, size_t workspace_bytes, int32_t* matched, int32_t* status, int wait, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * TabCNN inference engine (amt_tools/models/tabcnn.py:17-221; TabCNN.forward + SoftmaxGroups.finalize_output,
  * models/common.py:305-483).  The reference convolves each frame's 9-frame context window separately; the three unpadded 3x3
