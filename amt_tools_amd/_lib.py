@@ -23,120 +23,97 @@ class AmtxError(RuntimeError):
 ERR_UNSUPPORTED = -3       # AMTX_ERR_UNSUPPORTED (include/amtx.h)
 
 
+class _Pointer(C.c_void_p):
+    """The argument type of every pointer parameter but `const char*`: what c_void_p takes (None, a c_void_p, an integer address, byref(...),
+    a ctypes array or pointer) plus anything with data_ptr() (a torch tensor, host or device) or .ctypes.data (a numpy array).  Text is no
+    address: str and bytes, which c_void_p would pass as a pointer to their characters, are refused like every other type."""
+    @classmethod
+    def from_param(cls, obj):
+        if hasattr(obj, 'data_ptr'):
+            obj = obj.data_ptr()
+        elif hasattr(obj, 'ctypes'):
+            obj = obj.ctypes.data
+        elif isinstance(obj, (str, bytes)):
+            raise TypeError('a pointer argument, not text')
+        return C.c_void_p.from_param(obj)
+
+
+# One letter per C type: the notation of tests/golden/abi_signatures.json.
+_CTYPES = {'i': C.c_int, 'l': C.c_int64, 'z': C.c_size_t, 'f': C.c_float, 'd': C.c_double, 's': C.c_char_p, 'p': _Pointer}
+_SCALARS = {'int': 'i', 'int64_t': 'l', 'size_t': 'z', 'float': 'f', 'double': 'd'}
+_POINTEES = {'void', 'float', 'double', 'int', 'int32_t', 'int64_t', 'uint16_t', 'uint8_t'}       # plus the handle structs the header typedefs
+_PARAM = re.compile(r'(const )?(\w+) ?(\*{0,2}) ?(\w*)')
+
+
+def parse_header(text):
+    """{name: (letters, ends_in_stream)} for every function a header in the style of include/amtx.h declares: letters = the return type,
+    then one letter per parameter (_CTYPES; 'p' = any pointer but `const char*`), ends_in_stream = the last parameter is `void* stream`.
+    Between two ';' there is a handle typedef or such a declaration; anything else raises AmtxError -- nothing is skipped or guessed."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*(#.*|extern "C" \{|\})[ \t]*$', '', text, flags=re.M)      # preprocessor lines and the extern "C" bracket
+    handles, table = set(), {}
+
+    def letter(decl, param, is_return=False):
+        """(letter, parameter name) of one `type name`."""
+        m = _PARAM.fullmatch(param)
+        if m:
+            const, base, stars, name = m.groups()
+            if not stars and not const and base in _SCALARS:
+                return _SCALARS[base], name
+            if stars == '*' and const and base == 'char':
+                return 's', name
+            if stars and not is_return and (base in _POINTEES or base in handles):
+                return 'p', name
+        raise AmtxError(f'cannot map "{param}" in the declaration "{decl}"')
+
+    for decl in (' '.join(d.split()) for d in text.split(';')):
+        m = re.fullmatch(r'typedef struct (\w+) \1', decl)
+        if m:
+            handles.add(m.group(1))
+            continue
+        m = re.fullmatch(r'(.*?) ?\b(amtx_\w+) ?\((.*)\)', decl)
+        if not m:
+            if decl:
+                raise AmtxError(f'cannot read the declaration "{decl}"')
+            continue
+        ret, name, params = m.groups()
+        if name in table:
+            raise AmtxError(f'{name} is declared twice')
+        params = [] if params.strip() == 'void' else [p.strip() for p in params.split(',')]
+        letters, names = letter(decl, ret, is_return=True)[0], []
+        for param in params:
+            code, pname = letter(decl, param)
+            letters += code
+            names.append(pname)
+        if 'stream' in names and (names.index('stream') != len(names) - 1 or params[-1].replace(' ', '') != 'void*stream'):
+            raise AmtxError(f'`stream` must be the last parameter and a `void*` in the declaration "{decl}"')
+        table[name] = (letters, 'stream' in names)
+    return table
+
+
+_signatures = None
+
+
+def signatures():
+    """parse_header of include/amtx.h, read once per process."""
+    global _signatures
+    if _signatures is None:
+        with open(HEADER_PATH) as f:
+            _signatures = parse_header(f.read())
+    return _signatures
+
+
 def declared_symbols():
     """Every function name include/amtx.h declares."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(amtx_[a-z0-9_]+)\s*\(', text)))
+    return sorted(signatures())
 
 
-_P = C.c_void_p
-_I = C.c_int
-_L = C.c_int64
-_F = C.c_float
-
-_SIGNATURES = {
-    'amtx_last_error': (C.c_char_p, []),
-    'amtx_version': (_I, []),
-    'amtx_spec_plan_create': (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, _I, _I, _I]),
-    'amtx_spec_plan_destroy': (_I, [_P]),
-    'amtx_spec_num_bins': (_I, [_P]),
-    'amtx_spec_num_frames': (_L, [_P, _L]),
-    'amtx_spec_filterbank': (_I, [_P, _P]),
-    'amtx_spec_power': (_I, [_P, _P, _L, _L, _I, _P, _P, _P]),
-    'amtx_spec_scale': (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _P, _P]),
-    'amtx_of_model_create': (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, _I]),
-    'amtx_has_f16': (_I, []),
-    'amtx_of_model_destroy': (_I, [_P]),
-    'amtx_of_model_set_tensor': (_I, [_P, C.c_char_p, _P, _L]),
-    'amtx_of_model_finalize': (_I, [_P]),
-    'amtx_of_model_set_tensor_device': (_I, [_P, C.c_char_p, _P, _L]),
-    'amtx_of_model_finalize_device': (_I, [_P, _P]),
-    'amtx_of_workspace_bytes': (C.c_size_t, [_P, _I, _I]),
-    'amtx_of_forward': (_I, [_P, _P, _L, _L, _L, _L, _I, _I, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
-    'amtx_of_fuses_db_scale': (_I, [_P]),
-    'amtx_of_conv_stack_fused': (_I, [_P, _I, _I]),
-    'amtx_of_forward_power': (_I, [_P, _P, _L, _L, _L, _P, _P, _I, _I, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
-    'amtx_of_takes_feats16': (_I, [_P]),
-    'amtx_of_forward_feats16': (_I, [_P, _P, _I, _I, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
-    'amtx_of_offsets': (_I, [_P, _P, C.c_size_t, _I, _I, _P, _P, _P]),
-    'amtx_of_num_stages': (_I, []),
-    'amtx_of_stage_name': (C.c_char_p, [_I]),
-    'amtx_of_profile_enable': (_I, [_P, _I]),
-    'amtx_of_profile_read': (_I, [_P, C.POINTER(C.c_double), C.POINTER(_I)]),
-    'amtx_linear_packed_elems': (_L, [_I, _I, _I]),
-    'amtx_linear_pack': (_I, [_P, _I, _I, _I, _P]),
-    'amtx_linear_fwd': (_I, [_P, _L, _I, _P, _I, _P, _P, _L, _I, _L, _I, _I, _P]),
-    'amtx_split_planes': (_I, [_P, _L, _I, _P, _I, _L, _L, _P]),
-    'amtx_linear_fwd_split': (_I, [_P, _L, _L, _P, _P, _P, _L, _I, _L, _L, _I, _I, _P]),
-    'amtx_conv3x3_packed_elems': (_L, [_I, _I]),
-    'amtx_conv3x3_pack': (_I, [_P, _P, _I, _I, _P]),
-    'amtx_conv3x3_fwd': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
-    'amtx_conv3x3g_packed_elems': (_L, [_I, _I, _I]),
-    'amtx_conv3x3g_pack': (_I, [_P, _P, _I, _I, _I, _P]),
-    'amtx_conv3x3g_fwd': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    'amtx_bilstm_h_packed_elems': (_L, [_I, _I]),
-    'amtx_bilstm_h_pack': (_I, [_P, _P, _I, _I, _P]),
-    'amtx_bilstm_h_fwd': (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P]),
-    'amtx_conv1_fwd': (_I, [_P, _L, _L, _L, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    'amtx_bilstm_packed_elems': (_L, [_I]),
-    'amtx_bilstm_pack': (_I, [_P, _P, _I, _P]),
-    'amtx_bilstm_fwd': (_I, [_P, _P, _I, _I, _P, _I, _I, _P]),
-    'amtx_bilstm_pack_device': (_I, [_P, _P, _I, _P, _P, _P]),
-    'amtx_bilstm_train_fwd': (_I, [_P, _P, _I, _P, _P, _I, _I, _P]),
-    'amtx_bilstm_train_bwd': (_I, [_P, _P, _P, _I, _P, _I, _I, _P]),
-    'amtx_cqt_plan_create': (_I, [C.POINTER(_P), _I, _I, C.c_double, _I, _I, C.c_double, C.POINTER(C.c_double), _I, _I, _I]),
-    'amtx_cqt_plan_destroy': (_I, [_P]),
-    'amtx_cqt_num_harmonics': (_I, [_P]),
-    'amtx_cqt_num_frames': (_L, [_P, _L]),
-    'amtx_cqt_workspace_bytes': (C.c_size_t, [_P, _I, _L]),
-    'amtx_cqt_forward': (_I, [_P, _P, _L, _L, _I, _I, _P, C.c_size_t, _P, _P]),
-    'amtx_cqt_forward16': (_I, [_P, _P, _L, _L, _I, _I, _P, C.c_size_t, _P, _P]),
-    'amtx_cqt_forward16_split': (_I, [_P, _P, _L, _L, _I, _I, _P, C.c_size_t, _P, _L, _P]),
-    'amtx_bilstm_h_pack_device': (_I, [_P, _P, _I, _I, _P, _P, _P]),
-    'amtx_bilstm_h_train_fwd': (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
-    'amtx_bilstm_h_train_bwd': (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _I, _P]),
-    'amtx_bn_train_workspace_bytes': (C.c_size_t, [_I]),
-    'amtx_bn_relu_pool_train_fwd': (_I, [_P, _L, _I, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    'amtx_bn_relu_pool_train_bwd': (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    'amtx_bce_logits_loss_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
-    'amtx_bce_logits_loss': (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
-    'amtx_rms_norm_workspace_bytes': (C.c_size_t, [_I, _L]),
-    'amtx_rms_norm': (_I, [_P, _L, _L, _I, _P, _L, _P, C.c_size_t, _P]),
-    'amtx_spec_mel_layout': (_I, [_I, _I, _I, _I, _P, _P, _P]),
-    'amtx_notes_decode': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    'amtx_notes_rows': (_I, [_P, _P, _I, _I, _I, _P, _L, _I, _P, _P, _L, _P, _P]),
-    'amtx_tab_expand': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
-    'amtx_tab_notes': (_I, [_P, _I, _I, _I, _P, _I, _P, _L, _P, _L, _I, C.c_double, _P, _L, _P, _P]),
-    'amtx_eval_multipitch_counts': (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    'amtx_eval_tab_counts': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
-    'amtx_eval_notes_match_workspace_bytes': (C.c_size_t, [_L, _L]),
-    'amtx_eval_notes_match': (_I, [_P, _P, _L, _P, _P, _L, _I, C.c_double, C.c_double, C.c_double, _I, _P, C.c_size_t, _P, _P, _I, _P]),
-    'amtx_pianoroll_fwd': (_I, [_P, _L, _I, _I, _I, _I, _F, _P, _P]),
-    'amtx_matmul_workspace_bytes': (C.c_size_t, [_L, _L, _L]),
-    'amtx_matmul_f32': (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _L, _L, _L, _L, _P, C.c_size_t, _P]),
-    'amtx_linear_train_fwd': (_I, [_P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _P]),
-    'amtx_linear_bwd_workspace_bytes': (C.c_size_t, [_L, _I, _I]),
-    'amtx_linear_bwd': (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _L, _I, _I, _P, C.c_size_t, _P]),
-    'amtx_conv3x3_train_workspace_bytes': (C.c_size_t, [_L, _I, _I, _I]),
-    'amtx_conv3x3_train_fwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, C.c_size_t, _P]),
-    'amtx_conv3x3_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, C.c_size_t, _P]),
-    'amtx_tab_model_create': (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, _I]),
-    'amtx_tab_model_destroy': (_I, [_P]),
-    'amtx_tab_model_set_tensor': (_I, [_P, C.c_char_p, _P, _L]),
-    'amtx_tab_model_finalize': (_I, [_P]),
-    'amtx_tab_workspace_bytes': (C.c_size_t, [_P, _I, _I]),
-    'amtx_tab_forward': (_I, [_P, _P, _L, _L, _L, _L, _I, _I, _P, C.c_size_t, _P, _P, _P]),
-    'amtx_tab_pool_train_fwd': (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _P, _P]),
-    'amtx_tab_pool_train_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    'amtx_softmax_groups_loss_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
-    'amtx_softmax_groups_loss': (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
-}
+_funcs = {}            # name -> (function, number of parameters, its return value goes through check, it ends in `void* stream`)
 
 
 def lib():
-    """Load libamtx.so (once).  Raises AmtxError when the HIP extension has not been built."""
+    """Load libamtx.so (once) and give every function include/amtx.h declares its restype / argtypes.  Raises AmtxError when the HIP
+    extension has not been built, when it lacks a declared function, or when the header holds a declaration parse_header cannot map."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -147,15 +124,39 @@ def lib():
             handle = C.CDLL(LIB_PATH)
         except OSError as e:
             raise AmtxError(f'cannot load {LIB_PATH}: {e}') from e
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (letters, stream) in signatures().items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:
                 raise AmtxError(f'{LIB_PATH} does not export {name}') from e
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype = _CTYPES[letters[0]]
+            fn.argtypes = [_CTYPES[c] for c in letters[1:]]
+            _funcs[name] = (fn, len(letters) - 1, letters[0] in 'il', stream)
         _lib = handle
     return _lib
+
+
+def call(name, *args, device=None):
+    """Call the library's function `name`; tensors and arrays are passed as they are (_Pointer).  With `device`, the call runs under
+    torch.cuda.device(device), and a function whose last parameter is `void* stream` gets that device's current stream appended -- the
+    caller passes one argument fewer.  Without `device` the arguments go through as given (host-only functions, an explicit stream).
+    A signed integer return goes through check(); any other return value comes back as it is.  A wrong number of arguments is a TypeError
+    before the library is entered (ctypes alone lets surplus arguments through)."""
+    lib()
+    try:
+        fn, nargs, checked, stream = _funcs[name]
+    except KeyError:
+        raise AmtxError(f'include/amtx.h declares no function {name}') from None
+    fill_stream = stream and device is not None
+    if len(args) + fill_stream != nargs:
+        raise TypeError(f'{name} takes {nargs - fill_stream} arguments{" besides the stream" if fill_stream else ""} ({len(args)} given)')
+    if device is None:
+        rc = fn(*args)
+    else:
+        import torch
+        with torch.cuda.device(device):
+            rc = fn(*args, current_stream(device)) if stream else fn(*args)
+    return check(rc, name) if checked else rc
 
 
 def check(rc, what=''):

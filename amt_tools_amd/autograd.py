@@ -107,25 +107,19 @@ def matmul_f32(a, b, a_trans=False, b_trans=False, bias=None, out=None):
     assert k == k2
     if out is None:
         out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    L = _lib.lib()
-    need = int(L.amtx_matmul_workspace_bytes(m, n, k))
+    need = int(_lib.call('amtx_matmul_workspace_bytes', m, n, k))
     ws = _workspace(need, a.device) if need else None
-    with torch.cuda.device(a.device):
-        _lib.check(L.amtx_matmul_f32(_lib.ptr(a), a.stride(0), int(a_trans), _lib.ptr(b), b.stride(0), int(b_trans), _lib.ptr(bias), _lib.ptr(out),
-                                     out.stride(0), m, n, k, _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.current_stream(a.device)),
-                   'amtx_matmul_f32')
+    _lib.call('amtx_matmul_f32', a, a.stride(0), int(a_trans), b, b.stride(0), int(b_trans), bias, out, out.stride(0), m, n, k,
+              ws, ws.numel() if ws is not None else 0, device=a.device)
     return out
 
 
 def _colsum(x2):
     """Column sums of a (rows, n) matrix (bias gradients) through amtx_linear_bwd's db output."""
     m, n = x2.shape
-    L = _lib.lib()
     db = torch.empty(n, dtype=torch.float32, device=x2.device)
-    ws = _workspace(int(L.amtx_linear_bwd_workspace_bytes(m, n, 4)), x2.device)
-    with torch.cuda.device(x2.device):
-        _lib.check(L.amtx_linear_bwd(_lib.ptr(x2), x2.stride(0), None, 0, None, 0, None, 0, None, _lib.ptr(db), m, n, 4, _lib.ptr(ws), ws.numel(),
-                                     _lib.current_stream(x2.device)), 'amtx_linear_bwd')
+    ws = _workspace(int(_lib.call('amtx_linear_bwd_workspace_bytes', m, n, 4)), x2.device)
+    _lib.call('amtx_linear_bwd', x2, x2.stride(0), None, 0, None, 0, None, 0, None, db, m, n, 4, ws, ws.numel(), device=x2.device)
     return db
 
 
@@ -157,16 +151,12 @@ class LinearFunction(torch.autograd.Function):
         if not _ok2d(dy2):
             dy2 = dy2.contiguous()
         m = dy2.shape[0]
-        L = _lib.lib()
         dev = dy2.device
         dx = torch.empty((m, k), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         dw = torch.empty((n, k), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         db = torch.empty(n, dtype=torch.float32, device=dev) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        ws = _workspace(int(L.amtx_linear_bwd_workspace_bytes(m, n, k)), dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_linear_bwd(_lib.ptr(dy2), dy2.stride(0), _lib.ptr(x2), x2.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(dx),
-                                         k, _lib.ptr(dw), _lib.ptr(db), m, n, k, _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                       'amtx_linear_bwd')
+        ws = _workspace(int(_lib.call('amtx_linear_bwd_workspace_bytes', m, n, k)), dev)
+        _lib.call('amtx_linear_bwd', dy2, dy2.stride(0), x2, x2.stride(0), w, w.stride(0), dx, k, dw, db, m, n, k, ws, ws.numel(), device=dev)
         return (dx.reshape(ctx.shape) if dx is not None else None), dw, db
 
 
@@ -196,14 +186,11 @@ class Conv3x3Function(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         B, Ci, T, F = x.shape
         Co = weight.shape[0]
-        L = _lib.lib()
         xc = x.contiguous(memory_format=torch.channels_last) if Ci > 1 else x.contiguous()
         w = weight.contiguous()
         y = torch.empty((B, Co, T, F), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        ws = _workspace(int(L.amtx_conv3x3_train_workspace_bytes(B * T, F, Ci, Co)), x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.amtx_conv3x3_train_fwd(_lib.ptr(xc), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), B * T, T, F, Ci, Co, _lib.ptr(ws), ws.numel(),
-                                                _lib.current_stream(x.device)), 'amtx_conv3x3_train_fwd')
+        ws = _workspace(int(_lib.call('amtx_conv3x3_train_workspace_bytes', B * T, F, Ci, Co)), x.device)
+        _lib.call('amtx_conv3x3_train_fwd', xc, w, bias, y, B * T, T, F, Ci, Co, ws, ws.numel(), device=x.device)
         ctx.save_for_backward(xc, w)
         return y
 
@@ -212,7 +199,6 @@ class Conv3x3Function(torch.autograd.Function):
         xc, w = ctx.saved_tensors
         B, Ci, T, F = xc.shape
         Co = w.shape[0]
-        L = _lib.lib()
         dev = dy.device
         dyc = dy.contiguous(memory_format=torch.channels_last)
         dx = None
@@ -220,10 +206,8 @@ class Conv3x3Function(torch.autograd.Function):
             dx = torch.empty((B, Ci, T, F), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
         dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         db = torch.empty(Co, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-        ws = _workspace(int(L.amtx_conv3x3_train_workspace_bytes(B * T, F, Ci, Co)), dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_conv3x3_bwd(_lib.ptr(dyc), _lib.ptr(xc), _lib.ptr(w), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), B * T, T, F, Ci, Co,
-                                          _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), 'amtx_conv3x3_bwd')
+        ws = _workspace(int(_lib.call('amtx_conv3x3_train_workspace_bytes', B * T, F, Ci, Co)), dev)
+        _lib.call('amtx_conv3x3_bwd', dyc, xc, w, dx, dw, db, B * T, T, F, Ci, Co, ws, ws.numel(), device=dev)
         return dx, dw, db
 
 
@@ -242,14 +226,12 @@ def conv3x3(x, conv):
 
 
 def _pack(w_hh_f, w_hh_b):
-    L = _lib.lib()
     H = w_hh_f.shape[1]
-    n = int(L.amtx_bilstm_h_packed_elems(H, 2))
+    n = int(_lib.call('amtx_bilstm_h_packed_elems', H, 2))
     fwd = torch.empty(n, dtype=torch.int16, device=w_hh_f.device)
     bwd = torch.empty(n, dtype=torch.int16, device=w_hh_f.device)
     wf, wb = w_hh_f.detach().contiguous().float(), w_hh_b.detach().contiguous().float()
-    _lib.check(L.amtx_bilstm_h_pack_device(_lib.ptr(wf), _lib.ptr(wb), H, 2, _lib.ptr(fwd), _lib.ptr(bwd), _lib.current_stream(wf.device)),
-               'amtx_bilstm_h_pack_device')
+    _lib.call('amtx_bilstm_h_pack_device', wf, wb, H, 2, fwd, bwd, device=wf.device)
     return fwd, bwd
 
 
@@ -266,9 +248,8 @@ class BiLSTMFunction(torch.autograd.Function):
         x0 = groups[0][0]
         B, T = x0.shape[:2]
         H = groups[0][2].shape[1]
-        L = _lib.lib()
         dev = x0.device
-        n = int(L.amtx_bilstm_h_packed_elems(H, 2))
+        n = int(_lib.call('amtx_bilstm_h_packed_elems', H, 2))
         xproj = torch.empty((G, B * T, 8 * H), dtype=torch.float32, device=dev)
         frag_fwd = torch.empty((G, n), dtype=torch.int16, device=dev)
         frag_bwd = torch.empty((G, n), dtype=torch.int16, device=dev)
@@ -288,14 +269,11 @@ class BiLSTMFunction(torch.autograd.Function):
             else:
                 torch.addmm(bias, x2, w_ih.t(), out=xproj[g])
             wf, wb = w_hh_f.detach().contiguous().float(), w_hh_b.detach().contiguous().float()
-            _lib.check(L.amtx_bilstm_h_pack_device(_lib.ptr(wf), _lib.ptr(wb), H, 2, _lib.ptr(frag_fwd[g]), _lib.ptr(frag_bwd[g]),
-                                                   _lib.current_stream(dev)), 'amtx_bilstm_h_pack_device')
+            _lib.call('amtx_bilstm_h_pack_device', wf, wb, H, 2, frag_fwd[g], frag_bwd[g], device=dev)
             saved += [x2, w_ih]
         out = torch.empty((G, B, T, 2 * H), dtype=torch.float32, device=dev)
         save = torch.empty((G, B, T, 2, 5, H), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_bilstm_h_train_fwd(_lib.ptr(xproj), _lib.ptr(frag_fwd), H, 2, _lib.ptr(out), _lib.ptr(save), B, T, G,
-                                                 _lib.current_stream(dev)), 'amtx_bilstm_h_train_fwd')
+        _lib.call('amtx_bilstm_h_train_fwd', xproj, frag_fwd, H, 2, out, save, B, T, G, device=dev)
         ctx.save_for_backward(out, save, frag_bwd, *saved)
         ctx.hip_mm = [USE_HIP_DENSE and saved[2 * g].shape[1] % 4 == 0 for g in range(G)]
         ctx.dims = (G, B, T, H)
@@ -306,13 +284,10 @@ class BiLSTMFunction(torch.autograd.Function):
     def backward(ctx, *douts):
         out, save, frag_bwd, *saved = ctx.saved_tensors
         G, B, T, H = ctx.dims
-        L = _lib.lib()
         dev = out.device
         dout = torch.stack([d.contiguous().float() for d in douts], dim=0)
         dxproj = torch.empty((G, B * T, 8 * H), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_bilstm_h_train_bwd(_lib.ptr(dout), _lib.ptr(save), _lib.ptr(frag_bwd), H, 2, _lib.ptr(dxproj), B, T, G,
-                                                 _lib.current_stream(dev)), 'amtx_bilstm_h_train_bwd')
+        _lib.call('amtx_bilstm_h_train_bwd', dout, save, frag_bwd, H, 2, dxproj, B, T, G, device=dev)
         ones = torch.ones((1, B * T), dtype=torch.float32, device=dev)
         grads = [None]
         n = 4 * H
@@ -368,17 +343,14 @@ class BCELogitsLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, weight):
         B, T, K = logits.shape
-        L = _lib.lib()
         x = logits.detach().contiguous().float()
         y = labels.detach().contiguous().float()
         w = weight.detach().contiguous().float() if weight is not None else None
         need_grad = logits.requires_grad
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         grad = torch.empty((B, T, K), dtype=torch.float32, device=x.device) if need_grad else None
-        ws = _lib.alloc_workspace(int(L.amtx_bce_logits_loss_workspace_bytes(B, T, K)), x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.amtx_bce_logits_loss(_lib.ptr(x), K, _lib.ptr(y), _lib.ptr(w), B, T, K, _lib.ptr(loss), _lib.ptr(grad),
-                                              _lib.ptr(ws), ws.numel(), _lib.current_stream(x.device)), 'amtx_bce_logits_loss')
+        ws = _lib.alloc_workspace(int(_lib.call('amtx_bce_logits_loss_workspace_bytes', B, T, K)), x.device)
+        _lib.call('amtx_bce_logits_loss', x, K, y, w, B, T, K, loss, grad, ws, ws.numel(), device=x.device)
         # saved through autograd (not as a plain attribute of ctx): the (B,T,K) gradient is then released with the graph when backward never
         # runs (a labelled forward under enable_grad whose loss is only read)
         ctx.save_for_backward(*([grad] if grad is not None else []))
@@ -403,16 +375,12 @@ class BNReLUPoolFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, pool):
         B, Cc, T, F = x.shape
-        L = _lib.lib()
         Fo = F // 2 if pool else F
         y = torch.empty((B, Cc, T, Fo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         stats = torch.empty((4, Cc), dtype=torch.float32, device=x.device)
-        ws = _lib.alloc_workspace(int(L.amtx_bn_train_workspace_bytes(Cc)), x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.amtx_bn_relu_pool_train_fwd(_lib.ptr(x), B * T, F, Cc, int(pool), _lib.ptr(weight), _lib.ptr(bias), float(eps),
-                                                     float(momentum), _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(y),
-                                                     _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.current_stream(x.device)),
-                       'amtx_bn_relu_pool_train_fwd')
+        ws = _lib.alloc_workspace(int(_lib.call('amtx_bn_train_workspace_bytes', Cc)), x.device)
+        _lib.call('amtx_bn_relu_pool_train_fwd', x, B * T, F, Cc, int(pool), weight, bias, float(eps), float(momentum), running_mean, running_var,
+                  y, stats, ws, ws.numel(), device=x.device)
         ctx.save_for_backward(x, stats)
         ctx.pool = int(pool)
         ctx.ws = ws
@@ -423,15 +391,11 @@ class BNReLUPoolFunction(torch.autograd.Function):
     def backward(ctx, dy):
         x, stats = ctx.saved_tensors
         B, Cc, T, F = x.shape
-        L = _lib.lib()
         dy = dy.contiguous(memory_format=torch.channels_last).float()
         dx = torch.empty_like(x, memory_format=torch.channels_last)
         dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device) if ctx.affine else None
         dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device) if ctx.affine else None
-        with torch.cuda.device(x.device):
-            _lib.check(L.amtx_bn_relu_pool_train_bwd(_lib.ptr(x), B * T, F, Cc, ctx.pool, _lib.ptr(stats), _lib.ptr(dy), _lib.ptr(dx),
-                                                     _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ctx.ws), ctx.ws.numel(),
-                                                     _lib.current_stream(x.device)), 'amtx_bn_relu_pool_train_bwd')
+        _lib.call('amtx_bn_relu_pool_train_bwd', x, B * T, F, Cc, ctx.pool, stats, dy, dx, dgamma, dbeta, ctx.ws, ctx.ws.numel(), device=x.device)
         return dx, dgamma, dbeta, None, None, None, None, None
 
 
@@ -490,14 +454,11 @@ class TabWindowPoolFunction(torch.autograd.Function):
         T = int(num_windows)
         assert cols == T + 8 and F >= 8 and y3.dtype == torch.float32 and y3.is_cuda
         H = (F - 6) // 2
-        L = _lib.lib()
         dev = y3.device
         x = torch.empty((B * T, Cc * H), dtype=torch.float32, device=dev)
         rec = torch.empty((B * T, Cc * H), dtype=torch.uint8, device=dev)
         sb, sc, scol, sf = y3.stride()
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_tab_pool_train_fwd(_lib.ptr(y3), sb, sc, scol, sf, B, Cc, F, T, _lib.ptr(x), _lib.ptr(rec), _lib.current_stream(dev)),
-                       'amtx_tab_pool_train_fwd')
+        _lib.call('amtx_tab_pool_train_fwd', y3, sb, sc, scol, sf, B, Cc, F, T, x, rec, device=dev)
         ctx.save_for_backward(rec)
         ctx.dims = (B, Cc, F, T)
         return x
@@ -506,13 +467,10 @@ class TabWindowPoolFunction(torch.autograd.Function):
     def backward(ctx, dx):
         rec, = ctx.saved_tensors
         B, Cc, F, T = ctx.dims
-        L = _lib.lib()
         dev = dx.device
         dx = dx.contiguous()
         dmap = torch.empty((B, Cc, T + 8, F), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_tab_pool_train_bwd(_lib.ptr(dx), _lib.ptr(rec), B, Cc, F, T, _lib.ptr(dmap), _lib.current_stream(dev)),
-                       'amtx_tab_pool_train_bwd')
+        _lib.call('amtx_tab_pool_train_bwd', dx, rec, B, Cc, F, T, dmap, device=dev)
         return dmap, None
 
 
@@ -532,7 +490,6 @@ class SoftmaxGroupsLossFunction(torch.autograd.Function):
         B, T, K = logits.shape
         G, Cn = int(num_groups), int(num_classes)
         assert K == G * Cn and tuple(labels.shape) == (B, G, T)
-        L = _lib.lib()
         x = logits.detach()
         if x.dtype != torch.float32:
             x = x.float()
@@ -543,10 +500,8 @@ class SoftmaxGroupsLossFunction(torch.autograd.Function):
         need_grad = logits.requires_grad
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         grad = torch.empty((B, T, K), dtype=torch.float32, device=x.device) if need_grad else None
-        ws = _workspace(int(L.amtx_softmax_groups_loss_workspace_bytes(B, T, G, Cn)), x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.amtx_softmax_groups_loss(_lib.ptr(x), x.stride(1), _lib.ptr(y), _lib.ptr(w), B, T, G, Cn, _lib.ptr(loss), _lib.ptr(grad),
-                                                  _lib.ptr(ws), ws.numel(), _lib.current_stream(x.device)), 'amtx_softmax_groups_loss')
+        ws = _workspace(int(_lib.call('amtx_softmax_groups_loss_workspace_bytes', B, T, G, Cn)), x.device)
+        _lib.call('amtx_softmax_groups_loss', x, x.stride(1), y, w, B, T, G, Cn, loss, grad, ws, ws.numel(), device=x.device)
         ctx.save_for_backward(*([grad] if grad is not None else []))
         ctx.dtype = logits.dtype
         return loss

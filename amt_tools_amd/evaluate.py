@@ -370,9 +370,7 @@ class StackedMultipitchEvaluator(StackedEvaluator):
         B, S = est.shape[0], (est.shape[1] if est.dim() == 4 else 1)
         K, T = est.shape[-2:]
         counts = torch.empty((B, S, 3), dtype=torch.int64, device=est.device)
-        with torch.cuda.device(est.device):
-            _lib.check(_lib.lib().amtx_eval_multipitch_counts(_lib.ptr(est), _lib.ptr(ref), B, S, K, T, _lib.ptr(counts), _lib.current_stream(est.device)),
-                       'amtx_eval_multipitch_counts')
+        _lib.call('amtx_eval_multipitch_counts', est, ref, B, S, K, T, counts, device=est.device)
         return counts
 
     def results_from_counts(self, counts):
@@ -446,15 +444,12 @@ class StackedNoteEvaluator(StackedEvaluator):
         assert er.is_cuda and er.dtype == rr.dtype == torch.float64 and eo.dtype == ro.dtype == torch.int32 and eo.shape == ro.shape
         er, rr, eo, ro = er.contiguous(), rr.contiguous(), eo.contiguous(), ro.contiguous()
         dev, G = er.device, eo.shape[0] - 1
-        L = _lib.lib()
-        ws = _lib.alloc_workspace(int(L.amtx_eval_notes_match_workspace_bytes(er.shape[0], rr.shape[0])), dev)
+        ws = _lib.alloc_workspace(int(_lib.call('amtx_eval_notes_match_workspace_bytes', er.shape[0], rr.shape[0])), dev)
         counts = torch.empty((G, 3), dtype=torch.int32, device=dev)
         matched = torch.empty((G + 1,), dtype=torch.int32, device=dev)       # the last word: the call's status
         ratio = -1.0 if self.offset_ratio is None else float(self.offset_ratio)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_eval_notes_match(_lib.ptr(er), _lib.ptr(eo), er.shape[0], _lib.ptr(rr), _lib.ptr(ro), rr.shape[0], G, ONSET_TOLERANCE, ratio,
-                                               OFFSET_MIN_TOLERANCE, N_DECIMALS, _lib.ptr(ws), ws.numel(), _lib.ptr(matched), _lib.ptr(matched[G:]), 0,
-                                               _lib.current_stream(dev)), 'amtx_eval_notes_match')
+        _lib.call('amtx_eval_notes_match', er, eo, er.shape[0], rr, ro, rr.shape[0], G, ONSET_TOLERANCE, ratio, OFFSET_MIN_TOLERANCE, N_DECIMALS,
+                  ws, ws.numel(), matched, matched[G:], 0, device=dev)
         counts[:, 0] = matched[:G]
         counts[:, 1] = eo[1:] - eo[:-1]
         counts[:, 2] = ro[1:] - ro[:-1]
@@ -520,9 +515,7 @@ class _TabCounts(object):
             tuning, classes = np.zeros(S, dtype=np.int32), 1           # only count [4] is read then
         counts = torch.empty((B, 6), dtype=torch.int64, device=est.device)
         five = torch.empty((B, 5), dtype=torch.int64, device=est.device)
-        with torch.cuda.device(est.device):
-            _lib.check(_lib.lib().amtx_eval_tab_counts(_lib.ptr(est), _lib.ptr(ref), B, S, T, _lib.ptr(tuning), classes, _lib.ptr(five),
-                                                       _lib.current_stream(est.device)), 'amtx_eval_tab_counts')
+        _lib.call('amtx_eval_tab_counts', est, ref, B, S, T, tuning, classes, five, device=est.device)
         counts[:, :5] = five
         counts[:, 5] = S * T
         return counts

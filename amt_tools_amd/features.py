@@ -191,8 +191,7 @@ class _SpecPlanOwner(object):
             if not torch.cuda.is_available():
                 raise _lib.AmtxError('no GPU visible: the spectral front-end has no CPU fallback')
             handle = C.c_void_p()
-            with torch.cuda.device(index):
-                _lib.check(_lib.lib().amtx_spec_plan_create(C.byref(handle), *self._plan_args()), 'amtx_spec_plan_create')
+            _lib.call('amtx_spec_plan_create', C.byref(handle), *self._plan_args(), device=index)
             plan = plans[index] = handle
         return plan
 
@@ -212,7 +211,7 @@ class _SpecPlanOwner(object):
     def __del__(self):
         for plan in self.__dict__.get('_plans', {}).values():
             try:
-                _lib.lib().amtx_spec_plan_destroy(plan)
+                _lib.call('amtx_spec_plan_destroy', plan)
             except Exception:
                 pass
 
@@ -224,15 +223,13 @@ class _SpecPlanOwner(object):
         audio = audio.contiguous()
         B, N = audio.shape
         plan = self._get_plan(audio.device)
-        L = _lib.lib()
-        T = _lib.check(L.amtx_spec_num_frames(plan, N), 'amtx_spec_num_frames')
-        F = L.amtx_spec_num_bins(plan)
+        T = _lib.call('amtx_spec_num_frames', plan, N)
+        F = _lib.call('amtx_spec_num_bins', plan)
         power = torch.empty((B, T, F), dtype=torch.float32, device=audio.device)
         clip_max = torch.empty((B,), dtype=torch.float32, device=audio.device)
         with torch.cuda.device(audio.device):
             ev = self._prof_begin()
-            _lib.check(L.amtx_spec_power(plan, _lib.ptr(audio), N, audio.stride(0) if B > 1 else N, B, _lib.ptr(power), _lib.ptr(clip_max),
-                                         _lib.current_stream(audio.device)), 'amtx_spec_power')
+            _lib.call('amtx_spec_power', plan, audio, N, audio.stride(0) if B > 1 else N, B, power, clip_max, device=audio.device)
             self._prof_end('spec_power', ev)
         return power, clip_max
 
@@ -258,7 +255,6 @@ class _SpecPlanOwner(object):
         """K2: dB / scale + layout.  Returns (B,1,F,T) (reference layout) or (B,1,T,F) (model layout)."""
         import torch
         B, T, F = power.shape
-        L = _lib.lib()
         if self.decibels:
             transform = 0
         else:
@@ -266,9 +262,8 @@ class _SpecPlanOwner(object):
         out = torch.empty((B, 1, T, F) if model_layout else (B, 1, F, T), dtype=torch.float32, device=power.device)
         with torch.cuda.device(power.device):
             ev = self._prof_begin()
-            _lib.check(L.amtx_spec_scale(self._get_plan(power.device), _lib.ptr(power), _lib.ptr(clip_max), _lib.ptr(ref), B, T, transform,
-                                         1 if model_layout else 0, _lib.ptr(out), _lib.current_stream(power.device)),
-                       'amtx_spec_scale')
+            _lib.call('amtx_spec_scale', self._get_plan(power.device), power, clip_max, ref, B, T, transform, 1 if model_layout else 0, out,
+                      device=power.device)
             self._prof_end('spec_scale', ev)
         return out
 
@@ -352,7 +347,7 @@ class MelSpec(STFT):
     def filterbank(self):
         """Dense (n_mels, n_fft//2+1) float32 copy of the plan's filterbank (for inspection/tests)."""
         out = np.zeros((self.n_mels, self.n_fft // 2 + 1), dtype=np.float32)
-        _lib.check(_lib.lib().amtx_spec_filterbank(self._get_plan(), _lib.ptr(out)), 'amtx_spec_filterbank')
+        _lib.call('amtx_spec_filterbank', self._get_plan(), out)
         return out
 
 
@@ -398,11 +393,9 @@ class _CqtPlanOwner(object):
             fmin, harmonics, truncate = self._cqt_args()
             arr = (C.c_double * len(harmonics))(*[float(h) for h in harmonics])
             handle = C.c_void_p()
-            with torch.cuda.device(index):
-                _lib.check(_lib.lib().amtx_cqt_plan_create(C.byref(handle), int(self.sample_rate), int(self.hop_length), float(fmin),
-                                                           int(self.n_bins), int(self.bins_per_octave), float(self.gamma), arr,
-                                                           len(harmonics), int(truncate),
-                                                           int(str(self.librosa_version).startswith('0.9'))), 'amtx_cqt_plan_create')
+            _lib.call('amtx_cqt_plan_create', C.byref(handle), int(self.sample_rate), int(self.hop_length), float(fmin), int(self.n_bins),
+                      int(self.bins_per_octave), float(self.gamma), arr, len(harmonics), int(truncate),
+                      int(str(self.librosa_version).startswith('0.9')), device=index)
             plan = plans[index] = handle
         return plan
 
@@ -415,7 +408,7 @@ class _CqtPlanOwner(object):
     def __del__(self):
         for plan in self.__dict__.get('_plans', {}).values():
             try:
-                _lib.lib().amtx_cqt_plan_destroy(plan)
+                _lib.call('amtx_cqt_plan_destroy', plan)
             except Exception:
                 pass
 
@@ -425,19 +418,16 @@ class _CqtPlanOwner(object):
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2
         audio = audio.contiguous()
         B, N = audio.shape
-        L = _lib.lib()
         plan = self._get_plan(audio.device)
-        T = _lib.check(L.amtx_cqt_num_frames(plan, N), 'amtx_cqt_num_frames')
-        H = L.amtx_cqt_num_harmonics(plan)
-        need = L.amtx_cqt_workspace_bytes(plan, B, N)
+        T = _lib.call('amtx_cqt_num_frames', plan, N)
+        H = _lib.call('amtx_cqt_num_harmonics', plan)
+        need = _lib.call('amtx_cqt_workspace_bytes', plan, B, N)
         ws = self.__dict__.get('_workspace')
         if ws is None or ws.numel() < need or ws.device != audio.device:
             self.__dict__['_workspace'] = None
             ws = self.__dict__['_workspace'] = _lib.alloc_workspace(need, audio.device)
         out = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=audio.device)
-        with torch.cuda.device(audio.device):
-            _lib.check(L.amtx_cqt_forward(plan, _lib.ptr(audio), N, audio.stride(0) if B > 1 else N, B, int(bool(self.decibels)), _lib.ptr(ws), ws.numel(),
-                                          _lib.ptr(out), _lib.current_stream(audio.device)), 'amtx_cqt_forward')
+        _lib.call('amtx_cqt_forward', plan, audio, N, audio.stride(0) if B > 1 else N, B, int(bool(self.decibels)), ws, ws.numel(), out, device=audio.device)
         return out
 
     def process_batch16(self, audio, split=False):
@@ -450,23 +440,20 @@ class _CqtPlanOwner(object):
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2
         audio = audio.contiguous()
         B, N = audio.shape
-        L = _lib.lib()
         plan = self._get_plan(audio.device)
-        T = _lib.check(L.amtx_cqt_num_frames(plan, N), 'amtx_cqt_num_frames')
-        assert L.amtx_cqt_num_harmonics(plan) <= 8
-        need = L.amtx_cqt_workspace_bytes(plan, B, N)
+        T = _lib.call('amtx_cqt_num_frames', plan, N)
+        assert _lib.call('amtx_cqt_num_harmonics', plan) <= 8
+        need = _lib.call('amtx_cqt_workspace_bytes', plan, B, N)
         ws = self.__dict__.get('_workspace')
         if ws is None or ws.numel() < need or ws.device != audio.device:
             self.__dict__['_workspace'] = None
             ws = self.__dict__['_workspace'] = _lib.alloc_workspace(need, audio.device)
         out = torch.empty(((2,) if split else ()) + (B, T, self.n_bins, 8), dtype=torch.bfloat16, device=audio.device)
-        with torch.cuda.device(audio.device):
-            if split:
-                _lib.check(L.amtx_cqt_forward16_split(plan, _lib.ptr(audio), N, audio.stride(0) if B > 1 else N, B, int(bool(self.decibels)), _lib.ptr(ws),
-                                                      ws.numel(), _lib.ptr(out), out[0].numel(), _lib.current_stream(audio.device)), 'amtx_cqt_forward16_split')
-            else:
-                _lib.check(L.amtx_cqt_forward16(plan, _lib.ptr(audio), N, audio.stride(0) if B > 1 else N, B, int(bool(self.decibels)), _lib.ptr(ws), ws.numel(),
-                                                _lib.ptr(out), _lib.current_stream(audio.device)), 'amtx_cqt_forward16')
+        args = (plan, audio, N, audio.stride(0) if B > 1 else N, B, int(bool(self.decibels)), ws, ws.numel(), out)
+        if split:
+            _lib.call('amtx_cqt_forward16_split', *args, out[0].numel(), device=audio.device)
+        else:
+            _lib.call('amtx_cqt_forward16', *args, device=audio.device)
         return out
 
     def _process_host(self, audio):

@@ -377,8 +377,7 @@ class _EngineBase(object):
     def __init__(self, device, *create_args):
         self.device = device
         self.handle = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(getattr(_lib.lib(), self.ABI + '_create')(C.byref(self.handle), *create_args), self.ABI + '_create')
+        _lib.call(self.ABI + '_create', C.byref(self.handle), *create_args, device=device)
         self.version = None
         self.workspace = None
 
@@ -390,15 +389,13 @@ class _EngineBase(object):
         if self.version is None or not self._resync_on_device(items):
             # ONE device-to-host copy of all parameters and buffers (a copy per tensor is ~60 synchronisations per re-sync); the library
             # packs from host memory
-            L = _lib.lib()
             flat = torch.cat([v.detach().reshape(-1).to(torch.float32) for _, v in items]).cpu().numpy()
             off = 0
             for k, v in items:
                 n = v.numel()
-                _lib.check(getattr(L, self.ABI + '_set_tensor')(self.handle, k.encode(), _lib.ptr(flat[off:off + n]), n), self.ABI + '_set_tensor')
+                _lib.call(self.ABI + '_set_tensor', self.handle, k.encode(), flat[off:off + n], n)
                 off += n
-            with torch.cuda.device(self.device):
-                _lib.check(getattr(L, self.ABI + '_finalize')(self.handle), self.ABI + '_finalize')
+            _lib.call(self.ABI + '_finalize', self.handle, device=self.device)
         self.version = version
 
     def _resync_on_device(self, items):
@@ -412,7 +409,7 @@ class _EngineBase(object):
 
     def __del__(self):
         try:
-            getattr(_lib.lib(), self.ABI + '_destroy')(self.handle)
+            _lib.call(self.ABI + '_destroy', self.handle)
         except Exception:
             pass
 
@@ -434,15 +431,15 @@ class _OFEngine(_EngineBase):
         # tensors are handed over as device pointers and folded / packed by kernels -- the same bits as the host path.
         if not (self.device_sync and all(v.is_cuda and v.device == torch.device(self.device) and v.dtype == torch.float32 for _, v in items)):
             return False
-        L = _lib.lib()
         keep = []                                   # channels-last convolution weights (the GPU training layout) go through a dense device copy
         for k, v in items:
             t = v.detach()
             t = t if t.is_contiguous() else t.contiguous()
             keep.append(t)
-            _lib.check(L.amtx_of_model_set_tensor_device(self.handle, k.encode(), _lib.ptr(t), t.numel()), 'amtx_of_model_set_tensor_device')
+            _lib.call('amtx_of_model_set_tensor_device', self.handle, k.encode(), t, t.numel())
         with torch.cuda.device(self.device):
-            rc = L.amtx_of_model_finalize_device(self.handle, _lib.current_stream(self.device))
+            # not through _lib.call: AMTX_ERR_UNSUPPORTED is an answer here ("pack on the host"), every other error is raised below
+            rc = _lib.lib().amtx_of_model_finalize_device(self.handle, _lib.current_stream(self.device))
             if keep and rc == 0:
                 torch.cuda.current_stream(self.device).synchronize()     # the borrowed copies may go once the pack kernels have read them
         del keep
@@ -455,19 +452,18 @@ class _OFEngine(_EngineBase):
         return False
 
     def fuses_db_scale(self):
-        return bool(_lib.lib().amtx_of_fuses_db_scale(self.handle))
+        return bool(_lib.call('amtx_of_fuses_db_scale', self.handle))
 
     def takes_feats16(self):
         """0: no; 1: (B,T,F,8) 16-bit channels-last features (one-plane engine); 2: the same as two planes (2,B,T,F,8) (x3 engine, round 6)."""
-        return int(_lib.lib().amtx_of_takes_feats16(self.handle))
+        return int(_lib.call('amtx_of_takes_feats16', self.handle))
 
     def conv_stack_fused(self, batch, num_frames):
         """True when a forward pass of this shape runs the three convolution layers as one kernel (csrc/convf.hip)."""
-        return bool(_lib.lib().amtx_of_conv_stack_fused(self.handle, int(batch), int(num_frames)))
+        return bool(_lib.call('amtx_of_conv_stack_fused', self.handle, int(batch), int(num_frames)))
 
     def forward(self, feats, want_logits=True):
         """feats: (B,C,T,F) fp32 CUDA tensor (any strides), or PendingFeatures.  Returns binary maps + raw logits."""
-        L = _lib.lib()
         pending = feats if isinstance(feats, PendingFeatures) else None
         pending16 = isinstance(pending, PendingFeatures16)
         if pending16:
@@ -477,7 +473,7 @@ class _OFEngine(_EngineBase):
             feats = pending.power.unsqueeze(1)
         if not pending16:
             B, Cc, T, Fd = feats.shape
-        self._grow_workspace(L.amtx_of_workspace_bytes(self.handle, B, T), feats.device)
+        self._grow_workspace(_lib.call('amtx_of_workspace_bytes', self.handle, B, T), feats.device)
         n_out = self.n_out
         opts = dict(dtype=torch.float32, device=feats.device)
         onsets = torch.empty((B, n_out, T), **opts)
@@ -486,33 +482,24 @@ class _OFEngine(_EngineBase):
         lm = torch.empty((B, T, n_out), **opts) if want_logits else None
         lp = torch.empty((B, T, n_out), **opts) if want_logits else None
         sb, sc, st, sf = (0, 0, 0, 0) if pending16 else feats.stride()
-        with torch.cuda.device(feats.device):
-            if pending16:
-                _lib.check(L.amtx_of_forward_feats16(self.handle, _lib.ptr(feats), B, T, _lib.ptr(self.workspace), self.workspace.numel(),
-                                                     _lib.ptr(onsets), _lib.ptr(multi_pitch), _lib.ptr(lo), _lib.ptr(lm), _lib.ptr(lp),
-                                                     _lib.current_stream(feats.device)), 'amtx_of_forward_feats16')
-            elif pending is not None:
-                _lib.check(L.amtx_of_forward_power(self.handle, _lib.ptr(feats), sb, st, sf, _lib.ptr(pending.clip_max), _lib.ptr(pending.ref), B, T,
-                                                   _lib.ptr(self.workspace), self.workspace.numel(), _lib.ptr(onsets), _lib.ptr(multi_pitch),
-                                                   _lib.ptr(lo), _lib.ptr(lm), _lib.ptr(lp), _lib.current_stream(feats.device)),
-                           'amtx_of_forward_power')
-            else:
-                _lib.check(L.amtx_of_forward(self.handle, _lib.ptr(feats), sb, sc, st, sf, B, T, _lib.ptr(self.workspace),
-                                             self.workspace.numel(), _lib.ptr(onsets), _lib.ptr(multi_pitch), _lib.ptr(lo),
-                                             _lib.ptr(lm), _lib.ptr(lp), _lib.current_stream(feats.device)), 'amtx_of_forward')
+        ws, outs = self.workspace, (onsets, multi_pitch, lo, lm, lp)
+        if pending16:
+            _lib.call('amtx_of_forward_feats16', self.handle, feats, B, T, ws, ws.numel(), *outs, device=feats.device)
+        elif pending is not None:
+            _lib.call('amtx_of_forward_power', self.handle, feats, sb, st, sf, pending.clip_max, pending.ref, B, T, ws, ws.numel(), *outs,
+                      device=feats.device)
+        else:
+            _lib.call('amtx_of_forward', self.handle, feats, sb, sc, st, sf, B, T, ws, ws.numel(), *outs, device=feats.device)
         self._last = (B, T)
         return onsets, multi_pitch, lo, lm, lp
 
     def offsets(self, device, want_logits=True):
         """OnsetsFrames2: offset probabilities (B,O,T) [+ raw logits (B,T,O)] of the last forward."""
-        L = _lib.lib()
         B, T = self._last
         opts = dict(dtype=torch.float32, device=device)
         prob = torch.empty((B, self.n_out, T), **opts)
         logits = torch.empty((B, T, self.n_out), **opts) if want_logits else None
-        with torch.cuda.device(device):
-            _lib.check(L.amtx_of_offsets(self.handle, _lib.ptr(self.workspace), self.workspace.numel(), B, T, _lib.ptr(prob),
-                                         _lib.ptr(logits), _lib.current_stream(device)), 'amtx_of_offsets')
+        _lib.call('amtx_of_offsets', self.handle, self.workspace, self.workspace.numel(), B, T, prob, logits, device=device)
         return prob, logits
 
 
@@ -880,7 +867,7 @@ class _TabEngine(_EngineBase):
         self.forwards = 0                               # engine calls made (tests)
 
     def workspace_bytes(self, batch, num_windows):
-        return int(_lib.lib().amtx_tab_workspace_bytes(self.handle, int(batch), int(num_windows)))
+        return int(_lib.call('amtx_tab_workspace_bytes', self.handle, int(batch), int(num_windows)))
 
     def _chunks(self, B, T):
         """[(b0, b1, t0, t1)] covering (B, T) with every chunk's workspace under WORKSPACE_CAP (one window of one clip at the least)."""
@@ -902,7 +889,6 @@ class _TabEngine(_EngineBase):
     def forward(self, feats, view):
         """feats: the (B, T, C, F, 9) window view, `view` = tab_window_view(feats).  Returns logits (B, T, G*C) fp32 and tablature
         (B, G, T) int64."""
-        L = _lib.lib()
         B, T = feats.shape[:2]
         sb, sc, sf, st = view['strides']
         G, Cn = self.G, self.C
@@ -912,18 +898,16 @@ class _TabEngine(_EngineBase):
         self._grow_workspace(max(self.workspace_bytes(b1 - b0, t1 - t0) for b0, b1, t0, t1 in chunks), feats.device)
         base = feats.data_ptr()                          # element (0, 0, 0, 0, 0): column 0 of clip 0's sequence
         esz = feats.element_size()
-        with torch.cuda.device(feats.device):
-            stream = _lib.current_stream(feats.device)
-            for b0, b1, t0, t1 in chunks:
-                whole = len(chunks) == 1
-                lg = logits if whole else torch.empty((b1 - b0, t1 - t0, G * Cn), dtype=torch.float32, device=feats.device)
-                tb = tab if whole else torch.empty((b1 - b0, G, t1 - t0), dtype=torch.int64, device=feats.device)
-                ptr = C.c_void_p(base + (b0 * sb + t0 * st) * esz)     # windows are independent: a chunk starts at its first column
-                _lib.check(L.amtx_tab_forward(self.handle, ptr, sb, sc, sf, st, b1 - b0, t1 - t0, _lib.ptr(self.workspace),
-                                              self.workspace.numel(), _lib.ptr(lg), _lib.ptr(tb), stream), 'amtx_tab_forward')
-                if not whole:
-                    logits[b0:b1, t0:t1] = lg
-                    tab[b0:b1, :, t0:t1] = tb
+        for b0, b1, t0, t1 in chunks:
+            whole = len(chunks) == 1
+            lg = logits if whole else torch.empty((b1 - b0, t1 - t0, G * Cn), dtype=torch.float32, device=feats.device)
+            tb = tab if whole else torch.empty((b1 - b0, G, t1 - t0), dtype=torch.int64, device=feats.device)
+            ptr = base + (b0 * sb + t0 * st) * esz               # windows are independent: a chunk starts at its first column
+            _lib.call('amtx_tab_forward', self.handle, ptr, sb, sc, sf, st, b1 - b0, t1 - t0, self.workspace, self.workspace.numel(), lg, tb,
+                      device=feats.device)
+            if not whole:
+                logits[b0:b1, t0:t1] = lg
+                tab[b0:b1, :, t0:t1] = tb
         self.forwards += 1
         return logits, tab
 

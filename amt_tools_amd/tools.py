@@ -276,9 +276,7 @@ def tab_expand(tablature, profile, stacked=True, collapsed=False):
     co = torch.empty(lead + (P, T), dtype=torch.float32, device=dev) if collapsed else None
     if B * S * T > 0:
         start = np.ascontiguousarray(dof_start, dtype=np.int32)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().amtx_tab_expand(_lib.ptr(tab), B, S, T, _lib.ptr(start), num_classes, P, _lib.ptr(st), _lib.ptr(co),
-                                                  _lib.current_stream(dev)), 'amtx_tab_expand')
+        _lib.call('amtx_tab_expand', tab, B, S, T, start, num_classes, P, st, co, device=dev)
     return st, co
 
 
@@ -330,13 +328,10 @@ def rms_norm_batch(audio):
     assert audio.is_cuda and audio.dim() == 2 and audio.dtype == torch.float32
     audio = audio.contiguous()
     B, N = audio.shape
-    L = _lib.lib()
-    ws = _lib.alloc_workspace(int(L.amtx_rms_norm_workspace_bytes(B, N)), audio.device)
+    ws = _lib.alloc_workspace(int(_lib.call('amtx_rms_norm_workspace_bytes', B, N)), audio.device)
     out = torch.empty_like(audio)
-    with torch.cuda.device(audio.device):
-        # a one-clip batch may carry any stride in its size-1 dimension (numpy's x[None] has 0): the rows are N apart by definition then
-        _lib.check(L.amtx_rms_norm(_lib.ptr(audio), N, audio.stride(0) if B > 1 else N, B, _lib.ptr(out), out.stride(0) if B > 1 else N, _lib.ptr(ws), ws.numel(),
-                                   _lib.current_stream(audio.device)), 'amtx_rms_norm')
+    # a one-clip batch may carry any stride in its size-1 dimension (numpy's x[None] has 0): the rows are N apart by definition then
+    _lib.call('amtx_rms_norm', audio, N, audio.stride(0) if B > 1 else N, B, out, out.stride(0) if B > 1 else N, ws, ws.numel(), device=audio.device)
     return out
 
 

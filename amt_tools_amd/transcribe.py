@@ -223,18 +223,13 @@ def decode_notes_batch_async(onsets, multi_pitch, times, low=tools.DEFAULT_PIANO
     cap = T // 2 + 2
     pairs = torch.empty((B * K, cap, 2), dtype=torch.int32, device=dev)
     counts = torch.empty((B * K,), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        _lib.check(L.amtx_notes_decode(_lib.ptr(onsets), _lib.ptr(multi_pitch), B, K, T, cap, _lib.ptr(pairs), _lib.ptr(counts),
-                                       _lib.current_stream(dev)), 'amtx_notes_decode')
+    _lib.call('amtx_notes_decode', onsets, multi_pitch, B, K, T, cap, pairs, counts, device=dev)
 
     def rows_pass(capacity):
         rows = torch.empty((capacity, 3), dtype=torch.float64, device=dev)
         onset_col = torch.empty((capacity,), dtype=torch.float64, device=dev)
         offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_notes_rows(_lib.ptr(pairs), _lib.ptr(counts), B, K, cap, _lib.ptr(ext_d), stride, int(low), _lib.ptr(rows),
-                                         _lib.ptr(onset_col), capacity, _lib.ptr(offsets), _lib.current_stream(dev)), 'amtx_notes_rows')
+        _lib.call('amtx_notes_rows', pairs, counts, B, K, cap, ext_d, stride, int(low), rows, onset_col, capacity, offsets, device=dev)
         return _PendingNotes(rows, onset_col, offsets, B, rows_pass)
 
     # 1024 notes per clip on average covers any realistic transcription (the synthetic bench clips decode to ~400); a denser batch is
@@ -511,15 +506,12 @@ def decode_tab_notes_batch_async(tablature, times, profile, inhibition_window=No
         rel_d = _grid_on_device(_release_table(times, inhibition_window), dev)
         rel_stride = 0 if times.ndim == 1 else T
     has_min = minimum_duration is not None
-    L = _lib.lib()
 
     def rows_pass(capacity):
         rows = torch.empty((capacity, 3), dtype=torch.float64, device=dev)
         offsets = torch.empty((B * S + 1,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.amtx_tab_notes(_lib.ptr(tablature), B, S, T, _lib.ptr(tuning), num_classes, _lib.ptr(ext_d), stride, _lib.ptr(rel_d),
-                                        rel_stride, int(has_min), float(minimum_duration) if has_min else 0.0, _lib.ptr(rows), capacity,
-                                        _lib.ptr(offsets), _lib.current_stream(dev)), 'amtx_tab_notes')
+        _lib.call('amtx_tab_notes', tablature, B, S, T, tuning, num_classes, ext_d, stride, rel_d, rel_stride, int(has_min),
+                  float(minimum_duration) if has_min else 0.0, rows, capacity, offsets, device=dev)
         return _PendingTabNotes(rows, offsets, B, S, rows_pass)
 
     # a string holds at most one note per frame; 128 notes per string on average is far above any real tablature (a denser batch is caught

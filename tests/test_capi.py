@@ -1,18 +1,105 @@
-"""CPU-side checks of the C ABI: the shared library loads, exports every symbol include/amtx.h declares,
-and the ctypes table covers all of them.  No compute calls (no GPU here)."""
+"""CPU-side checks of the C ABI and its binding: the shared library loads and exports every symbol include/amtx.h declares, the ctypes
+signatures read from the header equal the pinned table, and _lib.call / the pointer argument type behave.  No GPU here."""
+import ctypes as C
+import json
 import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
 
 from amt_tools_amd import _lib
 
+GOLDEN_ABI = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'abi_signatures.json')
+
 
 def test_library_exports_every_declared_symbol():
+    """Every declared function is exported, and the table parse_header reads from include/amtx.h equals tests/golden/abi_signatures.json
+    exactly: row count, argument count and every letter (return type first; i int, l int64_t, z size_t, f float, d double, s const char*,
+    p any other pointer; then whether the function ends in `void* stream`).  The golden was dumped from the hand-written ctypes table
+    (_SIGNATURES in _lib.py) on the commit before the signatures were read from the header; a later header change shows up as a
+    reviewed diff of that file."""
     L = _lib.lib()
     declared = _lib.declared_symbols()
     assert len(declared) >= 20
     for name in declared:
         assert hasattr(L, name), f'{name} declared in include/amtx.h but not exported'
-    assert set(declared) == set(_lib._SIGNATURES), set(declared) ^ set(_lib._SIGNATURES)
+    with open(GOLDEN_ABI) as f:
+        golden = json.load(f)
+    with open(_lib.HEADER_PATH) as f:
+        parsed = {name: list(row) for name, row in _lib.parse_header(f.read()).items()}
+    assert sorted(parsed) == sorted(golden) == declared
+    for name in declared:
+        assert parsed[name] == golden[name], (name, parsed[name], golden[name])
     assert L.amtx_version() >= 100
+
+
+def test_parse_header_on_synthetic_text():
+    table = _lib.parse_header("""
+        #include <stdint.h>
+        typedef struct amtx_thing amtx_thing;
+        const char* amtx_name(void);   /* a void parameter list */
+        int64_t amtx_run(const amtx_thing* thing, /* where */ const float* x /*[n]*/,
+                         size_t n,      // how many
+                         double a, float b, int32_t* out,
+                         void* stream);
+        int amtx_thing_create(amtx_thing** thing, const char* name, int flags);
+    """)
+    assert table == {'amtx_name': ('s', False), 'amtx_run': ('lppzdfpp', True), 'amtx_thing_create': ('ipsi', False)}
+    for bad in ('int amtx_bad(long double x);', 'int amtx_bad(const float* x, void* stream, int n);', 'int amtx_bad(void (*fn)(int), int n);',
+                'int amtx_bad(const void* stream);', 'struct amtx_s* amtx_bad(void);', 'int amtx_bad(int n)\nint amtx_worse(void);'):
+        with pytest.raises(_lib.AmtxError, match='amtx_bad'):
+            _lib.parse_header(bad)
+
+
+def test_pointer_arguments():
+    """A host-only packer gives the same bytes whichever accepted form carries its pointers; text and floats are no pointers."""
+    n, k, planes = 7, 5, 2
+    w = np.random.default_rng(0).standard_normal((n, k)).astype(np.float32)
+    elems = _lib.call('amtx_linear_packed_elems', n, k, planes)
+    forms = {'numpy': lambda a: a, 'ptr': _lib.ptr, 'c_void_p': lambda a: C.c_void_p(a.ctypes.data), 'address': lambda a: a.ctypes.data}
+    packed = {}
+    for form, conv in forms.items():
+        out = np.full(elems, 0x5A5A, dtype=np.uint16)
+        assert _lib.call('amtx_linear_pack', conv(w), n, k, planes, conv(out)) == 0
+        packed[form] = out.tobytes()
+    assert len(set(packed.values())) == 1 and packed['numpy'] != np.full(elems, 0x5A5A, dtype=np.uint16).tobytes()
+    out = np.zeros(elems, dtype=np.uint16)
+    for bad in ('text', 1.5):
+        with pytest.raises(C.ArgumentError):
+            _lib.call('amtx_linear_pack', bad, n, k, planes, out)
+        with pytest.raises(C.ArgumentError):
+            _lib.lib().amtx_linear_pack(_lib.ptr(w), n, k, planes, bad)
+    w3 = np.random.default_rng(1).standard_normal((32, 32, 3, 3)).astype(np.float32)
+    out3 = np.zeros(_lib.call('amtx_conv3x3_packed_elems', 32, 1), dtype=np.uint16)
+    assert _lib.call('amtx_conv3x3_pack', w3, None, 32, 1, out3) == 0 and out3.any()             # None: the nullable scale
+
+
+def test_call_reports_errors():
+    h = C.c_void_p()
+    with pytest.raises(_lib.AmtxError, match='amtx_of_model_create.*model_complexity'):
+        _lib.call('amtx_of_model_create', C.byref(h), 229, 1, 6, 88, 1, 0)
+    with pytest.raises(_lib.AmtxError, match='amtx_no_such'):
+        _lib.call('amtx_no_such')
+    for args in ((7, 5), (7, 5, 2, 1)):                                                          # one argument short, one too many
+        with pytest.raises(TypeError, match='amtx_linear_packed_elems takes 3'):
+            _lib.call('amtx_linear_packed_elems', *args)
+
+
+def test_binding_imports_without_torch():
+    """_lib.py loaded by file path, outside the package, in a process where torch cannot be imported: lib() and a host-only call work."""
+    code = ('import sys, importlib.util\n'
+            'sys.modules["torch"] = None\n'
+            'spec = importlib.util.spec_from_file_location("amtx_lib_alone", sys.argv[1])\n'
+            'm = importlib.util.module_from_spec(spec)\n'
+            'spec.loader.exec_module(m)\n'
+            'm.lib()\n'
+            'assert m.call("amtx_version") >= 100 and m.call("amtx_last_error") is not None\n'
+            'assert "torch" not in {k for k, v in sys.modules.items() if v is not None}\n'
+            'print("ok", len(m.signatures()))\n')
+    r = subprocess.run([sys.executable, '-c', code, _lib.__file__], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith('ok'), r.stderr
 
 
 def test_host_only_queries():
@@ -26,12 +113,10 @@ def test_host_only_queries():
 
 
 def test_errors_are_reported_not_swallowed():
-    import ctypes as C
     L = _lib.lib()
     h = C.c_void_p()
     rc = L.amtx_of_model_create(C.byref(h), 229, 1, 6, 88, 1, 0)    # model_complexity 6: no kernels for its channel counts
     assert rc < 0 and b'model_complexity' in L.amtx_last_error()
-    import pytest
     with pytest.raises(_lib.AmtxError):
         _lib.check(rc, 'amtx_of_model_create')
     assert os.path.exists(_lib.LIB_PATH)
@@ -39,9 +124,6 @@ def test_errors_are_reported_not_swallowed():
 
 def test_missing_extension_fails_loudly_without_a_cpu_fallback(monkeypatch):
     """No HIP extension -> the product path raises; nothing quietly computes on the CPU (oracle/ is never imported by the package)."""
-    import sys
-    import numpy as np
-    import pytest
     from amt_tools_amd.features import MelSpec
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libamtx.so')

@@ -178,5 +178,5 @@ def _lib_checked():
     from amt_tools_amd import _lib
     L = _lib.lib()
     for name in ('amtx_tab_expand', 'amtx_tab_notes'):
-        assert name in _lib.declared_symbols() and name in _lib._SIGNATURES and hasattr(L, name), name
+        assert name in _lib.declared_symbols() and name in _lib.signatures() and hasattr(L, name), name
     return L

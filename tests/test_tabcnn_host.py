@@ -25,7 +25,7 @@ def test_tab_abi_is_exported():
     L = _lib.lib()
     declared = _lib.declared_symbols()
     for name in TAB_FUNCS:
-        assert name in declared and name in _lib._SIGNATURES and hasattr(L, name), name
+        assert name in declared and name in _lib.signatures() and hasattr(L, name), name
 
 
 @pytest.mark.parametrize('kwargs, word', [(dict(mc=2), b'model_complexity'), (dict(classes=33), b'num_classes'),

@@ -23,7 +23,7 @@ def test_tab_train_abi_is_exported():
     L = _lib.lib()
     declared = _lib.declared_symbols()
     for name in NEW_FUNCS:
-        assert name in declared and name in _lib._SIGNATURES and hasattr(L, name), name
+        assert name in declared and name in _lib.signatures() and hasattr(L, name), name
 
 
 def test_tab_train_argument_errors():
