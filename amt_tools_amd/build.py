@@ -34,8 +34,8 @@ def _deps():
 FILE_FLAGS = {'spec.hip': ['-fno-slp-vectorize'], 'convg.hip': ['-fno-slp-vectorize'], 'cqt_dec.hip': ['-fno-slp-vectorize']}
 
 
-# OPTIONAL (AMTX_BUILD_F16=1): compiled a second time with -DAMTX_F16 (IEEE half operands instead of bf16, public functions suffixed _f16:
-# csrc/amtx_f16_names.h) = the engine's precision 'f16'.  Off by default since round 6: it recompiles the six largest kernel files for a
+# OPTIONAL (AMTX_BUILD_F16=1): compiled a second time with -DAMTX_F16 (IEEE half operands instead of bf16, public functions in namespace
+# amtx_f16 instead of amtx_bf16: csrc/amtx_kernels_fmt.h) = the engine's precision 'f16'.  Off by default since round 6: it recompiles the six largest kernel files for a
 # mode no BASELINE config names; without it amtx_has_f16() is 0 and amtx_of_model_create refuses AMTX_PREC_F16.
 F16_TWINS = ('conv.hip', 'convf.hip', 'convg.hip', 'gemm.hip', 'lstm.hip', 'pack.hip')
 WITH_F16 = os.environ.get('AMTX_BUILD_F16', '0') not in ('', '0')

@@ -47,13 +47,15 @@ int amtx_grant_lds(const void* kernel, size_t bytes);
 
 // ------------------------------------------------------------------ 16-bit operand format of this translation unit
 // conv.hip, convf.hip, convg.hip, gemm.hip, lstm.hip and pack.hip are compiled TWICE (amt_tools_amd/build.py, F16_TWINS):
-// as they are, with bf16 operands, and with -DAMTX_F16 into a second object whose public functions carry the suffix _f16 (amtx_f16_names.h) and whose 16-bit values are IEEE
+// as they are, with bf16 operands and their public functions in namespace amtx_bf16, and with -DAMTX_F16 into a second object whose
+// public functions are in namespace amtx_f16 (both declared from amtx_kernels_fmt.h) and whose 16-bit values are IEEE
 // half precision: the same matrix rate on gfx950 (v_mfma_f32_16x16x32_f16), three more mantissa bits -- the engine's precision 'f16'.
 // In that build every name below that says "bf16" means "the 16-bit operand format of this build": bf16_t is a raw 16-bit pattern
 // either way, and no kernel touches the bits except through these helpers.
 typedef uint16_t bf16_t;   // raw 16-bit operand bits (bf16, or half in an AMTX_F16 build)
 
 #ifdef AMTX_F16
+#define AMTX_FMT_NS amtx_f16
 static inline __host__ __device__ bf16_t f32_to_bf16_rn(float f) {      // round to nearest even (hardware or compiler conversion)
     // saturating: a folded weight beyond half's range (a BatchNorm scale over a tiny running variance) becomes +-65504, not +-inf -> NaN
     // downstream.  This is the packers' conversion (host and pack.hip); the kernels' own pack_bf16x2 of activations stays
@@ -70,6 +72,7 @@ static inline __host__ __device__ float bf16_to_f32(bf16_t u) {
     return (float)h;
 }
 #else
+#define AMTX_FMT_NS amtx_bf16
 static inline __host__ __device__ bf16_t f32_to_bf16_rn(float f) {
     uint32_t u;
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -45,15 +45,9 @@ struct GemmArgs {
     // AMTX_T_SPLIT operands: elements between the hi and the lo plane of A / of C
     int64_t a_split = 0, c_split = 0;
 };
-bool amtx_gemm_has_roll_epilogue(const GemmArgs& g);
-int amtx_launch_gemm(const GemmArgs& g, hipStream_t stream);
-// several fp32-A / fp32-C / two-plane problems with one group count in one launch (generic 128 x 128 kernel)
+// the problems of one amtx_launch_gemm_multi
 constexpr int AMTX_GEMM_MULTI_MAX = 10;
 struct GemmMulti { GemmArgs p[AMTX_GEMM_MULTI_MAX]; int n; };
-int amtx_launch_gemm_multi(const GemmArgs* gs, int n, hipStream_t stream);
-void amtx_gemm_pack_dims(int N, int K, int* n_pad, int* k_pad);
-// host packing: W (N x K fp32 row-major, leading dim ldw) -> [planes][n_pad][k_pad] bf16
-void amtx_gemm_pack_host(const float* W, int64_t ldw, int N, int K, int planes, bf16_t* out);
 
 // ---------------------------------------------------------------- conv3x3 (C_in = 32) + folded BN + ReLU + MaxPool(1,2)
 struct ConvArgs {
@@ -78,39 +72,16 @@ struct ConvArgs {
     int64_t out_ts = 0;                                  // convg.hip only: elements between consecutive (b, t) rows of `out`; 0 = (F/2) * c_out
     int64_t in_split = 0, out_split = 0;                 // AMTX_T_SPLIT maps (conv.hip, two-plane mode): elements between the hi and the lo plane
 };
-int amtx_launch_conv3x3(const ConvArgs& c, hipStream_t stream);
 // convx.hip: the same layer (no fused first conv) on AMTX_T_SPLIT maps, two-plane weights: tiles DMA'd into a second LDS buffer under the matrix work
 int amtx_launch_convx3(const ConvArgs& c, hipStream_t stream);
 // convx.hip: conv.hip's fused first conv + 32 -> 32 layer (c_in = 1, two-plane weights) with a2 written as AMTX_T_SPLIT planes, two a1 tiles in LDS
 int amtx_launch_convx12(const ConvArgs& c, hipStream_t stream);
-size_t amtx_conv1_wfrag_elems(int c_in, int planes);
-// host packing of the fused first conv: weight (32, c_in, 3, 3) fp32 * scale[32] -> fragment order
-void amtx_conv1_pack_host(const float* w, const float* scale, int c_in, int planes, bf16_t* out);
-size_t amtx_conv3x3_wfrag_elems(int c_out, int planes);
-// host packing: weight (c_out, 32, 3, 3) fp32 * scale[c_out] -> fragment order
-void amtx_conv3x3_pack_host(const float* w, const float* scale, int c_out, int planes, bf16_t* out);
 
-// the whole stack layer1 -> layer2 -> layer3 of a one-channel, 32/32/64-channel, bf16 model in one kernel (convf.hip): `c2` as for
-// amtx_launch_conv3x3 with the fused first conv (feats, w1frag, shift1, wfrag, shift; `out` ignored), plus layer3's packed weights and
-// shift; out = [groups][B][T][F / 4][64] bf16.  amtx_conv_stack_fused_ok: the batch is large enough for its one-strip-per-CU granularity.
-bool amtx_conv_stack_fused_ok(int B, int T, int F, int groups);
-int amtx_launch_conv_stack(const ConvArgs& c2, const bf16_t* w3frag, int64_t w3_gs, const float* shift3, void* out, int64_t out_gs,
-                           int64_t out_plane, hipStream_t stream);
-
-// general channel counts (convg.hip): C_in a multiple of 16, weights staged in LDS per C_out chunk; `a.in` is [B][T][F][c_in]
-int amtx_conv3x3_gen_ntc(int c_in, int c_out);           // 0 = this pair of channel counts is not built
-size_t amtx_conv3x3_gen_wfrag_elems(int c_in, int c_out, int planes);
-void amtx_conv3x3_gen_pack_host(const float* w /*(c_out,c_in,3,3)*/, const float* scale, int c_in, int c_out, int planes, bf16_t* out);
-int amtx_launch_conv3x3_gen(const ConvArgs& c, int c_in, hipStream_t stream);
-// fused first conv of the general kernel (ConvArgs.feats / c_in / w1frag / shift1 as for conv.hip; `c_in` above = its output channels)
-// Two K orders: the weight tensor's own (ci, kh, kw) padded to whole 32-deep steps (one-channel inputs, and the two-plane x3 mode), and -- for
+// convg.hip's fused first conv has two K orders: the weight tensor's own (ci, kh, kw) padded to whole 32-deep steps (one-channel inputs, and the two-plane x3 mode), and -- for
 // 2 .. 8 input channels (round 5: in the two-plane mode too, both planes of the features staged once) -- TAP-MAJOR with the channels padded to 8 (k = 8 tap + ci, 9 taps -> 3 steps): the kernel then
 // stages its feature tile channels-last in bf16 and a lane's 8 K values of a step are ONE 16-byte LDS read (round 4; before, 16 scalar
 // gathers + 8 conversions per 16 positions made the first conv 41 % of the HCQT model's conv2 kernel).
 static inline __host__ __device__ bool amtx_conv1g_tapk(int c_in, int planes) { return (planes == 1 || planes == 2) && c_in >= 2 && c_in <= 8; }
-size_t amtx_conv1g_wfrag_elems(int c_in, int c_mid, int planes);
-void amtx_conv1g_pack_host(const float* w /*(c_mid,c_in,3,3)*/, const float* scale, int c_in, int c_mid, int planes, bf16_t* out);
-bool amtx_conv3x3_gen_can_fuse1(int c_in, int c_mid, int c_out, int planes);
 
 // ---------------------------------------------------------------- first conv (small C_in) + folded BN + ReLU, direct
 struct Conv1Args {
@@ -122,7 +93,6 @@ struct Conv1Args {
     int groups; int64_t w_gs, shift_gs, out_gs;
     int relu = 1;                                        // 0: plain convolution + shift (the training path applies BatchNorm first)
 };
-int amtx_launch_conv1(const Conv1Args& c, hipStream_t stream);
 
 // ---------------------------------------------------------------- BiLSTM recurrence (hidden = 128 per direction)
 struct LstmArgs {
@@ -134,17 +104,18 @@ struct LstmArgs {
     int hidden = 128;                                    // per direction; != 128: xproj [B][T][2][4 hidden], out [B][T][2 hidden]
     float* save = nullptr;                               // training only: [groups][B][T][2][5][128] post-activation i,f,g,o and c (4-clip kernel)
 };
-int amtx_launch_bilstm(const LstmArgs& l, hipStream_t stream);
-// training: device-side packing of fp32 W_hh into forward + transposed (backward) fragments; backward recurrence -> dL/d(xproj)
-int amtx_launch_bilstm_pack_dev(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream);
-int amtx_launch_bilstm_bwd(const float* dout, const float* save, const bf16_t* whh_t, int planes, float* dxproj, int B, int T, hipStream_t stream);
-size_t amtx_bilstm_wfrag_elems(int planes);              // per LSTM (both directions)
-void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* out);   // each (512,128)
-int amtx_launch_bilstm_pack_dev_h(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream);
-int amtx_launch_bilstm_bwd_h(const float* dout, const float* save, const bf16_t* whh_t, int hidden, int planes, float* dxproj, int B, int T, int groups,
-                             hipStream_t stream);
-size_t amtx_bilstm_wfrag_elems_h(int hidden, int planes);
-void amtx_bilstm_pack_host_h(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);   // each (4 hidden, hidden)
+
+// ---------------------------------------------------------------- the kernels and packers behind these structs, once per 16-bit operand format
+namespace amtx_bf16 {
+#include "amtx_kernels_fmt.h"
+}
+#ifdef AMTX_WITH_F16
+namespace amtx_f16 {
+#include "amtx_kernels_fmt.h"
+}
+#endif
+// unqualified names mean this translation unit's own format: bf16 everywhere but in the second build of the six files
+using namespace AMTX_FMT_NS;
 
 // ---------------------------------------------------------------- logits -> piano roll
 // out[b][k][t] = threshold < 0 ? sigmoid(x) : (sigmoid(x) < threshold ? 0 : 1), x = logits[(b*T+t)*ld + col0 + k]
@@ -161,23 +132,6 @@ int amtx_launch_cvt_pad_bf16(const float* src, int64_t ld_src, int n_src, bf16_t
 // fp32 rows -> AMTX_T_SPLIT rows (hi / lo planes `split` elements apart), columns n_src .. ld_dst zero
 int amtx_launch_cvt_split(const float* src, int64_t ld_src, int n_src, bf16_t* dst, int ld_dst, int64_t split, int64_t rows, hipStream_t stream);
 int amtx_launch_zero_cols(void* base, int64_t pitch_bytes, int width_bytes, int64_t rows, hipStream_t stream);
-
-// ---------------------------------------------------------------- device-side weight packing (pack.hip): kernels over the layouts of
-// amtx_pack_layouts.h, which the host packers loop over too, for a weight re-sync that does not leave the GPU (amtx_of_model_finalize_device)
-int amtx_pack_bn_fold_dev(const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var, int c_out, float* scale,
-                          float* shift, hipStream_t s);
-int amtx_pack_conv3x3_dev(const float* w, const float* scale, int c_out, int planes, bf16_t* out, hipStream_t s);
-int amtx_pack_conv1_dev(const float* w, const float* scale, int planes, bf16_t* out, hipStream_t s);
-int amtx_pack_conv_gen_dev(const float* w, const float* scale, int c_in, int c_out, int ntc, int planes, bf16_t* out, hipStream_t s);
-int amtx_pack_conv1g_dev(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out, hipStream_t s);
-int amtx_pack_scale_rows_dev(const float* w, const float* scale, int rows, int cols, float* out, hipStream_t s);
-int amtx_pack_linear_dev(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c, int perm_f,
-                         bf16_t* out, hipStream_t s);
-void amtx_pack_linear_host(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c, int perm_f,
-                           bf16_t* out);      // the same rows on the host (amtx_gemm_pack_host: all of them)
-int amtx_pack_head_fold_dev(const float* w_out, const float* w_fc1, const float* b_fc1, const float* b_out, int n_out, int dim_am, int kfc, int kfc_pad,
-                            int nf3, int fq, float* wfold, float* bfold, hipStream_t s);
-int amtx_pack_vec_add_dev(const float* a, const float* b, int n, float* out, hipStream_t s);
 
 // ---- cqt_dec.hip: the half-band decimator of the CQT pyramid (cqt.hip builds its Toeplitz fragments and calls it per level)
 constexpr int DEC_HALF = 150;                     // 301-tap Kaiser half-band filter

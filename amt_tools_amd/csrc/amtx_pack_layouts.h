@@ -2,7 +2,7 @@
 // `for (item = 0; item < n_items; ++item) layout(item, ..., put)`) and the device packers (pack.hip, lstm.hip: a grid-stride loop over
 // the same call), plus the BatchNorm fold and the hi / lo split they share.  A layout maps a work item to values and to positions
 // (fragment, element) or (matrix index); the writer `put` turns a position into memory and splits the value into the planes.
-// Everything here is `static inline`: six files are compiled twice with a different 16-bit format (amtx_f16_names.h), so a name with
+// Everything here is `static inline`: six files are compiled twice with a different 16-bit format (amtx_common.h: AMTX_FMT_NS), so a name with
 // external linkage would be one name with two meanings.
 #pragma once
 #include "amtx_common.h"

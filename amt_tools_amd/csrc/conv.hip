@@ -12,7 +12,6 @@
 // Eval-mode BatchNorm is folded on the host: scale into the weights, shift (+ conv bias) into `shift`.
 // Algorithmic HBM bytes per output position: 32 ch in + C_out/2 ch out (pooled), element size of the mode.
 
-#include "amtx_f16_names.h"
 #include "amtx_kernels.h"
 #include "amtx_pack_layouts.h"
 
@@ -936,6 +935,8 @@ __global__ __launch_bounds__(256) void conv1_kernel(Conv1Args a) {
 
 static_assert(CIN == AMTX_CONV_CIN, "the 3x3 fragments of amtx_pack_layouts.h are laid out for this kernel's input channels");
 
+namespace AMTX_FMT_NS {
+
 size_t amtx_conv3x3_wfrag_elems(int c_out, int planes) { return (size_t)amtx_layout_conv3x3_items(c_out) * planes; }
 
 void amtx_conv3x3_pack_host(const float* w, const float* scale, int c_out, int planes, bf16_t* out) {
@@ -988,7 +989,9 @@ int amtx_launch_conv1(const Conv1Args& a, hipStream_t stream) {
     return AMTX_OK;
 }
 
-#ifdef AMTX_CONV_TIMING
+}  // namespace AMTX_FMT_NS
+
+#if defined(AMTX_CONV_TIMING) && !defined(AMTX_F16)
 extern "C" int amtxdbg_conv_prof(unsigned long long* out32, int reset) {
     if (hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_conv_prof), 32 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (reset) {

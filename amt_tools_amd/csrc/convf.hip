@@ -34,7 +34,6 @@
 // hit 16 distinct 16-byte bank groups, and the 8 rows of a ds_write_b128 lane group 8 distinct ones), two bf16 feature slabs (68 rows x
 // 12 columns, dB-scaled while they are staged: amtx_of_forward_power) + scratch lines, layer1's Toeplitz fragments, the shift tables.
 
-#include "amtx_f16_names.h"
 #include "amtx_kernels.h"
 
 #include <algorithm>
@@ -628,6 +627,8 @@ static int convf_steps(int F) {
 // 62 output rows per strip (ninth layer1 unit) only where that saves a strip per clip, else 60
 static bool convf_halo(int T) { return (T + r3_of(true) - 1) / r3_of(true) < (T + r3_of(false) - 1) / r3_of(false); }
 
+namespace AMTX_FMT_NS {
+
 bool amtx_conv_stack_fused_ok(int B, int T, int F, int groups) {
     if (F < 4 || B <= 0 || T <= 0 || groups <= 0) return false;
     const int r3 = r3_of(convf_halo(T));
@@ -674,7 +675,9 @@ int amtx_launch_conv_stack(const ConvArgs& c2, const bf16_t* w3frag, int64_t w3_
     return AMTX_OK;
 }
 
-#ifdef AMTX_CONVF_TIMING
+}  // namespace AMTX_FMT_NS
+
+#if defined(AMTX_CONVF_TIMING) && !defined(AMTX_F16)
 extern "C" int amtxdbg_convf_prof(unsigned long long* out16, int reset) {
     if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_convf_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (reset) {

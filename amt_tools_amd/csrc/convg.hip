@@ -18,7 +18,6 @@
 //   * x3 precision: hi/lo planes of both operands, 3 MFMAs per product (as everywhere else in this library).
 // Algorithmic HBM bytes per output position: C_in in + C_out / 2 out, element size of the mode.
 
-#include "amtx_f16_names.h"
 #include "amtx_kernels.h"
 #include "amtx_pack_layouts.h"
 
@@ -775,7 +774,7 @@ __global__ __launch_bounds__(16 * FT, (FCL && CI16 == 2) ? CONVG_FCL_MINW : 1) v
 #endif
 }
 
-#ifdef AMTX_CONV_TIMING
+#if defined(AMTX_CONV_TIMING) && !defined(AMTX_F16)
 extern "C" int amtxdbg_convg_prof(unsigned long long* out8, int reset) {
     if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_convg_prof), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (reset) {
@@ -892,6 +891,8 @@ int dispatch_gen(const ConvArgs& a, hipStream_t s) {
 
 }  // namespace
 
+namespace AMTX_FMT_NS {
+
 // C_out chunk (in 16-channel tiles) the general kernel keeps in LDS at a time
 int amtx_conv3x3_gen_ntc(int c_in, int c_out) {
     if (c_in == 48 && c_out % 48 == 0) return 3;
@@ -952,3 +953,5 @@ int amtx_launch_conv3x3_gen(const ConvArgs& a, int c_in, hipStream_t stream) {
     amtx_set_error("conv3x3 (general): unsupported channel counts %d -> %d", c_in, a.c_out);
     return AMTX_ERR_UNSUPPORTED;
 }
+
+}  // namespace AMTX_FMT_NS

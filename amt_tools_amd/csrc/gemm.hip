@@ -10,7 +10,6 @@
 // * 128x128x32 block tile, 4 waves (2x2) of 64x64, register-staged double-buffered LDS with an XOR chunk
 //   swizzle so the 16 rows of a fragment read hit 16 distinct 16-byte slots.
 
-#include "amtx_f16_names.h"
 #include "amtx_kernels.h"
 
 #include <algorithm>
@@ -1297,7 +1296,7 @@ int launch(const GemmArgs& g, hipStream_t stream) {
 
 }  // namespace
 
-#ifdef AMTX_GEMM_TIMING
+#if defined(AMTX_GEMM_TIMING) && !defined(AMTX_F16)
 extern "C" void amtxdbg_gemm_prof(unsigned long long* out, int reset) {
     unsigned long long h[2][16];
     (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_gemm_prof), sizeof(h));
@@ -1305,6 +1304,8 @@ extern "C" void amtxdbg_gemm_prof(unsigned long long* out, int reset) {
     if (reset) { memset(h, 0, sizeof(h)); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_prof), h, sizeof(h)); }
 }
 #endif
+
+namespace AMTX_FMT_NS {
 
 void amtx_gemm_pack_dims(int N, int K, int* n_pad, int* k_pad) {
     *n_pad = ((N + BN - 1) / BN) * BN;
@@ -1452,3 +1453,5 @@ int amtx_launch_gemm(const GemmArgs& g, hipStream_t stream) {
     amtx_set_error("gemm: unsupported type combination");
     return AMTX_ERR_UNSUPPORTED;
 }
+
+}  // namespace AMTX_FMT_NS

@@ -19,7 +19,6 @@
 // The recurrence is a dependency chain (latency-bound, not roofline-bound): throughput comes from running
 // ceil(B/16) x 2 directions x groups blocks concurrently.
 
-#include "amtx_f16_names.h"
 #include "amtx_kernels.h"
 #include "amtx_pack_layouts.h"
 
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(LTHREADS) void bilstm4_bwd_kernel(LstmBwdArgs a) {
         for (int i = 0; i < 4; ++i) atomicAdd(&g_lstm_prof[i], lt_acc[i]);
 #endif
 }
-#ifdef AMTX_LSTM_TIMING
+#if defined(AMTX_LSTM_TIMING) && !defined(AMTX_F16)
 extern "C" int amtxdbg_lstm_prof(unsigned long long* out4, int reset) {
     if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_lstm_prof), 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (reset) {
@@ -969,6 +968,8 @@ int launch(const LstmArgs& a, hipStream_t stream) {
 
 }  // namespace
 
+namespace AMTX_FMT_NS {
+
 size_t amtx_bilstm_wfrag_elems(int planes) { return (size_t)2 * 512 * 128 * planes; }
 
 size_t amtx_bilstm_wfrag_elems_h(int hidden, int planes) { return (size_t)2 * 4 * hidden * hidden * planes; }
@@ -1068,3 +1069,5 @@ int amtx_launch_bilstm_bwd_h(const float* dout, const float* save, const bf16_t*
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
+
+}  // namespace AMTX_FMT_NS

@@ -15,7 +15,6 @@
 //   piano-roll finalize (sigmoid, threshold 0.5, transpose) x2
 
 #include "amtx_kernels.h"
-#include "amtx_kernels_f16.h"
 #include "amtx_model_common.h"
 #include "amtx_pack_layouts.h"
 
@@ -27,43 +26,20 @@ namespace {
 
 struct LinearPack { DevBuf w, b; int N = 0, K = 0, n_pad = 0, k_pad = 0, groups = 0; };     // w: [groups][planes][n_pad][k_pad], b: [groups][N]
 
-// The kernels and packers that exist once per 16-bit operand format (the files compiled twice: amtx_f16_names.h).  A model picks its
-// table when it is created and calls through it.
-struct KernelSet {
-    void (*pack_linear_host)(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c,
-                             int perm_f, bf16_t* out);
-    void (*bilstm_pack_host_h)(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);
-    void (*conv1_pack_host)(const float* w, const float* scale, int c_in, int planes, bf16_t* out);
-    void (*conv1g_pack_host)(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out);
-    void (*conv3x3_pack_host)(const float* w, const float* scale, int c_out, int planes, bf16_t* out);
-    void (*conv3x3_gen_pack_host)(const float* w, const float* scale, int c_in, int c_out, int planes, bf16_t* out);
-    int (*pack_conv1_dev)(const float* w, const float* scale, int planes, bf16_t* out, hipStream_t s);
-    int (*pack_conv1g_dev)(const float* w, const float* scale, int c_in, int c_mid, int planes, bf16_t* out, hipStream_t s);
-    int (*pack_conv3x3_dev)(const float* w, const float* scale, int c_out, int planes, bf16_t* out, hipStream_t s);
-    int (*pack_conv_gen_dev)(const float* w, const float* scale, int c_in, int c_out, int ntc, int planes, bf16_t* out, hipStream_t s);
-    int (*pack_linear_dev)(const float* W, int64_t ldw, int N, int K, int planes, int n_pad, int k_pad, int row0, int rows_owned, int perm_c,
-                           int perm_f, bf16_t* out, hipStream_t s);
-    int (*launch_bilstm_pack_dev_h)(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd,
-                                    hipStream_t stream);
-    int (*launch_conv1)(const Conv1Args& c, hipStream_t stream);
-    int (*launch_conv3x3)(const ConvArgs& c, hipStream_t stream);
-    int (*launch_conv3x3_gen)(const ConvArgs& c, int c_in, hipStream_t stream);
-    int (*launch_conv_stack)(const ConvArgs& c2, const bf16_t* w3frag, int64_t w3_gs, const float* shift3, void* out, int64_t out_gs,
-                             int64_t out_plane, hipStream_t stream);
-    int (*launch_gemm)(const GemmArgs& g, hipStream_t stream);
-    int (*launch_bilstm)(const LstmArgs& l, hipStream_t stream);
-};
-
-const KernelSet kKernelsBf16 = {
-    amtx_pack_linear_host, amtx_bilstm_pack_host_h, amtx_conv1_pack_host, amtx_conv1g_pack_host, amtx_conv3x3_pack_host, amtx_conv3x3_gen_pack_host,
-    amtx_pack_conv1_dev, amtx_pack_conv1g_dev, amtx_pack_conv3x3_dev, amtx_pack_conv_gen_dev, amtx_pack_linear_dev, amtx_launch_bilstm_pack_dev_h,
-    amtx_launch_conv1, amtx_launch_conv3x3, amtx_launch_conv3x3_gen, amtx_launch_conv_stack, amtx_launch_gemm, amtx_launch_bilstm};
+// The kernels and packers that exist once per 16-bit operand format (amtx_kernels_fmt.h): member `name` of a KernelSet is amtx_`name` of one
+// format namespace, its type the declaration's.  Struct and tables come from this one list, so a name that either namespace lacks does
+// not compile.  A model picks its table when it is created and calls through it.
+#define AMTX_FMT_KERNELS(X, ns)                                                                                                    \
+    X(ns, pack_linear_host) X(ns, bilstm_pack_host_h) X(ns, conv1_pack_host) X(ns, conv1g_pack_host) X(ns, conv3x3_pack_host)     \
+    X(ns, conv3x3_gen_pack_host) X(ns, pack_conv1_dev) X(ns, pack_conv1g_dev) X(ns, pack_conv3x3_dev) X(ns, pack_conv_gen_dev)    \
+    X(ns, pack_linear_dev) X(ns, launch_bilstm_pack_dev_h) X(ns, launch_conv1) X(ns, launch_conv3x3) X(ns, launch_conv3x3_gen)    \
+    X(ns, launch_conv_stack) X(ns, launch_gemm) X(ns, launch_bilstm)
+#define AMTX_KERNEL_FIELD(ns, name) decltype(&ns::amtx_##name) name;
+#define AMTX_KERNEL_ENTRY(ns, name) &ns::amtx_##name,
+struct KernelSet { AMTX_FMT_KERNELS(AMTX_KERNEL_FIELD, amtx_bf16) };
+const KernelSet kKernelsBf16 = {AMTX_FMT_KERNELS(AMTX_KERNEL_ENTRY, amtx_bf16)};
 #ifdef AMTX_WITH_F16
-const KernelSet kKernelsF16 = {
-    amtx_pack_linear_host_f16, amtx_bilstm_pack_host_h_f16, amtx_conv1_pack_host_f16, amtx_conv1g_pack_host_f16, amtx_conv3x3_pack_host_f16,
-    amtx_conv3x3_gen_pack_host_f16, amtx_pack_conv1_dev_f16, amtx_pack_conv1g_dev_f16, amtx_pack_conv3x3_dev_f16, amtx_pack_conv_gen_dev_f16,
-    amtx_pack_linear_dev_f16, amtx_launch_bilstm_pack_dev_h_f16, amtx_launch_conv1_f16, amtx_launch_conv3x3_f16, amtx_launch_conv3x3_gen_f16,
-    amtx_launch_conv_stack_f16, amtx_launch_gemm_f16, amtx_launch_bilstm_f16};
+const KernelSet kKernelsF16 = {AMTX_FMT_KERNELS(AMTX_KERNEL_ENTRY, amtx_f16)};
 #endif
 
 // Which convolution kernels a model runs.  make_conv_plan decides it once, when the model is created; resolve_conv adds what depends on

@@ -5,9 +5,8 @@
 // validate() inside train() (amt_tools/train.py:183-189) re-syncs the engine at every checkpoint; through the host that is a
 // device-to-host copy of every tensor, ~164 M double multiply-adds and the packing loops on one core, and the upload -- 30 - 60 ms; here
 // it is a handful of small kernels.
-// Compiled twice like the kernels that read the packed weights (amtx_f16_names.h): the 16-bit format is the build's.
+// Compiled twice like the kernels that read the packed weights (namespace AMTX_FMT_NS): the 16-bit format is the build's.
 
-#include "amtx_f16_names.h"
 #include "amtx_kernels.h"
 #include "amtx_pack_layouts.h"
 
@@ -72,6 +71,8 @@ __global__ void vec_add_kernel(const float* a, const float* b, int n, float* out
 }
 
 }  // namespace
+
+namespace AMTX_FMT_NS {
 
 int amtx_pack_bn_fold_dev(const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var, int c_out, float* scale,
                           float* shift, hipStream_t s) {
@@ -142,3 +143,5 @@ int amtx_pack_vec_add_dev(const float* a, const float* b, int n, float* out, hip
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
+
+}  // namespace AMTX_FMT_NS
