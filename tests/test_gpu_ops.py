@@ -278,6 +278,25 @@ def test_bilstm(planes, b, t):
     assert err < (3e-5 if planes == 2 else 3e-2), err
 
 
+@pytest.mark.parametrize('b,t', [(3, 50), (17, 33)])
+def test_bilstm_one_plane_fp32_io(b, t):
+    """bf16 arithmetic on fp32 xproj and output (lstm.hip: launch<1, F32, F32>), a combination the ABI exports and no model runs."""
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(b * 100 + t)
+    xproj = torch.randn(b, t, 2, 512, generator=g)
+    whh_f = (torch.rand(512, 128, generator=g) - 0.5) * 0.3
+    whh_b = (torch.rand(512, 128, generator=g) - 0.5) * 0.3
+    packed = np.zeros(L.amtx_bilstm_packed_elems(1), dtype=np.uint16)
+    _lib.check(L.amtx_bilstm_pack(_lib.ptr(whh_f.numpy()), _lib.ptr(whh_b.numpy()), 1, _lib.ptr(packed)))
+    wp = torch.from_numpy(packed.view(np.int16)).cuda()
+    x_d = xproj.cuda()
+    out = torch.full((b, t, 256), 9.0, dtype=torch.float32, device='cuda')
+    _lib.check(L.amtx_bilstm_fwd(_lib.ptr(x_d), _lib.ptr(wp), 1, F32, _lib.ptr(out), b, t, _stream()), 'amtx_bilstm_fwd')
+    ref = _lstm_ref(xproj, whh_f, whh_b)
+    err = (out.cpu() - ref).abs().max().item()
+    assert err < 3e-2, err
+
+
 def test_pianoroll_threshold_and_probabilities():
     L = _lib.lib()
     b, t, keys, ld, col0 = 3, 70, 88, 176, 88

@@ -15,10 +15,11 @@ def _rel(a, b):
     return (a - b).abs().max().item() / max(1e-12, b.abs().max().item())
 
 
-@pytest.mark.parametrize('H', [128, 256])
-@pytest.mark.parametrize('B,T,I', [(1, 1, 16), (3, 20, 64), (8, 37, 176), (5, 64, 512)])
+@pytest.mark.parametrize('B,T,I,H', [(B, T, I, H) for H in (128, 256) for B, T, I in [(1, 1, 16), (3, 20, 64), (8, 37, 176), (5, 64, 512)]] +
+                         [(B, T, I, H) for H in (384, 512) for B, T, I in [(3, 20, 64), (5, 64, 512)]])
 def test_bilstm_autograd_matches_torch_lstm(B, T, I, H):
-    """hidden 128: register-stationary kernels; hidden 256 (model_complexity 3): the streaming forward / backward kernels."""
+    """hidden 128: register-stationary kernels; hidden 256, 384, 512 (model_complexity 3, 4, 5): the streaming forward / backward kernels,
+    one instantiation per hidden size.  The recurrences alone, against tighter lines: tests/test_gpu_bilstm_train.py."""
     from amt_tools_amd.autograd import bilstm
     torch.manual_seed(B * 1000 + T)
     ref = torch.nn.LSTM(I, H, batch_first=True, bidirectional=True).double()
