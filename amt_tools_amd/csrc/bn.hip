@@ -2,7 +2,10 @@
 // the acoustic model (amt_tools/models/onsetsframes.py:375-416, driven by amt_tools/train.py:126-141 through autograd).
 // On ROCm the stock path is MIOpen BatchNorm + separate ReLU / max-pool elementwise kernels and their backward kernels over fp32
 // maps (5 of the 14 ms of a training step at 8 clips x 625 frames); here each direction is two passes over the conv output:
-//   forward : (1) per-channel sum / sum of squares (fp32 per thread, fp64 across partials: deterministic, no atomics)
+//   forward : (1) per-channel mean / variance in one read: every thread sums x (fp64) and (x - k)^2 about a pivot k of its own (fp32), the
+//                 threads' and blocks' (count, sum, M2) are merged in fp64 by the pairwise formula (deterministic, no atomics).  Not E[x^2] - E[x]^2
+//                 over raw values: that loses the variance once a channel's |mean| is large against its spread (a bias-dominated or
+//                 dead filter), and torch / MIOpen do not lose it there
 //             (2) y = max over the pooling pair of relu(x * scale + shift), running statistics updated like nn.BatchNorm2d
 //   backward: (1) dz = dy routed to the pair's winner where it is positive; per-channel sum(dz), sum(dz * xhat)
 //             (2) dx = gamma * invstd * (dz - mean(dz) - xhat * mean(dz * xhat))
@@ -17,6 +20,7 @@ namespace {
 
 constexpr int BN_THREADS = 256;
 constexpr int BN_MAX_PARTIALS = 1024;
+static_assert(BN_MAX_PARTIALS % 64 == 0, "bn_stats_final_kernel: a whole number of partials per lane");
 
 struct BnArgs {
     const float* x; int64_t rows; int F, C;       // x [rows][F][C]
@@ -29,49 +33,119 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-// ---- forward pass 1: partial[blk][2][C] = sum, sum of squares over the block's positions
-__global__ __launch_bounds__(BN_THREADS) void bn_stats_partial_kernel(const float* __restrict__ x, int64_t P, int C, float* __restrict__ partial) {
-    extern __shared__ float red[];                // [2][BN_THREADS][4]
+// ---- forward pass 1: partial [blk] { double s[C], m2[C]; } = sum(x) and sum((x - mean_blk)^2) over the block's positions.  Every thread
+// sums x in fp64 and (x - k)^2 in fp32 about a pivot k of its own, its first element: the squares are of the size of the channel's spread,
+// not of its offset, and no load waits for another thread.  The threads' sums are then moved to one pivot per block and channel (the
+// first position row's) and reduced in fp64.
+__global__ __launch_bounds__(BN_THREADS) void bn_stats_partial_kernel(const float* __restrict__ x, int64_t P, int C, double* __restrict__ partial) {
+    extern __shared__ double red64[];             // double s[BN_THREADS][4], q[BN_THREADS][4]; float4 K[BN_THREADS]; int n[BN_THREADS]
+    double* rs = red64;
+    double* rq = red64 + 4 * BN_THREADS;
+    float4* rk = reinterpret_cast<float4*>(red64 + 8 * BN_THREADS);
+    int* rn = reinterpret_cast<int*>(rk + BN_THREADS);
     const int c4n = C >> 2;                       // float4 groups per position
     const int tid = threadIdx.x;
     const int cg = tid % c4n, pr = tid / c4n, prn = BN_THREADS / c4n;
-    float4 s = make_float4(0, 0, 0, 0), q = make_float4(0, 0, 0, 0);
-    if (pr < prn)
-        for (int64_t p = (int64_t)blockIdx.x * prn + pr; p < P; p += (int64_t)gridDim.x * prn) {
-            const float4 v = *reinterpret_cast<const float4*>(x + p * C + 4 * cg);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            q.x = fmaf(v.x, v.x, q.x); q.y = fmaf(v.y, v.y, q.y); q.z = fmaf(v.z, v.z, q.z); q.w = fmaf(v.w, v.w, q.w);
+    const int64_t p0 = (int64_t)blockIdx.x * prn + pr;
+    float k[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    int nt = 0;
+    auto add = [&](const float4& v) {
+        const float v_[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float d = v_[j] - k[j];
+            s[j] += (double)v_[j];
+            q[j] = fmaf(d, d, q[j]);
         }
-    float4* rs = reinterpret_cast<float4*>(red);
-    rs[tid] = s; rs[BN_THREADS + tid] = q;
+    };
+    if (pr < prn && p0 < P) {
+        const int64_t st = (int64_t)gridDim.x * prn;
+        const float* xp = x + 4 * cg;
+        const float4 v = *reinterpret_cast<const float4*>(xp + p0 * C);
+        k[0] = v.x; k[1] = v.y; k[2] = v.z; k[3] = v.w;
+        int64_t p = p0;
+        for (; p + 3 * st < P; p += 4 * st) {     // four independent loads in flight: the pass is bound by their latency
+            const float4 v0 = *reinterpret_cast<const float4*>(xp + p * C), v1 = *reinterpret_cast<const float4*>(xp + (p + st) * C);
+            const float4 v2 = *reinterpret_cast<const float4*>(xp + (p + 2 * st) * C), v3 = *reinterpret_cast<const float4*>(xp + (p + 3 * st) * C);
+            add(v0); add(v1); add(v2); add(v3);
+            nt += 4;
+        }
+        for (; p < P; p += st) {
+            add(*reinterpret_cast<const float4*>(xp + p * C));
+            ++nt;
+        }
+    }
+    if (tid < c4n) rk[tid] = make_float4(k[0], k[1], k[2], k[3]);    // position row 0: blockIdx.x * prn < P by the launch, always there
+    __syncthreads();
+    const float4 K4 = rk[cg];
+    const float K[4] = {K4.x, K4.y, K4.z, K4.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                 // sum((x - K)^2) = q + e (2 sum(x - k) + n e), e = k - K; a thread without positions adds 0
+        const double e = (double)k[j] - (double)K[j], sk = s[j] - (double)nt * (double)k[j];
+        rs[4 * tid + j] = s[j];
+        rq[4 * tid + j] = (double)q[j] + e * (2.0 * sk + (double)nt * e);
+    }
+    rn[tid] = nt;
     __syncthreads();
     if (tid < c4n) {                              // fixed order: deterministic
-        float4 a = make_float4(0, 0, 0, 0), b = make_float4(0, 0, 0, 0);
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+        int nb = 0;
         for (int r = 0; r < prn; ++r) {
-            const float4 u = rs[r * c4n + tid], w = rs[BN_THREADS + r * c4n + tid];
-            a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
-            b.x += w.x; b.y += w.y; b.z += w.z; b.w += w.w;
+            const double* u = rs + 4 * (r * c4n + tid);
+            const double* w = rq + 4 * (r * c4n + tid);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { a[j] += u[j]; b[j] += w[j]; }
+            nb += rn[r * c4n + tid];
         }
-        float* out = partial + (int64_t)blockIdx.x * 2 * C;
-        *reinterpret_cast<float4*>(out + 4 * tid) = a;
-        *reinterpret_cast<float4*>(out + C + 4 * tid) = b;
+        double* out = partial + (int64_t)blockIdx.x * 2 * C + 4 * tid;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double sk = a[j] - (double)nb * (double)K[j], m2 = b[j] - sk * sk / (double)nb;
+            out[j] = a[j];
+            out[C + j] = m2 > 0.0 ? m2 : 0.0;
+        }
     }
 }
 
 // ---- forward pass 1b: mean / invstd, fused affine (scale, shift), running statistics (momentum < 0: cumulative average is the caller's job)
-__global__ void bn_stats_final_kernel(const float* __restrict__ partial, int nblk, int C, double n, const float* __restrict__ gamma,
+__global__ void bn_stats_final_kernel(const double* __restrict__ partial, int nblk, int C, int64_t P, int prn, const float* __restrict__ gamma,
                                       const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
                                       float* __restrict__ running_var, float* __restrict__ stats /*[4][C]: mean, invstd, gamma, beta*/) {
     // one wave per channel: lanes stride over the partials, fixed-order butterfly in fp64 (a single thread walking 1024 partials
-    // was 0.3 ms of pure load latency per layer)
+    // was 0.3 ms of pure load latency per layer).  The blocks' n_b, mean_b = s_b / n_b and M2_b are merged by the pairwise formula
+    // M2 = sum(M2_b) + sum(n_b (mean_b - mean)^2) in fp64; each lane keeps its s_b in registers between the two sums.
+    // n_b: the partial kernel deals chunks of prn positions to the blocks in turn; only the last chunk can be short.
+    constexpr int PER_LANE = BN_MAX_PARTIALS / 64;
     const int c = blockIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 64) { s += partial[(int64_t)b * 2 * C + c]; q += partial[(int64_t)b * 2 * C + C + c]; }
-    s = wave_sum_f64(s); q = wave_sum_f64(q);
+    const double n = (double)P;
+    const int64_t chunks = (P + prn - 1) / prn;
+    const int64_t cnt = chunks / nblk;            // >= 1: the launch has at most one block per chunk
+    const int rem = (int)(chunks % nblk), last_blk = (int)((chunks - 1) % nblk);
+    const double n_lo = (double)(cnt * prn), n_hi = (double)((cnt + 1) * prn);
+    const double n_last = (last_blk < rem ? n_hi : n_lo) - (double)(chunks * prn - P);
+    const double i_lo = 1.0 / n_lo, i_hi = 1.0 / n_hi, i_last = 1.0 / n_last;
+    double sb[PER_LANE];
+    double sm = 0.0, m2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) {
+        const int b = threadIdx.x + 64 * i;
+        sb[i] = b < nblk ? partial[(int64_t)b * 2 * C + c] : 0.0;
+        m2 += b < nblk ? partial[(int64_t)b * 2 * C + C + c] : 0.0;
+        sm += sb[i];
+    }
+    sm = wave_sum_f64(sm);                        // the butterfly leaves the same sum in every lane
+    const double mean = sm / n;
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) {
+        const int b = threadIdx.x + 64 * i;
+        const double nb = b == last_blk ? n_last : b < rem ? n_hi : n_lo, ib = b == last_blk ? i_last : b < rem ? i_hi : i_lo;
+        const double d = sb[i] * ib - mean;
+        m2 = b < nblk ? fma(nb * d, d, m2) : m2;
+    }
+    m2 = wave_sum_f64(m2);
     if (threadIdx.x != 0) return;
-    const double mean = s / n;
-    double var = q / n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
+    const double var = m2 / n;
     const double invstd = 1.0 / sqrt(var + (double)eps);
     const double g = gamma ? (double)gamma[c] : 1.0, bt = beta ? (double)beta[c] : 0.0;
     stats[c] = (float)mean;
@@ -238,8 +312,9 @@ int nblocks_for(int64_t items, int per_block) {
 
 }  // namespace
 
-// workspace (floats): partial sums [BN_MAX_PARTIALS][2][C] + per-channel constants [2][C]
-extern "C" size_t amtx_bn_train_workspace_bytes(int channels) { return ((size_t)BN_MAX_PARTIALS * 2 + 2) * channels * sizeof(float); }
+// workspace: forward partials [BN_MAX_PARTIALS][2][C] doubles; backward partial sums [BN_MAX_PARTIALS][2][C] + per-channel constants
+// [2][C] (floats) in the same bytes
+extern "C" size_t amtx_bn_train_workspace_bytes(int channels) { return (size_t)BN_MAX_PARTIALS * 4 * channels * sizeof(float); }
 
 extern "C" int amtx_bn_relu_pool_train_fwd(const float* x, int64_t rows, int num_bins, int channels, int pool, const float* gamma,
                                            const float* beta, float eps, float momentum, float* running_mean, float* running_var,
@@ -250,11 +325,10 @@ extern "C" int amtx_bn_relu_pool_train_fwd(const float* x, int64_t rows, int num
     hipStream_t s = (hipStream_t)stream_;
     const int C = channels, prn = BN_THREADS / (C / 4);
     const int64_t P = rows * num_bins;
-    float* partial = (float*)workspace;
     const int nblk = nblocks_for(P, prn * 16);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nblk), dim3(BN_THREADS), 2 * BN_THREADS * sizeof(float4), s, x, P, C, partial);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nblk), dim3(BN_THREADS), BN_THREADS * (8 * sizeof(double) + sizeof(float4) + sizeof(int)), s, x, P, C, (double*)workspace);
     AMTX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, s, partial, nblk, C, (double)P, gamma, beta, eps, momentum,
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, s, (const double*)workspace, nblk, C, P, prn, gamma, beta, eps, momentum,
                        running_mean, running_var, stats);
     AMTX_CHECK_LAUNCH();
     BnArgs a{x, rows, num_bins, C, pool};
