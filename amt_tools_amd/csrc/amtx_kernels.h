@@ -94,15 +94,15 @@ struct Conv1Args {
     int relu = 1;                                        // 0: plain convolution + shift (the training path applies BatchNorm first)
 };
 
-// ---------------------------------------------------------------- BiLSTM recurrence (hidden = 128 per direction)
+// ---------------------------------------------------------------- BiLSTM recurrence (`hidden` = 128, 256, 384 or 512 per direction)
 struct LstmArgs {
-    const void* xproj; int x_type;                       // [B][T][2][512]: W_ih x + b_ih + b_hh, gate order i,f,g,o
+    const void* xproj; int x_type;                       // [B][T][2][4 hidden]: W_ih x + b_ih + b_hh, gate order i,f,g,o
     const bf16_t* whh; int planes;                       // packed fragments [dir][...], see lstm.hip
-    void* out; int out_type;                             // [B][T][256] = h_fwd | h_bwd
+    void* out; int out_type;                             // [B][T][2 hidden] = h_fwd | h_bwd
     int B, T;
-    int groups; int64_t x_gs, w_gs, out_gs;
-    int hidden = 128;                                    // per direction; != 128: xproj [B][T][2][4 hidden], out [B][T][2 hidden]
-    float* save = nullptr;                               // training only: [groups][B][T][2][5][128] post-activation i,f,g,o and c (4-clip kernel)
+    int groups; int64_t x_gs, w_gs, out_gs;              // independent LSTMs of the same (B, T) and the elements between their xproj / whh / out
+    int hidden = 128;                                    // per direction
+    float* save = nullptr;                               // training only: [groups][B][T][2][5][hidden] post-activation i,f,g,o and c
 };
 
 // ---------------------------------------------------------------- the kernels and packers behind these structs, once per 16-bit operand format

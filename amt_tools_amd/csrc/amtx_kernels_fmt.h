@@ -42,18 +42,15 @@ size_t amtx_conv1g_wfrag_elems(int c_in, int c_mid, int planes);
 void amtx_conv1g_pack_host(const float* w /*(c_mid,c_in,3,3)*/, const float* scale, int c_in, int c_mid, int planes, bf16_t* out);
 bool amtx_conv3x3_gen_can_fuse1(int c_in, int c_mid, int c_out, int planes);
 
-// ---------------------------------------------------------------- lstm.hip
+// ---------------------------------------------------------------- lstm.hip: hidden = 128, 256, 384 or 512 per direction
 int amtx_launch_bilstm(const LstmArgs& l, hipStream_t stream);
-// training: device-side packing of fp32 W_hh into forward + transposed (backward) fragments; backward recurrence -> dL/d(xproj)
-int amtx_launch_bilstm_pack_dev(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream);
-int amtx_launch_bilstm_bwd(const float* dout, const float* save, const bf16_t* whh_t, int planes, float* dxproj, int B, int T, hipStream_t stream);
-size_t amtx_bilstm_wfrag_elems(int planes);              // per LSTM (both directions)
-void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* out);   // each (512,128)
-int amtx_launch_bilstm_pack_dev_h(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream);
-int amtx_launch_bilstm_bwd_h(const float* dout, const float* save, const bf16_t* whh_t, int hidden, int planes, float* dxproj, int B, int T, int groups,
-                             hipStream_t stream);
-size_t amtx_bilstm_wfrag_elems_h(int hidden, int planes);
-void amtx_bilstm_pack_host_h(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);   // each (4 hidden, hidden)
+size_t amtx_bilstm_wfrag_elems(int hidden, int planes);  // per LSTM (both directions)
+void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);   // each (4 hidden, hidden)
+// training: device-side packing of fp32 W_hh into forward + transposed (backward) fragments; backward recurrence -> dL/d(xproj) of
+// `groups` independent LSTMs of the same (B, T) (hidden 256 / 384 / 512: two planes only)
+int amtx_launch_bilstm_pack_dev(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream);
+int amtx_launch_bilstm_bwd(const float* dout, const float* save, const bf16_t* whh_t, int hidden, int planes, float* dxproj, int B, int T, int groups,
+                           hipStream_t stream);
 
 // ---------------------------------------------------------------- pack.hip: device-side weight packing, kernels over the layouts of
 // amtx_pack_layouts.h, which the host packers loop over too, for a weight re-sync that does not leave the GPU (amtx_of_model_finalize_device)

@@ -1,4 +1,4 @@
-// Persistent BiLSTM recurrence for gfx950 (hidden = 128 per direction).
+// Persistent BiLSTM recurrence for gfx950 (hidden = 128 per direction: W_hh stationary in registers; 256 / 384 / 512: streamed, further down).
 //
 // Replaces the time loop of nn.LSTM(batch_first, bidirectional) inside LanguageModel.forward
 // (amt_tools/models/onsetsframes.py:466-575; the reference's 512-frame eval chunking is a numerical
@@ -44,6 +44,74 @@ __device__ __forceinline__ float tanh_f(float x) {
     if (FAST) return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * x)), -1.0f);
     return tanhf(x);
 }
+
+// ---- what the kernels of this file share ----
+
+// One cell, forward: the post-activation gates from the four pre-activations, then c <- f c + i g in place and h = o tanh(c).  Two helpers, so
+// that a kernel with several cells per lane can run all activations first (lstm4_step).
+struct Gates { float i, f, g, o; };
+template <bool FAST>
+__device__ __forceinline__ Gates lstm_gates(float ai, float af, float ag, float ao) {
+    return {sigmoid_f<FAST>(ai), sigmoid_f<FAST>(af), tanh_f<FAST>(ag), sigmoid_f<FAST>(ao)};
+}
+template <bool FAST>
+__device__ __forceinline__ float lstm_cell(const Gates& z, float& c) {
+    c = z.f * c + z.i * z.g;
+    return z.o * tanh_f<FAST>(c);
+}
+
+// Four consecutive fp32 values -> the 16-bit operand planes of an LDS tile: one plane rounds, two planes split into hi + lo (lo = 0 with one
+// plane); store16 writes them at byte `off` of each plane, the planes `plane_bytes` apart.
+template <int NS>
+__device__ __forceinline__ void split16(const float (&v)[4], uint2& hi, uint2& lo) {
+    lo = make_uint2(0, 0);
+    if (NS == 2) {
+        split_bf16x2(v[0], v[1], hi.x, lo.x);
+        split_bf16x2(v[2], v[3], hi.y, lo.y);
+    } else {
+        hi = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+    }
+}
+template <int NS>
+__device__ __forceinline__ void store16(char* tile, int plane_bytes, int off, uint2 hi, uint2 lo) {
+    *reinterpret_cast<uint2*>(tile + off) = hi;
+    if (NS == 2) *reinterpret_cast<uint2*>(tile + plane_bytes + off) = lo;
+}
+
+// Step s of a direction's walk over T frames -> frame.  Steps past the end repeat the last one: the kernels run them unconditionally (loads
+// stay in bounds, stores are masked) instead of branching around them.  (T by reference, as the lambdas this replaces captured it: by value
+// hipcc shares T - 1 with the clamp and emits another, equivalent subtraction, which reschedules every kernel around it.)
+__device__ __forceinline__ int step_frame(int s, const int& T, const int& reverse) {
+    s = s < T ? s : T - 1;
+    return reverse == 0 ? s : T - 1 - s;
+}
+
+// W_hh fragment groups streamed from L2 (both streaming kernels).  A group is SGK k-steps x NS planes of 1-KiB fragments, a wave's groups of one
+// step consecutive in memory.  Wave-uniform base (scalar registers) + one per-lane byte offset: every fragment load is `global_load saddr +
+// voffset`, without a 64-bit address pair per load held in vector registers across the loop.
+template <int SGK, int NS>
+struct FragStream {
+    typedef const __attribute__((address_space(1))) char* gchar_p;      // explicitly global: the asm below must not turn the loads into flat ones
+    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+    typedef __attribute__((address_space(1))) u32x4_t gu4_t;
+    const char* base;
+    gchar_p wb;
+    unsigned wlane;
+    __device__ __forceinline__ FragStream(const char* base_, int lane) : base(base_), wb((gchar_p)base_), wlane(lane * 16) {}
+    // once per step.  Opaque to the optimiser: otherwise it hoists one 64-bit vector address per fragment load out of the loop (128 VGPRs)
+    __device__ __forceinline__ void rewind() {
+        wb = (gchar_p)base;
+        asm volatile("" : "+s"(wb));
+    }
+    __device__ __forceinline__ uint4 load(int gi, int k, int p) const {
+        return __builtin_bit_cast(uint4, *reinterpret_cast<const gu4_t*>(wb + ((gi * SGK + k) * NS + p) * 1024 + wlane));
+    }
+    __device__ __forceinline__ void load_group(int gi, uint4 (&dst)[SGK][NS]) const {
+        static_for<0, SGK>([&](auto kc) {
+            static_for<0, NS>([&](auto pc) { dst[decltype(kc)::value][decltype(pc)::value] = load(gi, decltype(kc)::value, decltype(pc)::value); });
+        });
+    }
+};
 
 // raw (still packed) x-projection registers of one step: converting bf16 -> fp32 right after the load would
 // put the wait for the prefetch at the load instead of at the first use one step later.
@@ -114,23 +182,11 @@ __device__ __forceinline__ void lstm_step(char* smem, int cur, const uint4 (&wf)
         float h[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float ig = sigmoid_f<FAST>(acc[ub][0][r]);
-            const float fg = sigmoid_f<FAST>(acc[ub][1][r]);
-            const float gg = tanh_f<FAST>(acc[ub][2][r]);
-            const float og = sigmoid_f<FAST>(acc[ub][3][r]);
-            c[ub][r] = fg * c[ub][r] + ig * gg;
-            h[r] = og * tanh_f<FAST>(c[ub][r]);
+            h[r] = lstm_cell<FAST>(lstm_gates<FAST>(acc[ub][0][r], acc[ub][1][r], acc[ub][2][r], acc[ub][3][r]), c[ub][r]);
         }
-        uint2 hiw, low = make_uint2(0, 0);
-        if (NS == 2) {
-            split_bf16x2(h[0], h[1], hiw.x, low.x);
-            split_bf16x2(h[2], h[3], hiw.y, low.y);
-        } else {
-            hiw = make_uint2(pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3]));
-        }
-        const int hoff = (clip * HP + 16 * UB * wave + 16 * ub + 4 * g) * 2;
-        *reinterpret_cast<uint2*>(hn + hoff) = hiw;
-        if (NS == 2) *reinterpret_cast<uint2*>(hn + HBUF_BYTES + hoff) = low;
+        uint2 hiw, low;
+        split16<NS>(h, hiw, low);
+        store16<NS>(hn, HBUF_BYTES, (clip * HP + 16 * UB * wave + 16 * ub + 4 * g) * 2, hiw, low);
         if (clip_ok) {
             const int64_t e = (int64_t)t * 256 + 16 * ub;
             if (OUT_TYPE == AMTX_T_BF16) *reinterpret_cast<uint2*>(obase + e * 2) = hiw;
@@ -183,7 +239,7 @@ __global__ __launch_bounds__(LTHREADS) void bilstm_kernel(LstmArgs a) {
     // one step, so a one-step lookahead stalls every step).  Four steps per iteration so the ring slots are named
     // registers (no copies, no dynamic indexing).
     typename XRaw<X_TYPE>::type x0[UB][4], x1[UB][4], x2[UB][4], x3[UB][4];
-    auto tidx = [&](int s) { s = s < T ? s : T - 1; return (int64_t)(dir == 0 ? s : T - 1 - s); };
+    auto tidx = [&](int s) { return (int64_t)step_frame(s, T, dir); };
     load_x<X_TYPE>(xbase, tidx(0) * 1024, x0);
     load_x<X_TYPE>(xbase, tidx(1) * 1024, x1);
     load_x<X_TYPE>(xbase, tidx(2) * 1024, x2);
@@ -269,19 +325,14 @@ __device__ __forceinline__ void lstm4_step(char* smem, int cur, const uint4 (&wf
     // The cells of a lane are independent chains of ~12 dependent operations (five of them exp / rcp pairs): all arithmetic first, the
     // (per-lane predicated) stores behind it -- with a predicated store between the cells hipcc runs the chains one after the other
     // (a branch around each store), which is most of what a second clip per lane costs.
-    float ig[NC], fg[NC], gg[NC], og[NC], h[NC];
+    Gates z[NC];
+    float h[NC];
     uint32_t hiw[NC], low[NC];
 #pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        ig[j] = sigmoid_f<FAST>(acc[0][RSTEP * j]);
-        fg[j] = sigmoid_f<FAST>(acc[1][RSTEP * j]);
-        gg[j] = tanh_f<FAST>(acc[2][RSTEP * j]);
-        og[j] = sigmoid_f<FAST>(acc[3][RSTEP * j]);
-    }
+    for (int j = 0; j < NC; ++j) z[j] = lstm_gates<FAST>(acc[0][RSTEP * j], acc[1][RSTEP * j], acc[2][RSTEP * j], acc[3][RSTEP * j]);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-        c[j] = fg[j] * c[j] + ig[j] * gg[j];
-        h[j] = og[j] * tanh_f<FAST>(c[j]);
+        h[j] = lstm_cell<FAST>(z[j], c[j]);
         low[j] = 0;
         if (NS == 2) split_bf16x2(h[j], 0.f, hiw[j], low[j]);
         else hiw[j] = pack_bf16x2(h[j], 0.f);
@@ -295,7 +346,7 @@ __device__ __forceinline__ void lstm4_step(char* smem, int cur, const uint4 (&wf
     for (int j = 0; j < NC; ++j) {
         if (NC == 1 && save && clip_ok[j]) {     // training: post-activation gates and the new cell state, [b][t][dir][5][128] (save points at [b][0][dir][0][unit])
             float* sv = save + (int64_t)t * (2 * 5 * H);
-            sv[0] = ig[j]; sv[H] = fg[j]; sv[2 * H] = gg[j]; sv[3 * H] = og[j]; sv[4 * H] = c[j];
+            sv[0] = z[j].i; sv[H] = z[j].f; sv[2 * H] = z[j].g; sv[3 * H] = z[j].o; sv[4 * H] = c[j];
         }
         if (clip_ok[j]) {
             if (OUT_TYPE == AMTX_T_BF16) *reinterpret_cast<unsigned short*>(obase[j] + (int64_t)t * 256 * 2) = (unsigned short)hiw[j];
@@ -347,7 +398,7 @@ __global__ __launch_bounds__(LTHREADS) void bilstm4_kernel(LstmArgs a) {
     }
 
     typename XScalar<X_TYPE>::type x0[NC][4], x1[NC][4], x2[NC][4], x3[NC][4];
-    auto tidx = [&](int s) { s = s < T ? s : T - 1; return (int64_t)(dir == 0 ? s : T - 1 - s); };
+    auto tidx = [&](int s) { return (int64_t)step_frame(s, T, dir); };
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
         load_x4<X_TYPE>(xbase[j], tidx(0) * 1024, x0[j]);
@@ -430,7 +481,7 @@ __global__ __launch_bounds__(LTHREADS) void bilstm4_bwd_kernel(LstmBwdArgs a) {
     // the forward pass of direction 0 ran t = 0..T-1, of direction 1 t = T-1..0: walk them backwards.  Step s reads the saved
     // values of frame t(s) and the cell state of the step BEFORE it in forward order, which is frame t(s+1): the seven values of
     // step s+1 are requested (unconditionally, clamped) before step s's mat-vec, so their latency is off the dependency chain.
-    auto frame = [&](int s_) { s_ = s_ < T ? s_ : T - 1; return dir == 0 ? T - 1 - s_ : s_; };
+    auto frame = [&](int s) { return step_frame(s, T, dir == 0); };
     float n_i, n_f, n_g, n_o, n_c, n_do;
     {
         const float* sv = sv0 + (int64_t)frame(0) * (2 * 5 * H);
@@ -575,13 +626,10 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
 
     for (int i = tid; i < 2 * NS * HBG / 16; i += 512) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0, 0, 0, 0);
 
-    // fragment (u, q, ks, p) of direction dir: uint4 index ((((dir * NU + u) * 4 + q) * KSN + ks) * NS + p) * 64 + lane;
-    // a wave's groups of one step are consecutive in memory
-    // wave-uniform base (scalar registers) + one per-lane byte offset: every fragment load is `global_load saddr + voffset`, without
-    // a 64-bit address pair per load held in vector registers across the loop
+    // fragment (u, q, ks, p) of direction dir: uint4 index ((((dir * NU + u) * 4 + q) * KSN + ks) * NS + p) * 64 + lane
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const char* wbase = reinterpret_cast<const char*>(a.whh + (int64_t)grp * a.w_gs) + ((int64_t)(dir * NU + wave_u * UPW) * 4 * KSN * NS) * 1024;
-    const unsigned wlane = lane * 16;
+    FragStream<SGK, NS> ws(wbase, lane);
     const char* xbase = reinterpret_cast<const char*>(a.xproj) +
                         ((int64_t)grp * a.x_gs + (int64_t)(clip_ok ? b : 0) * T * 8 * HH + dir * 4 * HH + 16 * UPW * wave + 4 * g) * XES;
     char* obase = reinterpret_cast<char*>(a.out) +
@@ -594,7 +642,7 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
         for (int r = 0; r < 4; ++r) c[ub][r] = 0.f;
 
     typedef typename XRaw<X_TYPE>::type xraw_t;
-    auto tidx = [&](int s) { s = s < T ? s : T - 1; return (int64_t)(dir == 0 ? s : T - 1 - s); };
+    auto tidx = [&](int s) { return (int64_t)step_frame(s, T, dir); };
     auto load_xrow = [&](int64_t t, xraw_t (&dst)[UPW][4]) {
 #pragma unroll
         for (int ub = 0; ub < UPW; ++ub)
@@ -606,13 +654,6 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
     uint4 wpin[PIN ? NPIN : 1][SGK][NS];          // register-resident groups
     // group gi -> kind (0 registers, 1 LDS, 2 streamed) and index within its kind: see kind_of / sidx_of / gi_of_sidx below
     char* wlds = smem + 2 * NS * HBG + wave * (NPIN * SGK * NS * 1024);      // this wave's LDS-resident groups
-    typedef const __attribute__((address_space(1))) char* gchar_p;      // explicitly global: the asm below must not turn the loads into flat ones
-    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-    typedef __attribute__((address_space(1))) u32x4_t gu4_t;
-    gchar_p wb = (gchar_p)wbase;
-    auto load_frag = [&](int gi, int k, int p) {
-        return __builtin_bit_cast(uint4, *reinterpret_cast<const gu4_t*>(wb + ((gi * SGK + k) * NS + p) * 1024 + wlane));
-    };
     if constexpr (PIN || PINL) {
         static_for<0, NG>([&](auto ic) {
             constexpr int gi = decltype(ic)::value;
@@ -623,9 +664,9 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
                     constexpr int k = decltype(kc)::value;
                     static_for<0, NS>([&](auto pc) {
                         constexpr int p = decltype(pc)::value;
-                        const uint4 v = load_frag(gi, k, p);
+                        const uint4 v = ws.load(gi, k, p);
                         if constexpr (kind == 0) wpin[pidx][k][p] = v;
-                        else *reinterpret_cast<uint4*>(wlds + ((pidx * SGK + k) * NS + p) * 1024 + wlane) = v;
+                        else *reinterpret_cast<uint4*>(wlds + ((pidx * SGK + k) * NS + p) * 1024 + ws.wlane) = v;
                     });
                 });
             }
@@ -637,17 +678,13 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
     static_for<0, RS - 1>([&](auto sc) {
         constexpr int si = decltype(sc)::value;
         constexpr int gi = PIN ? (si >> 1) * 4 + 2 + (si & 1) : (PINL ? si + si / (PER - 1) + 1 : si);
-        static_for<0, SGK>([&](auto kc) {
-            static_for<0, NS>([&](auto pc) { w[si % RS][decltype(kc)::value][decltype(pc)::value] = load_frag(gi, decltype(kc)::value, decltype(pc)::value); });
-        });
+        ws.load_group(gi, w[si % RS]);
     });
     __syncthreads();
 
     int cur = 0;
     for (int s = 0; s < T; ++s) {
-        // opaque to the optimiser: otherwise it hoists one 64-bit vector address per fragment load out of the loop (128 VGPRs)
-        wb = (gchar_p)wbase;
-        asm volatile("" : "+s"(wb));
+        ws.rewind();
         const char* hb = smem + cur * NS * HBG;
         // the h fragments of a step: in registers while they are at most 64 (HH = 384 in two planes would be 96: read at their use)
         constexpr bool HF_REG = KSN * NS <= 16;
@@ -677,9 +714,7 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
                 // behind the last RS - 1 streamed groups: the first ones of the next step
                 constexpr int sn = (si + RS - 1) % NSG;
                 constexpr int gn = PIN ? (sn >> 1) * 4 + 2 + (sn & 1) : (PINL ? sn + sn / (PER - 1) + 1 : sn);
-                static_for<0, SGK>([&](auto kc) {
-                    static_for<0, NS>([&](auto pc) { w[sn % RS][decltype(kc)::value][decltype(pc)::value] = load_frag(gn, decltype(kc)::value, decltype(pc)::value); });
-                });
+                ws.load_group(gn, w[sn % RS]);
             }
             f32x4_t d = acc[ub][q];
             static_for<0, SGK>([&](auto kc) {
@@ -689,7 +724,7 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
                 if constexpr (kind == 0) {
                     w0 = wpin[pidx][k][0]; w1 = wpin[pidx][k][NS - 1];
                 } else if constexpr (kind == 1) {
-                    w0 = *reinterpret_cast<const uint4*>(wlds + ((pidx * SGK + k) * NS + 0) * 1024 + wlane);
+                    w0 = *reinterpret_cast<const uint4*>(wlds + ((pidx * SGK + k) * NS + 0) * 1024 + ws.wlane);
                     w1 = w0;
                 } else {
                     w0 = w[si % RS][k][0]; w1 = w[si % RS][k][NS - 1];
@@ -718,13 +753,9 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
             float h[4], sv[4][4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float ig = sigmoid_f<FAST>(acc[ub][0][r]);
-                const float fg = sigmoid_f<FAST>(acc[ub][1][r]);
-                const float gg = tanh_f<FAST>(acc[ub][2][r]);
-                const float og = sigmoid_f<FAST>(acc[ub][3][r]);
-                c[ub][r] = fg * c[ub][r] + ig * gg;
-                h[r] = og * tanh_f<FAST>(c[ub][r]);
-                sv[0][r] = ig; sv[1][r] = fg; sv[2][r] = gg; sv[3][r] = og;
+                const Gates z = lstm_gates<FAST>(acc[ub][0][r], acc[ub][1][r], acc[ub][2][r], acc[ub][3][r]);
+                h[r] = lstm_cell<FAST>(z, c[ub][r]);
+                sv[0][r] = z.i; sv[1][r] = z.f; sv[2][r] = z.g; sv[3][r] = z.o;
             }
             if (a.save && clip_ok) {                          // training: post-activation gates and the cell state, [B][T][2][5][HH]
                 float* sp = a.save + ((((int64_t)grp * a.B + b) * T + t) * 2 + dir) * (5 * HH) + 16 * UPW * wave + 16 * ub + 4 * g;
@@ -732,16 +763,9 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
                 for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(sp + q * HH) = make_float4(sv[q][0], sv[q][1], sv[q][2], sv[q][3]);
                 *reinterpret_cast<float4*>(sp + 4 * HH) = make_float4(c[ub][0], c[ub][1], c[ub][2], c[ub][3]);
             }
-            uint2 hiw, low = make_uint2(0, 0);
-            if (NS == 2) {
-                split_bf16x2(h[0], h[1], hiw.x, low.x);
-                split_bf16x2(h[2], h[3], hiw.y, low.y);
-            } else {
-                hiw = make_uint2(pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3]));
-            }
-            const int hoff = (clip * HPG + 16 * UPW * wave + 16 * ub + 4 * g) * 2;
-            *reinterpret_cast<uint2*>(hn + hoff) = hiw;
-            if (NS == 2) *reinterpret_cast<uint2*>(hn + HBG + hoff) = low;
+            uint2 hiw, low;
+            split16<NS>(h, hiw, low);
+            store16<NS>(hn, HBG, (clip * HPG + 16 * UPW * wave + 16 * ub + 4 * g) * 2, hiw, low);
             if (clip_ok) {
                 const int64_t e = t * 2 * HH + 16 * ub;
                 if (OUT_TYPE == AMTX_T_BF16) *reinterpret_cast<uint2*>(obase + e * 2) = hiw;
@@ -795,15 +819,8 @@ __global__ __launch_bounds__(512) void bilstm_stream_bwd_kernel(LstmBwdHArgs a) 
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int grp = blockIdx.z;
     const char* wbase = reinterpret_cast<const char*>(a.whh_t + (int64_t)grp * a.w_gs) + ((int64_t)(dir * 8 + wave_u) * UT * KSN * NS) * 1024;
-    const unsigned wlane = lane * 16;
-    typedef const __attribute__((address_space(1))) char* gchar_p;
-    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-    typedef __attribute__((address_space(1))) u32x4_t gu4_t;
-    gchar_p wb = (gchar_p)wbase;
+    FragStream<SGK, NS> ws(wbase, lane);
     uint4 w[RS][SGK][NS];
-    auto load_frag = [&](int gi, int k, int p) {
-        return __builtin_bit_cast(uint4, *reinterpret_cast<const gu4_t*>(wb + ((gi * SGK + k) * NS + p) * 1024 + wlane));
-    };
 
     const int64_t bb = (int64_t)grp * a.B + (clip_ok ? b : 0);
     const float* sv0 = a.save + ((bb * T) * 2 + dir) * (5 * HH) + unit0;          // + t * (2*5*HH) + 16 ut + q * HH
@@ -816,7 +833,7 @@ __global__ __launch_bounds__(512) void bilstm_stream_bwd_kernel(LstmBwdHArgs a) 
     float dh_rec[UT], dc_rec[UT];
 #pragma unroll
     for (int ut = 0; ut < UT; ++ut) { dh_rec[ut] = 0.f; dc_rec[ut] = 0.f; }
-    auto frame = [&](int s_) { s_ = s_ < T ? s_ : T - 1; return dir == 0 ? T - 1 - s_ : s_; };
+    auto frame = [&](int s) { return step_frame(s, T, dir == 0); };
     float nv[UT][6];                                                              // i, f, g, o, c, dout of the next step
     auto load_next = [&](int tn) {
 #pragma unroll
@@ -829,23 +846,16 @@ __global__ __launch_bounds__(512) void bilstm_stream_bwd_kernel(LstmBwdHArgs a) 
     };
     load_next(frame(0));
     uint4 wpin[PINB ? NPINB : 1][SGK][NS];
-    static_for<0, NPINB>([&](auto gc) {
-        static_for<0, SGK>([&](auto kc) {
-            static_for<0, NS>([&](auto pc) { wpin[decltype(gc)::value][decltype(kc)::value][decltype(pc)::value] = load_frag(4 * decltype(gc)::value, decltype(kc)::value, decltype(pc)::value); });
-        });
-    });
+    static_for<0, NPINB>([&](auto gc) { ws.load_group(4 * decltype(gc)::value, wpin[decltype(gc)::value]); });
     static_for<0, RS - 1>([&](auto sc) {
         constexpr int si = decltype(sc)::value;
         constexpr int gi = PINB ? (si / 3) * 4 + 1 + si % 3 : si;        // streamed group si -> group index
-        static_for<0, SGK>([&](auto kc) {
-            static_for<0, NS>([&](auto pc) { w[si % RS][decltype(kc)::value][decltype(pc)::value] = load_frag(gi, decltype(kc)::value, decltype(pc)::value); });
-        });
+        ws.load_group(gi, w[si % RS]);
     });
     __syncthreads();
 
     for (int s = 0; s < T; ++s) {
-        wb = (gchar_p)wbase;
-        asm volatile("" : "+s"(wb));                          // see bilstm_stream_kernel: keeps the fragment addresses scalar
+        ws.rewind();
         const int t = frame(s);
         float cur[UT][6];
 #pragma unroll
@@ -891,9 +901,7 @@ __global__ __launch_bounds__(512) void bilstm_stream_bwd_kernel(LstmBwdHArgs a) 
             if constexpr (!pinned) {
                 constexpr int sn = (si + RS - 1) % NSGB;                         // behind the last RS - 1 streamed groups
                 constexpr int gn = PINB ? (sn / 3) * 4 + 1 + sn % 3 : sn;
-                static_for<0, SGK>([&](auto kc) {
-                    static_for<0, NS>([&](auto pc) { w[sn % RS][decltype(kc)::value][decltype(pc)::value] = load_frag(gn, decltype(kc)::value, decltype(pc)::value); });
-                });
+                ws.load_group(gn, w[sn % RS]);
             }
             static_for<0, SGK>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
@@ -918,156 +926,154 @@ __global__ __launch_bounds__(512) void bilstm_stream_bwd_kernel(LstmBwdHArgs a) 
     }
 }
 
-template <int HH, int NS, int X_TYPE, int OUT_TYPE>
-int launch_stream(const LstmArgs& a, hipStream_t stream) {
-    // h tiles + (bf16 mode) the LDS-resident quarter of W_hh: 8 waves x (groups / 4) x 4 KiB
-    // h tiles + (bf16 mode) the LDS-resident groups of W_hh: 8 waves x 4 groups x 4 KiB at either hidden size
-    const size_t lds = 2 * (size_t)NS * 16 * (HH + 8) * 2 + (NS == 1 && HH <= 384 ? (size_t)8 * 4 * 4096 : 0);
-    auto kern = bilstm_stream_kernel<HH, NS, X_TYPE, OUT_TYPE>;
-    AMTX_GRANT_LDS(kern, lds);
-    dim3 grid((unsigned)((a.B + 15) / 16), 2, (unsigned)a.groups);
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, a);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+// ---- kernel selection: amtx_launch_bilstm is its argument checks -> lstm_route -> one switch that launches (the table: DESIGN.md 5.10) ----
+
+// The A/B switch of this file, read once per process.  AMTX_LSTM_NO8: four-clip blocks where eight-clip blocks would run
+struct LstmSwitches { bool no8; };
+const LstmSwitches& lstm_switches() {
+    static const LstmSwitches sw = {getenv("AMTX_LSTM_NO8") != nullptr};
+    return sw;
 }
 
-template <int HH>
-int dispatch_stream(const LstmArgs& a, hipStream_t stream) {
-    if (a.planes == 1 && a.x_type == AMTX_T_BF16 && a.out_type == AMTX_T_BF16) return launch_stream<HH, 1, AMTX_T_BF16, AMTX_T_BF16>(a, stream);
-    if (a.planes == 2 && a.x_type == AMTX_T_F32 && a.out_type == AMTX_T_F32) return launch_stream<HH, 2, AMTX_T_F32, AMTX_T_F32>(a, stream);
-    amtx_set_error("bilstm (hidden %d): unsupported precision/type combination", HH);
+// The kernel a problem runs on: bilstm4_kernel<.., 1>, bilstm4_kernel<.., 2>, bilstm_kernel (hidden 128: W_hh stationary in registers) or
+// bilstm_stream_kernel (hidden 256 / 384 / 512), its (planes, xproj type = out type) instantiation, grid and dynamic LDS bytes.  LSTM_ERROR
+// carries the code and the text for a problem that no kernel takes.
+enum LstmFamily { LSTM_CLIPS4, LSTM_CLIPS8, LSTM_CLIPS16, LSTM_STREAM, LSTM_ERROR };
+enum LstmInst { LSTM_BF16, LSTM_BF16_F32IO, LSTM_X3, LSTM_NO_INST };     // (1, bf16), (1, fp32), (2, fp32)
+struct LstmRouted { LstmFamily family; LstmInst inst; dim3 grid; size_t lds; int code; const char* error; };
+
+// Pure: sizes, types and whether `save` is asked for; no pointer is dereferenced, nothing is launched, no environment is read.
+LstmRouted lstm_route(const LstmArgs& a, const LstmSwitches& sw) {
+    const bool io16 = a.x_type == AMTX_T_BF16 && a.out_type == AMTX_T_BF16, io32 = a.x_type == AMTX_T_F32 && a.out_type == AMTX_T_F32;
+    const LstmInst inst = a.planes == 1 && io16 ? LSTM_BF16 : (a.planes == 1 && io32 ? LSTM_BF16_F32IO : (a.planes == 2 && io32 ? LSTM_X3 : LSTM_NO_INST));
+    auto error = [](int code, const char* msg) { return LstmRouted{LSTM_ERROR, LSTM_NO_INST, dim3(), 0, code, msg}; };
+    auto on = [&](LstmFamily family, int clips, size_t lds) {
+        return LstmRouted{family, inst, dim3((unsigned)((a.B + clips - 1) / clips), 2, (unsigned)a.groups), lds, AMTX_OK, nullptr};
+    };
+    if (a.hidden != H) {
+        if (a.save && a.planes != 2) return error(AMTX_ERR_ARG, "bilstm: the training forward (save) is built for the two-plane precision");
+        if (a.hidden != 256 && a.hidden != 384 && a.hidden != 512) return error(AMTX_ERR_UNSUPPORTED, "bilstm: unsupported hidden size (128, 256, 384 and 512 are built)");
+        if (inst != LSTM_BF16 && inst != LSTM_X3) return error(AMTX_ERR_UNSUPPORTED, "bilstm: unsupported precision/type combination");
+        // the two h tiles + (one plane, up to hidden 384) the LDS-resident groups of W_hh: 8 waves x 4 groups x 4 KiB at either hidden size
+        return on(LSTM_STREAM, 16, 2 * (size_t)a.planes * 16 * (a.hidden + 8) * 2 + (a.planes == 1 && a.hidden <= 384 ? (size_t)8 * 4 * 4096 : 0));
+    }
+    if (inst == LSTM_NO_INST) return error(AMTX_ERR_UNSUPPORTED, "bilstm: unsupported precision/type combination");
+    const size_t lds = 2 * (size_t)a.planes * HBUF_BYTES;
+    // clips per block, by the number of blocks the four-clip mapping would make.  The training forward (save) exists for that mapping only
+    const int64_t blocks4 = (int64_t)((a.B + 3) / 4) * 2 * a.groups;
+    if (a.save) return on(LSTM_CLIPS4, 4, lds);
+    // more than 1024 (four per CU): sixteen clips per block, a quarter of the total wave-steps
+    if (blocks4 > 1024) return on(LSTM_CLIPS16, 16, lds);
+    // More than 256, where four-clip blocks would outnumber the CUs: eight clips per block.  Two co-resident blocks share a SIMD's matrix pipe
+    // and issue slots and a step takes 1650 cycles instead of the 1070 a block has to itself (0.54 vs 0.35 ms per 625 steps, measured at 1024
+    // and 512 clips); the eight-clip block does the same 16 MFMAs per wave and step for twice the clips, one block per CU.  One plane only:
+    // with two planes a step is 48 MFMAs per wave and the eight-clip block's doubled gate arithmetic sits on top of them (1.64 ms per 625
+    // steps at 1024 clips against 1.25 for two co-resident four-clip blocks).
+    if (!sw.no8 && a.planes == 1 && blocks4 > 256) return on(LSTM_CLIPS8, 8, lds);
+    return on(LSTM_CLIPS4, 4, lds);
+}
+
+// f(the hidden size of a streaming kernel as a std::integral_constant); the callers have checked that the size is built
+template <typename F>
+int with_hidden(int hidden, F&& f) {
+    switch (hidden) {
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 384: return f(std::integral_constant<int, 384>{});
+        case 512: return f(std::integral_constant<int, 512>{});
+    }
+    amtx_set_error("bilstm: unsupported hidden size %d (128, 256, 384 and 512 are built)", hidden);
     return AMTX_ERR_UNSUPPORTED;
 }
 
-// clips per block: 4 while that still leaves fewer blocks than ~4 per CU, else 16 (a quarter of the total wave-steps)
-inline bool use_four_clip_blocks(const LstmArgs& a) { return (int64_t)((a.B + 3) / 4) * 2 * a.groups <= 1024; }
-
-template <int NS, int X_TYPE, int OUT_TYPE>
-int launch(const LstmArgs& a, hipStream_t stream) {
-    const size_t lds = 2 * NS * HBUF_BYTES;
-    // Eight clips per block once four-clip blocks would outnumber the CUs: two co-resident blocks share a SIMD's matrix pipe and issue
-    // slots and a step takes 1650 cycles instead of the 1070 a block has to itself (0.54 vs 0.35 ms per 625 steps, measured at 1024 and
-    // 512 clips); the eight-clip block does the same 16 MFMAs per wave and step for twice the clips, one block per CU.
-    static const bool no8 = getenv("AMTX_LSTM_NO8") != nullptr;       // A/B switch
-    const int64_t blocks4 = (int64_t)((a.B + 3) / 4) * 2 * a.groups;
-    // (one plane only: in the two-plane mode a step is 48 MFMAs per wave and the eight-clip block's doubled gate arithmetic sits on top of
-    // them -- 1.64 ms per 625 steps at 1024 clips against 1.25 for two co-resident four-clip blocks, round 5)
-    if (!a.save && !no8 && NS == 1 && blocks4 > 256 && use_four_clip_blocks(a)) {
-        dim3 grid((unsigned)((a.B + 7) / 8), 2, (unsigned)a.groups);
-        hipLaunchKernelGGL((bilstm4_kernel<NS, X_TYPE, OUT_TYPE, 2>), grid, dim3(LTHREADS), lds, stream, a);
-    } else if (use_four_clip_blocks(a) || a.save) {     // the training forward (save != null) exists for the 4-clip mapping only
-        dim3 grid((unsigned)((a.B + 3) / 4), 2, (unsigned)a.groups);
-        hipLaunchKernelGGL((bilstm4_kernel<NS, X_TYPE, OUT_TYPE>), grid, dim3(LTHREADS), lds, stream, a);
-    } else {
-        dim3 grid((unsigned)((a.B + 15) / 16), 2, (unsigned)a.groups);
-        hipLaunchKernelGGL((bilstm_kernel<NS, X_TYPE, OUT_TYPE>), grid, dim3(LTHREADS), lds, stream, a);
-    }
+// every recurrence kernel runs 512 threads; dynamic LDS beyond the default 64 KiB is granted first
+template <typename K, typename A>
+int launch_kernel(K kern, dim3 grid, size_t lds, hipStream_t stream, const A& a) {
+    AMTX_GRANT_LDS(kern, lds);
+    hipLaunchKernelGGL(kern, grid, dim3(LTHREADS), lds, stream, a);
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
+}
+
+template <int NS, int XT>
+int launch_routed(const LstmRouted& r, const LstmArgs& a, hipStream_t stream) {
+    switch (r.family) {
+        case LSTM_CLIPS4: return launch_kernel(bilstm4_kernel<NS, XT, XT>, r.grid, r.lds, stream, a);
+        case LSTM_CLIPS8: return launch_kernel(bilstm4_kernel<NS, XT, XT, 2>, r.grid, r.lds, stream, a);
+        case LSTM_CLIPS16: return launch_kernel(bilstm_kernel<NS, XT, XT>, r.grid, r.lds, stream, a);
+        case LSTM_STREAM:
+            if constexpr (NS == 2 || XT == AMTX_T_BF16)       // the streaming kernels are built for LSTM_BF16 and LSTM_X3
+                return with_hidden(a.hidden, [&](auto hh) { return launch_kernel(bilstm_stream_kernel<decltype(hh)::value, NS, XT, XT>, r.grid, r.lds, stream, a); });
+            break;
+        case LSTM_ERROR: break;
+    }
+    amtx_set_error("bilstm: route without a kernel");
+    return AMTX_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
 namespace AMTX_FMT_NS {
 
-size_t amtx_bilstm_wfrag_elems(int planes) { return (size_t)2 * 512 * 128 * planes; }
-
-size_t amtx_bilstm_wfrag_elems_h(int hidden, int planes) { return (size_t)2 * 4 * hidden * hidden * planes; }
+size_t amtx_bilstm_wfrag_elems(int hidden, int planes) { return (size_t)2 * 4 * hidden * hidden * planes; }
 
 // wave w of the hidden-128 kernels owns unit tiles UB w .. UB w + UB - 1 and the backward kernels run AMTX_LSTM_BWD_WAVES waves: what
 // amtx_layout_bilstm / _transposed (amtx_pack_layouts.h) lay the fragments out for
 static_assert(16 * UB * LWAVES == H && LWAVES == AMTX_LSTM_BWD_WAVES, "W_hh fragment layouts");
 
 // fragment order of every forward kernel: [dir][unit tile][gate][k-step][plane][lane][8]
-void amtx_bilstm_pack_host_h(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out) {
+void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out) {
     const AmtxFragPut put{out, planes};
     for (int item = 0, n = amtx_layout_bilstm_items(hidden); item < n; ++item) amtx_layout_bilstm(item, whh_fwd, whh_bwd, hidden, put);
 }
-
-void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* out) { amtx_bilstm_pack_host_h(whh_fwd, whh_bwd, H, planes, out); }
 
 int amtx_launch_bilstm(const LstmArgs& a, hipStream_t stream) {
     AMTX_REQUIRE(a.xproj && a.whh && a.out, "bilstm: null pointer");
     AMTX_REQUIRE(a.B > 0 && a.T > 0 && a.groups > 0, "bilstm: bad sizes");
     AMTX_REQUIRE(a.planes == 1 || a.planes == 2, "bilstm: planes must be 1 or 2");
-    if (a.hidden != H) {
-        AMTX_REQUIRE(!a.save || a.planes == 2, "bilstm: the training forward (save) is built for the two-plane precision");
-        if (a.hidden == 256) return dispatch_stream<256>(a, stream);
-        if (a.hidden == 384) return dispatch_stream<384>(a, stream);
-        if (a.hidden == 512) return dispatch_stream<512>(a, stream);
-        amtx_set_error("bilstm: unsupported hidden size %d (128, 256, 384 and 512 are built)", a.hidden);
-        return AMTX_ERR_UNSUPPORTED;
+    const LstmRouted r = lstm_route(a, lstm_switches());
+    switch (r.inst) {
+        case LSTM_BF16: return launch_routed<1, AMTX_T_BF16>(r, a, stream);
+        case LSTM_BF16_F32IO: return launch_routed<1, AMTX_T_F32>(r, a, stream);
+        case LSTM_X3: return launch_routed<2, AMTX_T_F32>(r, a, stream);
+        case LSTM_NO_INST: break;
     }
-    if (a.planes == 1 && a.x_type == AMTX_T_BF16 && a.out_type == AMTX_T_BF16) return launch<1, AMTX_T_BF16, AMTX_T_BF16>(a, stream);
-    if (a.planes == 1 && a.x_type == AMTX_T_F32 && a.out_type == AMTX_T_F32) return launch<1, AMTX_T_F32, AMTX_T_F32>(a, stream);
-    if (a.planes == 2 && a.x_type == AMTX_T_F32 && a.out_type == AMTX_T_F32) return launch<2, AMTX_T_F32, AMTX_T_F32>(a, stream);
-    amtx_set_error("bilstm: unsupported precision/type combination");
-    return AMTX_ERR_UNSUPPORTED;
+    amtx_set_error("%s (hidden %d)", r.error, a.hidden);
+    return r.code;
 }
 
-int amtx_launch_bilstm_pack_dev(const float* whh_fwd, const float* whh_bwd, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream) {
+int amtx_launch_bilstm_pack_dev(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream) {
     AMTX_REQUIRE(whh_fwd && whh_bwd && frag_fwd && frag_bwd && (planes == 1 || planes == 2), "bilstm pack: bad argument");
-    hipLaunchKernelGGL(bilstm_pack_dev_kernel<H>, dim3(64), dim3(256), 0, stream, whh_fwd, whh_bwd, H, AmtxFragPut{frag_fwd, planes}, AmtxFragPut{frag_bwd, planes});
+    AMTX_REQUIRE(hidden == H || hidden == 256 || hidden == 384 || hidden == 512, "bilstm pack: hidden size %d is not built (128, 256, 384, 512)", hidden);
+    const AmtxFragPut fwd{frag_fwd, planes}, bwd{frag_bwd, planes};
+    // hidden 128 (every training step of the shipped models) has its size at compile time, the other sizes share one kernel
+    if (hidden == H) hipLaunchKernelGGL(bilstm_pack_dev_kernel<H>, dim3(64), dim3(256), 0, stream, whh_fwd, whh_bwd, H, fwd, bwd);
+    else hipLaunchKernelGGL(bilstm_pack_dev_kernel<0>, dim3(256), dim3(256), 0, stream, whh_fwd, whh_bwd, hidden, fwd, bwd);
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
 
-int amtx_launch_bilstm_bwd(const float* dout, const float* save, const bf16_t* whh_t, int planes, float* dxproj, int B, int T, hipStream_t stream) {
+int amtx_launch_bilstm_bwd(const float* dout, const float* save, const bf16_t* whh_t, int hidden, int planes, float* dxproj, int B, int T, int groups,
+                           hipStream_t stream) {
+    AMTX_REQUIRE(groups >= 1, "bilstm backward: bad group count");
     AMTX_REQUIRE(dout && save && whh_t && dxproj, "bilstm backward: null pointer");
     AMTX_REQUIRE(B > 0 && T > 0 && (planes == 1 || planes == 2), "bilstm backward: bad sizes");
-    LstmBwdArgs a;
-    a.dout = dout; a.save = save; a.whh_t = whh_t; a.planes = planes; a.dxproj = dxproj; a.B = B; a.T = T;
-    dim3 grid((unsigned)((B + 3) / 4), 2);
-    const size_t lds = 2 * (size_t)planes * GBUF_BYTES;
-    if (planes == 2) {
-        AMTX_GRANT_LDS(bilstm4_bwd_kernel<2>, lds);
-        hipLaunchKernelGGL(bilstm4_bwd_kernel<2>, grid, dim3(LTHREADS), lds, stream, a);
-    } else {
-        hipLaunchKernelGGL(bilstm4_bwd_kernel<1>, grid, dim3(LTHREADS), lds, stream, a);
-    }
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
-}
-
-int amtx_launch_bilstm_pack_dev_h(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* frag_fwd, bf16_t* frag_bwd, hipStream_t stream) {
-    AMTX_REQUIRE(whh_fwd && whh_bwd && frag_fwd && frag_bwd && (planes == 1 || planes == 2), "bilstm pack: bad argument");
-    if (hidden == H) return amtx_launch_bilstm_pack_dev(whh_fwd, whh_bwd, planes, frag_fwd, frag_bwd, stream);
-    AMTX_REQUIRE(hidden == 256 || hidden == 384 || hidden == 512, "bilstm pack: hidden size %d is not built (128, 256, 384, 512)", hidden);
-    hipLaunchKernelGGL(bilstm_pack_dev_kernel<0>, dim3(256), dim3(256), 0, stream, whh_fwd, whh_bwd, hidden, AmtxFragPut{frag_fwd, planes}, AmtxFragPut{frag_bwd, planes});
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
-}
-
-int amtx_launch_bilstm_bwd_h(const float* dout, const float* save, const bf16_t* whh_t, int hidden, int planes, float* dxproj, int B, int T, int groups,
-                             hipStream_t stream) {
-    AMTX_REQUIRE(groups >= 1, "bilstm backward: bad group count");
+    const int64_t w_gs = (int64_t)amtx_bilstm_wfrag_elems(hidden, planes), bt = (int64_t)B * T;
+    const dim3 grid((unsigned)((B + 3) / 4), 2);
     if (hidden == H) {
         for (int g = 0; g < groups; ++g) {        // the register-stationary kernel takes one LSTM per launch
-            const int64_t bt = (int64_t)B * T;
-            int rc = amtx_launch_bilstm_bwd(dout + g * bt * 2 * H, save + g * bt * 2 * 5 * H, whh_t + (size_t)g * amtx_bilstm_wfrag_elems(planes), planes,
-                                            dxproj + g * bt * 8 * H, B, T, stream);
+            const LstmBwdArgs a{dout + g * bt * 2 * H, save + g * bt * 2 * 5 * H, whh_t + g * w_gs, planes, dxproj + g * bt * 8 * H, B, T};
+            const size_t lds = 2 * (size_t)planes * GBUF_BYTES;
+            const int rc = planes == 2 ? launch_kernel(bilstm4_bwd_kernel<2>, grid, lds, stream, a) : launch_kernel(bilstm4_bwd_kernel<1>, grid, lds, stream, a);
             if (rc != AMTX_OK) return rc;
         }
         return AMTX_OK;
     }
-    AMTX_REQUIRE(dout && save && whh_t && dxproj, "bilstm backward: null pointer");
-    AMTX_REQUIRE(B > 0 && T > 0 && planes == 2 && (hidden == 256 || hidden == 384 || hidden == 512),
+    AMTX_REQUIRE(planes == 2 && (hidden == 256 || hidden == 384 || hidden == 512),
                  "bilstm backward: hidden 256 / 384 / 512 are built for the two-plane precision only (got hidden %d, planes %d)", hidden, planes);
-    LstmBwdHArgs a{dout, save, whh_t, dxproj, B, T, (int64_t)amtx_bilstm_wfrag_elems_h(hidden, planes)};
-    dim3 grid((unsigned)((B + 3) / 4), 2, (unsigned)groups);
-    const size_t lds = 2 * (size_t)planes * 5 * (4 * hidden + 8) * 2;
-    if (hidden == 256) {
-        AMTX_GRANT_LDS((bilstm_stream_bwd_kernel<256, 2>), lds);
-        hipLaunchKernelGGL((bilstm_stream_bwd_kernel<256, 2>), grid, dim3(512), lds, stream, a);
-    } else if (hidden == 384) {
-        AMTX_GRANT_LDS((bilstm_stream_bwd_kernel<384, 2>), lds);
-        hipLaunchKernelGGL((bilstm_stream_bwd_kernel<384, 2>), grid, dim3(512), lds, stream, a);
-    } else {
-        AMTX_GRANT_LDS((bilstm_stream_bwd_kernel<512, 2>), lds);
-        hipLaunchKernelGGL((bilstm_stream_bwd_kernel<512, 2>), grid, dim3(512), lds, stream, a);
-    }
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+    const LstmBwdHArgs a{dout, save, whh_t, dxproj, B, T, w_gs};
+    return with_hidden(hidden, [&](auto hh) {
+        return launch_kernel(bilstm_stream_bwd_kernel<decltype(hh)::value, 2>, dim3(grid.x, 2, (unsigned)groups), 2 * (size_t)planes * 5 * (4 * hidden + 8) * 2, stream, a);
+    });
 }
 
 }  // namespace AMTX_FMT_NS

@@ -30,9 +30,9 @@ struct LinearPack { DevBuf w, b; int N = 0, K = 0, n_pad = 0, k_pad = 0, groups 
 // format namespace, its type the declaration's.  Struct and tables come from this one list, so a name that either namespace lacks does
 // not compile.  A model picks its table when it is created and calls through it.
 #define AMTX_FMT_KERNELS(X, ns)                                                                                                    \
-    X(ns, pack_linear_host) X(ns, bilstm_pack_host_h) X(ns, conv1_pack_host) X(ns, conv1g_pack_host) X(ns, conv3x3_pack_host)     \
+    X(ns, pack_linear_host) X(ns, bilstm_pack_host) X(ns, conv1_pack_host) X(ns, conv1g_pack_host) X(ns, conv3x3_pack_host)     \
     X(ns, conv3x3_gen_pack_host) X(ns, pack_conv1_dev) X(ns, pack_conv1g_dev) X(ns, pack_conv3x3_dev) X(ns, pack_conv_gen_dev)    \
-    X(ns, pack_linear_dev) X(ns, launch_bilstm_pack_dev_h) X(ns, launch_conv1) X(ns, launch_conv3x3) X(ns, launch_conv3x3_gen)    \
+    X(ns, pack_linear_dev) X(ns, launch_bilstm_pack_dev) X(ns, launch_conv1) X(ns, launch_conv3x3) X(ns, launch_conv3x3_gen)    \
     X(ns, launch_conv_stack) X(ns, launch_gemm) X(ns, launch_bilstm)
 #define AMTX_KERNEL_FIELD(ns, name) decltype(&ns::amtx_##name) name;
 #define AMTX_KERNEL_ENTRY(ns, name) &ns::amtx_##name,
@@ -224,7 +224,7 @@ extern "C" int amtx_of_model_create(amtx_of_model** out, int dim_in, int in_chan
     m->kfc = m->nf3 * m->fq;
     m->kfc_pad = (m->kfc + 63) / 64 * 64;
     m->hid = m->dim_lm / 2; m->xw = 8 * m->hid;
-    m->hh_elems = amtx_bilstm_wfrag_elems_h(m->hid, m->planes);
+    m->hh_elems = amtx_bilstm_wfrag_elems(m->hid, m->planes);
     m->plan = make_conv_plan(in_channels, model_complexity, precision, switches_from_env());
     m->head_names = {"onset_head"};
     if (has_offsets) m->head_names.push_back("offset_head");
@@ -291,7 +291,7 @@ struct HostPack {
     }
     int vec_add(const float* a, const float* b, int n, float* out) { for (int i = 0; i < n; ++i) out[i] = a[i] + b[i]; return AMTX_OK; }
     int copy(float* out, const float* src, size_t n) { memcpy(out, src, n * sizeof(float)); return AMTX_OK; }
-    int bilstm(const float* whh_fwd, const float* whh_bwd, bf16_t* out) { m->k->bilstm_pack_host_h(whh_fwd, whh_bwd, m->hid, m->planes, out); return AMTX_OK; }
+    int bilstm(const float* whh_fwd, const float* whh_bwd, bf16_t* out) { m->k->bilstm_pack_host(whh_fwd, whh_bwd, m->hid, m->planes, out); return AMTX_OK; }
     // The ONE step with a loop structure of its own: n_out x dim_am x kfc double multiply-adds (164 M at model_complexity 2) would be
     // many times slower on a CPU one output element at a time, as head_fold_kernel (pack.hip) does them.  Output rows are dealt to a few
     // host threads; a row is accumulated over W_fc1's rows in W_fc1's own, contiguous column order and permuted when it is written.
@@ -369,7 +369,7 @@ struct DevicePack {
         return AMTX_OK;
     }
     int bilstm(const float* whh_fwd, const float* whh_bwd, bf16_t* out) {
-        return dry ? AMTX_OK : m->k->launch_bilstm_pack_dev_h(whh_fwd, whh_bwd, m->hid, m->planes, out, hh_bwd, s);
+        return dry ? AMTX_OK : m->k->launch_bilstm_pack_dev(whh_fwd, whh_bwd, m->hid, m->planes, out, hh_bwd, s);
     }
     int head_fold(const float* w_out, const float* w_fc1, const float* b_fc1, const float* b_out, float* wfold, float* bfold) {
         return dry ? AMTX_OK : amtx_pack_head_fold_dev(w_out, w_fc1, b_fc1, b_out, m->n_out, m->dim_am, m->kfc, m->kfc_pad, m->nf3, m->fq, wfold, bfold, s);

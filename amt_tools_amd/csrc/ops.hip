@@ -86,40 +86,45 @@ extern "C" int amtx_conv1_fwd(const float* feats, int64_t stride_b, int64_t stri
     return amtx_launch_conv1(a, (hipStream_t)stream);
 }
 
-extern "C" int64_t amtx_bilstm_packed_elems(int planes) { return (int64_t)amtx_bilstm_wfrag_elems(planes); }
+// ---- BiLSTM.  The entry points without `_h` are the hidden-128 case of their `_h` siblings.
+static bool bilstm_hidden_built(int hidden) { return hidden == 128 || hidden == 256 || hidden == 384 || hidden == 512; }
 
-extern "C" int amtx_bilstm_pack(const float* host_whh_fwd, const float* host_whh_bwd, int planes, uint16_t* host_out) {
-    AMTX_REQUIRE(host_whh_fwd && host_whh_bwd && host_out && (planes == 1 || planes == 2), "amtx_bilstm_pack: bad argument");
-    amtx_bilstm_pack_host(host_whh_fwd, host_whh_bwd, planes, host_out);
-    return AMTX_OK;
-}
-
-extern "C" int amtx_bilstm_fwd(const void* xproj, const uint16_t* whh_packed, int planes, int elem_type, void* out, int batch,
-                               int num_frames, void* stream) {
+// `groups` independent LSTMs of one (batch, num_frames), densely packed one after the other; xproj and out of one element type
+static LstmArgs bilstm_args(const void* xproj, const uint16_t* whh_packed, int hidden, int planes, int elem_type, void* out, float* save, int batch,
+                            int num_frames, int groups) {
+    const int64_t bt = (int64_t)batch * num_frames;
     LstmArgs l;
     l.xproj = xproj; l.x_type = elem_type; l.whh = whh_packed; l.planes = planes; l.out = out; l.out_type = elem_type;
-    l.B = batch; l.T = num_frames; l.groups = 1; l.x_gs = l.w_gs = l.out_gs = 0;
-    return amtx_launch_bilstm(l, (hipStream_t)stream);
+    l.B = batch; l.T = num_frames; l.hidden = hidden; l.save = save;
+    l.groups = groups; l.x_gs = bt * 8 * hidden; l.w_gs = (int64_t)amtx_bilstm_wfrag_elems(hidden, planes); l.out_gs = bt * 2 * hidden;
+    return l;
 }
 
 extern "C" int64_t amtx_bilstm_h_packed_elems(int hidden, int planes) {
-    if (hidden != 128 && hidden != 256 && hidden != 384 && hidden != 512) return 0;
-    return (int64_t)amtx_bilstm_wfrag_elems_h(hidden, planes);
+    return bilstm_hidden_built(hidden) ? (int64_t)amtx_bilstm_wfrag_elems(hidden, planes) : 0;
 }
 
 extern "C" int amtx_bilstm_h_pack(const float* host_whh_fwd, const float* host_whh_bwd, int hidden, int planes, uint16_t* host_out) {
     AMTX_REQUIRE(host_whh_fwd && host_whh_bwd && host_out && (planes == 1 || planes == 2), "amtx_bilstm_h_pack: bad argument");
-    AMTX_REQUIRE(hidden == 128 || hidden == 256 || hidden == 384 || hidden == 512, "amtx_bilstm_h_pack: hidden size %d is not built (128, 256, 384, 512)", hidden);
-    amtx_bilstm_pack_host_h(host_whh_fwd, host_whh_bwd, hidden, planes, host_out);
+    AMTX_REQUIRE(bilstm_hidden_built(hidden), "amtx_bilstm_h_pack: hidden size %d is not built (128, 256, 384, 512)", hidden);
+    amtx_bilstm_pack_host(host_whh_fwd, host_whh_bwd, hidden, planes, host_out);
     return AMTX_OK;
 }
 
 extern "C" int amtx_bilstm_h_fwd(const void* xproj, const uint16_t* whh_packed, int hidden, int planes, int elem_type, void* out, int batch,
                                  int num_frames, void* stream) {
-    LstmArgs l;
-    l.xproj = xproj; l.x_type = elem_type; l.whh = whh_packed; l.planes = planes; l.out = out; l.out_type = elem_type;
-    l.B = batch; l.T = num_frames; l.groups = 1; l.x_gs = l.w_gs = l.out_gs = 0; l.hidden = hidden;
-    return amtx_launch_bilstm(l, (hipStream_t)stream);
+    return amtx_launch_bilstm(bilstm_args(xproj, whh_packed, hidden, planes, elem_type, out, nullptr, batch, num_frames, 1), (hipStream_t)stream);
+}
+
+extern "C" int64_t amtx_bilstm_packed_elems(int planes) { return amtx_bilstm_h_packed_elems(128, planes); }
+
+extern "C" int amtx_bilstm_pack(const float* host_whh_fwd, const float* host_whh_bwd, int planes, uint16_t* host_out) {
+    return amtx_bilstm_h_pack(host_whh_fwd, host_whh_bwd, 128, planes, host_out);
+}
+
+extern "C" int amtx_bilstm_fwd(const void* xproj, const uint16_t* whh_packed, int planes, int elem_type, void* out, int batch,
+                               int num_frames, void* stream) {
+    return amtx_bilstm_h_fwd(xproj, whh_packed, 128, planes, elem_type, out, batch, num_frames, stream);
 }
 
 extern "C" int amtx_pianoroll_fwd(const float* logits, int64_t ld, int col0, int batch, int num_frames, int keys, float threshold,
@@ -139,44 +144,35 @@ extern "C" int amtx_bce_logits_loss(const float* logits, int64_t ld, const float
     return amtx_launch_bce_loss(logits, ld, labels, weight, batch, num_frames, keys, loss, grad, (float*)workspace, (hipStream_t)stream);
 }
 
-// ---- training entry points of the BiLSTM (amt_tools_amd/autograd.py)
-extern "C" int amtx_bilstm_pack_device(const float* whh_fwd, const float* whh_bwd, int planes, uint16_t* frag_fwd, uint16_t* frag_bwd, void* stream) {
-    return amtx_launch_bilstm_pack_dev(whh_fwd, whh_bwd, planes, (bf16_t*)frag_fwd, (bf16_t*)frag_bwd, (hipStream_t)stream);
-}
-
-extern "C" int amtx_bilstm_train_fwd(const float* xproj, const uint16_t* whh_packed, int planes, float* out, float* save, int batch, int num_frames,
-                                     void* stream) {
-    AMTX_REQUIRE(xproj && whh_packed && out && save, "amtx_bilstm_train_fwd: null pointer");
-    LstmArgs l;
-    l.xproj = xproj; l.x_type = AMTX_T_F32; l.whh = (const bf16_t*)whh_packed; l.planes = planes; l.out = out; l.out_type = AMTX_T_F32;
-    l.B = batch; l.T = num_frames; l.groups = 1; l.x_gs = l.w_gs = l.out_gs = 0; l.save = save;
-    AMTX_REQUIRE(planes == 2, "amtx_bilstm_train_fwd: training runs in the fp32-class (two-plane) precision");
-    return amtx_launch_bilstm(l, (hipStream_t)stream);
-}
-
-extern "C" int amtx_bilstm_train_bwd(const float* dout, const float* save, const uint16_t* whh_t_packed, int planes, float* dxproj, int batch,
-                                     int num_frames, void* stream) {
-    return amtx_launch_bilstm_bwd(dout, save, (const bf16_t*)whh_t_packed, planes, dxproj, batch, num_frames, (hipStream_t)stream);
-}
-
-// ---- training recurrences for any built hidden size (128: the register-stationary kernels, 256 / 384: the streaming ones)
+// ---- training entry points of the BiLSTM (amt_tools_amd/autograd.py) for any built hidden size (128: the register-stationary kernels,
+// 256 / 384 / 512: the streaming ones) and their hidden-128 forms
 extern "C" int amtx_bilstm_h_pack_device(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, uint16_t* frag_fwd, uint16_t* frag_bwd,
                                          void* stream) {
-    return amtx_launch_bilstm_pack_dev_h(whh_fwd, whh_bwd, hidden, planes, frag_fwd, frag_bwd, (hipStream_t)stream);
+    return amtx_launch_bilstm_pack_dev(whh_fwd, whh_bwd, hidden, planes, frag_fwd, frag_bwd, (hipStream_t)stream);
 }
 
 extern "C" int amtx_bilstm_h_train_fwd(const float* xproj, const uint16_t* whh_packed, int hidden, int planes, float* out, float* save, int batch,
                                        int num_frames, int groups, void* stream) {
     AMTX_REQUIRE(save && groups >= 1, "amtx_bilstm_h_train_fwd: null save buffer / bad group count");
-    const int64_t bt = (int64_t)batch * num_frames;
-    LstmArgs l;
-    l.xproj = xproj; l.x_type = AMTX_T_F32; l.whh = whh_packed; l.planes = planes; l.out = out; l.out_type = AMTX_T_F32;
-    l.B = batch; l.T = num_frames; l.hidden = hidden; l.save = save;
-    l.groups = groups; l.x_gs = bt * 8 * hidden; l.w_gs = (int64_t)amtx_bilstm_wfrag_elems_h(hidden, planes); l.out_gs = bt * 2 * hidden;
-    return amtx_launch_bilstm(l, (hipStream_t)stream);
+    return amtx_launch_bilstm(bilstm_args(xproj, whh_packed, hidden, planes, AMTX_T_F32, out, save, batch, num_frames, groups), (hipStream_t)stream);
 }
 
 extern "C" int amtx_bilstm_h_train_bwd(const float* dout, const float* save, const uint16_t* whh_t_packed, int hidden, int planes, float* dxproj,
                                        int batch, int num_frames, int groups, void* stream) {
-    return amtx_launch_bilstm_bwd_h(dout, save, whh_t_packed, hidden, planes, dxproj, batch, num_frames, groups, (hipStream_t)stream);
+    return amtx_launch_bilstm_bwd(dout, save, whh_t_packed, hidden, planes, dxproj, batch, num_frames, groups, (hipStream_t)stream);
+}
+
+extern "C" int amtx_bilstm_pack_device(const float* whh_fwd, const float* whh_bwd, int planes, uint16_t* frag_fwd, uint16_t* frag_bwd, void* stream) {
+    return amtx_bilstm_h_pack_device(whh_fwd, whh_bwd, 128, planes, frag_fwd, frag_bwd, stream);
+}
+
+extern "C" int amtx_bilstm_train_fwd(const float* xproj, const uint16_t* whh_packed, int planes, float* out, float* save, int batch, int num_frames,
+                                     void* stream) {
+    AMTX_REQUIRE(planes == 2, "amtx_bilstm_train_fwd: training runs in the fp32-class (two-plane) precision");     // (the `_h` entry point takes one plane at hidden 128)
+    return amtx_bilstm_h_train_fwd(xproj, whh_packed, 128, planes, out, save, batch, num_frames, 1, stream);
+}
+
+extern "C" int amtx_bilstm_train_bwd(const float* dout, const float* save, const uint16_t* whh_t_packed, int planes, float* dxproj, int batch,
+                                     int num_frames, void* stream) {
+    return amtx_bilstm_h_train_bwd(dout, save, whh_t_packed, 128, planes, dxproj, batch, num_frames, 1, stream);
 }

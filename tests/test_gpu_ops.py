@@ -254,7 +254,7 @@ def test_bilstm_h_entry_runs_hidden_128_like_the_fixed_entry():
 
 
 @pytest.mark.parametrize('planes', [1, 2])
-# b <= 2048 runs the four-clips-per-block kernel, larger batches the sixteen-clip one (lstm.hip: use_four_clip_blocks)
+# b <= 2048 runs the four-clips-per-block kernel, larger batches the sixteen-clip one (lstm.hip: lstm_route)
 # and from 513 clips on (four-clip blocks would outnumber the 256 CUs) the eight-clips-per-block mapping bilstm4_kernel<.., NC = 2>: both
 # sides of every batch-size threshold of the dispatch are here (512 | 513, 2048 | 2049), with ragged last blocks (521 = 65 x 8 + 1,
 # 2047) and the clip_ok[1] = false tail (513, 521: the last block holds one clip)
@@ -280,7 +280,7 @@ def test_bilstm(planes, b, t):
 
 @pytest.mark.parametrize('b,t', [(3, 50), (17, 33)])
 def test_bilstm_one_plane_fp32_io(b, t):
-    """bf16 arithmetic on fp32 xproj and output (lstm.hip: launch<1, F32, F32>), a combination the ABI exports and no model runs."""
+    """bf16 arithmetic on fp32 xproj and output (lstm.hip: LSTM_BF16_F32IO), a combination the ABI exports and no model runs."""
     L = _lib.lib()
     g = torch.Generator().manual_seed(b * 100 + t)
     xproj = torch.randn(b, t, 2, 512, generator=g)
@@ -360,3 +360,57 @@ def test_skinny_gemm_returns_the_bits_of_the_two_buffer_kernel(tmp_path):
     for k in a.files:
         assert np.abs(a[k]).max() > 0
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
+_LSTM_NO8_AB = r'''
+import os, sys
+import numpy as np, torch
+sys.path.insert(0, os.getcwd())
+from amt_tools_amd import _lib
+L = _lib.lib()
+outs = {}
+for b, t in ((513, 7), (521, 40)):
+    g = torch.Generator().manual_seed(b * 100 + t)
+    xproj = torch.randn(b, t, 2, 512, generator=g)
+    whh_f = (torch.rand(512, 128, generator=g) - 0.5) * 0.3
+    whh_b = (torch.rand(512, 128, generator=g) - 0.5) * 0.3
+    packed = np.zeros(L.amtx_bilstm_packed_elems(1), dtype=np.uint16)
+    _lib.check(L.amtx_bilstm_pack(_lib.ptr(whh_f.numpy()), _lib.ptr(whh_b.numpy()), 1, _lib.ptr(packed)))
+    wp = torch.from_numpy(packed.view(np.int16)).cuda()
+    x_d = xproj.cuda().to(torch.bfloat16).contiguous()
+    out = torch.full((b, t, 256), 9.0, dtype=torch.bfloat16, device='cuda')
+    _lib.check(L.amtx_bilstm_fwd(_lib.ptr(x_d), _lib.ptr(wp), 1, 0, _lib.ptr(out), b, t, _lib.current_stream()), 'amtx_bilstm_fwd')
+    outs[f'{b}_{t}'] = out.view(torch.int16).cpu().numpy()
+np.savez(sys.argv[1], **outs)
+'''
+
+
+def test_bilstm_eight_clip_blocks_return_the_bits_of_four_clip_blocks(tmp_path):
+    """From 513 clips on the one-plane recurrence runs eight clips per block (lstm.hip: lstm_route, bilstm4_kernel<.., NC = 2>);
+    AMTX_LSTM_NO8=1 keeps four clips per block.  Same W_hh fragments, same h tile packing, same k order: the kernel's header comment says
+    both produce the same bits.  (513, 7): the smallest batch on the eight-clip mapping, its last block holds one clip; (521, 40): a
+    ragged last block.  Each side is also held to test_bilstm's bound against the fp64 recurrence."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = {}
+    for tag, extra in (('eight', {}), ('four', {'AMTX_LSTM_NO8': '1'})):
+        env = {k: v for k, v in os.environ.items() if k != 'AMTX_LSTM_NO8'}
+        env.update(extra)
+        files[tag] = str(tmp_path / f'{tag}.npz')
+        subprocess.check_call([sys.executable, '-c', _LSTM_NO8_AB, files[tag]], env=env, cwd=root, timeout=120)
+    eight, four = np.load(files['eight']), np.load(files['four'])
+    assert sorted(eight.files) == sorted(four.files) == ['513_7', '521_40']
+    for b, t in ((513, 7), (521, 40)):
+        g = torch.Generator().manual_seed(b * 100 + t)
+        xproj = torch.randn(b, t, 2, 512, generator=g)
+        whh_f = (torch.rand(512, 128, generator=g) - 0.5) * 0.3
+        whh_b = (torch.rand(512, 128, generator=g) - 0.5) * 0.3
+        ref = _lstm_ref(xproj.to(torch.bfloat16).float(), whh_f, whh_b)
+        for tag, got in (('eight', eight), ('four', four)):
+            out = torch.from_numpy(got[f'{b}_{t}']).view(torch.bfloat16).float()
+            err = (out - ref).abs().max().item()
+            print(f'{tag}-clip blocks, ({b}, {t}): max abs err {err:.3e}')
+            assert err < 3e-2, (tag, b, t, err)
+        np.testing.assert_array_equal(eight[f'{b}_{t}'], four[f'{b}_{t}'], err_msg=f'({b}, {t})')
