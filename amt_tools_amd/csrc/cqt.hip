@@ -93,6 +93,9 @@ __global__ __launch_bounds__(256) void cqt_pad_kernel(float* __restrict__ pyr, i
 // amplitude_to_db(ref = max) -> clamp -80 -> /80 + 1 (or plain magnitude), truncated to t_out frames; from the POWER map
 __global__ __launch_bounds__(256) void cqt_scale_kernel(const float* __restrict__ mag, const float* __restrict__ maxbuf, int n_bins, int64_t t_buf,
                                                         int64_t t_out, int decibels, float* __restrict__ out) {
+    // no contraction: with 10 log10(a) - offs fused into one fma, the bin that IS the maximum came out as the rounding residue of offs instead
+    // of 0 dB -- 1 - 2^-24 on the scaled map wherever 10 log10(max power) <= -64 dB (quiet clips), where the reference has exactly 1.0
+#pragma clang fp contract(off)
     const int bh = blockIdx.y;
     const float ref = maxbuf[bh];                            // `mag` and `maxbuf` hold POWERS (re^2 + im^2 as the basis products' epilogue leaves them:
                                                              // no root there, no square here)
@@ -126,6 +129,7 @@ constexpr int SC16_TT = 32;
 constexpr int SC16_U = 9;          // 72 bins = one round of 8 rows x 9
 __global__ __launch_bounds__(256) void cqt_scale16_kernel(const float* __restrict__ mag, const float* __restrict__ maxbuf, int n_harm, int n_bins, int nbc,
                                                           int64_t t_buf, int64_t t_out, int decibels, uint4* __restrict__ out16, int64_t lo_plane) {
+#pragma clang fp contract(off)                               // like cqt_scale_kernel: the same bits, and a map's maximum is exactly 1.0
     // lo_plane != 0 (amtx_cqt_forward16_split, the x3 engine's hand-over): a second map, lo = 16-bit(v - 16-bit(v)), lo_plane 16-byte slots
     // behind the first -- the two planes split_bf16x2 makes of the fp32 feature, i.e. what the two-plane conv kernels made of it themselves
     extern __shared__ __attribute__((aligned(16))) char smem[];          // [planes][SC16_TT][nbc + 1] slots of 16 bytes, then 8 x 2 floats

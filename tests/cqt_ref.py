@@ -1,0 +1,421 @@
+"""The CQT / VQT / HCQT front-end of csrc/cqt.hip and csrc/cqt_dec.hip in float64, the way the kernels formulate it: per octave the
+sparsified one-sided FFT basis of the oracle folded back into its n_fft-tap complex kernel, applied to strided windows of the progressively
+decimated signal.  Host only: NumPy and oracle/cqt_np.py, whose pieces (wavelet_basis, sparsify_rows, decimation_filter,
+early_downsample_count, wavelet_lengths, alpha_of) are called, never restated.
+
+vqt_time_domain(y, ..., mode=)
+    'exact'   nothing is rounded: the identity the kernel design rests on (equal to cq.vqt to 2.5e-14 of the map maximum)
+    'ideal'   the operand roundings of the kernels and nothing else: the signal of a basis product in two bf16 planes, its weights rounded
+              to fp32 and split into two bf16 planes, the lo.lo product dropped; decimator taps in fp32; every pyramid level rounded to
+              fp32; all accumulation in float64.  What the arithmetic allows: the GPU tests' bounds lie above it, the mutations far above.
+    mutate=   one stage of the ideal evaluation broken (MUTATIONS): what a one-plane bug, a dropped k-step or a wrong pad would cost.
+
+Also here: the plan layout the library derives (levels, n_fft, hop, columns -- plan_layout) and the route cqt_forward_impl takes for it
+(expected_route: its conditions restated by hand), the case table of tests/test_gpu_cqt_edges.py, the seeded inputs and the tolerances.
+
+Not modelled and not asserted anywhere: a decimator whose INPUT is split into two bf16 planes only (the 1.07e-3 failure recorded in
+cqt_dec.hip).  Emulated here (mutate='decim_two_plane_input': the signal of every decimation in two bf16 planes) it takes the 8-octave
+CQT from 3.9e-6 to 5.6e-6 of the map maximum: the size of the ideal evaluation's own rounding, not separable from it at any honest factor.
+"""
+import numpy as np
+
+from oracle import cqt_np as cq
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# tolerances.  TOL_LIN and TOL_DB_BROADBAND are 4 x the largest value the kernels gave on the MI355X over all cases of
+# tests/test_gpu_cqt_edges.py, within the caps TOL_LIN <= 5e-5 (a tenth of the smallest one-plane mutation, 8 x the ideal evaluation's worst
+# on whole clips) and TOL_DB_BROADBAND <= 1e-4.  The kernels sit where the arithmetic does: the ideal evaluation (exact accumulation) of the
+# two worst cases gives 1.1e-5 (linear, n = 3) and 3.2e-5 (dB, the loud clip of the batch).
+# ------------------------------------------------------------------------------------------------------------------------------
+TOL_LIN = 4.5e-5             # max |got - ref| / max(ref), decibels=False.  4 x 1.12e-5 (CQT 84 / 12 on a clip of 3 samples); whole clips <= 6.2e-6
+TOL_DB_BROADBAND = 1e-4      # max |got - ref| of the scaled dB map, noise clips.  The cap: 4 x the measured 3.10e-5 would be 1.24e-4
+TOL_DB_TONAL = 1e-3          # the TOL of tests/test_gpu_cqt.py, tonal synth_clip inputs.  Measured 3.98e-4 at most (ideal: 3.7e-4 there)
+MUTATION_FACTOR = 10         # every mutation moves the linear metric by at least this many TOL_LIN.  Smallest: 5.4e-4 (12 x)
+EXACT_TOL = 1e-10            # exact evaluation against cq.vqt, of the map maximum.  Measured: 2.5e-14 at most
+
+# Largest value per case family on the MI355X: (linear, dB on noise clips, dB on tonal clips or None).
+MEASURED = {
+    'sweep':   (1.12e-5, 2.39e-5, None),        # CQT 84 / 12 at n = 1 .. 9001, HCQT 72 / 12 from 2049; linear worst at n = 3, 5.9e-6 from n = 193 up
+    'plan':    (5.63e-6, 2.24e-5, 3.96e-4),     # the 17 plans, librosa 0.10
+    'plan09':  (5.04e-6, 1.78e-5, None),        # four of them under the reflecting pad
+    'reflect': (4.70e-6, 2.73e-5, None),        # the shortest clips the reflecting pad takes
+    'abi':     (6.20e-6, 3.10e-5, 3.98e-4),     # the strided batch: each clip alone and in the batch, both strides (the same bits)
+    'amin':    (3.97e-6, 1.88e-5, None),
+}
+
+C1 = cq.C1_HZ
+
+
+def bf16(x):
+    """Round to nearest even onto 8 mantissa bits (f32_to_bf16_rn), returned as float64."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000
+    return u.astype(np.uint32).view(np.float32).astype(np.float64)
+
+
+def f32(x):
+    return np.asarray(x, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def two_planes(x):
+    """hi = bf16(x), lo = bf16(x - hi) of fp32 values (split_bf16x2 / the host packer)."""
+    x = f32(x)
+    hi = bf16(x)
+    return hi, bf16(f32(x - hi))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the transform
+# ------------------------------------------------------------------------------------------------------------------------------
+MUTATIONS = ('weights_one_plane', 'signal_one_plane', 'taps_one_plane', 'drop_kstep', 'pad_shift', 'decim_reads_pad', 'decim_two_plane_input')
+
+
+def _decimate(y, taps, ypad=None):
+    """out[m] = sqrt(2) sum_k taps[k] y[2 m + k - HALF], zero beyond the ends (cq.decimate2 with the taps handed in).  `ypad`: (left,
+    right) samples that a wrong decimator would read there instead of zeros."""
+    half = cq.DECIM_HALF
+    n_out = (len(y) + 1) // 2
+    if ypad is None:
+        full = np.convolve(y, taps[::-1], mode='full')
+        return np.sqrt(2.0) * full[half:half + 2 * n_out:2]
+    ext = np.concatenate([ypad[0][-half:], y, ypad[1][:half + 1]])
+    off = len(ypad[0][-half:])
+    full = np.convolve(ext, taps[::-1], mode='full')
+    return np.sqrt(2.0) * full[half + off:half + off + 2 * n_out:2]
+
+
+def _pad(y, half, lv, shift=False):
+    if lv != '0.9':
+        return np.pad(y, (half, half), mode='constant')
+    # shift: the reflection taken one sample off (the edge sample repeated) -- numpy's 'symmetric'
+    return np.pad(y, (half, half), mode='symmetric' if shift else 'reflect')
+
+
+def folded_kernel(freqs, my_sr, sr_base, gamma, alpha, lengths_base):
+    """(nf, n_fft) complex: resp[k, t] = sum_n kern[k, n] ypad[t hop + n] is what `fft_basis @ rfft(frame)` of cq.vqt computes, final
+    1 / sqrt(length) included."""
+    basis, blen, n_fft = cq.wavelet_basis(freqs, my_sr, gamma, alpha)
+    basis = basis * (blen[:, None] / float(n_fft))
+    fb = cq.sparsify_rows(np.fft.fft(basis, n=n_fft, axis=1)[:, :n_fft // 2 + 1]) * np.sqrt(sr_base / my_sr)
+    e = np.exp(-2j * np.pi * np.outer(np.arange(n_fft // 2 + 1), np.arange(n_fft)) / n_fft)
+    return (fb @ e) / np.sqrt(lengths_base)[:, None], n_fft
+
+
+def vqt_time_domain(y, sr=22050, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, gamma=0.0, lv='0.10', mode='exact', mutate=None,
+                    kstep=None):
+    """Complex (n_bins, T), the shape and value of cq.vqt.  mode 'exact' | 'ideal'; mutate: one of MUTATIONS (ideal mode only);
+    kstep = (octave, 32-deep step) for 'drop_kstep' (default: octave 0, the middle step)."""
+    assert mode in ('exact', 'ideal') and (mutate is None or (mode == 'ideal' and mutate in MUTATIONS))
+    ideal = mode == 'ideal'
+    y = np.asarray(y, dtype=np.float64)
+    if fmin is None:
+        fmin = C1
+    n_octaves = int(np.ceil(float(n_bins) / bins_per_octave))
+    n_filters = min(bins_per_octave, n_bins)
+    freqs = fmin * 2.0 ** (np.arange(n_bins) / bins_per_octave)
+    alpha = cq.alpha_of(bins_per_octave, lv)
+    _, cutoff = cq.wavelet_lengths(freqs, sr, gamma, alpha)
+    assert cutoff <= sr / 2.0
+    count = cq.early_downsample_count(sr / 2.0, cutoff, hop_length, n_octaves)
+    taps = cq.decimation_filter()
+    if ideal:
+        taps = bf16(taps) if mutate == 'taps_one_plane' else f32(taps)
+        y = f32(y)
+
+    def decim(sig, half):
+        if ideal and mutate == 'decim_two_plane_input':
+            hi, lo = two_planes(sig)
+            sig = hi + lo
+        ypad = None
+        if mutate == 'decim_reads_pad' and lv == '0.9':
+            p = _pad(sig, max(half, cq.DECIM_HALF + 1), lv)
+            w = max(half, cq.DECIM_HALF + 1)
+            left, right = p[:w].copy(), p[w + len(sig):].copy()
+            left[:w - half] = 0.0                                   # only the pad that exists in the pyramid buffer (n_fft / 2 samples a side)
+            right[half:] = 0.0
+            ypad = (left, right)
+        out = _decimate(sig, taps, ypad)
+        return f32(out) if ideal else out
+
+    sr_base = sr / 2.0 ** count
+    lengths_all, _ = cq.wavelet_lengths(freqs, sr_base, gamma, alpha)
+    # the kernels pad every level by the largest n_fft / 2 of the plan; only the decimator mutation sees the difference
+    banks = []
+    my_sr = sr_base
+    for i in range(n_octaves):
+        sl = slice(-n_filters, None) if i == 0 else slice(-n_filters * (i + 1), -n_filters * i)
+        banks.append(folded_kernel(freqs[sl], my_sr, sr_base, gamma, alpha, lengths_all[sl]) + (sl,))
+        if (hop_length >> count) % (2 ** (i + 1)) == 0:
+            my_sr /= 2.0
+    pad_all = max(n_fft for _, n_fft, _ in banks) // 2
+    for _ in range(count):
+        y = decim(y, pad_all)
+    my_y, my_hop = y, hop_length // 2 ** count
+    resp = []
+    for i, (kern, n_fft, sl) in enumerate(banks):
+        yp = _pad(my_y, n_fft // 2, lv, shift=(mutate == 'pad_shift'))
+        T = 1 + (len(yp) - n_fft) // my_hop
+        frames = yp[np.arange(n_fft)[None, :] + my_hop * np.arange(T)[:, None]]           # (T, n_fft)
+        if not ideal:
+            r = kern @ frames.T
+        else:
+            k = kern.copy()
+            if mutate == 'drop_kstep':
+                o, ks = kstep if kstep is not None else (0, n_fft // 64)
+                if o == i:
+                    k[:, 32 * ks:32 * ks + 32] = 0.0
+            s_hi, s_lo = two_planes(frames)
+            if mutate == 'signal_one_plane':
+                s_lo = np.zeros_like(s_lo)
+            parts = []
+            for w in (k.real, k.imag):
+                w_hi, w_lo = two_planes(w)
+                if mutate == 'weights_one_plane':
+                    w_lo = np.zeros_like(w_lo)
+                parts.append(w_hi @ s_hi.T + w_hi @ s_lo.T + w_lo @ s_hi.T)
+            r = parts[0] + 1j * parts[1]
+        resp.append(r)
+        if my_hop % 2 == 0:
+            my_hop //= 2
+            if i + 1 < len(banks):
+                my_y = decim(my_y, pad_all)
+    max_col = min(r.shape[-1] for r in resp)
+    out = np.empty((n_bins, max_col), dtype=np.complex128)
+    end = n_bins
+    for r in resp:
+        n_oct = r.shape[0]
+        if end < n_oct:
+            out[:end] = r[-end:, :max_col]
+        else:
+            out[end - n_oct:end] = r[:, :max_col]
+        end -= n_oct
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the plan the library derives from a configuration, and the route its forward takes
+# ------------------------------------------------------------------------------------------------------------------------------
+def plan_layout(cfg):
+    """Per pyramid level {level: dict(n_fft, hop, ncols, banks)} and the plan's pad, as amtx_cqt_plan_create lays them out: harmonic h's
+    octave j sits on level early(h) + j; a level's n_fft is the largest of its banks'; (re, im) columns per filter."""
+    sr, hop, n_bins, bpo, gamma, lv = cfg['sr'], cfg['hop'], cfg['n_bins'], cfg['bpo'], cfg['gamma'], cfg['lv']
+    alpha = cq.alpha_of(bpo, lv)
+    n_oct = int(np.ceil(float(n_bins) / bpo))
+    nf = min(bpo, n_bins)
+    levels = {}
+    for h in sorted(cfg['harmonics']):
+        freqs = h * cfg['fmin'] * 2.0 ** (np.arange(n_bins) / bpo)
+        _, cutoff = cq.wavelet_lengths(freqs, sr, gamma, alpha)
+        assert cutoff <= sr / 2.0, (cfg, h)
+        c = cq.early_downsample_count(sr / 2.0, cutoff, hop, n_oct)
+        for j in range(n_oct):
+            hi, lo = n_bins - nf * j, max(0, n_bins - nf * (j + 1))
+            lengths, _ = cq.wavelet_lengths(freqs[lo:hi], sr / 2.0 ** (c + j), gamma, alpha)
+            n_fft = int(2.0 ** np.ceil(np.log2(max(lengths))))
+            L = levels.setdefault(c + j, dict(n_fft=0, hop=hop >> (c + j), ncols=0, banks=0, hop_exact=(hop >> (c + j)) << (c + j) == hop))
+            L['n_fft'] = max(L['n_fft'], n_fft)
+            L['ncols'] += 2 * (hi - lo)
+            L['banks'] += 1
+    n_levels = max(levels) + 1
+    pad = (max(L['n_fft'] for L in levels.values()) // 2 + 3) & ~3
+    return levels, n_levels, pad
+
+
+def level_lengths(n, n_levels):
+    out = [n]
+    for _ in range(1, n_levels):
+        out.append((out[-1] + 1) // 2)
+    return out
+
+
+def expected_route(cfg, n):
+    """'windowed128' | 'windowed256' | 'windowed128+256' | 'gemm:<reason>': the conditions of cqt_forward_impl, by hand.  Windowed needs at
+    most 10 levels and 16 harmonics and, on EVERY level that holds banks: n_fft 128 or 256, at most 256 columns, a power-of-two hop in
+    4 .. 512, and at least 4 samples of signal."""
+    levels, n_levels, _ = plan_layout(cfg)
+    lens = level_lengths(n, n_levels)
+    if n_levels > 10 or len(cfg['harmonics']) > 16:
+        return 'gemm:levels'
+    for l in sorted(levels):
+        L = levels[l]
+        if L['n_fft'] not in (128, 256):
+            return 'gemm:n_fft'
+        if L['ncols'] > 256:
+            return 'gemm:columns'
+        if L['hop'] < 4 or L['hop'] & (L['hop'] - 1) or L['hop'] > 512:
+            return 'gemm:hop'
+        if lens[l] < 4:
+            return 'gemm:short'
+    ks = sorted({L['n_fft'] for L in levels.values()})
+    return 'windowed' + '+'.join(str(k) for k in ks)
+
+
+def min_reflect_samples(cfg):
+    """Smallest clip the librosa-0.9 reflecting pad accepts: the last level must be longer than the plan's pad."""
+    _, n_levels, pad = plan_layout(cfg)
+    return pad * 2 ** (n_levels - 1) + 1
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# inputs
+# ------------------------------------------------------------------------------------------------------------------------------
+def _seed(name):
+    return sum((i + 1) * ord(ch) for i, ch in enumerate(name)) % (2 ** 31)
+
+
+def noise(n, name='noise', scale=0.1, draw=0):
+    """fp32 white noise, seeded by name; `draw` picks another sequence for the same name."""
+    return (scale * np.random.default_rng(_seed(name) + 1000003 * draw).standard_normal(n)).astype(np.float32)
+
+
+def tonal(n, i=9):
+    from amt_tools_amd.synth import synth_clip
+    return synth_clip(i, num_samples=n)
+
+
+def make_input(case):
+    if case['input'] == 'tonal':
+        return tonal(case['n'], case['draw'])
+    return noise(case['n'], case['seed_name'], draw=case['draw']) * np.float32(case['gain'])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# cases
+# ------------------------------------------------------------------------------------------------------------------------------
+def cfg(n_bins, bpo, sr=22050, hop=512, fmin=C1, gamma=0.0, harmonics=(1.0,), lv='0.10', default_gamma=False):
+    if default_gamma:
+        gamma = cq.default_gamma(bpo)
+    return dict(sr=sr, hop=hop, fmin=float(fmin), n_bins=n_bins, bpo=bpo, gamma=float(gamma), harmonics=tuple(float(h) for h in harmonics), lv=lv)
+
+
+HCQT_DEFAULT = (0.5, 1, 2, 3, 4, 5)
+HALF_TO_7 = (0.5, 1, 2, 3, 4, 5, 6, 7)
+HALF_TO_11 = (0.5,) + tuple(range(1, 12))
+SWEEP = (1, 2, 3, 192, 193, 300, 511, 512, 513, 1023, 2049, 4095, 4097, 9001)       # 192 / 193: the deepest of CQT 84 / 12's seven levels has 3 / 4 samples
+
+# (name, configuration, why, route at librosa 0.10, route at librosa 0.9 or None where the plan is not run under 0.9).  The routes are derived
+# by hand from the level layout and the conditions of cqt_forward_impl (expected_route restates them): tests/test_cqt_ref.py confirms each
+# against plan_layout, tests/test_gpu_cqt_edges.py against the kernels the profiler sees.  Level layouts (n_fft per level, top octave first):
+#   k128               128 x 7                      single-early   - 256 (level 0 empty)      single        256
+#   partial-78         512 256 x 6 (0.9: 256 x 7)   partial-30     512 256 256                sr16k         512 x 6
+#   sr44k              256 x 8, hops 512 .. 4       bpo36          1024 x 3                   bpo48         1024 x 2
+#   hop384             256 x 5, hops 384 .. 24      hop1024        256 x 7, hops 1024 .. 16   hop64 / 128   256 x 4 / 5, hops down to 8
+#   vqt-gamma5         256 256 256 128 64, hop 256  hvqt-123       256 .. 32 on 8 levels      hcqt-8        256 x 8, up to 6 banks / 144 columns
+#   hcqt-12            512 on level 0 (harmonics 7, 11: top octave from 1831 / 2877 Hz), 256 below; up to 9 banks / 216 columns
+PLANS = (
+    ('k128', cfg(42, 6), 'n_fft 128 on all 7 levels: cqt_basis_kernel<4>', 'windowed128', 'windowed128'),
+    ('single-early', cfg(8, 12, fmin=32 * C1), 'one level behind one early decimation', 'windowed256', None),
+    ('single', cfg(12, 12, fmin=64 * C1), 'one level, no decimation: the memset reset of the maxima', 'windowed256', 'windowed256'),
+    ('partial-78', cfg(78, 12), 'lowest octave holds 6 of 12 filters; n_fft 512 on top (0.10 only)', 'gemm:n_fft', 'windowed256'),
+    ('partial-30-hop256', cfg(30, 12, hop=256, fmin=8 * C1), 'partial lowest octave, mixed n_fft 512 / 256', 'gemm:n_fft', None),
+    ('sr16k', cfg(72, 12, sr=16000), '16 kHz: n_fft 512 throughout', 'gemm:n_fft', None),
+    ('sr44k', cfg(96, 12, sr=44100), '44.1 kHz: eight levels down to hop 4', 'windowed256', None),
+    ('bpo36', cfg(108, 36, fmin=4 * C1), 'n_fft 1024', 'gemm:n_fft', 'gemm:n_fft'),
+    ('bpo48', cfg(96, 48, fmin=4 * C1), 'n_fft 1024', 'gemm:n_fft', None),
+    ('hop384', cfg(60, 12, hop=384, fmin=2 * C1), 'hop not a power of two', 'gemm:hop', None),
+    ('hop1024', cfg(84, 12, hop=1024), 'hop above 512', 'gemm:hop', None),
+    ('hop64', cfg(48, 12, hop=64, fmin=4 * C1), 'small hop, windowed', 'windowed256', None),
+    ('hop128', cfg(60, 12, hop=128, fmin=2 * C1), 'small hop, windowed', 'windowed256', None),
+    ('vqt-gamma5', cfg(60, 12, hop=256, gamma=5.0), 'n_fft 64 on the lowest level', 'gemm:n_fft', None),
+    ('hvqt-123', cfg(60, 12, harmonics=(1, 2, 3), default_gamma=True), 'n_fft 64 / 32 levels, three harmonics', 'gemm:n_fft', None),
+    ('hcqt-8', cfg(48, 12, harmonics=HALF_TO_7), 'eight harmonics: more than one 128-column slice', 'windowed256', None),
+    ('hcqt-12', cfg(36, 12, harmonics=HALF_TO_11), 'twelve harmonics: up to 9 banks and 216 columns on a level', 'gemm:n_fft', None),
+)
+PLAN_N, PLAN_N_TONAL = 6000, 9001
+ABI_N = 9001
+
+# Which sequence of a case's seeded generator (noise) or which synth_clip (tonal) a case uses, where it is not the first.  The dB metric is
+# ill-conditioned by itself: a bin m dB below the map's maximum turns a linear error e (relative to the maximum) into 0.1086 e 10^(m / 20)
+# of the scaled map, white noise leaves a CQT's lowest octave 6 dB per octave below its highest, and a tonal clip has bins at the -80 dB
+# floor.  Chosen with the ideal evaluation alone (never with a kernel): the first draw whose ideal dB error is at most 2e-5 (noise; the
+# best of 30 draws, 2.8e-5, for the 192-bin map) or 4e-4 (tonal), so that half of each bound is met with room (tests/test_cqt_ref.py).
+DRAWS = {'sweep-cqt84-n2': 2,          # both samples of one sign: with opposite signs the two taps' one-plane errors cancel (1.8e-4)
+         'sweep-cqt84-n9001': 1, 'sweep-hcqt72-n2049': 1, 'sweep-hcqt72-n9001': 1, 'plan-partial-78-lv09-noise': 5, 'plan-sr44k-noise': 1,
+         'plan-bpo36-lv09-noise': 3, 'plan-hcqt-12-noise': 1, 'reflect-cqt84-shortest': 1, 'reflect-cqt192-shortest': 13,
+         'plan-k128-tonal': 2, 'plan-single-early-tonal': 1, 'plan-single-tonal': 4, 'plan-partial-78-tonal': 1, 'plan-partial-30-hop256-tonal': 1,
+         'plan-sr16k-tonal': 2, 'plan-sr44k-tonal': 1, 'plan-bpo36-tonal': 2, 'plan-bpo48-tonal': 0, 'plan-hop384-tonal': 1, 'plan-hop1024-tonal': 1,
+         'plan-hop64-tonal': 29, 'plan-hop128-tonal': 11, 'plan-vqt-gamma5-tonal': 1, 'plan-hvqt-123-tonal': 8, 'plan-hcqt-8-tonal': 16,
+         'plan-hcqt-12-tonal': 16}
+ABI_GAINS = (('noise', 1.0), ('quiet', 1e-3), ('loud', 1e4))      # a 140 dB spread around the silent clip of the batch
+ABI_PLANS = (('cqt84', cfg(84, 12)), ('hcqt72', cfg(72, 12, harmonics=HCQT_DEFAULT)), ('cqt84-lv09', cfg(84, 12, lv='0.9')))
+ABI_TONAL_DRAW, ABI_NOISE_DRAW = 59, 4      # synth_clip(59): the first of 60 whose ideal dB error is below 4e-4 on all three plans
+
+
+def _case(name, family, c, n, inp, route=None, seed_name=None, draw=None, gain=1.0):
+    return dict(name=name, family=family, cfg=c, n=n, input=inp, route=route, seed_name=seed_name or name,
+                draw=DRAWS.get(name, 0) if draw is None else draw, gain=gain)
+
+
+def cqt_cases():
+    """Every (configuration, clip) tests/test_gpu_cqt_edges.py compares with the oracle; case['route'] where the route is asserted."""
+    cases = []
+    for n in SWEEP:
+        cases.append(_case(f'sweep-cqt84-n{n}', 'sweep', cfg(84, 12), n, 'noise', 'gemm:short' if n <= 192 else 'windowed256'))
+    for n in SWEEP:
+        if n >= 2049:
+            cases.append(_case(f'sweep-hcqt72-n{n}', 'sweep', cfg(72, 12, harmonics=HCQT_DEFAULT), n, 'noise', 'windowed256'))
+    for name, c, _, route, route09 in PLANS:
+        cases.append(_case(f'plan-{name}-noise', 'plan', c, PLAN_N, 'noise', route))
+        cases.append(_case(f'plan-{name}-tonal', 'plan', c, PLAN_N_TONAL, 'tonal', None))
+        if route09:
+            c9 = dict(c, lv='0.9')
+            n9 = max(PLAN_N, min_reflect_samples(c9) + 37)
+            cases.append(_case(f'plan-{name}-lv09-noise', 'plan09', c9, n9, 'noise', route09))
+    for c, tag in ((cfg(84, 12, lv='0.9'), 'cqt84'), (cfg(192, 24, lv='0.9'), 'cqt192')):
+        cases.append(_case(f'reflect-{tag}-shortest', 'reflect', c, min_reflect_samples(c), 'noise', None))
+    for tag, c in ABI_PLANS:                       # the clips of the strided batch, each on its own
+        for kind, gain in ABI_GAINS:
+            cases.append(_case(f'abi-{tag}-{kind}', 'abi', c, ABI_N, 'noise', None, seed_name='abi-batch', draw=ABI_NOISE_DRAW, gain=gain))
+        cases.append(_case(f'abi-{tag}-tonal', 'abi', c, ABI_N, 'tonal', None, draw=ABI_TONAL_DRAW))
+    assert len({c['name'] for c in cases}) == len(cases)
+    return cases
+
+
+def is_module_kind(c):
+    """('CQT' | 'VQT' | 'HCQT' | 'HVQT') a configuration is built from in amt_tools_amd.features."""
+    multi = len(c['harmonics']) > 1
+    if c['gamma'] == 0.0:
+        return 'HCQT' if multi else 'CQT'
+    return 'HVQT' if multi else 'VQT'
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# evaluation of a whole case (all harmonics), metrics
+# ------------------------------------------------------------------------------------------------------------------------------
+def oracle_mag(c, y):
+    """Linear magnitudes (H, n_bins, T) of the oracle, the harmonics truncated to the common expected frame count like cq.hvqt_process_audio."""
+    hs = sorted(c['harmonics'])
+    kw = dict(sample_rate=c['sr'], hop_length=c['hop'], n_bins=c['n_bins'], bins_per_octave=c['bpo'], gamma=c['gamma'], decibels=False, lv=c['lv'])
+    if len(hs) == 1:
+        return cq.vqt_process_audio(y, fmin=hs[0] * c['fmin'], **kw)
+    return cq.hvqt_process_audio(y, fmin=c['fmin'], harmonics=list(hs), **kw)
+
+
+def ref_mag(c, y, mode, mutate=None, kstep=None):
+    """The same map from vqt_time_domain."""
+    hs = sorted(c['harmonics'])
+    maps = [np.abs(vqt_time_domain(y, c['sr'], c['hop'], h * c['fmin'], c['n_bins'], c['bpo'], c['gamma'], c['lv'], mode, mutate, kstep)) for h in hs]
+    t = min(m.shape[-1] for m in maps)
+    if len(hs) > 1:
+        t = min([t] + [cq.vqt_expected_frames(len(y), c['sr'], c['hop'], h * c['fmin'], c['n_bins'], c['bpo'], c['gamma']) for h in hs])
+    return np.stack([m[:, :t] for m in maps])
+
+
+def to_db(mag):
+    """(H, n_bins, T) linear -> the scaled dB map, every harmonic against its own maximum."""
+    return np.concatenate([cq.post_proc(cq.amplitude_to_db(m)) for m in mag], axis=0)
+
+
+def lin_metric(got, ref, rows=slice(None), frames=None):
+    """max over harmonics of max |got - ref| / max(ref); `rows` / `frames` restrict where the difference is looked for, not the maximum."""
+    worst = 0.0
+    for g, r in zip(np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)):
+        d = np.abs(g - r)[rows]
+        if frames is not None:
+            d = d[:, frames]
+        worst = max(worst, float(d.max()) / max(float(r.max()), 1e-300))
+    return worst
+
+
+def db_metric(got, ref):
+    return float(np.abs(np.asarray(got, dtype=np.float64) - np.asarray(ref, dtype=np.float64)).max())
