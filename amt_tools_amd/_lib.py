@@ -1,5 +1,5 @@
 """
-ctypes binding of the amtx C ABI (include/amtx.h -> amt_tools_amd/csrc/libamtx.so).
+ctypes binding of the amtx C ABI (include/amtx.h and the headers beside it, EXTRA_HEADERS -> amt_tools_amd/csrc/libamtx.so).
 
 The product path has NO fallback: if the shared library is missing or a call fails, an exception is
 raised.  Pointers handed to the library are raw device addresses (`tensor.data_ptr()`), the stream is
@@ -12,6 +12,9 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMTX_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libamtx.so')      # AMTX_LIB_PATH: a debug / timing build of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'amtx.h')
+# Further headers of the same library, bound the same way.  signatures() / declared_symbols() stay the table of amtx.h alone (pinned by
+# tests/golden/abi_signatures.json); each of these has its own pinned table (tests/golden/abi_signatures_tracks.json).
+EXTRA_HEADERS = ('amtx_tracks.h',)
 
 _lib = None
 
@@ -108,11 +111,30 @@ def declared_symbols():
     return sorted(signatures())
 
 
+_extra_signatures = None
+
+
+def extra_signatures():
+    """{header name: parse_header of it} for EXTRA_HEADERS, read once per process.  A name declared twice across headers raises."""
+    global _extra_signatures
+    if _extra_signatures is None:
+        tables, seen = {}, set(signatures())
+        for header in EXTRA_HEADERS:
+            with open(os.path.join(os.path.dirname(HEADER_PATH), header)) as f:
+                tables[header] = parse_header(f.read())
+            twice = seen & set(tables[header])
+            if twice:
+                raise AmtxError(f'{sorted(twice)[0]} is declared in {header} and in another header')
+            seen |= set(tables[header])
+        _extra_signatures = tables
+    return _extra_signatures
+
+
 _funcs = {}            # name -> (function, number of parameters, its return value goes through check, it ends in `void* stream`)
 
 
 def lib():
-    """Load libamtx.so (once) and give every function include/amtx.h declares its restype / argtypes.  Raises AmtxError when the HIP
+    """Load libamtx.so (once) and give every function include/amtx.h and EXTRA_HEADERS declare its restype / argtypes.  Raises AmtxError when the HIP
     extension has not been built, when it lacks a declared function, or when the header holds a declaration parse_header cannot map."""
     global _lib
     if _lib is None:
@@ -124,7 +146,10 @@ def lib():
             handle = C.CDLL(LIB_PATH)
         except OSError as e:
             raise AmtxError(f'cannot load {LIB_PATH}: {e}') from e
-        for name, (letters, stream) in signatures().items():
+        bound = dict(signatures())
+        for table in extra_signatures().values():
+            bound.update(table)
+        for name, (letters, stream) in bound.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:
@@ -146,7 +171,7 @@ def call(name, *args, device=None):
     try:
         fn, nargs, checked, stream = _funcs[name]
     except KeyError:
-        raise AmtxError(f'include/amtx.h declares no function {name}') from None
+        raise AmtxError(f'include/amtx.h and {", ".join(EXTRA_HEADERS)} declare no function {name}') from None
     fill_stream = stream and device is not None
     if len(args) + fill_stream != nargs:
         raise TypeError(f'{name} takes {nargs - fill_stream} arguments{" besides the stream" if fill_stream else ""} ({len(args)} given)')

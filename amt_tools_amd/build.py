@@ -21,7 +21,7 @@ def _sources():
 
 def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
-    hdrs.append(os.path.join(ROOT, 'include', 'amtx.h'))
+    hdrs += [os.path.join(ROOT, 'include', f) for f in os.listdir(os.path.join(ROOT, 'include')) if f.endswith('.h')]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -18,6 +18,7 @@
 // Algorithmic HBM bytes per frame: hop*4 read + n_out*4 written (2048 + 916 B for mel-229).
 
 #include "amtx_common.h"
+#include "../../include/amtx_tracks.h"
 
 #include <math.h>
 #include <algorithm>
@@ -109,6 +110,48 @@ __device__ __forceinline__ float fetch_padded(const float* clip, int64_t idx, in
         if (idx >= 0 && idx < n) return clip[idx];
     }
     return 0.0f;
+}
+
+// Where the frames of one clip (= one output map of `num_frames` rows) come from.  Output row t of the clip is frame `first + t` of the
+// track `base[0 .. len)`: its window starts at sample (first + t) * hop - half of that track, and every read is bounded by the TRACK
+// (full-window fast path or fetch_padded), so the plan's padding shows only where the track itself ends.  Rows t >= frames carry no
+// frame.  The header depends on the block alone (blockIdx and kernel arguments): it lives in scalar registers.
+struct ClipSrc {
+    const float* base;
+    int64_t len, first, frames;
+};
+
+// The power kernels take the header from one of two sources (template switch SRC):
+// equal clips, amtx_spec_power: clip b is the whole track audio + b * audio_stride of num_samples samples, all `num_frames` rows valid;
+struct EqualClips {
+    static constexpr bool kClips = false;
+    int64_t num_samples, audio_stride;
+    __device__ __forceinline__ ClipSrc at(const float* audio, unsigned clip_idx, int64_t num_frames) const {
+        return {audio + (int64_t)clip_idx * audio_stride, num_samples, 0, num_frames};
+    }
+};
+// clips cut from longer tracks, amtx_spec_power_clips: a device table of {track_start, track_len, first_frame, frames} per clip.  Rows
+// t >= frames are written as zeros, and `power` may be null (maxima only).
+struct ClipTable {
+    static constexpr bool kClips = true;
+    const int64_t* desc;
+    __device__ __forceinline__ ClipSrc at(const float* audio, unsigned clip_idx, int64_t num_frames) const {
+        const int64_t* d = desc + 4 * (int64_t)clip_idx;
+        return {audio + d[0], d[1], d[2], d[3] < num_frames ? d[3] : num_frames};      // never a row past the clip's map, whatever the table says
+    }
+};
+
+// Clips only: the rows a wave owns (t = chunk * fpw * WAVES + i * WAVES + wave, i < fpw) that lie past the clip's frames carry no frame
+// and are written as zeros.  Called after the frame loop, when the frame pipeline's registers are dead, or instead of it by a block
+// whose whole chunk lies past the frames.
+__device__ __forceinline__ void zero_rows_past(float* __restrict__ clip_power, int64_t frames, int64_t num_frames, unsigned chunk, int fpw,
+                                               int wave, int lane, int n_out) {
+    for (int i = 0; i < fpw; ++i) {
+        const int64_t t = ((int64_t)chunk * fpw + i) * WAVES + wave;
+        if (t < frames || t >= num_frames) continue;
+        float* row = clip_power + t * n_out;
+        for (int k = lane; k < n_out; k += 64) row[k] = 0.0f;
+    }
 }
 
 // |E + W O|^2 and |E - W O|^2 for the real-FFT untangling of the pair (Z[k], Z[M-k]).
@@ -216,9 +259,8 @@ __device__ unsigned long long g_spec_prof[8];
 #define SPEC_TICK(SLOT) do {} while (0)
 #endif
 
-template <int FPW, bool MEL, bool MELLDS>
-__global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const float* __restrict__ audio, int64_t num_samples,
-                                                         int64_t audio_stride, int64_t num_frames,
+template <int FPW, bool MEL, bool MELLDS, class SRC>
+__global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const float* __restrict__ audio, SRC src, int64_t num_frames,
                                                          float* __restrict__ power, unsigned* __restrict__ clip_max) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -236,7 +278,14 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
     const unsigned logical = xcd_remap(blockIdx.x, gridDim.x);
     const unsigned clip_idx = logical / chunks;
     const unsigned chunk = logical % chunks;
-    const float* clip = audio + (int64_t)clip_idx * audio_stride;
+    const ClipSrc cs = src.at(audio, clip_idx, num_frames);
+    const float* clip = cs.base;
+    const int64_t num_samples = cs.len;
+    const bool store = !SRC::kClips || power != nullptr;
+    if (SRC::kClips && (int64_t)chunk * FPB >= cs.frames) {   // the whole chunk lies past the clip's frames (block-uniform): zeros, nothing staged
+        if (store) zero_rows_past(power + (int64_t)clip_idx * num_frames * p.n_out, cs.frames, num_frames, chunk, FPW, wave, lane, p.n_out);
+        return;
+    }
 
     // block-shared tables: untangling twiddles exp(-2 pi i k / 2048) for k < 512 (k + 512 is the same value times -i: a swap and
     // a sign, applied where it is used) and the pass-B twiddles
@@ -270,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
     float xr[16], xi[16];
 #define SPEC_LOAD_FRAME(T_)                                                                              \
     do {                                                                                                 \
-        const int64_t s0_ = (T_) * p.hop - half;                                                         \
+        const int64_t s0_ = (cs.first + (T_)) * p.hop - half;                                            \
         if (s0_ >= 0 && s0_ + NFFT <= num_samples) {                                                     \
             const float* src_ = clip + s0_ + 2 * lane;                                                   \
             _Pragma("unroll") for (int n1 = 0; n1 < 16; ++n1) { xr[n1] = src_[128 * n1]; xi[n1] = src_[128 * n1 + 1]; } \
@@ -285,7 +334,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
 
     {
         const int64_t tfirst = (int64_t)chunk * FPB + wave;
-        if (tfirst < num_frames) SPEC_LOAD_FRAME(tfirst);
+        if (tfirst < cs.frames) SPEC_LOAD_FRAME(tfirst);
     }
 
 #ifdef AMTX_SPEC_TIMING
@@ -295,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
 #pragma unroll 1
     for (int i = 0; i < FPW; ++i) {
         const int64_t t = (int64_t)chunk * FPB + i * WAVES + wave;
-        if (t >= num_frames) break;
+        if (t >= cs.frames) break;
 #ifdef AMTX_SPEC_TIMING
         prof_t = __builtin_readcyclecounter();
         prof_acc[5] += 1;
@@ -307,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
         for (int n1 = 0; n1 < 16; ++n1) v[n1] = make_float2(xr[n1] * wre[n1], xi[n1] * wim[n1]);
         {
             const int64_t tnext = t + WAVES;
-            if (i + 1 < FPW && tnext < num_frames) SPEC_LOAD_FRAME(tnext);
+            if (i + 1 < FPW && tnext < cs.frames) SPEC_LOAD_FRAME(tnext);
         }
 
         SPEC_TICK(0);
@@ -350,14 +399,14 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
             for (int r = 0; r < MAX_MEL_ROUNDS; ++r) {
                 const int row = r < rounds ? mrow[r * 64 + lane] : -1;
                 if (row >= 0) {
-                    out_row[row] = res[r];
+                    if (store) out_row[row] = res[r];
                     run_max = fmaxf(run_max, res[r]);
                 }
             }
         } else {
             for (int k = lane; k < p.n_out; k += 64) {
                 const float val = pb[pidx(k)];
-                out_row[k] = val;
+                if (store) out_row[k] = val;
                 run_max = fmaxf(run_max, val);
             }
         }
@@ -365,6 +414,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
         SPEC_TICK(4);
     }
 #undef SPEC_LOAD_FRAME
+    if (SRC::kClips && store) zero_rows_past(power + (int64_t)clip_idx * num_frames * p.n_out, cs.frames, num_frames, chunk, FPW, wave, lane, p.n_out);
 #ifdef AMTX_SPEC_TIMING
     if (threadIdx.x == 0)
         for (int i = 0; i < 6; ++i) atomicAdd(&g_spec_prof[i], prof_acc[i]);
@@ -388,13 +438,15 @@ __global__ __launch_bounds__(256, 2) void spec_power_kernel(SpecDev p, const flo
 constexpr int RING_HOP = 512;
 constexpr int RING_ELEMS = 4096;                 // floats; window of an iteration: 3 hops + 2048 = 3584, new per iteration: 2048
 
-template <int FPW, int S0, int S1, int S2, int S3>
-__global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, const float* __restrict__ audio, int64_t num_samples,
-                                                              int64_t audio_stride, int64_t num_frames, float* __restrict__ power,
-                                                              unsigned* __restrict__ clip_max) {
+template <int FPW, int S0, int S1, int S2, int S3, class SRC>
+__global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, const float* __restrict__ audio, SRC src, int64_t num_frames,
+                                                              float* __restrict__ power, unsigned* __restrict__ clip_max) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NSLOT = S0 + S1 + S2 + S3;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    // the clips form has no register to spare (launch bound 256): its wave index, and with it the frame index, the row pointer and the
+    // wave's LDS bases, are pinned to scalar registers
+    const int wave = SRC::kClips ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     float2* xb = reinterpret_cast<float2*>(smem) + wave * XB_ELEMS;
     float* pb = reinterpret_cast<float*>(smem + WAVES * XB_ELEMS * sizeof(float2)) + wave * PB_ELEMS;
     float2* twp = reinterpret_cast<float2*>(smem + WAVES * XB_ELEMS * sizeof(float2) + WAVES * PB_ELEMS * sizeof(float));
@@ -406,7 +458,14 @@ __global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, cons
     const unsigned chunks = (unsigned)((num_frames + FPB - 1) / FPB);
     const unsigned logical = xcd_remap(blockIdx.x, gridDim.x);
     const unsigned clip_idx = logical / chunks, chunk = logical % chunks;
-    const float* clip = audio + (int64_t)clip_idx * audio_stride;
+    const ClipSrc cs = src.at(audio, clip_idx, num_frames);
+    const float* clip = cs.base;
+    const int64_t num_samples = cs.len;
+    const bool store = !SRC::kClips || power != nullptr;
+    if (SRC::kClips && (int64_t)chunk * FPB >= cs.frames) {   // the whole chunk lies past the clip's frames (block-uniform): zeros, nothing staged
+        if (store) zero_rows_past(power + (int64_t)clip_idx * num_frames * p.n_out, cs.frames, num_frames, chunk, FPW, wave, lane, p.n_out);
+        return;
+    }
 
     for (int i = tid; i < M / 2; i += 256) twp[i] = p.tw_post[i];
     if (tid < 64) tw2l[tid] = p.tw_fft[(16 * (tid >> 4) * (tid & 15)) & (M - 1)];
@@ -431,9 +490,9 @@ __global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, cons
     for (int r = 0; r < 4; ++r) orow[r] = p.mel_row[r * 64 + lane];
     for (int i = pidx(M + 1) + lane; i < PB_ELEMS; i += 64) pb[i] = 0.0f;
 
-    // ---- sample staging.  sb = first sample of the block's first frame; sample s lives at ring[(s - sb) & (RING_ELEMS - 1)].
+    // ---- sample staging.  sb = first sample (of the track) of the block's first frame; sample s lives at ring[(s - sb) & (RING_ELEMS - 1)].
     const int64_t half = p.center ? NFFT / 2 : 0;
-    const int64_t sb = (int64_t)chunk * FPB * RING_HOP - half;
+    const int64_t sb = (cs.first + (int64_t)chunk * FPB) * RING_HOP - half;
     // 2048 samples starting at s0: thread tid takes the pairs (2 tid + 512 m, + 1), m = 0..3 (consecutive lanes, consecutive 8 bytes)
     float2 pre[4];
 #define RING_FETCH(S0_)                                                                                  \
@@ -466,7 +525,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, cons
 #pragma unroll 1
     for (int i = 0; i < FPW; ++i) {
         const int64_t t = (int64_t)chunk * FPB + i * WAVES + wave;
-        const bool active = t < num_frames;
+        const bool active = t < cs.frames;
         __syncthreads();                                      // window i is in the ring (and the tables, first time round)
         float2 v[16];
         {
@@ -509,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, cons
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (orow[r] >= 0) {
-                out_row[orow[r]] = res[r];
+                if (store) out_row[orow[r]] = res[r];
                 run_max = fmaxf(run_max, res[r]);
             }
         }
@@ -517,6 +576,7 @@ __global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, cons
     }
 #undef RING_FETCH
 #undef RING_STORE
+    if (SRC::kClips && store) zero_rows_past(power + (int64_t)clip_idx * num_frames * p.n_out, cs.frames, num_frames, chunk, FPW, wave, lane, p.n_out);
     run_max = wave_max_f32(run_max);
     if (lane == 0 && run_max > 0.0f) atomicMax(clip_max + clip_idx, __float_as_uint(run_max));
 }
@@ -525,9 +585,9 @@ __global__ __launch_bounds__(256, 2) void spec_power_ring_kernel(SpecDev p, cons
 // frame, the n_fft real samples as m = n_fft / 2 complex points in a wave-private LDS buffer, in-place radix-2 decimation-in-time
 // (bit-reversed on the way in, log2(m) butterfly passes separated by wave-level LDS ordering only), the same real-FFT untangling and
 // the same lane-per-row mel gather as the tuned 2048 kernel.  Not tuned: ~log2(m) LDS round trips per frame instead of two.
-__global__ __launch_bounds__(256) void spec_power_pow2_kernel(SpecDev p, int log2m, int fpw, const float* __restrict__ audio, int64_t num_samples,
-                                                           int64_t audio_stride, int64_t num_frames, float* __restrict__ power,
-                                                           unsigned* __restrict__ clip_max, int mel) {
+template <class SRC>
+__global__ __launch_bounds__(256) void spec_power_pow2_kernel(SpecDev p, int log2m, int fpw, const float* __restrict__ audio, SRC src,
+                                                           int64_t num_frames, float* __restrict__ power, unsigned* __restrict__ clip_max, int mel) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = 1 << log2m, nfft = 2 * m;
@@ -537,15 +597,22 @@ __global__ __launch_bounds__(256) void spec_power_pow2_kernel(SpecDev p, int log
     const int fpb = fpw * WAVES;
     const unsigned chunks = (unsigned)((num_frames + fpb - 1) / fpb);
     const unsigned clip_idx = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
-    const float* clip = audio + (int64_t)clip_idx * audio_stride;
+    const ClipSrc cs = src.at(audio, clip_idx, num_frames);
+    const float* clip = cs.base;
+    const int64_t num_samples = cs.len;
+    const bool store = !SRC::kClips || power != nullptr;
+    if (SRC::kClips && (int64_t)chunk * fpb >= cs.frames) {   // the whole chunk lies past the clip's frames (block-uniform): zeros, nothing staged
+        if (store) zero_rows_past(power + (int64_t)clip_idx * num_frames * p.n_out, cs.frames, num_frames, chunk, fpw, wave, lane, p.n_out);
+        return;
+    }
     const int rounds = mel ? (p.n_mels + 63) / 64 : 0;
     for (int i = m + 1 + lane; i < pb_elems; i += 64) pb[i] = 0.0f;
     float run_max = 0.0f;
     const int64_t half = p.center ? nfft / 2 : 0;
     for (int i = 0; i < fpw; ++i) {
         const int64_t t = (int64_t)chunk * fpb + i * WAVES + wave;
-        if (t >= num_frames) break;
-        const int64_t s0 = t * p.hop - half;
+        if (t >= cs.frames) break;
+        const int64_t s0 = (cs.first + t) * p.hop - half;
         // windowed samples -> bit-reversed complex points
         for (int j = lane; j < m; j += 64) {
             const float xr = fetch_padded(clip, s0 + 2 * j, num_samples, p.pad_mode) * p.window[2 * j];
@@ -582,19 +649,20 @@ __global__ __launch_bounds__(256) void spec_power_pow2_kernel(SpecDev p, int log
                 float acc = 0.0f;
                 for (int j = 0; j < p.round_max[r]; ++j) acc = fmaf(wt[j * 64], pb[min(start + j, pb_elems - 1)], acc);
                 if (row >= 0) {
-                    out_row[row] = acc;
+                    if (store) out_row[row] = acc;
                     run_max = fmaxf(run_max, acc);
                 }
             }
         } else {
             for (int k = lane; k < p.n_out; k += 64) {
                 const float val = pb[k];
-                out_row[k] = val;
+                if (store) out_row[k] = val;
                 run_max = fmaxf(run_max, val);
             }
         }
         wave_lds_sync();
     }
+    if (SRC::kClips && store) zero_rows_past(power + (int64_t)clip_idx * num_frames * p.n_out, cs.frames, num_frames, chunk, fpw, wave, lane, p.n_out);
     run_max = wave_max_f32(run_max);
     if (lane == 0 && run_max > 0.0f) atomicMax(clip_max + clip_idx, __float_as_uint(run_max));
 }
@@ -954,15 +1022,11 @@ extern "C" int amtx_spec_filterbank(const amtx_spec_plan* plan, float* host_out)
     return AMTX_OK;
 }
 
-extern "C" int amtx_spec_power(const amtx_spec_plan* plan, const float* audio, int64_t num_samples, int64_t audio_stride,
-                               int batch, float* power, float* clip_max, void* stream_) {
-    AMTX_REQUIRE(plan && audio && power && clip_max, "amtx_spec_power: null argument");
-    AMTX_REQUIRE(batch > 0 && num_samples > 0 && audio_stride >= num_samples, "amtx_spec_power: bad batch/num_samples/stride");
-    if (plan->pad_mode == AMTX_PAD_REFLECT)
-        AMTX_REQUIRE(num_samples > plan->n_fft / 2, "amtx_spec_power: reflect padding needs more than n_fft/2 samples");
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t T = amtx_spec_num_frames(plan, num_samples);
-    AMTX_REQUIRE(T > 0, "amtx_spec_power: clip too short for one frame");
+// K1 launch for either source of the clips' headers (EqualClips / ClipTable): the power-of-two kernel for n_fft != 2048, the ring kernel
+// for the BASELINE log-mel shape, the general kernel otherwise.  T = rows per clip; `what` names the entry point in messages.
+template <class SRC>
+static int spec_power_launch(const amtx_spec_plan* plan, const float* audio, SRC src, int batch, int64_t T, float* power, float* clip_max,
+                             hipStream_t stream, const char* what) {
     AMTX_CHECK_HIP(hipMemsetAsync(clip_max, 0, sizeof(float) * batch, stream));
     if (plan->n_fft != NFFT) {
         int log2m = 0;
@@ -970,11 +1034,12 @@ extern "C" int amtx_spec_power(const amtx_spec_plan* plan, const float* audio, i
         const int m = plan->n_fft / 2, fpw = 8;
         const int64_t chunks_g = (T + fpw * WAVES - 1) / (fpw * WAVES);
         const int64_t nblocks_g = chunks_g * batch;
-        AMTX_REQUIRE(nblocks_g < (1ll << 31), "amtx_spec_power: grid too large");
+        AMTX_REQUIRE(nblocks_g < (1ll << 31), "%s: grid too large", what);
         const size_t lds_g = (size_t)WAVES * m * sizeof(float2) + (size_t)WAVES * (m + 1 + 128 + 3) * sizeof(float);
-        AMTX_GRANT_LDS(spec_power_pow2_kernel, lds_g);
-        hipLaunchKernelGGL(spec_power_pow2_kernel, dim3((unsigned)nblocks_g), dim3(256), lds_g, stream, plan->dev, log2m, fpw, audio, num_samples,
-                           audio_stride, T, power, (unsigned*)clip_max, plan->n_mels > 0 ? 1 : 0);
+        auto kern = spec_power_pow2_kernel<SRC>;
+        AMTX_GRANT_LDS(kern, lds_g);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks_g), dim3(256), lds_g, stream, plan->dev, log2m, fpw, audio, src, T, power,
+                           (unsigned*)clip_max, plan->n_mels > 0 ? 1 : 0);
         AMTX_CHECK_LAUNCH();
         return AMTX_OK;
     }
@@ -982,7 +1047,7 @@ extern "C" int amtx_spec_power(const amtx_spec_plan* plan, const float* audio, i
     constexpr int FPB = FPW * WAVES;
     const int64_t chunks = (T + FPB - 1) / FPB;
     const int64_t nblocks = chunks * batch;
-    AMTX_REQUIRE(nblocks < (1ll << 31), "amtx_spec_power: grid too large");
+    AMTX_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", what);
     const int mel_rounds = plan->n_mels > 0 ? (plan->n_mels + 63) / 64 : 0;
     const int mel_slots = mel_rounds > 0 ? plan->dev.round_off[mel_rounds - 1] + plan->dev.round_max[mel_rounds - 1] : 0;
     const bool mel_lds = mel_rounds > 0 && mel_slots <= MEL_LDS_MAX_SLOTS;
@@ -990,8 +1055,7 @@ extern "C" int amtx_spec_power(const amtx_spec_plan* plan, const float* audio, i
                        2 * 64 * MAX_MEL_ROUNDS * sizeof(int) + (mel_lds ? (size_t)mel_slots * 64 * sizeof(float) : 0);
     auto launch = [&](auto kern) -> int {
         AMTX_GRANT_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds, stream, plan->dev, audio, num_samples, audio_stride, T, power,
-                           (unsigned*)clip_max);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds, stream, plan->dev, audio, src, T, power, (unsigned*)clip_max);
         return AMTX_OK;
     };
     // the BASELINE log-mel shape (hop 512, four mel rounds of 4 / 8 / 20 / 32 tap slots = librosa's 229 Slaney rows at 22.05 kHz) has its own
@@ -1000,22 +1064,41 @@ extern "C" int amtx_spec_power(const amtx_spec_plan* plan, const float* audio, i
     const auto& dv = plan->dev;
     if (!no_ring && plan->hop == RING_HOP && mel_rounds == 4 && dv.round_max[0] == 4 && dv.round_max[1] == 8 && dv.round_max[2] == 20 &&
         dv.round_max[3] == 32 && dv.round_off[1] == 4 && dv.round_off[2] == 12 && dv.round_off[3] == 32) {
-        auto kern = spec_power_ring_kernel<FPW, 4, 8, 20, 32>;
+        auto kern = spec_power_ring_kernel<FPW, 4, 8, 20, 32, SRC>;
         const size_t lds_r = WAVES * XB_ELEMS * sizeof(float2) + WAVES * PB_ELEMS * sizeof(float) + (M / 2 + 64) * sizeof(float2) +
                              64 * 4 * sizeof(int) + RING_ELEMS * sizeof(float);
         AMTX_GRANT_LDS(kern, lds_r);
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_r, stream, plan->dev, audio, num_samples, audio_stride, T, power,
-                           (unsigned*)clip_max);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_r, stream, plan->dev, audio, src, T, power, (unsigned*)clip_max);
         AMTX_CHECK_LAUNCH();
         return AMTX_OK;
     }
     int rc;
-    if (mel_lds) rc = launch(spec_power_kernel<FPW, true, true>);
-    else if (plan->n_mels > 0) rc = launch(spec_power_kernel<FPW, true, false>);
-    else rc = launch(spec_power_kernel<FPW, false, false>);
+    if (mel_lds) rc = launch(spec_power_kernel<FPW, true, true, SRC>);
+    else if (plan->n_mels > 0) rc = launch(spec_power_kernel<FPW, true, false, SRC>);
+    else rc = launch(spec_power_kernel<FPW, false, false, SRC>);
     if (rc != AMTX_OK) return rc;
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
+}
+
+extern "C" int amtx_spec_power(const amtx_spec_plan* plan, const float* audio, int64_t num_samples, int64_t audio_stride,
+                               int batch, float* power, float* clip_max, void* stream_) {
+    AMTX_REQUIRE(plan && audio && power && clip_max, "amtx_spec_power: null argument");
+    AMTX_REQUIRE(batch > 0 && num_samples > 0 && audio_stride >= num_samples, "amtx_spec_power: bad batch/num_samples/stride");
+    if (plan->pad_mode == AMTX_PAD_REFLECT)
+        AMTX_REQUIRE(num_samples > plan->n_fft / 2, "amtx_spec_power: reflect padding needs more than n_fft/2 samples");
+    const int64_t T = amtx_spec_num_frames(plan, num_samples);
+    AMTX_REQUIRE(T > 0, "amtx_spec_power: clip too short for one frame");
+    return spec_power_launch(plan, audio, EqualClips{num_samples, audio_stride}, batch, T, power, clip_max, (hipStream_t)stream_, "amtx_spec_power");
+}
+
+// Clips cut from longer tracks (include/amtx_tracks.h).  The descriptor table is device memory: its contents are validated where it is built
+// (amt_tools_amd/tracks.py, clip_descriptors), not here.
+extern "C" int amtx_spec_power_clips(const amtx_spec_plan* plan, const float* audio, const int64_t* desc, int batch, int64_t num_frames,
+                                     float* power, float* clip_max, void* stream_) {
+    AMTX_REQUIRE(plan && audio && desc && clip_max, "amtx_spec_power_clips: null argument");
+    AMTX_REQUIRE(batch > 0 && num_frames > 0, "amtx_spec_power_clips: bad batch/num_frames");
+    return spec_power_launch(plan, audio, ClipTable{desc}, batch, num_frames, power, clip_max, (hipStream_t)stream_, "amtx_spec_power_clips");
 }
 
 extern "C" int amtx_spec_scale(const amtx_spec_plan* plan, const float* power, const float* clip_max, const float* ref,

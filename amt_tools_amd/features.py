@@ -9,9 +9,10 @@ paper scripts can be handed these objects unchanged:
 
     process_audio(audio: np.ndarray (N,)) -> np.ndarray (C, F, T) float32      # seam S1
 
-plus two additions the reference does not have:
+plus additions the reference does not have:
 
     process_batch(audio: torch.Tensor (B, N) on the GPU) -> torch.Tensor (B, C, F, T)   # batched, stays on device
+    process_clips(clips: tracks.TrackClips) -> torch.Tensor (B, 1, F, T)                # frames cut from resident tracks, track-level dB
     frontend()  -> nn.Module for `TranscriptionModel.frontend` (models/common.py:56-57,107-120): the
                    fused seam -- features are computed on the device inside `pre_proc`.
 
@@ -272,6 +273,34 @@ class _SpecPlanOwner(object):
         power, clip_max = self.power_batch(audio)
         return self.scale_batch(power, clip_max, ref, model_layout)
 
+    # ---- clips cut from device-resident tracks (amt_tools_amd/tracks.py) -----------------------------------
+    def power_clips(self, clips):
+        """K1 on a TrackClips: (power (B,T,F) fp32, track_max (B,)).  Row t of clip b is frame first_frame[b] + t of its track, bit for
+        bit the row amtx_spec_power gives for the whole track; track_max is the maximum of the clip's TRACK (TrackBank.db_ref).  The clips'
+        OWN maxima, which the kernel also reduces (the ABI takes no null clip_max), are dropped on purpose: a bank exists for the track's."""
+        import torch
+        bank = clips.bank
+        if bank.module is not self and (type(bank.module) is not type(self) or bank.module._plan_args() != self._plan_args()):
+            raise ValueError('the clips come from a bank of another module: its track maxima are those of its own plan')
+        audio = bank.audio
+        B, T = clips.num_clips, clips.num_frames
+        plan = self._get_plan(audio.device)
+        F = _lib.call('amtx_spec_num_bins', plan)
+        power = torch.empty((B, T, F), dtype=torch.float32, device=audio.device)
+        own_max = torch.empty((B,), dtype=torch.float32, device=audio.device)     # written, never read (docstring)
+        with torch.cuda.device(audio.device):
+            ev = self._prof_begin()
+            _lib.call('amtx_spec_power_clips', plan, audio, clips.desc_dev, B, T, power, own_max, device=audio.device)
+            self._prof_end('spec_power', ev)
+        return power, clips.db_ref
+
+    def process_clips(self, clips, model_layout=False):
+        """Features of a TrackClips on the device, (B, 1, F, T) float32 (model layout: (B, 1, T, F)): the slices
+        [first_frame, first_frame + num_frames) of the tracks' own feature maps, bit for bit -- scaled against the track's maximum,
+        the 80 dB floor below that same maximum, edge frames from the track's samples (SURVEY finding F7)."""
+        power, track_max = self.power_clips(clips)
+        return self.scale_batch(power, track_max, track_max, model_layout)
+
     def _process_host(self, audio, empty_rows):
         import torch
         if audio.shape[-1] == 0:
@@ -455,6 +484,12 @@ class _CqtPlanOwner(object):
         else:
             _lib.call('amtx_cqt_forward16', *args, device=audio.device)
         return out
+
+    def power_clips(self, clips):
+        raise NotImplementedError(f'{type(self).__name__}: the decimation pyramid has no clip form (clips come from STFT / MelSpec banks)')
+
+    def process_clips(self, clips, model_layout=False):
+        return self.power_clips(clips)
 
     def _process_host(self, audio):
         import torch

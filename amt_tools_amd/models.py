@@ -96,11 +96,27 @@ class TranscriptionModel(nn.Module):
         batch = tools.dict_to_device(batch, self.device)
         audio = tools.unpack_dict(batch, tools.KEY_AUDIO)
         feats = tools.unpack_dict(batch, tools.KEY_FEATS)
-        if audio is not None and len(self.frontend):
+        from .tracks import TrackClips
+        if isinstance(audio, TrackClips):
+            # clips cut from device-resident tracks: the slices of the tracks' own feature maps (track-level dB scale)
+            frontend_feats = self._clips_module(audio).process_clips(audio, model_layout=True).transpose(-1, -2)
+            feats = frontend_feats if feats is None else torch.cat((feats, frontend_feats), dim=1)
+        elif audio is not None and len(self.frontend):
             frontend_feats = self.frontend(audio.unsqueeze(-2))
             feats = frontend_feats if feats is None else torch.cat((feats, frontend_feats), dim=1)
         batch[tools.KEY_FEATS] = feats
         return batch
+
+    def _clips_module(self, clips):
+        """The feature module that turns a TrackClips batch entry into features: the model's ONE SpectralFrontend over an STFT / MelSpec,
+        on the device the clips' bank lives on.  Anything else raises -- clips are never silently skipped."""
+        from .features import _SpecPlanOwner, _index_of
+        module = self.frontend[0].module if len(self.frontend) == 1 and isinstance(self.frontend[0], SpectralFrontend) else None
+        if not isinstance(module, _SpecPlanOwner):
+            raise TypeError('a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend over an STFT / MelSpec module')
+        if torch.device(self.device).type != 'cuda' or _index_of(self.device) != clips.device.index:
+            raise ValueError(f'the clips live on {clips.device}, the model on {self.device}')
+        return module
 
     def forward(self, feats):
         raise NotImplementedError
@@ -563,6 +579,14 @@ class OnsetsFrames(TranscriptionModel):
             return None
         batch = tools.dict_to_device(batch, self.device)
         audio = batch[tools.KEY_AUDIO]
+        from .tracks import TrackClips
+        if isinstance(audio, TrackClips):
+            # clips cut from resident tracks: the same deferred dB scale, against the TRACK's maximum (own maximum = reference = track_max)
+            if cqt or not self._get_engine(audio.device).fuses_db_scale():
+                return None                                          # the ordinary path: pre_proc -> process_clips (or its error)
+            power, track_max = self._clips_module(audio).power_clips(audio)
+            batch[tools.KEY_FEATS] = PendingFeatures(module, power, clip_max=track_max)
+            return batch
         if not (torch.is_tensor(audio) and audio.is_cuda and audio.dim() == 2):
             return None
         if cqt:
