@@ -72,6 +72,40 @@ struct ConvArgs {
     int64_t out_ts = 0;                                  // convg.hip only: elements between consecutive (b, t) rows of `out`; 0 = (F/2) * c_out
     int64_t in_split = 0, out_split = 0;                 // AMTX_T_SPLIT maps (conv.hip, two-plane mode): elements between the hi and the lo plane
 };
+// conv.hip / convx.hip: the tiling of a map in tiles of at most ft_max (even) frequency columns x tt frames.  The columns are dealt evenly: ft is
+// the even width that ntf tiles need to cover F rounded up to even; ntiles = ntf ntt B in 64 bits, for the launcher's grid bound.
+struct ConvTiling { int ft, ntf, ntt; int64_t ntiles; };
+static inline ConvTiling amtx_conv_tiling(int B, int T, int F, int ft_max, int tt) {
+    const int fe = (F + 1) & ~1;
+    const int ntf = (fe + ft_max - 1) / ft_max, ntt = (T + tt - 1) / tt;
+    return {2 * (((fe >> 1) + ntf - 1) / ntf), ntf, ntt, (int64_t)ntf * ntt * B};
+}
+// The kernels divide an index x < n by a tile's column count as (x * inv) >> 16: inv, or 0 where that is not x / cols for every such x.
+static inline int amtx_conv_recip(int cols, int n) {
+    const int inv = 65536 / cols + 1;
+    for (int x = 0; x < n; ++x)
+        if (((x * inv) >> 16) != x / cols) return 0;
+    return inv;
+}
+// What a convolution launcher's route answers when it refuses the arguments: the launcher's return code and amtx_last_error text (the routes
+// are pure and set no error themselves).  code == AMTX_OK: a launch.
+struct ConvRefusal { int code = AMTX_OK; char text[192] = {0}; };
+#define AMTX_ROUTE_REFUSE(r, code_, ...)                                  \
+    do {                                                                   \
+        (r).err.code = (code_);                                            \
+        snprintf((r).err.text, sizeof((r).err.text), __VA_ARGS__);         \
+        return (r);                                                        \
+    } while (0)
+#define AMTX_ROUTE_REQUIRE(r, cond, ...) do { if (!(cond)) AMTX_ROUTE_REFUSE(r, AMTX_ERR_ARG, __VA_ARGS__); } while (0)
+// the launcher's side of it
+#define AMTX_RETURN_REFUSAL(r)                                             \
+    do {                                                                   \
+        if ((r).err.code != AMTX_OK) {                                     \
+            amtx_set_error("%s", (r).err.text);                            \
+            return (r).err.code;                                           \
+        }                                                                  \
+    } while (0)
+
 // convx.hip: the same layer (no fused first conv) on AMTX_T_SPLIT maps, two-plane weights: tiles DMA'd into a second LDS buffer under the matrix work
 int amtx_launch_convx3(const ConvArgs& c, hipStream_t stream);
 // convx.hip: conv.hip's fused first conv + 32 -> 32 layer (c_in = 1, two-plane weights) with a2 written as AMTX_T_SPLIT planes, two a1 tiles in LDS

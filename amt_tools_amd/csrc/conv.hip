@@ -113,13 +113,13 @@ __device__ __forceinline__ TileCoord tile_coord(int tile, int ntf, int ntt, int 
 // Threads per block: four waves everywhere.  The kernel is written for any multiple of 64 (NTH / NW below), but more waves per
 // SIMD do not pay on gfx950: eight per block need <= 128 VGPRs and spill (72 weight + 48 fragment-ring + 16 accumulator registers
 // alone), six (168 VGPRs) leave one block resident per CU (measured 5.9 vs 2.85 ms for the fused c_in = 1 kernel).
-constexpr int conv_threads(bool fuse1, int ks, int ns) { return 256; }
+constexpr int CONV_THREADS = 256;
 
 template <int NT, int NS, int IN_TYPE, int OUT_TYPE, bool FUSE1, int KS>
-__global__ __launch_bounds__(conv_threads(FUSE1, KS, NS), (NS == 1 ? conv_threads(FUSE1, KS, NS) / 128 : 1)) void conv3x3_kernel(ConvArgs a, int ft, int ntf, int ntt, int inv_cols, int ntiles) {
+__global__ __launch_bounds__(CONV_THREADS, (NS == 1 ? CONV_THREADS / 128 : 1)) void conv3x3_kernel(ConvArgs a, int ft, int ntf, int ntt, int inv_cols, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int COUT = NT * 16;
-    constexpr int NTH = conv_threads(FUSE1, KS, NS), NW = NTH / 64;
+    constexpr int NTH = CONV_THREADS, NW = NTH / 64;
     constexpr int PB = FUSE1 ? CM_BYTES : PLANE_BYTES;      // bytes of one input-tile plane in LDS
     constexpr int FW = fw_pitch(KS);
     // next-tile register prefetch only where the register budget keeps 2 waves per SIMD (C_out = 32)
@@ -791,83 +791,75 @@ __global__ __launch_bounds__(conv_threads(FUSE1, KS, NS), (NS == 1 ? conv_thread
 #undef CONV_ISSUE_FEAT_LOADS
 }
 
-template <int NT, int NS, int IN_TYPE, int OUT_TYPE, bool FUSE1, int KS = 0>
-int launch_conv(const ConvArgs& a, hipStream_t stream) {
-    const int fe = (a.F + 1) & ~1;
-    const int ntf = (fe + FT_MAX - 1) / FT_MAX;
-    const int ft = 2 * (((fe >> 1) + ntf - 1) / ntf);
-    const int ntt = (a.T + TT - 1) / TT;
-    const int64_t nblocks = (int64_t)ntf * ntt * a.B;
-    AMTX_REQUIRE(nblocks < (1ll << 31), "conv3x3: grid too large");
-    const size_t lds = (size_t)NS * (FUSE1 ? CM_BYTES : PLANE_BYTES) + (FUSE1 ? ((size_t)a.c_in * FROWS * fw_pitch(KS) + FSLACK) * sizeof(float) : 0) + (size_t)NT * 16 * sizeof(float) +
-                       (FUSE1 && KS == 1 ? (size_t)NS * 1024 : 0);   // + the Toeplitz first conv's scratch lines
-    auto kern = conv3x3_kernel<NT, NS, IN_TYPE, OUT_TYPE, FUSE1, KS>;
-    AMTX_GRANT_LDS(kern, lds);   // the size grows with c_in
-    const int cols = ft + 2;
-    const int inv_cols = 65536 / cols + 1;
-    for (int pos = 0; pos < 1024; ++pos)
-        if (((pos * inv_cols) >> 16) != pos / cols) {
-            amtx_set_error("conv3x3: internal: reciprocal division inexact for cols=%d", cols);
-            return AMTX_ERR_ARG;
-        }
-    if (FUSE1 && a.c_in == 1) {
-        const int fcols = ft + 4, inv_fcols = 65536 / fcols + 1;
-        for (int it = 0; it < FPRE * 256; ++it)
-            if (((it * inv_fcols) >> 16) != it / fcols) {
-                amtx_set_error("conv3x3: internal: reciprocal division inexact for fcols=%d", fcols);
-                return AMTX_ERR_ARG;
-            }
-    }
-    // persistent grid: two resident blocks per CU in total
-    int64_t gx = nblocks;
-    const int64_t per_group = std::max<int64_t>(1, 512 / std::max(1, a.groups));
-    if (gx > per_group) gx = per_group;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)a.groups), dim3(conv_threads(FUSE1, KS, NS)), lds, stream, a, ft, ntf, ntt, inv_cols, (int)nblocks);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+// ---- kernel selection: amtx_launch_conv3x3 is its argument checks -> conv_route -> conv_kernel_of and one launch (the table: DESIGN.md 5.11) ----
+
+// The A/B switch of this file, read once per process.  AMTX_NO_CONVX=1 keeps this file's register-staged kernel on the two-plane maps
+struct ConvSwitches { bool no_convx; };
+static const ConvSwitches& conv_switches() {
+    static const ConvSwitches sw = {getenv("AMTX_NO_CONVX") != nullptr};
+    return sw;
 }
 
-// A/B switch: AMTX_NO_CONVX=1 keeps this file's register-staged kernel on the two-plane maps
-static bool no_convx() { static const bool v = getenv("AMTX_NO_CONVX") != nullptr; return v; }
+// CONV_HERE: conv3x3_kernel<nt, ns, in_type, out_type, ks > 0, ks> with the geometry below; CONV_X12 / CONV_X3: the launch is convx.hip's
+enum ConvTarget { CONV_HERE, CONV_X12, CONV_X3 };
+// ks: K steps of the fused first conv (1 for 9 c_in <= 16, else 4), 0 = not fused; ft .. ntiles: kernel arguments
+struct ConvRouted { ConvRefusal err; ConvTarget target; int nt, ns, in_type, out_type, ks, ft, ntf, ntt, inv_cols, ntiles; unsigned gx; size_t lds; };
 
-template <int NT, int NS>
-int dispatch_types(const ConvArgs& a, hipStream_t s) {
+// Pure: sizes, types, strides and which pointers are set; nothing is dereferenced or launched, no environment is read.
+static ConvRouted conv_route(const ConvArgs& a, const ConvSwitches& sw) {
+    ConvRouted r = {};
+    r.target = CONV_HERE; r.nt = a.c_out / 16; r.ns = a.planes;
+    if (r.nt != 2 && r.nt != 4) AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3: unsupported c_out=%d (supported: 32 and 64, with C_in = 32)", a.c_out);
     if (a.feats) {
-        if (NT != 2) {
-            amtx_set_error("conv3x3: the fused first conv feeds a 32 -> 32 layer only");
-            return AMTX_ERR_UNSUPPORTED;
+        if (r.nt != 2) AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3: the fused first conv feeds a 32 -> 32 layer only");
+        r.ks = a.c_in * 9 <= 16 ? 1 : 4;
+        r.in_type = r.out_type = a.out_type == AMTX_T_BF16 ? AMTX_T_BF16 : AMTX_T_F32;
+        if (r.ks == 1 && a.out_type == AMTX_T_SPLIT) {
+            if (r.ns != 2) AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3: two-plane maps exist in the two-plane mode only");
+            AMTX_ROUTE_REQUIRE(r, a.out_split > 0 && a.out_split % 8 == 0, "conv3x3: two-plane output needs a plane stride");
+            if (!sw.no_convx && a.c_in == 1) { r.target = CONV_X12; return r; }
+            r.out_type = AMTX_T_SPLIT;
         }
-        if (a.c_in * 9 <= 16) {
-            if (a.out_type == AMTX_T_BF16) return launch_conv<2, NS, AMTX_T_BF16, AMTX_T_BF16, true, 1>(a, s);
-            if (a.out_type == AMTX_T_SPLIT) {
-                if constexpr (NS == 2) {
-                    AMTX_REQUIRE(a.out_split > 0 && a.out_split % 8 == 0, "conv3x3: two-plane output needs a plane stride");
-                    if (!no_convx() && a.c_in == 1) return amtx_launch_convx12(a, s);
-                    return launch_conv<2, NS, AMTX_T_F32, AMTX_T_SPLIT, true, 1>(a, s);
-                }
-                amtx_set_error("conv3x3: two-plane maps exist in the two-plane mode only");
-                return AMTX_ERR_UNSUPPORTED;
-            }
-            return launch_conv<2, NS, AMTX_T_F32, AMTX_T_F32, true, 1>(a, s);
-        }
-        if (a.out_type == AMTX_T_BF16) return launch_conv<2, NS, AMTX_T_BF16, AMTX_T_BF16, true, 4>(a, s);
-        return launch_conv<2, NS, AMTX_T_F32, AMTX_T_F32, true, 4>(a, s);
-    }
-    if (a.in_type == AMTX_T_BF16 && a.out_type == AMTX_T_BF16) {
-        // (an LDS-DMA double-buffered variant of this layer was measured in rounds 1 - 2: 4 % slower on conv3, which is bandwidth-bound,
+    } else if (a.in_type == AMTX_T_SPLIT && a.out_type == AMTX_T_SPLIT && r.ns == 2) {
+        AMTX_ROUTE_REQUIRE(r, a.in_split > 0 && a.in_split % 8 == 0 && a.out_split > 0 && a.out_split % 8 == 0, "conv3x3: two-plane maps need plane strides");
+        if (!sw.no_convx) { r.target = CONV_X3; return r; }
+        r.in_type = r.out_type = AMTX_T_SPLIT;
+    } else {
+        // (an LDS-DMA double-buffered variant of the bf16 layer was measured in rounds 1 - 2: 4 % slower on conv3, which is bandwidth-bound,
         // and never the default; it and its AMTX_CONV_DMA switch are gone)
-        return launch_conv<NT, NS, AMTX_T_BF16, AMTX_T_BF16, false>(a, s);
+        if (a.in_type != a.out_type || (a.in_type != AMTX_T_BF16 && a.in_type != AMTX_T_F32))
+            AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3: in/out element types must match (bf16/bf16 or f32/f32)");
+        r.in_type = r.out_type = a.in_type;
     }
-    if (a.in_type == AMTX_T_F32 && a.out_type == AMTX_T_F32) return launch_conv<NT, NS, AMTX_T_F32, AMTX_T_F32, false>(a, s);
-    if (a.in_type == AMTX_T_SPLIT && a.out_type == AMTX_T_SPLIT) {
-        if constexpr (NS == 2) {
-            AMTX_REQUIRE(a.in_split > 0 && a.in_split % 8 == 0 && a.out_split > 0 && a.out_split % 8 == 0, "conv3x3: two-plane maps need plane strides");
-            if (!no_convx()) return amtx_launch_convx3(a, s);
-            return launch_conv<NT, NS, AMTX_T_SPLIT, AMTX_T_SPLIT, false>(a, s);
-        }
+    const ConvTiling t = amtx_conv_tiling(a.B, a.T, a.F, FT_MAX, TT);
+    AMTX_ROUTE_REQUIRE(r, t.ntiles < (1ll << 31), "conv3x3: grid too large");
+    r.ft = t.ft; r.ntf = t.ntf; r.ntt = t.ntt; r.ntiles = (int)t.ntiles;
+    r.lds = (size_t)r.ns * (r.ks ? CM_BYTES : PLANE_BYTES) + (r.ks ? ((size_t)a.c_in * FROWS * fw_pitch(r.ks) + FSLACK) * sizeof(float) : 0) + (size_t)r.nt * 16 * sizeof(float) +
+            (r.ks == 1 ? (size_t)r.ns * 1024 : 0);   // the size grows with c_in; + the Toeplitz first conv's scratch lines
+    r.inv_cols = amtx_conv_recip(t.ft + 2, 1024);
+    AMTX_ROUTE_REQUIRE(r, r.inv_cols, "conv3x3: internal: reciprocal division inexact for cols=%d", t.ft + 2);
+    AMTX_ROUTE_REQUIRE(r, !(r.ks && a.c_in == 1) || amtx_conv_recip(t.ft + 4, FPRE * 256), "conv3x3: internal: reciprocal division inexact for fcols=%d", t.ft + 4);
+    // persistent grid: two resident blocks per CU in total
+    r.gx = (unsigned)std::min<int64_t>(t.ntiles, std::max<int64_t>(1, 512 / std::max(1, a.groups)));
+    return r;
+}
+
+// the instantiations that are built, by the route's (nt, ns, in_type, out_type, ks)
+using ConvKernel = void (*)(ConvArgs, int, int, int, int, int);
+constexpr int conv_key(int nt, int ns, int in, int out, int ks) { return (((nt * 4 + ns) * 4 + in) * 4 + out) * 8 + ks; }
+static ConvKernel conv_kernel_of(const ConvRouted& r) {
+    constexpr int B16 = AMTX_T_BF16, F32 = AMTX_T_F32, SPL = AMTX_T_SPLIT;
+#define CONV_CASE(NT, NS, IN, OUT, KS) case conv_key(NT, NS, IN, OUT, KS): return conv3x3_kernel<NT, NS, IN, OUT, (KS > 0), KS>;
+    switch (conv_key(r.nt, r.ns, r.in_type, r.out_type, r.ks)) {
+        CONV_CASE(2, 1, B16, B16, 0) CONV_CASE(2, 1, F32, F32, 0) CONV_CASE(4, 1, B16, B16, 0) CONV_CASE(4, 1, F32, F32, 0)
+        CONV_CASE(2, 2, B16, B16, 0) CONV_CASE(2, 2, F32, F32, 0) CONV_CASE(4, 2, B16, B16, 0) CONV_CASE(4, 2, F32, F32, 0)
+        CONV_CASE(2, 2, SPL, SPL, 0) CONV_CASE(4, 2, SPL, SPL, 0)
+        CONV_CASE(2, 1, B16, B16, 1) CONV_CASE(2, 1, F32, F32, 1) CONV_CASE(2, 1, B16, B16, 4) CONV_CASE(2, 1, F32, F32, 4)
+        CONV_CASE(2, 2, B16, B16, 1) CONV_CASE(2, 2, F32, F32, 1) CONV_CASE(2, 2, B16, B16, 4) CONV_CASE(2, 2, F32, F32, 4)
+        CONV_CASE(2, 2, F32, SPL, 1)
     }
-    amtx_set_error("conv3x3: in/out element types must match (bf16/bf16 or f32/f32)");
-    return AMTX_ERR_UNSUPPORTED;
+#undef CONV_CASE
+    return nullptr;
 }
 
 // ------------------------------------------------------------------ first conv: direct, fp32 math
@@ -957,20 +949,18 @@ void amtx_conv1_pack_host(const float* w, const float* scale, int c_in, int plan
 
 int amtx_launch_conv3x3(const ConvArgs& a, hipStream_t stream) {
     AMTX_REQUIRE((a.in || a.feats) && a.wfrag && a.shift && a.out, "conv3x3: null pointer");
-    if (a.feats) {
-        AMTX_REQUIRE(a.w1frag && a.shift1 && a.c_in > 0 && 9 * a.c_in <= 64, "conv3x3: fused first conv needs w1frag/shift1 and 9*c_in <= 64");
-    }
+    if (a.feats) AMTX_REQUIRE(a.w1frag && a.shift1 && a.c_in > 0 && 9 * a.c_in <= 64, "conv3x3: fused first conv needs w1frag/shift1 and 9*c_in <= 64");
     AMTX_REQUIRE(a.B > 0 && a.T > 0 && a.F >= 2 && a.groups > 0, "conv3x3: bad sizes");
     AMTX_REQUIRE(a.planes == 1 || a.planes == 2, "conv3x3: planes must be 1 or 2");
-    const int key = (a.c_out / 16) * 10 + a.planes;
-    switch (key) {
-        case 21: return dispatch_types<2, 1>(a, stream);
-        case 22: return dispatch_types<2, 2>(a, stream);
-        case 41: return dispatch_types<4, 1>(a, stream);
-        case 42: return dispatch_types<4, 2>(a, stream);
-    }
-    amtx_set_error("conv3x3: unsupported c_out=%d (supported: 32 and 64, with C_in = 32)", a.c_out);
-    return AMTX_ERR_UNSUPPORTED;
+    const ConvRouted r = conv_route(a, conv_switches());
+    AMTX_RETURN_REFUSAL(r);
+    if (r.target != CONV_HERE) return r.target == CONV_X12 ? amtx_launch_convx12(a, stream) : amtx_launch_convx3(a, stream);
+    const ConvKernel kern = conv_kernel_of(r);
+    AMTX_REQUIRE(kern, "conv3x3: internal: the route names a kernel that is not built");
+    AMTX_GRANT_LDS(kern, r.lds);
+    hipLaunchKernelGGL(kern, dim3(r.gx, (unsigned)a.groups), dim3(CONV_THREADS), r.lds, stream, a, r.ft, r.ntf, r.ntt, r.inv_cols, r.ntiles);
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
 }
 
 int amtx_launch_conv1(const Conv1Args& a, hipStream_t stream) {
@@ -981,10 +971,8 @@ int amtx_launch_conv1(const Conv1Args& a, hipStream_t stream) {
     const int64_t total = (int64_t)a.B * a.T * a.F * (a.c_out / 8);
     int64_t nblocks = (total + 255) / 256;
     if (nblocks > 256 * 32) nblocks = 256 * 32;
-    if (a.out_type == AMTX_T_BF16)
-        hipLaunchKernelGGL(conv1_kernel<AMTX_T_BF16>, dim3((unsigned)nblocks, (unsigned)a.groups), dim3(256), lds, stream, a);
-    else
-        hipLaunchKernelGGL(conv1_kernel<AMTX_T_F32>, dim3((unsigned)nblocks, (unsigned)a.groups), dim3(256), lds, stream, a);
+    const auto kern = a.out_type == AMTX_T_BF16 ? conv1_kernel<AMTX_T_BF16> : conv1_kernel<AMTX_T_F32>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks, (unsigned)a.groups), dim3(256), lds, stream, a);
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }

@@ -622,18 +622,40 @@ static int convf_steps(int F) {
     return n;
 }
 
-// One launch handles `groups` heads x B clips x T frames.  The caller decides WHEN (amtx_conv_stack_fused_ok): below ~one strip per
-// CU the two-kernel path's finer tiles fill the chip better.
-// 62 output rows per strip (ninth layer1 unit) only where that saves a strip per clip, else 60
-static bool convf_halo(int T) { return (T + r3_of(true) - 1) / r3_of(true) < (T + r3_of(false) - 1) / r3_of(false); }
+// ---- kernel selection: amtx_launch_conv_stack is its argument checks -> convf_route -> one launch (the table: DESIGN.md 5.11).  No A/B switch here.
+
+// One launch handles `groups` heads x B clips x T frames in strips of r3 output rows.  halo: 62 output rows per strip (ninth layer1 unit) only
+// where that saves a strip per clip, else 60.  The one strip geometry of the launch and of amtx_conv_stack_fused_ok.
+struct ConvfStrips { bool halo; int ntt; int64_t nstrips; };
+static ConvfStrips convf_strips(int B, int T) {
+    const bool halo = (T + r3_of(true) - 1) / r3_of(true) < (T + r3_of(false) - 1) / r3_of(false);
+    const int ntt = (T + r3_of(halo) - 1) / r3_of(halo);
+    return {halo, ntt, (int64_t)B * ntt};
+}
+constexpr int64_t CONVF_MAX_STRIPS = 1ll << 30;
+
+struct ConvfRouted { ConvRefusal err; ConvfStrips st; int nstep, per_block; unsigned gx; };   // convf_kernel<st.halo>; nstep, st.ntt, st.nstrips, per_block: its arguments
+
+// Pure: positive sizes only (F >= 4), which both callers have checked
+static ConvfRouted convf_route(int B, int T, int F, int groups) {
+    ConvfRouted r = {};
+    r.st = convf_strips(B, T);
+    AMTX_ROUTE_REQUIRE(r, r.st.nstrips < CONVF_MAX_STRIPS, "conv_stack: grid too large");
+    r.nstep = convf_steps(F);
+    AMTX_ROUTE_REQUIRE(r, (int64_t)r.nstep * (r.st.nstrips + 1) < (1ll << 31), "conv_stack: too many steps");
+    const int64_t gx = std::min<int64_t>(r.st.nstrips, std::max(1, 256 / groups));             // one resident block per CU in total
+    r.per_block = (int)((r.st.nstrips + gx - 1) / gx);
+    r.gx = (unsigned)((r.st.nstrips + r.per_block - 1) / r.per_block);
+    return r;
+}
 
 namespace AMTX_FMT_NS {
 
+// The caller decides WHEN: below ~one strip per CU the two-kernel path's finer tiles fill the chip better
 bool amtx_conv_stack_fused_ok(int B, int T, int F, int groups) {
     if (F < 4 || B <= 0 || T <= 0 || groups <= 0) return false;
-    const int r3 = r3_of(convf_halo(T));
-    const int64_t strips = (int64_t)B * ((T + r3 - 1) / r3) * groups;
-    return strips >= 256 && (int64_t)B * ((T + r3 - 1) / r3) < (1ll << 30);
+    const ConvfStrips st = convf_strips(B, T);
+    return st.nstrips * groups >= 256 && st.nstrips < CONVF_MAX_STRIPS;
 }
 
 int amtx_launch_conv_stack(const ConvArgs& c2, const bf16_t* w3frag, int64_t w3_gs, const float* shift3, void* out, int64_t out_gs,
@@ -652,25 +674,15 @@ int amtx_launch_conv_stack(const ConvArgs& c2, const bf16_t* w3frag, int64_t w3_
     a.w3frag = w3frag; a.w3_gs = w3_gs; a.shift3 = shift3;
     a.out = (bf16_t*)out; a.out_gs = out_gs; a.out_plane = out_plane;
     a.B = c2.B; a.T = c2.T; a.F = c2.F;
-    const bool halo = convf_halo(c2.T);
-    const int r3 = r3_of(halo);
-    const int ntt = (c2.T + r3 - 1) / r3;
-    const int64_t nstrips = (int64_t)c2.B * ntt;
-    AMTX_REQUIRE(nstrips < (1ll << 30), "conv_stack: grid too large");
-    const int nstep = convf_steps(c2.F);
-    AMTX_REQUIRE((int64_t)nstep * (nstrips + 1) < (1ll << 31), "conv_stack: too many steps");
-    int gx = std::max(1, 256 / c2.groups);             // one resident block per CU in total
-    if (gx > nstrips) gx = (int)nstrips;
-    const int per_block = (int)((nstrips + gx - 1) / gx);
-    gx = (int)((nstrips + per_block - 1) / per_block);
-    auto kern = halo ? convf_kernel<true> : convf_kernel<false>;
-    AMTX_GRANT_LDS(convf_kernel<true>, LDS_BYTES);
-    AMTX_GRANT_LDS(convf_kernel<false>, LDS_BYTES);
+    const ConvfRouted r = convf_route(c2.B, c2.T, c2.F, c2.groups);
+    AMTX_RETURN_REFUSAL(r);
+    const auto kern = r.st.halo ? convf_kernel<true> : convf_kernel<false>;
+    AMTX_GRANT_LDS(kern, LDS_BYTES);
     int dbg = 0;
 #if defined(AMTX_CONVF_TIMING) || defined(AMTX_CONVF_ABLATE)
     if (const char* e = getenv("AMTX_CONVF_DBG")) dbg = atoi(e);
 #endif
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)c2.groups), dim3(512), LDS_BYTES, stream, a, nstep, ntt, (int)nstrips, per_block, dbg);
+    hipLaunchKernelGGL(kern, dim3(r.gx, (unsigned)c2.groups), dim3(512), LDS_BYTES, stream, a, r.nstep, r.st.ntt, (int)r.st.nstrips, r.per_block, dbg);
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }

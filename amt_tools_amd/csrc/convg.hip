@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -785,108 +786,142 @@ extern "C" int amtxdbg_convg_prof(unsigned long long* out8, int reset) {
 }
 #endif
 
-// f_base / ntf_only: the launch covers the column tiles [f_base, f_base + ntf_only FT) of the map only (0: all of it).  STRIP: ONE column of
+// ---- kernel selection: amtx_launch_conv3x3_gen is its argument checks -> convg_route -> gen_kernel_of and one launch per routed launch (the
+// tables: DESIGN.md 5.11) ----
+
+// The A/B switches of this file, read once per process.  AMTX_CONVG_NO_WDMA: never two weight chunks resident with the next one's
+// DMA under the matrix work (w_all 2); AMTX_CONVG_NO_CSPLIT: the two-plane kernels never deal the C_out chunks to blocks (w_all 3);
+// AMTX_CONVG_NO_STRIP: one launch of 32-column tiles, whatever the map's width
+struct ConvgSwitches { bool no_wdma, no_csplit, no_strip; };
+static const ConvgSwitches& convg_switches() {
+    static const ConvgSwitches sw = {getenv("AMTX_CONVG_NO_WDMA") != nullptr, getenv("AMTX_CONVG_NO_CSPLIT") != nullptr, getenv("AMTX_CONVG_NO_STRIP") != nullptr};
+    return sw;
+}
+
+// What conv3x3_gen_kernel is built as, per (CI16, NTC): the template arguments behind <CI16, NTC> of every variant, in one table that the route
+// computes its geometry from and gen_kernel names the kernel from
+enum GenVariant { GEN_BF16, GEN_X3, GEN_ONE, GEN_ONE_STRIP, GEN_ONE_X3, GEN_TAP, GEN_TAP6, GEN_TAP16, GEN_TAP16_STRIP, GEN_TAP_X3, GEN_TAP_X3_SPLIT, GEN_VARIANTS };
+struct GenTraits { int ns, ft, in_type, out_type, ks1; bool fcl; int cmax; bool f16in, strip; int only; };   // only: the one CI16 it is built for, 0 = all
+constexpr GenTraits GEN_TRAITS[GEN_VARIANTS] = {
+    {1, 32, AMTX_T_BF16, AMTX_T_BF16, 0, false, 0, false, false, 0}, // GEN_BF16: the layer alone, one plane
+    // (16-column tiles = two 256-thread blocks per CU were measured for it too: 22.5 vs 15.9 ms for conv2 at mc 3, the kernels need more
+    // than 256 VGPRs so only one of the two blocks is resident)
+    {2, 16, AMTX_T_F32, AMTX_T_F32, 0, false, 0, false, false, 0},   // GEN_X3: the layer alone, two planes
+    {1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1, false, false, 0}, // GEN_ONE: fused first conv from one fp32 channel
+    {1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1, false, true, 3},  // GEN_ONE_STRIP: its strip tiles
+    {2, 16, AMTX_T_F32, AMTX_T_F32, 1, false, 0, false, false, 0},   // GEN_ONE_X3: one fp32 channel, two planes
+    {1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, false, false, 0},  // GEN_TAP: tap-major fused first conv from 2 .. 8 fp32 channels
+    {1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 6, false, false, 2},  // GEN_TAP6: the HCQT shape (6 harmonics, amt_tools/features/hvqt.py:107-133) has its own item count
+    {1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true, false, 2},   // GEN_TAP16: from 16-bit channels-last features (amtx_cqt_forward16)
+    {1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true, true, 2},    // GEN_TAP16_STRIP: its strip tiles
+    // two planes, 2 .. 8 input channels: tap-major as well (round 5: the K-major form gathered and split 8 fp32 values per lane, k-step and 16
+    // positions -- 52 % of the HCQT model's x3 conv2; the packed weights follow amtx_conv1g_tapk, so there is no run-time switch back)
+    // (32-column tiles for the 32-channel shape -- eight waves, 149 KB of LDS, 256 registers with 12 spilled -- measured the same: 4.80 vs 4.83 ms)
+    {2, 16, AMTX_T_F32, AMTX_T_F32, 3, true, 0, false, false, 0},    // GEN_TAP_X3
+    {2, 16, AMTX_T_F32, AMTX_T_SPLIT, 3, true, 0, false, false, 2},  // GEN_TAP_X3_SPLIT: a2 as split planes for convx.hip's conv3
+};
+// `only`: the strip kernel of the one-channel first conv exists for OnsetsFrames2 as shipped (model_complexity 3, 229 mel bins), the others for the
+// 32-channel (HCQT) shape
+constexpr bool gen_built(int ci16, GenVariant v) { return v < GEN_VARIANTS && (GEN_TRAITS[v].only == 0 || GEN_TRAITS[v].only == ci16); }
+
+using GenKernel = void (*)(ConvArgs, int, int, int, int, int, int, int);
+template <int CI16, int NTC, GenVariant V>
+GenKernel gen_kernel() {
+    constexpr GenTraits t = GEN_TRAITS[V];
+    if constexpr (gen_built(CI16, V)) return conv3x3_gen_kernel<CI16, NTC, t.ns, t.ft, t.in_type, t.out_type, t.ks1, t.fcl, t.cmax, t.f16in, t.strip>;
+    else return nullptr;
+}
+template <int CI16, int NTC, int... V>
+GenKernel gen_kernel_of(GenVariant v, std::integer_sequence<int, V...>) {
+    const GenKernel all[] = {gen_kernel<CI16, NTC, (GenVariant)V>()...};
+    return all[v];
+}
+static GenKernel gen_kernel_of(int ci16, GenVariant v) {
+    const auto all = std::make_integer_sequence<int, GEN_VARIANTS>();
+    return ci16 == 2 ? gen_kernel_of<2, 2>(v, all) : ci16 == 3 ? gen_kernel_of<3, 3>(v, all) : ci16 == 4 ? gen_kernel_of<4, 2>(v, all) :
+           ci16 == 5 ? gen_kernel_of<5, 1>(v, all) : nullptr;          // the C_out chunk of each: amtx_conv3x3_gen_ntc
+}
+
+constexpr size_t GEN_LDS_MAX = 160 * 1024;
+
+// One launch: kernel arguments, grid, block, LDS.  w_all: how the C_out chunks' weights live in LDS (0 one chunk at a time, 1 all resident, 2 two
+// resident with the next chunk's DMA under the matrix work, 3 one chunk per block, the chunks dealt to blocks)
+struct GenLaunch { ConvRefusal err; GenVariant v; int ntf, ntt, nchunks, ntiles, w_all, sh_off, f_base; unsigned gx, block; size_t lds; };
+struct GenRouted { ConvRefusal err; int ci16, nlaunch; GenLaunch launch[2]; };   // launch[1]: the strip tiles
+
+// f_base / ntf_only: the launch covers the column tiles [f_base, f_base + ntf_only FT) of the map only (0: all of it).  A strip variant: ONE column of
 // strip tiles (three 16-frame blocks x 8 columns each) at f_base.
-template <int CI16, int NTC, int NS, int FT, int IN_TYPE, int OUT_TYPE, int KS1 = 0, bool FCL = false, int CMAX = 0, bool F16IN = false, bool STRIP = false>
-int launch_gen(const ConvArgs& a, hipStream_t stream, int f_base = 0, int ntf_only = 0) {
+static GenLaunch gen_launch(const ConvArgs& a, int ci16, int ntc, GenVariant v, int f_base, int ntf_only, const ConvgSwitches& sw) {
+    const GenTraits& t = GEN_TRAITS[v];
+    GenLaunch r = {}; r.v = v; r.f_base = f_base; r.block = 16 * t.ft;
     const int fe = a.F & ~1;                                  // columns that reach a pooled output
-    const int ntf = STRIP ? 1 : ntf_only > 0 ? ntf_only : (fe + FT - 1) / FT;
-    const int ntt = STRIP ? ((a.T + GTT - 1) / GTT + 2) / 3 : (a.T + GTT - 1) / GTT;
-    const int64_t ntiles = (int64_t)ntf * ntt * a.B;
-    AMTX_REQUIRE(ntiles < (1ll << 31), "conv3x3: grid too large");
-    if (KS1 == 0) AMTX_REQUIRE((int64_t)a.T * a.F * 16 * CI16 * (IN_TYPE == AMTX_T_BF16 ? 2 : 4) < (1ll << 32),
-                               "conv3x3 (general): a clip's input map must be smaller than 4 GiB");
-    const int nchunks = a.c_out / (16 * NTC);
-    const size_t lds_x = (size_t)NS * (16 * CI16 / 8) * g_cplane(FT), wchunk = (size_t)NTC * NS * g_wfrags_per_tile(CI16) * 1024;
-    const size_t lds_f = KS1 > 0 ? (FCL ? (size_t)NS * ((GROWS + 2) * (FT + 4) * 16 + 128) : (size_t)a.c_in * (GROWS + 2) * (FT + 5) * sizeof(float)) +
-                                   (size_t)CI16 * KS1 * NS * 1024 + 16 * CI16 * 4 : 0;
-    constexpr bool PIPE = FCL && CI16 == 2 && NS == 1;        // two input tiles + two feature tiles, one resident weight chunk
+    r.ntf = t.strip ? 1 : ntf_only > 0 ? ntf_only : (fe + t.ft - 1) / t.ft;
+    r.ntt = t.strip ? ((a.T + GTT - 1) / GTT + 2) / 3 : (a.T + GTT - 1) / GTT;
+    const int64_t ntiles = (int64_t)r.ntf * r.ntt * a.B;
+    AMTX_ROUTE_REQUIRE(r, ntiles < (1ll << 31), "conv3x3: grid too large");
+    if (t.ks1 == 0) AMTX_ROUTE_REQUIRE(r, (int64_t)a.T * a.F * 16 * ci16 * (t.in_type == AMTX_T_BF16 ? 2 : 4) < (1ll << 32),
+                                       "conv3x3 (general): a clip's input map must be smaller than 4 GiB");
+    r.ntiles = (int)ntiles; r.nchunks = a.c_out / (16 * ntc);
+    const size_t lds_x = (size_t)t.ns * (16 * ci16 / 8) * g_cplane(t.ft), wchunk = (size_t)ntc * t.ns * g_wfrags_per_tile(ci16) * 1024;
+    const size_t ftile = (size_t)(GROWS + 2) * (t.ft + 4) * 16;      // one plane of the channels-last feature tile
+    const size_t lds_f = t.ks1 > 0 ? (t.fcl ? t.ns * (ftile + 128) : (size_t)a.c_in * (GROWS + 2) * (t.ft + 5) * sizeof(float)) +
+                                     (size_t)ci16 * t.ks1 * t.ns * 1024 + 16 * ci16 * 4 : 0;
+    const bool pipe = t.fcl && ci16 == 2 && t.ns == 1;        // two input tiles + two feature tiles, one resident weight chunk (conv3x3_gen_kernel PIPE)
     const size_t lds_sh = 16 + (size_t)a.c_out * sizeof(float);
-    static const bool no_wdma = getenv("AMTX_CONVG_NO_WDMA") != nullptr;     // A/B switch
-    int w_all = !PIPE && nchunks > 1 && lds_x + nchunks * wchunk + lds_f + lds_sh <= 160 * 1024;
-    if (!w_all && !PIPE && NS == 1 && nchunks > 1 && !no_wdma && lds_x + 2 * wchunk + lds_f + lds_sh <= 160 * 1024) w_all = 2;
-    static const bool no_csplit = getenv("AMTX_CONVG_NO_CSPLIT") != nullptr;  // A/B switch
-    if (!w_all && !PIPE && NS == 2 && nchunks > 1 && !no_csplit) w_all = 3;
-    size_t lds = PIPE ? 2 * lds_x + wchunk + lds_f + (size_t)(GROWS + 2) * (FT + 4) * 16
-                      : lds_x + (w_all == 1 ? nchunks : (w_all == 2 ? 2 : 1)) * wchunk + lds_f;
-    if (PIPE) AMTX_REQUIRE(nchunks == 1, "conv3x3 (general): the pipelined 32-channel variant takes one C_out chunk");
-    const int sh_off = (int)((lds + 15) / 16 * 16);           // [c_out] fp32 shift behind everything else
-    lds = (size_t)sh_off + (size_t)a.c_out * sizeof(float);
-    AMTX_REQUIRE(lds <= 160 * 1024, "conv3x3 (general): tile + weights + features do not fit the LDS (%zu bytes)", lds);
-    if (F16IN) AMTX_REQUIRE((int64_t)a.T * a.F < (1ll << 27), "conv3x3 (general): a clip's 16-bit feature map must be smaller than 2 GiB");
-    auto kern = conv3x3_gen_kernel<CI16, NTC, NS, FT, IN_TYPE, OUT_TYPE, KS1, FCL, CMAX, F16IN, STRIP>;
-    AMTX_GRANT_LDS(kern, lds);
+    r.w_all = pipe || r.nchunks <= 1 ? 0 : lds_x + r.nchunks * wchunk + lds_f + lds_sh <= GEN_LDS_MAX ? 1 :
+              t.ns == 1 && !sw.no_wdma && lds_x + 2 * wchunk + lds_f + lds_sh <= GEN_LDS_MAX ? 2 : t.ns == 2 && !sw.no_csplit ? 3 : 0;
+    const size_t lds = pipe ? 2 * lds_x + wchunk + lds_f + ftile : lds_x + (r.w_all == 1 ? r.nchunks : (r.w_all == 2 ? 2 : 1)) * wchunk + lds_f;
+    if (pipe) AMTX_ROUTE_REQUIRE(r, r.nchunks == 1, "conv3x3 (general): the pipelined 32-channel variant takes one C_out chunk");
+    r.sh_off = (int)((lds + 15) / 16 * 16);                   // [c_out] fp32 shift behind everything else
+    r.lds = (size_t)r.sh_off + (size_t)a.c_out * sizeof(float);
+    AMTX_ROUTE_REQUIRE(r, r.lds <= GEN_LDS_MAX, "conv3x3 (general): tile + weights + features do not fit the LDS (%zu bytes)", r.lds);
+    if (t.f16in) AMTX_ROUTE_REQUIRE(r, (int64_t)a.T * a.F < (1ll << 27), "conv3x3 (general): a clip's 16-bit feature map must be smaller than 2 GiB");
     // persistent grid: as many blocks as fit the chip at once (LDS allows 160 KiB / lds per CU), a multiple of 8 per group so a
     // block's tiles stay on its XCD
-    const int per_cu = std::max(1, (int)(160 * 1024 / lds));
-    int64_t gx = std::max<int64_t>(8, (256 * per_cu / std::max(1, a.groups)) / 8 * 8);
-    if (w_all == 3) {                                         // a multiple of 8 nchunks blocks, every one with a first tile
-        gx = std::max<int64_t>(8 * nchunks, gx / (8 * nchunks) * (8 * nchunks));
-        while (gx > 8 * nchunks && gx / nchunks > ntiles) gx -= 8 * nchunks;
-        if (gx / nchunks > ntiles) { w_all = 0; gx = std::min<int64_t>(std::max<int64_t>(8, (256 * per_cu / std::max(1, a.groups)) / 8 * 8), ntiles); }
-    } else if (gx > ntiles) gx = ntiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)a.groups), dim3(16 * FT), lds, stream, a, ntf, ntt, nchunks, (int)ntiles, w_all, sh_off, f_base);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+    const int64_t fill = std::max<int64_t>(8, (256 * std::max(1, (int)(GEN_LDS_MAX / r.lds)) / std::max(1, a.groups)) / 8 * 8);
+    int64_t gx = std::min(fill, ntiles);
+    if (r.w_all == 3) {                                       // a multiple of 8 nchunks blocks, every one with a first tile
+        const int step = 8 * r.nchunks;
+        gx = std::max<int64_t>(step, fill / step * step);
+        while (gx > step && gx / r.nchunks > ntiles) gx -= step;
+        if (gx / r.nchunks > ntiles) { r.w_all = 0; gx = std::min(fill, ntiles); }
+    }
+    r.gx = (unsigned)gx;
+    return r;
 }
 
-// A map whose last column tile would hold 8 columns or fewer (72 = 2 x 32 + 8; 229 mel bins = 7 x 32 + 4 columns that reach a pooled
-// output): those columns as strip tiles, in a launch of their own behind `main_launch` over the whole tiles.  Both take (f_base, ntf_only).
-// AMTX_CONVG_NO_STRIP=1: one launch of 32-column tiles, the A/B switch.
-static bool no_strip() { static const bool v = getenv("AMTX_CONVG_NO_STRIP") != nullptr; return v; }
-template <class Main, class Strip>
-int launch_with_strip(const ConvArgs& a, Main&& main_launch, Strip&& strip_launch) {
+// Pure: channel counts, sizes, types and which pointers are set; nothing is dereferenced or launched, no environment is read.  `c_in`: this
+// layer's input channels (a.c_in: the fused first conv's).  Also answers for a probe that no check has seen (amtx_conv3x3_gen_can_fuse1).
+static GenRouted convg_route(const ConvArgs& a, int c_in, const ConvgSwitches& sw) {
+    GenRouted r = {};
+    const int ntc = amtx_conv3x3_gen_ntc(c_in, a.c_out);
+    if (!ntc) AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3 (general): unsupported channel counts %d -> %d", c_in, a.c_out);
+    r.ci16 = c_in / 16;
+    const bool tapk = amtx_conv1g_tapk(a.c_in, a.planes), out16 = a.out_type == AMTX_T_BF16;
+    GenVariant v, strip = GEN_VARIANTS;                       // strip: the variant that takes a narrow last column tile, if the first has one
+    if (a.feats16) {                                          // fused first conv from 16-bit channels-last features (amtx_cqt_forward16)
+        if (!(r.ci16 == 2 && tapk && out16))
+            AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3 (general): 16-bit channels-last features: 2 .. 8 input channels, 32 first-layer channels, one-plane modes only");
+        v = GEN_TAP16; strip = GEN_TAP16_STRIP;
+    } else if (a.feats) {                                     // fused first conv
+        if (tapk && out16) v = r.ci16 == 2 && a.c_in <= 6 ? GEN_TAP6 : GEN_TAP;
+        else if (a.planes == 1 && out16 && a.c_in == 1) { v = GEN_ONE; strip = GEN_ONE_STRIP; }
+        else if (a.planes == 2 && tapk && a.out_type == AMTX_T_F32) v = GEN_TAP_X3;
+        else if (a.planes == 2 && tapk && r.ci16 == 2 && a.out_type == AMTX_T_SPLIT && a.out_split > 0) v = GEN_TAP_X3_SPLIT;
+        else if (a.planes == 2 && a.out_type == AMTX_T_F32 && (9 * a.c_in + 31) / 32 == 1) v = GEN_ONE_X3;
+        else AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3 (general): fused first conv: unsupported c_in / precision");
+    } else if (a.planes == 1 && a.in_type == AMTX_T_BF16 && out16) v = GEN_BF16;
+    else if (a.planes == 2 && a.in_type == AMTX_T_F32 && a.out_type == AMTX_T_F32) v = GEN_X3;
+    else AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "conv3x3 (general): unsupported precision/type combination");
+    // A map whose last column tile would hold 8 columns or fewer (72 = 2 x 32 + 8; 229 mel bins = 7 x 32 + 4 columns that reach a pooled
+    // output): those columns as strip tiles, in a launch of their own behind the one over the whole tiles
     const int fe = a.F & ~1, rem = fe % 32;
-    if (no_strip() || fe <= 32 || rem == 0 || rem > 8) return main_launch(0, 0);
-    const int rc = main_launch(0, fe / 32);
-    return rc != AMTX_OK ? rc : strip_launch(fe - rem, 0);
-}
-
-template <int CI16, int NTC>
-int dispatch_gen(const ConvArgs& a, hipStream_t s) {
-    if (a.feats16) {                                            // fused first conv from 16-bit channels-last features (amtx_cqt_forward16)
-        if constexpr (CI16 == 2) {
-            if (amtx_conv1g_tapk(a.c_in, a.planes) && a.out_type == AMTX_T_BF16) {
-                return launch_with_strip(a, [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true>(a, s, f_base, ntf); },
-                                         [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 0, true, true>(a, s, f_base, ntf); });
-            }
-        }
-        amtx_set_error("conv3x3 (general): 16-bit channels-last features: 2 .. 8 input channels, 32 first-layer channels, one-plane modes only");
-        return AMTX_ERR_UNSUPPORTED;
-    }
-    if (a.feats) {                                              // fused first conv
-        const int ks1 = (9 * a.c_in + 31) / 32;
-        if (amtx_conv1g_tapk(a.c_in, a.planes) && a.out_type == AMTX_T_BF16) {
-            if constexpr (CI16 == 2) {       // the HCQT shape (6 harmonics, amt_tools/features/hvqt.py:107-133) has its own item count
-                if (a.c_in <= 6) return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true, 6>(a, s);
-            }
-            return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 3, true>(a, s);
-        }
-        if (a.planes == 1 && a.out_type == AMTX_T_BF16 && a.c_in == 1) {   // one input channel (2 .. 8 channels: the tap-major variant above)
-            auto whole = [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1>(a, s, f_base, ntf); };
-            if constexpr (CI16 == 3)         // OnsetsFrames2 as shipped (model_complexity 3, 229 mel bins): the strip kernel exists for this shape only
-                return launch_with_strip(a, whole, [&](int f_base, int ntf) { return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16, 1, false, 1, false, true>(a, s, f_base, ntf); });
-            return whole(0, 0);
-        }
-        // two-plane modes.  2 .. 8 input channels: tap-major as well (round 5: the K-major form gathered and split 8 fp32 values per lane, k-step
-        // and 16 positions -- 52 % of the HCQT model's x3 conv2; the packed weights follow amtx_conv1g_tapk, so there is no run-time switch back)
-        // (32-column tiles for the 32-channel shape -- eight waves, 149 KB of LDS, 256 registers with 12 spilled -- measured the same: 4.80 vs 4.83 ms)
-        if (a.planes == 2 && amtx_conv1g_tapk(a.c_in, 2)) {
-            if (a.out_type == AMTX_T_F32) return launch_gen<CI16, NTC, 2, 16, AMTX_T_F32, AMTX_T_F32, 3, true>(a, s);
-            if constexpr (CI16 == 2) {   // a2 as split planes for convx.hip's conv3
-                if (a.out_type == AMTX_T_SPLIT && a.out_split > 0) return launch_gen<CI16, NTC, 2, 16, AMTX_T_F32, AMTX_T_SPLIT, 3, true>(a, s);
-            }
-        }
-        if (a.planes == 2 && a.out_type == AMTX_T_F32 && ks1 == 1) return launch_gen<CI16, NTC, 2, 16, AMTX_T_F32, AMTX_T_F32, 1>(a, s);      // one input channel
-        amtx_set_error("conv3x3 (general): fused first conv: unsupported c_in / precision");
-        return AMTX_ERR_UNSUPPORTED;
-    }
-    // (16-column tiles = two 256-thread blocks per CU were measured too: 22.5 vs 15.9 ms for conv2 at mc 3, the kernels need more
-    // than 256 VGPRs so only one of the two blocks is resident)
-    if (a.planes == 1 && a.in_type == AMTX_T_BF16 && a.out_type == AMTX_T_BF16) return launch_gen<CI16, NTC, 1, 32, AMTX_T_BF16, AMTX_T_BF16>(a, s);
-    if (a.planes == 2 && a.in_type == AMTX_T_F32 && a.out_type == AMTX_T_F32) return launch_gen<CI16, NTC, 2, 16, AMTX_T_F32, AMTX_T_F32>(a, s);
-    amtx_set_error("conv3x3 (general): unsupported precision/type combination");
-    return AMTX_ERR_UNSUPPORTED;
+    const bool split = gen_built(r.ci16, strip) && !sw.no_strip && fe > 32 && rem > 0 && rem <= 8;
+    r.launch[0] = gen_launch(a, r.ci16, ntc, v, 0, split ? fe / 32 : 0, sw);
+    if (split) r.launch[1] = gen_launch(a, r.ci16, ntc, strip, fe - rem, 0, sw);
+    r.nlaunch = split ? 2 : 1;
+    r.err = r.launch[0].err.code != AMTX_OK ? r.launch[0].err : r.launch[1].err;
+    return r;
 }
 
 }  // namespace
@@ -922,16 +957,13 @@ void amtx_conv1g_pack_host(const float* w, const float* scale, int c_in, int c_m
     for (int item = 0, n = amtx_layout_conv1g_items(c_in, c_mid, tapk); item < n; ++item) amtx_layout_conv1g(item, w, scale, c_in, tapk, put);
 }
 
-// does the fused-first-conv variant fit the LDS for this layer?
+// does the fused-first-conv variant exist and fit the LDS for this layer?  What the route answers for such a launch on a one-tile map
 bool amtx_conv3x3_gen_can_fuse1(int c_in, int c_mid, int c_out, int planes) {
-    const bool tapk = amtx_conv1g_tapk(c_in, planes);
-    if (c_in < 1 || c_in > (tapk ? 8 : 7) || !amtx_conv3x3_gen_ntc(c_mid, c_out)) return false;
-    const int ft = planes == 2 ? 16 : 32, ntc = amtx_conv3x3_gen_ntc(c_mid, c_out);
-    const bool pipe = tapk && c_mid == 32 && planes == 1;      // two input tiles and two feature tiles (conv3x3_gen_kernel PIPE)
-    const size_t feat = tapk ? (size_t)(pipe ? 2 : 1) * planes * ((GROWS + 2) * (ft + 4) * 16 + 128) : (size_t)c_in * (GROWS + 2) * (ft + 5) * sizeof(float);
-    const size_t lds = (size_t)(pipe ? 2 : 1) * planes * (c_mid / 8) * g_cplane(ft) + (size_t)ntc * planes * g_wfrags_per_tile(c_mid / 16) * 1024 + feat +
-                       (size_t)(c_mid / 16) * amtx_conv1g_ksteps(c_in, tapk) * planes * 1024 + c_mid * 4 + 16 + (size_t)c_out * 4;   // + this layer's shift
-    return lds <= 160 * 1024;
+    static const float probe = 0.f;                           // never read: the route only asks which pointers are set
+    ConvArgs q = {};
+    q.feats = &probe; q.c_in = c_in; q.planes = planes; q.c_out = c_out; q.out_type = planes == 1 ? AMTX_T_BF16 : AMTX_T_F32;
+    q.B = q.T = q.groups = 1; q.F = 2;
+    return convg_route(q, c_mid, convg_switches()).err.code == AMTX_OK;
 }
 
 int amtx_launch_conv3x3_gen(const ConvArgs& a, int c_in, hipStream_t stream) {
@@ -946,12 +978,17 @@ int amtx_launch_conv3x3_gen(const ConvArgs& a, int c_in, hipStream_t stream) {
                               "conv3x3 (general): fused first conv needs w1frag / shift1 and c_in <= 7 (8 in the one-plane modes)");
     AMTX_REQUIRE(a.B > 0 && a.T > 0 && a.F >= 2 && a.groups > 0, "conv3x3 (general): bad sizes");
     AMTX_REQUIRE(a.planes == 1 || a.planes == 2, "conv3x3 (general): planes must be 1 or 2");
-    if (c_in == 48 && amtx_conv3x3_gen_ntc(c_in, a.c_out) == 3) return dispatch_gen<3, 3>(a, stream);
-    if (c_in == 32 && amtx_conv3x3_gen_ntc(c_in, a.c_out) == 2) return dispatch_gen<2, 2>(a, stream);
-    if (c_in == 64 && amtx_conv3x3_gen_ntc(c_in, a.c_out) == 2) return dispatch_gen<4, 2>(a, stream);
-    if (c_in == 80 && amtx_conv3x3_gen_ntc(c_in, a.c_out) == 1) return dispatch_gen<5, 1>(a, stream);
-    amtx_set_error("conv3x3 (general): unsupported channel counts %d -> %d", c_in, a.c_out);
-    return AMTX_ERR_UNSUPPORTED;
+    const GenRouted r = convg_route(a, c_in, convg_switches());
+    AMTX_RETURN_REFUSAL(r);
+    for (int i = 0; i < r.nlaunch; ++i) {
+        const GenLaunch& l = r.launch[i];
+        const GenKernel kern = gen_kernel_of(r.ci16, l.v);
+        AMTX_REQUIRE(kern, "conv3x3 (general): internal: the route names a kernel that is not built");
+        AMTX_GRANT_LDS(kern, l.lds);
+        hipLaunchKernelGGL(kern, dim3(l.gx, (unsigned)a.groups), dim3(l.block), l.lds, stream, a, l.ntf, l.ntt, l.nchunks, l.ntiles, l.w_all, l.sh_off, l.f_base);
+        AMTX_CHECK_LAUNCH();
+    }
+    return AMTX_OK;
 }
 
 }  // namespace AMTX_FMT_NS

@@ -666,48 +666,46 @@ __global__ __launch_bounds__(512) void convx12_kernel(ConvArgs a, int ft, int nt
     }
 }
 
-template <bool MC>
-int launch_x12(const ConvArgs& a, hipStream_t stream) {
-    constexpr int FT = Y12<MC>::FT, LDSB = Y12<MC>::LDS;
-    const int fe = (a.F + 1) & ~1;
-    const int ntf = (fe + FT - 1) / FT;
-    const int ft = 2 * (((fe >> 1) + ntf - 1) / ntf);
-    const int ntt = (a.T + XT - 1) / XT;
-    const int64_t nblocks = (int64_t)ntf * ntt * a.B;
-    AMTX_REQUIRE(nblocks < (1ll << 31), "convx12: grid too large");
-    auto kern = convx12_kernel<MC>;
-    AMTX_GRANT_LDS(kern, LDSB);
-    int64_t gx = std::max<int64_t>(8, 256 / std::max(1, a.groups) / 8 * 8);
-    if (gx > nblocks) gx = nblocks;
-    const int fcols = ft + 4, inv_fcols = 65536 / fcols + 1;
-    for (int it = 0; it < (MC ? Y12<MC>::FROWS * fcols : YFPRE * 256); ++it)
-        if (((it * inv_fcols) >> 16) != it / fcols) {
-            amtx_set_error("convx12: internal: reciprocal division inexact for fcols=%d", fcols);
-            return AMTX_ERR_ARG;
-        }
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)a.groups), dim3(512), LDSB, stream, a, ft, ntf, ntt, (int)nblocks, inv_fcols);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+// ---- kernel selection: each launcher is its argument checks -> a route -> one launch (the tables: DESIGN.md 5.11).  This file has no A/B switch:
+// AMTX_NO_CONVX is conv.hip's, which then never hands over, and AMTX_NO_CONVX12M the engine's (ofmodel.hip)
+// mc: convx12's 2 .. 8-channel form (convx12_kernel<true>); nt: convx3's 16-channel output tiles (convx3_kernel<nt>); ft .. inv_fcols: kernel
+// arguments (inv_fcols: convx12 only)
+struct ConvxRouted { ConvRefusal err; bool mc; int nt, ft, ntf, ntt, ntiles, inv_fcols; unsigned gx; size_t lds; };
+
+// The part both routes share: tiles of at most ft_max columns, and the persistent grid -- one block per CU (152 KiB of LDS each), the blocks of one
+// group a multiple of 8 so that a block's tiles stay on its XCD
+static bool convx_tiles(const ConvArgs& a, int ft_max, ConvxRouted& r) {
+    const ConvTiling t = amtx_conv_tiling(a.B, a.T, a.F, ft_max, XT);
+    if (t.ntiles >= (1ll << 31)) return false;
+    r.ft = t.ft; r.ntf = t.ntf; r.ntt = t.ntt; r.ntiles = (int)t.ntiles;
+    r.gx = (unsigned)std::min<int64_t>(t.ntiles, std::max<int64_t>(8, 256 / std::max(1, a.groups) / 8 * 8));
+    return true;
 }
 
-template <int NT>
-int launch_x3(const ConvArgs& a, hipStream_t stream) {
-    const int fe = (a.F + 1) & ~1;
-    const int ntf = (fe + XFT - 1) / XFT;
-    const int ft = 2 * (((fe >> 1) + ntf - 1) / ntf);
-    const int ntt = (a.T + XT - 1) / XT;
-    const int64_t nblocks = (int64_t)ntf * ntt * a.B;
-    AMTX_REQUIRE(nblocks < (1ll << 31), "convx3: grid too large");
-    AMTX_REQUIRE((int64_t)XROWS * a.F * CIN < (1ll << 31), "convx3: map too wide");
-    const size_t lds = 2 * (size_t)XBUF;
-    auto kern = convx3_kernel<NT>;
-    AMTX_GRANT_LDS(kern, lds);
-    // persistent grid: one block per CU (152 KiB of LDS each), blocks of one group a multiple of 8 so that a block's tiles stay on its XCD
-    int64_t gx = std::max<int64_t>(8, 256 / std::max(1, a.groups) / 8 * 8);
-    if (gx > nblocks) gx = nblocks;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)a.groups), dim3(512), lds, stream, a, ft, ntf, ntt, (int)nblocks);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+// Pure, as conv_route: nothing is dereferenced or launched
+static ConvxRouted convx12_route(const ConvArgs& a) {
+    ConvxRouted r = {};
+    r.mc = a.feats16 != nullptr;
+    if (r.mc) {
+        AMTX_ROUTE_REQUIRE(r, a.c_in >= 2 && a.c_in <= 8 && !a.feats && !a.f_clip_max, "convx12: 16-bit channels-last features are the 2 .. 8-channel form");
+        AMTX_ROUTE_REQUIRE(r, a.in_split >= (int64_t)a.B * a.T * a.F * 8 && a.in_split % 8 == 0 && ((uintptr_t)a.feats16 % 16) == 0 && (int64_t)a.T * a.F < (1ll << 31),
+                           "convx12: feats16 needs its lo plane in_split elements (a multiple of 8, >= B T F 8) behind the hi plane, 16-byte aligned");
+    } else AMTX_ROUTE_REQUIRE(r, a.feats && a.c_in == 1, "convx12: fp32 features are the one-channel form");
+    AMTX_ROUTE_REQUIRE(r, convx_tiles(a, r.mc ? Y12<true>::FT : Y12<false>::FT, r), "convx12: grid too large");
+    r.lds = r.mc ? Y12<true>::LDS : Y12<false>::LDS;
+    r.inv_fcols = amtx_conv_recip(r.ft + 4, r.mc ? Y12<true>::FROWS * (r.ft + 4) : YFPRE * 256);
+    AMTX_ROUTE_REQUIRE(r, r.inv_fcols, "convx12: internal: reciprocal division inexact for fcols=%d", r.ft + 4);
+    return r;
+}
+
+static ConvxRouted convx3_route(const ConvArgs& a) {
+    ConvxRouted r = {};
+    r.nt = a.c_out / 16;
+    if (a.c_out != 64 && a.c_out != 32) AMTX_ROUTE_REFUSE(r, AMTX_ERR_UNSUPPORTED, "convx3: unsupported c_out=%d", a.c_out);
+    AMTX_ROUTE_REQUIRE(r, convx_tiles(a, XFT, r), "convx3: grid too large");
+    AMTX_ROUTE_REQUIRE(r, (int64_t)XROWS * a.F * CIN < (1ll << 31), "convx3: map too wide");
+    r.lds = 2 * (size_t)XBUF;
+    return r;
 }
 
 }  // namespace
@@ -720,14 +718,13 @@ int amtx_launch_convx12(const ConvArgs& a, hipStream_t stream) {
     AMTX_REQUIRE(a.w1frag && a.shift1 && a.wfrag && a.shift && a.out && a.c_out == 32 && a.planes == 2 && a.out_type == AMTX_T_SPLIT,
                  "convx12: 32 -> 32 channels, two-plane weights and maps only");
     AMTX_REQUIRE(a.out_split > 0 && a.out_split % 8 == 0 && ((uintptr_t)a.out % 16) == 0, "convx12: planes must be 16-byte aligned");
-    if (a.feats16) {
-        AMTX_REQUIRE(a.c_in >= 2 && a.c_in <= 8 && !a.feats && !a.f_clip_max, "convx12: 16-bit channels-last features are the 2 .. 8-channel form");
-        AMTX_REQUIRE(a.in_split >= (int64_t)a.B * a.T * a.F * 8 && a.in_split % 8 == 0 && ((uintptr_t)a.feats16 % 16) == 0 && (int64_t)a.T * a.F < (1ll << 31),
-                     "convx12: feats16 needs its lo plane in_split elements (a multiple of 8, >= B T F 8) behind the hi plane, 16-byte aligned");
-        return launch_x12<true>(a, stream);
-    }
-    AMTX_REQUIRE(a.feats && a.c_in == 1, "convx12: fp32 features are the one-channel form");
-    return launch_x12<false>(a, stream);
+    const ConvxRouted r = convx12_route(a);
+    AMTX_RETURN_REFUSAL(r);
+    const auto kern = r.mc ? convx12_kernel<true> : convx12_kernel<false>;
+    AMTX_GRANT_LDS(kern, r.lds);
+    hipLaunchKernelGGL(kern, dim3(r.gx, (unsigned)a.groups), dim3(512), r.lds, stream, a, r.ft, r.ntf, r.ntt, r.ntiles, r.inv_fcols);
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
 }
 
 // 32 -> c_out channels on AMTX_T_SPLIT maps; the caller (amtx_launch_conv3x3) has checked pointers, sizes and plane strides
@@ -735,8 +732,11 @@ int amtx_launch_convx3(const ConvArgs& a, hipStream_t stream) {
     AMTX_REQUIRE(a.in && a.wfrag && a.shift && a.out && a.planes == 2 && a.in_type == AMTX_T_SPLIT && a.out_type == AMTX_T_SPLIT, "convx3: two-plane maps and weights only");
     AMTX_REQUIRE(a.in_split > 0 && a.in_split % 8 == 0 && a.out_split > 0 && a.out_split % 8 == 0 && ((uintptr_t)a.in % 16) == 0 && ((uintptr_t)a.out % 16) == 0,
                  "convx3: planes must be 16-byte aligned");
-    if (a.c_out == 64) return launch_x3<4>(a, stream);
-    if (a.c_out == 32) return launch_x3<2>(a, stream);
-    amtx_set_error("convx3: unsupported c_out=%d", a.c_out);
-    return AMTX_ERR_UNSUPPORTED;
+    const ConvxRouted r = convx3_route(a);
+    AMTX_RETURN_REFUSAL(r);
+    const auto kern = r.nt == 4 ? convx3_kernel<4> : convx3_kernel<2>;
+    AMTX_GRANT_LDS(kern, r.lds);
+    hipLaunchKernelGGL(kern, dim3(r.gx, (unsigned)a.groups), dim3(512), r.lds, stream, a, r.ft, r.ntf, r.ntt, r.ntiles);
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
 }

@@ -135,3 +135,42 @@ def test_missing_extension_fails_loudly_without_a_cpu_fallback(monkeypatch):
     import amt_tools_amd, pathlib
     src = ''.join(p.read_text() for p in pathlib.Path(amt_tools_amd.__file__).parent.glob('*.py'))
     assert 'import oracle' not in src and 'from oracle' not in src
+
+
+# Arguments the convolution launchers refuse before anything is launched: (entry point, arguments after the pointers, return code, amtx_last_error).
+# Dummy non-null host pointers; shape B 1, T 17, F 10 unless the case says otherwise.  conv3x3_fwd: (elem_type, planes, B, T, F, c_out, null input);
+# conv3x3g_fwd: (elem_type, planes, B, T, F, c_in, c_out); conv1_fwd: (out_type, B, T, F, c_in, c_out).
+CONV_REFUSALS = [
+    ('amtx_conv3x3_fwd', (0, 1, 1, 17, 10, 48, False), -3, 'conv3x3: unsupported c_out=48 (supported: 32 and 64, with C_in = 32)'),
+    ('amtx_conv3x3_fwd', (2, 1, 1, 17, 10, 32, False), -3, 'conv3x3: in/out element types must match (bf16/bf16 or f32/f32)'),
+    ('amtx_conv3x3_fwd', (2, 2, 1, 17, 10, 32, False), -1, 'conv3x3: two-plane maps need plane strides'),
+    ('amtx_conv3x3_fwd', (0, 1, 1, 17, 1, 32, False), -1, 'conv3x3: bad sizes'),
+    ('amtx_conv3x3_fwd', (0, 1, 0, 17, 10, 32, False), -1, 'conv3x3: bad sizes'),
+    ('amtx_conv3x3_fwd', (0, 3, 1, 17, 10, 32, False), -1, 'conv3x3: planes must be 1 or 2'),
+    ('amtx_conv3x3_fwd', (0, 1, 1, 17, 10, 32, True), -1, 'conv3x3: null pointer'),
+    ('amtx_conv3x3g_fwd', (0, 1, 1, 17, 10, 40, 32), -3, 'conv3x3 (general): unsupported channel counts 40 -> 32'),
+    ('amtx_conv3x3g_fwd', (1, 1, 1, 17, 10, 48, 48), -3, 'conv3x3 (general): unsupported precision/type combination'),
+    ('amtx_conv3x3g_fwd', (0, 2, 1, 17, 10, 64, 64), -3, 'conv3x3 (general): unsupported precision/type combination'),
+    ('amtx_conv3x3g_fwd', (0, 1, 1, 17, 1, 48, 48), -1, 'conv3x3 (general): bad sizes'),
+    ('amtx_conv1_fwd', (1, 1, 17, 10, 1, 12), -1, 'conv1: bad sizes'),
+    ('amtx_conv1_fwd', (1, 1, 17, 10, 64, 64), -1, 'conv1: weights do not fit LDS'),
+]
+
+
+@pytest.mark.parametrize('entry,args,code,text', CONV_REFUSALS, ids=[f'{e[5:]}-{i}' for i, (e, *_) in enumerate(CONV_REFUSALS)])
+def test_conv_launchers_refuse_with_the_recorded_code_and_text(entry, args, code, text):
+    """Return code and amtx_last_error of the op-level convolution entry points for arguments their checks and routes refuse, as recorded
+    before the launchers were split into checks -> route -> launch.  Nothing reaches a launch, so this needs no GPU."""
+    L = _lib.lib()
+    host = np.zeros(64, dtype=np.float32)
+    p = _lib.ptr(host)
+    if entry == 'amtx_conv3x3_fwd':
+        elem, planes, b, t, f, c_out, null_in = args
+        rc = L.amtx_conv3x3_fwd(None if null_in else p, elem, p, planes, p, p, b, t, f, c_out, None)
+    elif entry == 'amtx_conv3x3g_fwd':
+        elem, planes, b, t, f, c_in, c_out = args
+        rc = L.amtx_conv3x3g_fwd(p, elem, p, planes, p, p, b, t, f, c_in, c_out, None)
+    else:
+        out_type, b, t, f, c_in, c_out = args
+        rc = L.amtx_conv1_fwd(p, f * t, 0, f, 1, p, p, p, out_type, b, t, f, c_in, c_out, None)
+    assert (rc, L.amtx_last_error().decode()) == (code, text)

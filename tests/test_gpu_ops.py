@@ -195,6 +195,70 @@ def test_conv1(cin, f, layout):
     assert (out.cpu() - ref).abs().max().item() < 2e-5
 
 
+# The kernel instantiation behind each op-level convolution entry point at B 2, T 17, F 10, as the profiler names it; recorded before the
+# launchers were split into checks -> route -> launch (element types among the template arguments: 0 = bf16, 1 = fp32).  Keys: conv3x3 /
+# conv3x3g: (c_in, c_out, planes); conv1: (c_in, c_out, out_type).
+CONV_KERNELS = {
+    ('conv3x3', 32, 32, 1): 'conv3x3_kernel<2, 1, 0, 0, false, 0>',
+    ('conv3x3', 32, 64, 1): 'conv3x3_kernel<4, 1, 0, 0, false, 0>',
+    ('conv3x3', 32, 32, 2): 'conv3x3_kernel<2, 2, 1, 1, false, 0>',
+    ('conv3x3', 32, 64, 2): 'conv3x3_kernel<4, 2, 1, 1, false, 0>',
+    ('conv3x3g', 32, 32, 1): 'conv3x3_gen_kernel<2, 2, 1, 32, 0, 0, 0, false, 0, false, false>',
+    ('conv3x3g', 48, 48, 1): 'conv3x3_gen_kernel<3, 3, 1, 32, 0, 0, 0, false, 0, false, false>',
+    ('conv3x3g', 48, 96, 1): 'conv3x3_gen_kernel<3, 3, 1, 32, 0, 0, 0, false, 0, false, false>',
+    ('conv3x3g', 64, 64, 1): 'conv3x3_gen_kernel<4, 2, 1, 32, 0, 0, 0, false, 0, false, false>',
+    ('conv3x3g', 64, 128, 1): 'conv3x3_gen_kernel<4, 2, 1, 32, 0, 0, 0, false, 0, false, false>',
+    ('conv3x3g', 80, 80, 1): 'conv3x3_gen_kernel<5, 1, 1, 32, 0, 0, 0, false, 0, false, false>',
+    ('conv3x3g', 80, 160, 1): 'conv3x3_gen_kernel<5, 1, 1, 32, 0, 0, 0, false, 0, false, false>',
+    ('conv3x3g', 32, 32, 2): 'conv3x3_gen_kernel<2, 2, 2, 16, 1, 1, 0, false, 0, false, false>',
+    ('conv3x3g', 48, 48, 2): 'conv3x3_gen_kernel<3, 3, 2, 16, 1, 1, 0, false, 0, false, false>',
+    ('conv3x3g', 48, 96, 2): 'conv3x3_gen_kernel<3, 3, 2, 16, 1, 1, 0, false, 0, false, false>',
+    ('conv3x3g', 64, 64, 2): 'conv3x3_gen_kernel<4, 2, 2, 16, 1, 1, 0, false, 0, false, false>',
+    ('conv3x3g', 64, 128, 2): 'conv3x3_gen_kernel<4, 2, 2, 16, 1, 1, 0, false, 0, false, false>',
+    ('conv3x3g', 80, 80, 2): 'conv3x3_gen_kernel<5, 1, 2, 16, 1, 1, 0, false, 0, false, false>',
+    ('conv3x3g', 80, 160, 2): 'conv3x3_gen_kernel<5, 1, 2, 16, 1, 1, 0, false, 0, false, false>',
+    ('conv1', 1, 32, 1): 'conv1_kernel<1>',
+    ('conv1', 1, 32, 0): 'conv1_kernel<0>',
+}
+
+
+@pytest.mark.parametrize('case', sorted(CONV_KERNELS), ids=lambda c: '-'.join(map(str, c)))
+def test_conv_entry_points_launch_the_recorded_kernel(case):
+    """Each entry point launches exactly one kernel, and it is the instantiation (template arguments included) that the route table of
+    DESIGN.md 5.11 names for these arguments.  Operands are zeros: only the launch is looked at."""
+    import re
+    L = _lib.lib()
+    op, cin, cout, mode = case
+    b, t, f = 2, 17, 10
+    shift = torch.zeros(cout, device='cuda')
+    if op == 'conv1':
+        x, w = torch.zeros(b, cin, f, t, device='cuda'), torch.zeros(cout, cin, 3, 3, device='cuda')
+        out = torch.zeros(b, t, f, cout, device='cuda', dtype=torch.float32 if mode == F32 else torch.bfloat16)
+        sb, sc, sf, st = x.stride()
+        run = lambda: _lib.check(L.amtx_conv1_fwd(_lib.ptr(x), sb, sc, st, sf, _lib.ptr(w), _lib.ptr(shift), _lib.ptr(out), mode,    # noqa: E731
+                                                  b, t, f, cin, cout, _stream()), 'amtx_conv1_fwd')
+    else:
+        dtype, elem = (torch.bfloat16, BF16) if mode == 1 else (torch.float32, F32)
+        n = L.amtx_conv3x3_packed_elems(cout, mode) if op == 'conv3x3' else L.amtx_conv3x3g_packed_elems(cin, cout, mode)
+        assert n > 0
+        x, wp = torch.zeros(b, t, f, cin, device='cuda', dtype=dtype), torch.zeros(n, device='cuda', dtype=torch.int16)
+        out = torch.zeros(b, t, f // 2, cout, device='cuda', dtype=dtype)
+        if op == 'conv3x3':
+            run = lambda: _lib.check(L.amtx_conv3x3_fwd(_lib.ptr(x), elem, _lib.ptr(wp), mode, _lib.ptr(shift), _lib.ptr(out),          # noqa: E731
+                                                        b, t, f, cout, _stream()), 'amtx_conv3x3_fwd')
+        else:
+            run = lambda: _lib.check(L.amtx_conv3x3g_fwd(_lib.ptr(x), elem, _lib.ptr(wp), mode, _lib.ptr(shift), _lib.ptr(out),         # noqa: E731
+                                                         b, t, f, cin, cout, _stream()), 'amtx_conv3x3g_fwd')
+    run()                                                             # the LDS grant and lazy module load stay out of the profile
+    torch.cuda.synchronize()
+    with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+        run()
+        torch.cuda.synchronize()
+    ran = [(m.group(0), e.count) for e in prof.key_averages() for m in [re.search(r'conv\w*_kernel<[^>]*>', e.key)] if m]
+    print(f'CONVROUTE {case!r}: {ran}')
+    assert ran == [(CONV_KERNELS[case], 1)], (case, [e.key for e in prof.key_averages()])
+
+
 def _lstm_ref(xproj, whh_f, whh_b, H=128):
     """xproj (B,T,2,4H) -> (B,T,2H), explicit loop in fp64."""
     B, T = xproj.shape[:2]
