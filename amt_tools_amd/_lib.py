@@ -1,5 +1,5 @@
 """
-ctypes binding of the amtx C ABI (include/amtx.h and the headers beside it, EXTRA_HEADERS -> amt_tools_amd/csrc/libamtx.so).
+ctypes binding of the amtx C ABI (include/amtx.h and the headers beside it, EXTRA_HEADERS and LATER_HEADERS -> amt_tools_amd/csrc/libamtx.so).
 
 The product path has NO fallback: if the shared library is missing or a call fails, an exception is
 raised.  Pointers handed to the library are raw device addresses (`tensor.data_ptr()`), the stream is
@@ -15,6 +15,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'amtx.h')
 # Further headers of the same library, bound the same way.  signatures() / declared_symbols() stay the table of amtx.h alone (pinned by
 # tests/golden/abi_signatures.json); each of these has its own pinned table (tests/golden/abi_signatures_tracks.json).
 EXTRA_HEADERS = ('amtx_tracks.h',)
+# Headers added since, each pinned by a table of its own again (tests/golden/abi_signatures_pyramid.json): EXTRA_HEADERS and
+# extra_signatures() are themselves pinned, so they keep answering what they answered.
+LATER_HEADERS = ('amtx_pyramid.h',)
 
 _lib = None
 
@@ -114,27 +117,41 @@ def declared_symbols():
 _extra_signatures = None
 
 
-def extra_signatures():
-    """{header name: parse_header of it} for EXTRA_HEADERS, read once per process.  A name declared twice across headers raises."""
+def _header_tables():
+    """({header: table} of EXTRA_HEADERS, the same of LATER_HEADERS), read once per process.  A name declared twice across headers raises."""
     global _extra_signatures
     if _extra_signatures is None:
-        tables, seen = {}, set(signatures())
-        for header in EXTRA_HEADERS:
-            with open(os.path.join(os.path.dirname(HEADER_PATH), header)) as f:
-                tables[header] = parse_header(f.read())
-            twice = seen & set(tables[header])
-            if twice:
-                raise AmtxError(f'{sorted(twice)[0]} is declared in {header} and in another header')
-            seen |= set(tables[header])
-        _extra_signatures = tables
+        seen = set(signatures())
+        both = []
+        for headers in (EXTRA_HEADERS, LATER_HEADERS):
+            tables = {}
+            for header in headers:
+                with open(os.path.join(os.path.dirname(HEADER_PATH), header)) as f:
+                    tables[header] = parse_header(f.read())
+                twice = seen & set(tables[header])
+                if twice:
+                    raise AmtxError(f'{sorted(twice)[0]} is declared in {header} and in another header')
+                seen |= set(tables[header])
+            both.append(tables)
+        _extra_signatures = tuple(both)
     return _extra_signatures
+
+
+def extra_signatures():
+    """{header name: parse_header of it} for EXTRA_HEADERS."""
+    return _header_tables()[0]
+
+
+def later_signatures():
+    """{header name: parse_header of it} for LATER_HEADERS."""
+    return _header_tables()[1]
 
 
 _funcs = {}            # name -> (function, number of parameters, its return value goes through check, it ends in `void* stream`)
 
 
 def lib():
-    """Load libamtx.so (once) and give every function include/amtx.h and EXTRA_HEADERS declare its restype / argtypes.  Raises AmtxError when the HIP
+    """Load libamtx.so (once) and give every function include/amtx.h, EXTRA_HEADERS and LATER_HEADERS declare its restype / argtypes.  Raises AmtxError when the HIP
     extension has not been built, when it lacks a declared function, or when the header holds a declaration parse_header cannot map."""
     global _lib
     if _lib is None:
@@ -147,7 +164,7 @@ def lib():
         except OSError as e:
             raise AmtxError(f'cannot load {LIB_PATH}: {e}') from e
         bound = dict(signatures())
-        for table in extra_signatures().values():
+        for table in list(extra_signatures().values()) + list(later_signatures().values()):
             bound.update(table)
         for name, (letters, stream) in bound.items():
             try:
@@ -171,7 +188,7 @@ def call(name, *args, device=None):
     try:
         fn, nargs, checked, stream = _funcs[name]
     except KeyError:
-        raise AmtxError(f'include/amtx.h and {", ".join(EXTRA_HEADERS)} declare no function {name}') from None
+        raise AmtxError(f'include/amtx.h and {", ".join(EXTRA_HEADERS + LATER_HEADERS)} declare no function {name}') from None
     fill_stream = stream and device is not None
     if len(args) + fill_stream != nargs:
         raise TypeError(f'{name} takes {nargs - fill_stream} arguments{" besides the stream" if fill_stream else ""} ({len(args)} given)')

@@ -15,6 +15,7 @@
 // is not bit-reproducible anyway), then |.|, per-(clip, harmonic) max, dB, /80+1.
 
 #include "amtx_kernels.h"
+#include "../../include/amtx_pyramid.h"
 
 #include <cstdlib>
 
@@ -53,6 +54,18 @@ __device__ __forceinline__ float row_max_f32(float v) {
     v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false)));   // row_half_mirror
     v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false)));   // row_mirror
     return v;
+}
+
+// a wave-uniform value the compiler cannot prove uniform (loaded through a table pointer), into scalar registers
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// re^2 + im^2 as two rounded squares and their rounded sum (no fma)
+__device__ __forceinline__ float power_unfused(float re, float im) {
+#pragma clang fp contract(off)
+    return re * re + im * im;
 }
 
 // level 0 of the pyramid: the clip copied between its centre paddings.  `zero_pads`: the paddings are written here too (zeros, librosa
@@ -249,257 +262,27 @@ struct BasisArgs {
 
 struct BasisLevs { int n; int lev[BAS_MAXLEV]; int b0[BAS_MAXLEV + 1]; };   // levels of a launch; blocks [b0[i], b0[i + 1]) work on level lev[i]
 
+// The clip form (include/amtx_pyramid.h): a tile belongs to a clip DESCRIPTOR instead of a batch index.  Clip b is frames
+// [first, first + frames) of one track of a bank whose level signals are resident; BasisLevel.sig is then the level's buffer (the audio, or the
+// pyramid behind its left pad) and the track's own base and length come from its row of the track table.  BasisArgs.B / mag / mag_pitch
+// describe the clip-sized maps [B][n_harm][n_bins][num_frames]; BasisLevel.frames = num_frames, sig_gs / len and BasisArgs.rows are unused.
+struct BasisClips {
+    const int64_t* tab;                    // [tracks][cols]: the track table of include/amtx_pyramid.h
+    const int64_t* desc;                   // [B][3] = {track, first_frame, frames}; null: clip b = track b, whole (the maxima launch)
+    int cols, rows_col, num_frames;
+    int base_col[BAS_MAXLEV], len_col[BAS_MAXLEV];   // per level: the table columns of the track's first element in BasisLevel.sig and of its length
+};
+
 // grid: (blocks of all levels of this K, column slices of 128): all levels of a call run side by side, the small deep ones under the large
 // shallow ones.  256-thread blocks, two per CU: a wave keeps the basis of ITS two column tiles in registers and walks the tile's frames on
 // its own (a dependent read -> MFMA chain per 16 frames), so what fills the matrix pipe is the other waves of the CU; a level with more than
 // 128 columns (HCQT's middle levels stack 144) runs a second slice of blocks for the rest, which stages the same signal again (an L2 hit).
-template <int KS>
-__global__ __launch_bounds__(256, 2) void cqt_basis_kernel(BasisArgs a, BasisLevs ls) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // [hi plane | lo plane] of the padded window, then 16 maxima
-    constexpr int K = 32 * KS;
-    // this block's level: the launch deals its blocks to the levels by their work (staged samples + a per-tile charge)
-    int li = 0;
-    while (li + 1 < ls.n && (int)blockIdx.x >= ls.b0[li + 1]) ++li;
-    const BasisLevel& L = a.lev[ls.lev[li]];
-    const int bid = (int)blockIdx.x - ls.b0[li], nblk = ls.b0[li + 1] - ls.b0[li];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // `hop` below is the frame stride of the STAGED copy: the level's hop, or K where the hop is larger (level 0, hop 512 > K = 256: rows do
-    // not overlap and only the K samples of every frame are staged, back to back)
-    const int ghop = L.hop, ft = L.ft;
-    const int hop = min(ghop, K), lh = __builtin_ctz(hop);        // powers of two
-    const int pad = bas_pad(hop);                                  // pad samples behind every `hop`
-    const int ws = (ft - 1) * hop + K;                             // samples of a tile's window
-    const int wsp = ws + pad * ((ws + hop - 1) / hop);             // ... in LDS
-    const int plane = ((wsp + 7) & ~7) * 2;                        // bytes per plane
-    unsigned* lmax = reinterpret_cast<unsigned*>(smem + 2 * plane);
-
-    // ---- this wave's columns: two 16-column tiles per wave, four waves = one slice of 128 columns; waves beyond the slice's columns share
-    // the frame tiles of a column group
-    const int col0 = 128 * blockIdx.y;                             // first column of this slice
-    if (col0 >= L.ncols) return;
-    const int nct = (min(L.ncols - col0, 128) + 15) >> 4;          // 16-column tiles with real columns in the slice (<= 8)
-    const int ncg = (nct + 1) >> 1;                                // column groups of two tiles (1 .. 4)
-    const int wpg = 4 / ncg;                                       // waves per group (4, 2, 1, 1)
-    const bool idle = wave >= ncg * wpg;
-    const int cg = (idle ? 0 : wave % ncg) + 4 * blockIdx.y, sub = wave / ncg;
-    const int g = lane >> 4, fl = lane & 15;
-    uint4 wh[2][KS], wl[2][KS];
-    {
-        const int64_t wplane = (int64_t)L.n_pad * L.k_pad;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int n = min((2 * cg + c) * 16 + fl, L.n_pad - 1);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                wh[c][ks] = *reinterpret_cast<const uint4*>(L.w + (int64_t)n * L.k_pad + ks * 32 + 8 * g);
-                wl[c][ks] = *reinterpret_cast<const uint4*>(L.w + wplane + (int64_t)n * L.k_pad + ks * 32 + 8 * g);
-            }
-        }
-    }
-    // pair maps of this lane's four columns per tile: columns n0 + 4 g + {0, 1} = (re, im) of one filter, + {2, 3} of the next
-    int2 pm[2][2];
-    bool pv[2][2];
-    int rl[2][2], ro[2][2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int n = (2 * cg + c) * 16 + 4 * g + 2 * h;
-            pv[c][h] = !idle && n < L.ncols;
-            pm[c][h] = L.map[min(n, L.ncols - 2) >> 1];
-            // frames of this filter's harmonic (0: the lane's columns do not exist): read ONCE -- indexed per lane inside the frame loop it was
-            // a memory round trip per filter and 16 frames
-            rl[c][h] = pv[c][h] ? a.rows[pm[c][h].y & 15] : 0;
-            ro[c][h] = pm[c][h].x * (int)a.mag_pitch;            // row offset inside the clip's map
-        }
-    // byte offset of this lane's operand inside a frame's window: sample 8 g of k-step 0 (+ 32 samples per k-step), pads included
-    auto soff = [&](int s) { return (s + pad * (s >> lh)) * 2; };
-    // ... split for the matrix loop: frame f starts at byte f * fstride, k-step ks of this lane koff[ks] bytes further
-    const int fstride = 2 * (hop + pad);
-    int koff[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) koff[ks] = soff(ks * 32 + 8 * g);
-
-    // ---- tile loop.  Staging: four samples per thread and step (a 16-byte load at any 4-byte boundary: clips of odd length in one buffer), in
-    // ROUNDS of six steps whose loads are issued back to back from clamped addresses (a load -> test -> store loop pays one memory round
-    // trip per step); what lies outside the signal is zeroed at the split.  Staged indices are multiples of 4 and so are the window origins,
-    // so a group hangs over the signal's END only (by 1 - 3 samples when the length is not a multiple of 4): its values are picked out of
-    // the clamped load by the distance it was moved.  The block's barriers wait for LDS traffic only (the stores of a tile's magnitudes
-    // and the maxima's atomics stay in flight), and the other block of the CU covers a tile's load round trips.
-    struct __attribute__((packed, aligned(4))) f32x4_a4 { float x, y, z, w; };
-    constexpr int NST = 6, NSTF = 9;             // loads per round: the general path / a tile inside the signal (fewer temporaries: 36 registers of loads fit)
-    const int ntile = L.tiles_per_clip * a.B;
-    if (tid < 16) lmax[tid] = 0u;
-#ifdef AMTX_CQT_TIMING
-    unsigned long long bq_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bq_t = __builtin_readcyclecounter();
-#endif
-    for (int tile = bid; tile < ntile; tile += nblk) {
-        BQ_TICK(0);
-        const int b = tile / L.tiles_per_clip, tt = tile - b * L.tiles_per_clip;
-        const int f0 = tt * ft;                                    // first frame of the tile
-        const float* sig = L.sig + (int64_t)b * L.sig_gs;
-        const int64_t s0 = (int64_t)f0 * ghop - K / 2 + L.off;     // first sample of the window (index into sig)
-        // staged index i -> signal index: identity while the windows overlap, frame-wise (hop > K) otherwise
-        auto sidx = [&](int i) { return s0 + (ghop > K ? (int64_t)(i >> lh) * ghop + (i & (hop - 1)) : (int64_t)i); };
-        // a tile whose whole window lies inside the signal (all but a clip's first and last tiles): no clamping, no picking -- a third of the
-        // instructions of the general case below (which was 37 % of the kernel's vector instructions)
-        const int64_t s_end = s0 + (ghop > K ? (int64_t)(ft - 1) * ghop + K : (int64_t)ws);
-        if (s0 >= 0 && s_end <= L.len) {
-            const float* st = sig + s0;                            // wave-uniform base, 32-bit offsets per lane
-            for (int base = 0; base < ws; base += 1024 * NSTF) {
-                f32x4_a4 rr[NSTF];
-#pragma unroll
-                for (int n = 0; n < NSTF; ++n) {
-                    const int i = min(base + 4 * tid + 1024 * n, ws - 4);
-                    rr[n] = *reinterpret_cast<const f32x4_a4*>(st + (unsigned)(ghop > K ? (i >> lh) * ghop + (i & (hop - 1)) : i));
-                }
-#pragma unroll
-                for (int n = 0; n < NSTF; ++n) {
-                    const int i = base + 4 * tid + 1024 * n;
-                    uint32_t h0, h1, l0, l1;
-                    split_bf16x2(rr[n].x, rr[n].y, h0, l0);
-                    split_bf16x2(rr[n].z, rr[n].w, h1, l1);
-                    if (i < ws) {
-                        const int o = soff(i);
-                        *reinterpret_cast<uint2*>(smem + o) = make_uint2(h0, h1);
-                        *reinterpret_cast<uint2*>(smem + plane + o) = make_uint2(l0, l1);
-                    }
-                }
-            }
-        } else
-        for (int base = 0; base < ws; base += 1024 * NST) {
-            f32x4_a4 rr[NST];
-#pragma unroll
-            for (int n = 0; n < NST; ++n) {
-                const int64_t q = sidx(min(base + 4 * tid + 1024 * n, ws - 4));
-                rr[n] = *reinterpret_cast<const f32x4_a4*>(sig + min(max(q, (int64_t)0), L.len - 4));
-            }
-#pragma unroll
-            for (int n = 0; n < NST; ++n) {
-                const int i = base + 4 * tid + 1024 * n;
-                const int64_t q = sidx(min(i, ws - 4));
-                // 0: as loaded; 1 - 3: the load was moved back by that much; 4: nothing of the group exists
-                const int d = (q < 0 || q >= L.len) ? 4 : (int)(q - min(q, L.len - 4));
-                const float r[4] = {rr[n].x, rr[n].y, rr[n].z, rr[n].w};
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    // element e of the group is element e + d of the load, if that exists
-                    float x = r[e];
-                    if (e + 1 < 4) x = d == 1 ? r[e + 1] : x;
-                    if (e + 2 < 4) x = d == 2 ? r[e + 2] : x;
-                    if (e + 3 < 4) x = d == 3 ? r[e + 3] : x;
-                    v[e] = e + d < 4 ? x : 0.f;
-                }
-                uint32_t h0, h1, l0, l1;
-                split_bf16x2(v[0], v[1], h0, l0);
-                split_bf16x2(v[2], v[3], h1, l1);
-                if (i < ws) {
-                    const int o = soff(i);                         // four samples never straddle a pad (blocks are multiples of 4)
-                    *reinterpret_cast<uint2*>(smem + o) = make_uint2(h0, h1);
-                    *reinterpret_cast<uint2*>(smem + plane + o) = make_uint2(l0, l1);
-                }
-            }
-        }
-        BQ_TICK(1);
-        lds_only_barrier();
-        BQ_TICK(2);
-        float mx[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-        const int nft = idle ? 0 : min(ft, L.frames - f0 + 15) >> 4;   // 16-frame tiles with real frames (a wave without columns has none)
-        float* magb = a.mag + (int64_t)b * a.mag_gs;               // wave-uniform base, 32-bit offsets per lane (a clip's map is < 2^31 elements)
-        // TWO 16-frame tiles per step: four independent accumulator chains and twice the reads in flight (one tile at a time, a wave waited for
-        // every k-step's reads in front of its six dependent MFMAs)
-        for (int q = sub; q < nft; q += 2 * wpg) {
-            const int q2 = q + wpg < nft ? q + wpg : q;            // the second tile of the step (the first again when there is none: not stored)
-            const int fr[2] = {q * 16 + fl, q2 * 16 + fl};         // this lane's frames inside the tile
-            f32x4_t acc[2][2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) acc[u][c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            // operand reads run BAS_AHEAD k-steps ahead of the matrix instructions that use them, both pinned: left to itself hipcc reads a
-            // k-step's four operands right in front of its twelve instructions (an LDS round trip per k-step, ~45 % on top of the matrix time)
-            const int fbase[2] = {fr[0] * fstride, fr[1] * fstride};
-            constexpr int NB = BAS_AHEAD + 1;              // operand sets in flight (a ring)
-            uint4 ah[NB][2], al[NB][2];
-            auto fetch = [&](int ks) {
-                const int sl = ks % NB;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int o = fbase[u] + koff[ks];
-                    if (hop >= 8) {
-                        ah[sl][u] = *reinterpret_cast<const uint4*>(smem + o);
-                        al[sl][u] = *reinterpret_cast<const uint4*>(smem + plane + o);
-                    } else {                                       // hop 4: windows start at 8-byte boundaries
-                        const uint2 h0 = *reinterpret_cast<const uint2*>(smem + o), h1 = *reinterpret_cast<const uint2*>(smem + o + 8);
-                        const uint2 l0 = *reinterpret_cast<const uint2*>(smem + plane + o), l1 = *reinterpret_cast<const uint2*>(smem + plane + o + 8);
-                        ah[sl][u] = make_uint4(h0.x, h0.y, h1.x, h1.y);
-                        al[sl][u] = make_uint4(l0.x, l0.y, l1.x, l1.y);
-                    }
-                }
-            };
-#pragma unroll
-            for (int ks = 0; ks < BAS_AHEAD; ++ks) fetch(ks);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if (ks + BAS_AHEAD < KS) fetch(ks + BAS_AHEAD);
-                __builtin_amdgcn_sched_barrier(0);
-                // per accumulator hi.hi, hi.lo, lo.hi (gemm_tile's order), the four accumulators taking turns
-#pragma unroll
-                for (int pr = 0; pr < 3; ++pr) {
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int c = 0; c < 2; ++c)
-                            acc[u][c] = mfma16(pr == 2 ? wl[c][ks] : wh[c][ks], pr == 1 ? al[ks % NB][u] : ah[ks % NB][u], acc[u][c]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (u == 1 && q2 == q) break;                      // wave-uniform
-                const int m = f0 + fr[u];
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        if (m < rl[c][h]) {
-                            const float re = acc[u][c][2 * h], im = acc[u][c][2 * h + 1];
-                            const float v = re * re + im * im;           // power: the scaling kernels take its logarithm (or its root)
-                            magb[(unsigned)(ro[c][h] + m)] = v;
-                            mx[c][h] = fmaxf(mx[c][h], v);
-                        }
-                    }
-            }
-        }
-        BQ_TICK(3);
-        // per-(clip, harmonic) maxima: magnitudes are >= 0, so uint order == float order
-        // the 16 lanes of a row (one lane group g) hold the same four filters: their maximum by DPP, one LDS atomic per row and filter (64
-        // lanes on <= 6 addresses each were half of the kernel's LDS bank-conflict cycles)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float m = row_max_f32(mx[c][h]);
-                if (fl == 0 && m > 0.f) atomicMax(lmax + (pm[c][h].y & 15), __float_as_uint(m));
-            }
-        lds_only_barrier();                                        // everybody is done with the staged copy, the maxima are in
-        if (tid < 16) {
-            const unsigned v = lmax[tid];
-            lmax[tid] = 0u;                                        // for the next tile (ordered behind its barrier)
-            if (v != 0u) atomicMax(reinterpret_cast<unsigned*>(a.maxbuf) + (int64_t)b * a.n_harm + tid, v);
-        }
-        BQ_TICK(4);
-#ifdef AMTX_CQT_TIMING
-        bq_acc[7] += 1;
-#endif
-    }
-#ifdef AMTX_CQT_TIMING
-    if (tid == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&g_bas_prof[i], bq_acc[i]);
-#endif
-}
+#define CQT_BASIS_CLIPS 0
+#include "cqt_basis_kernel.h"            // cqt_basis_kernel<KS>: equal clips side by side in a batch
+#undef CQT_BASIS_CLIPS
+#define CQT_BASIS_CLIPS 1
+#include "cqt_basis_kernel.h"            // cqt_basis_clips_kernel<KS>: clips cut from resident pyramids
+#undef CQT_BASIS_CLIPS
 
 struct Level {
     int nfft = 0, ncols = 0, hop = 0;
@@ -824,6 +607,82 @@ extern "C" size_t amtx_cqt_workspace_bytes(const amtx_cqt_plan* p, int batch, in
     return dims(p, batch, num_samples).total;
 }
 
+namespace {
+
+// the plans, level lengths `len` and map widths `t_buf` whose basis products the windowed kernel computes; every other goes through the
+// generic GEMM
+bool basis_windowed(const amtx_cqt_plan* p, const std::vector<int64_t>& len, int64_t t_buf) {
+    const int nl = (int)p->levels.size();
+    bool windowed = nl <= BAS_MAXLEV && p->n_harm <= 16 && (int64_t)p->n_harm * p->n_bins * t_buf < (1ll << 31);
+    for (int l = 0; l < nl && windowed; ++l) {
+        const Level& L = p->levels[l];
+        if (L.banks.empty()) continue;
+        windowed = (L.nfft == 128 || L.nfft == 256) && L.k_pad >= L.nfft && L.ncols <= 256 && L.ncols % 2 == 0 && L.hop >= 4 && (L.hop & (L.hop - 1)) == 0 &&
+                   (L.hop <= 512) && len[l] >= 4;
+    }
+    return windowed;
+}
+
+// the plan's part of a level's BasisLevel and its tiling over `frames` frames per clip; sig / sig_gs / len / off are the caller's
+void basis_level(const Level& L, int frames, BasisLevel& bl) {
+    bl.w = L.d_w; bl.map = L.d_map; bl.n_pad = L.n_pad; bl.k_pad = L.k_pad; bl.ncols = L.ncols; bl.hop = L.hop;
+    bl.frames = frames;
+    const int hs0 = std::min(L.hop, L.nfft);
+    int ftl = std::max(16, std::min(128, ((BAS_MAXWIN - L.nfft) / hs0 + 1) / 16 * 16));
+    ftl = std::min(ftl, (bl.frames + 15) / 16 * 16);
+    bl.ft = ftl;
+    bl.tiles_per_clip = (bl.frames + ftl - 1) / ftl;
+}
+
+// one launch per n_fft over the levels of `ba`; cl: the clip form (cqt_basis_clips_kernel)
+int basis_launch(const amtx_cqt_plan* p, const BasisArgs& ba, const BasisClips* cl, hipStream_t s) {
+    const int nl = ba.nlev, B = ba.B;
+    for (int kk = 128; kk <= 256; kk *= 2) {
+        BasisLevs ls;
+        ls.n = 0;
+        size_t lds = 0;
+        for (int l = 0; l < nl; ++l) {
+            const BasisLevel& bl = ba.lev[l];
+            if (bl.frames <= 0 || p->levels[l].nfft != kk) continue;
+            const int hs = std::min(bl.hop, kk);               // frame stride of the staged copy (cqt_basis_kernel)
+            const int ws_s = (bl.ft - 1) * hs + kk;
+            const int wsp = ws_s + bas_pad(hs) * ((ws_s + hs - 1) / hs);
+            lds = std::max(lds, (size_t)((wsp + 7) & ~7) * 2 * 2 + 64);
+            ls.lev[ls.n++] = l;
+        }
+        if (!ls.n) continue;
+        // two 256-thread blocks per CU; the levels (and the second column slice of the wide ones) share the chip: 512 blocks dealt EVENLY to the
+        // levels (dealing them by staged samples, by matrix work or by a mix was measured slower, 2.2 - 2.6 against 1.97 ms for the
+        // front-end: the deep levels' tiles are as many as the shallow ones' and a tile's fixed costs -- barriers, a load round trip, the
+        // maxima's atomics -- weigh as much as its size)
+        int slices = 1;
+        for (int i = 0; i < ls.n; ++i) slices = std::max(slices, (ba.lev[ls.lev[i]].ncols + 127) / 128);
+        ls.b0[0] = 0;
+        for (int i = 0; i < ls.n; ++i) {
+            const int64_t tiles = (int64_t)ba.lev[ls.lev[i]].tiles_per_clip * B;
+            ls.b0[i + 1] = ls.b0[i] + (int)std::min<int64_t>(std::max(8, 512 / ls.n), tiles);
+        }
+        const unsigned gx = (unsigned)ls.b0[ls.n];
+        if (cl && kk == 256) {
+            AMTX_GRANT_LDS(cqt_basis_clips_kernel<8>, lds);
+            hipLaunchKernelGGL(cqt_basis_clips_kernel<8>, dim3(gx, slices), dim3(256), lds, s, ba, ls, *cl);
+        } else if (cl) {
+            AMTX_GRANT_LDS(cqt_basis_clips_kernel<4>, lds);
+            hipLaunchKernelGGL(cqt_basis_clips_kernel<4>, dim3(gx, slices), dim3(256), lds, s, ba, ls, *cl);
+        } else if (kk == 256) {
+            AMTX_GRANT_LDS(cqt_basis_kernel<8>, lds);
+            hipLaunchKernelGGL(cqt_basis_kernel<8>, dim3(gx, slices), dim3(256), lds, s, ba, ls);
+        } else {
+            AMTX_GRANT_LDS(cqt_basis_kernel<4>, lds);
+            hipLaunchKernelGGL(cqt_basis_kernel<4>, dim3(gx, slices), dim3(256), lds, s, ba, ls);
+        }
+        AMTX_CHECK_LAUNCH();
+    }
+    return AMTX_OK;
+}
+
+}  // namespace
+
 // out16 != null: the map as [B][T][n_bins][8] bf16 (amtx_cqt_forward16) instead of `out`
 static int cqt_forward_impl(const amtx_cqt_plan* p, const float* audio, int64_t num_samples, int64_t audio_stride, int batch, int decibels,
                             void* workspace, size_t workspace_bytes, float* out, void* out16, void* stream_, int64_t lo_plane = 0) {
@@ -870,13 +729,7 @@ static int cqt_forward_impl(const amtx_cqt_plan* p, const float* audio, int64_t 
     // the basis products of all levels: the windowed kernel (cqt_basis_kernel), one launch per level on the same stream; AMTX_CQT_GEMM_BASIS=1
     // keeps round 4's path (all levels in ONE launch of the generic fp32-A two-plane GEMM) for the A/B
     static const bool gemm_basis = getenv("AMTX_CQT_GEMM_BASIS") != nullptr;
-    bool windowed = !gemm_basis && nl <= BAS_MAXLEV && p->n_harm <= 16 && (int64_t)p->n_harm * p->n_bins * d.t_buf < (1ll << 31);
-    for (int l = 0; l < nl && windowed; ++l) {
-        const Level& L = p->levels[l];
-        if (L.banks.empty()) continue;
-        windowed = (L.nfft == 128 || L.nfft == 256) && L.k_pad >= L.nfft && L.ncols <= 256 && L.ncols % 2 == 0 && L.hop >= 4 && (L.hop & (L.hop - 1)) == 0 &&
-                   (L.hop <= 512) && d.len[l] >= 4;
-    }
+    const bool windowed = !gemm_basis && basis_windowed(p, d.len, d.t_buf);
     if (windowed) {
         BasisArgs ba;
         ba.nlev = nl; ba.B = B; ba.ntiles = 0;
@@ -894,49 +747,10 @@ static int cqt_forward_impl(const amtx_cqt_plan* p, const float* audio, int64_t 
             // librosa 0.9's reflecting pads live in the pyramid buffer on both sides of the signal: there every sample the windows touch exists
             bl.off = 0;
             if (!zero_pads) { bl.sig -= p->pad; bl.off = p->pad; bl.len = d.stride[l]; }
-            bl.w = L.d_w; bl.map = L.d_map; bl.n_pad = L.n_pad; bl.k_pad = L.k_pad; bl.ncols = L.ncols; bl.hop = L.hop;
-            bl.frames = (int)d.frames[l];
-            const int hs0 = std::min(L.hop, L.nfft);
-            int ftl = std::max(16, std::min(128, ((BAS_MAXWIN - L.nfft) / hs0 + 1) / 16 * 16));
-            ftl = std::min(ftl, (bl.frames + 15) / 16 * 16);
-            bl.ft = ftl;
-            bl.tiles_per_clip = (bl.frames + ftl - 1) / ftl;
+            basis_level(L, (int)d.frames[l], bl);
         }
-        for (int kk = 128; kk <= 256; kk *= 2) {
-            BasisLevs ls;
-            ls.n = 0;
-            size_t lds = 0;
-            for (int l = 0; l < nl; ++l) {
-                const BasisLevel& bl = ba.lev[l];
-                if (bl.frames <= 0 || p->levels[l].nfft != kk) continue;
-                const int hs = std::min(bl.hop, kk);               // frame stride of the staged copy (cqt_basis_kernel)
-                const int ws_s = (bl.ft - 1) * hs + kk;
-                const int wsp = ws_s + bas_pad(hs) * ((ws_s + hs - 1) / hs);
-                lds = std::max(lds, (size_t)((wsp + 7) & ~7) * 2 * 2 + 64);
-                ls.lev[ls.n++] = l;
-            }
-            if (!ls.n) continue;
-            // two 256-thread blocks per CU; the levels (and the second column slice of the wide ones) share the chip: 512 blocks dealt EVENLY to the
-            // levels (dealing them by staged samples, by matrix work or by a mix was measured slower, 2.2 - 2.6 against 1.97 ms for the
-            // front-end: the deep levels' tiles are as many as the shallow ones' and a tile's fixed costs -- barriers, a load round trip, the
-            // maxima's atomics -- weigh as much as its size)
-            int slices = 1;
-            for (int i = 0; i < ls.n; ++i) slices = std::max(slices, (ba.lev[ls.lev[i]].ncols + 127) / 128);
-            ls.b0[0] = 0;
-            for (int i = 0; i < ls.n; ++i) {
-                const int64_t tiles = (int64_t)ba.lev[ls.lev[i]].tiles_per_clip * B;
-                ls.b0[i + 1] = ls.b0[i] + (int)std::min<int64_t>(std::max(8, 512 / ls.n), tiles);
-            }
-            const unsigned gx = (unsigned)ls.b0[ls.n];
-            if (kk == 256) {
-                AMTX_GRANT_LDS(cqt_basis_kernel<8>, lds);
-                hipLaunchKernelGGL(cqt_basis_kernel<8>, dim3(gx, slices), dim3(256), lds, s, ba, ls);
-            } else {
-                AMTX_GRANT_LDS(cqt_basis_kernel<4>, lds);
-                hipLaunchKernelGGL(cqt_basis_kernel<4>, dim3(gx, slices), dim3(256), lds, s, ba, ls);
-            }
-            AMTX_CHECK_LAUNCH();
-        }
+        const int rc = basis_launch(p, ba, nullptr, s);
+        if (rc != AMTX_OK) return rc;
     } else {
     // the basis products of ALL levels in one launch (same kernel, per-level A / W / sizes; 8 launches before)
     GemmArgs gs[AMTX_GEMM_MULTI_MAX];
@@ -1009,4 +823,212 @@ extern "C" int amtx_cqt_forward16_split(const amtx_cqt_plan* p, const float* aud
                                         void* workspace, size_t workspace_bytes, void* out16, int64_t plane_elems, void* stream_) {
     AMTX_REQUIRE(out16 && plane_elems > 0 && plane_elems % 8 == 0, "amtx_cqt_forward16_split: null pointer / plane stride not a multiple of 8 elements");
     return cqt_forward_impl(p, audio, num_samples, audio_stride, batch, decibels, workspace, workspace_bytes, nullptr, out16, stream_, plane_elems / 8);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Clips cut from the resident pyramids of whole tracks (include/amtx_pyramid.h).  The tables are device memory: the track table is checked
+// on its host copy where the bank is built (amtx_cqt_pyramid_build), the descriptors where they are made (amt_tools_amd/tracks.py).
+namespace {
+
+int pyr_cols(const amtx_cqt_plan* p) { return 4 + 3 * (int)p->levels.size() + p->n_harm; }
+
+// the basis products of `B` clips of `num_frames` frames (desc) or of the table's `B` tracks whole (desc = null, num_frames = the longest's
+// rows): power maps into `mag` and / or maxima into `maxima`
+int clips_basis(const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tab, const int64_t* desc, int B, int64_t num_frames,
+                float* mag, float* maxima, hipStream_t s) {
+    const int nl = (int)p->levels.size();
+    BasisArgs ba;
+    ba.nlev = nl; ba.B = B; ba.ntiles = 0;
+    ba.mag = mag; ba.mag_gs = (int64_t)p->n_harm * p->n_bins * num_frames; ba.mag_pitch = num_frames;
+    ba.maxbuf = maxima; ba.n_harm = p->n_harm;
+    for (int h = 0; h < 16; ++h) ba.rows[h] = 0;
+    BasisClips cl;
+    cl.tab = tab; cl.desc = desc; cl.cols = pyr_cols(p); cl.rows_col = 4 + 3 * nl; cl.num_frames = (int)num_frames;
+    for (int l = 0; l < nl; ++l) {
+        const Level& L = p->levels[l];
+        BasisLevel& bl = ba.lev[l];
+        bl = BasisLevel();
+        cl.base_col[l] = 4 + 3 * l;
+        if (L.banks.empty()) { bl.frames = 0; cl.len_col[l] = 4 + 3 * l + 1; continue; }
+        if (!p->lib09 && l == 0) {            // zero pads: level 0 is the audio where it lies
+            bl.sig = audio; bl.off = 0;
+            cl.base_col[l] = 0; cl.len_col[l] = 1;
+        } else if (!p->lib09) {               // the samples behind the level's left pad; everything outside them reads as zero
+            bl.sig = pyramid + p->pad; bl.off = 0;
+            cl.len_col[l] = 4 + 3 * l + 1;
+        } else {                              // reflecting pads: every sample of the level's stride exists
+            bl.sig = pyramid; bl.off = p->pad;
+            cl.len_col[l] = 4 + 3 * l + 2;
+        }
+        basis_level(L, (int)num_frames, bl);
+    }
+    return basis_launch(p, ba, &cl, s);
+}
+
+int clips_check(const char* fn, const amtx_cqt_plan* p, int batch, int64_t num_frames) {
+    AMTX_REQUIRE(batch > 0 && batch < 65536 && num_frames > 0 && num_frames < (1ll << 31), "%s: bad batch/num_frames", fn);
+    if (!basis_windowed(p, std::vector<int64_t>(p->levels.size(), 4), num_frames)) {
+        amtx_set_error("%s: this plan's basis products have no clip form (the windowed kernel does not cover it)", fn);
+        return AMTX_ERR_UNSUPPORTED;
+    }
+    return AMTX_OK;
+}
+
+int clips_scaled(const char* fn, const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tab, const int64_t* desc, int batch,
+                 int64_t num_frames, const float* refs, int decibels, void* workspace, size_t workspace_bytes, float* out, void* out16,
+                 int64_t lo_plane, void* stream_) {
+    AMTX_REQUIRE(p && audio && pyramid && tab && desc && refs && workspace && (out || out16), "%s: null argument", fn);
+    int rc = clips_check(fn, p, batch, num_frames);
+    if (rc != AMTX_OK) return rc;
+    AMTX_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", fn);
+    const size_t need = amtx_cqt_clips_workspace_bytes(p, batch, num_frames);
+    AMTX_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream_;
+    float* mag = (float*)workspace;
+    rc = clips_basis(p, audio, pyramid, tab, desc, batch, num_frames, mag, nullptr, s);
+    if (rc != AMTX_OK) return rc;
+    // the whole-track scaling kernels with a clip-sized map (t_buf = t_out = num_frames) and the tracks' maxima as references
+    if (out16) {
+        AMTX_REQUIRE(p->n_harm <= 8 && ((uintptr_t)out16 % 16) == 0, "%s: at most 8 harmonics, output 16-byte aligned", fn);
+        const int nbc = std::min(p->n_bins, 120);
+        const size_t lds = (size_t)(lo_plane ? 2 : 1) * SC16_TT * (nbc + 1) * 16 + 64;
+        AMTX_GRANT_LDS(cqt_scale16_kernel, lds);
+        hipLaunchKernelGGL(cqt_scale16_kernel, dim3((unsigned)((num_frames + SC16_TT - 1) / SC16_TT), batch), dim3(256), lds, s, (const float*)mag, refs,
+                           p->n_harm, p->n_bins, nbc, num_frames, num_frames, decibels, (uint4*)out16, lo_plane);
+    } else {
+        hipLaunchKernelGGL(cqt_scale_kernel, dim3(8, batch * p->n_harm), dim3(256), 0, s, (const float*)mag, refs, p->n_bins, num_frames, num_frames,
+                           decibels, out);
+    }
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
+}
+
+}  // namespace
+
+extern "C" int amtx_cqt_track_cols(const amtx_cqt_plan* p) {
+    AMTX_REQUIRE(p, "amtx_cqt_track_cols: null plan");
+    return pyr_cols(p);
+}
+
+extern "C" int amtx_cqt_track_layout(const amtx_cqt_plan* p, int64_t num_samples, int64_t* level_len, int64_t* level_stride, int64_t* rows_h,
+                                     int64_t* frames) {
+    AMTX_REQUIRE(p && level_len && level_stride && rows_h && frames, "amtx_cqt_track_layout: null argument");
+    AMTX_REQUIRE(num_samples > 0, "amtx_cqt_track_layout: bad num_samples");
+    const int nl = (int)p->levels.size();
+    const CqtDims d = dims(p, 1, num_samples);
+    if (nl > 16 || !basis_windowed(p, d.len, d.t_buf)) {
+        amtx_set_error("amtx_cqt_track_layout: no clip form: the windowed basis kernel does not cover this plan (n_fft 128 or 256 on every level; "
+                       "or a pyramid level of these %lld samples has fewer than 4)", (long long)num_samples);
+        return AMTX_ERR_UNSUPPORTED;
+    }
+    AMTX_REQUIRE(d.t_out > 0, "amtx_cqt_track_layout: track too short for one frame");
+    // amtx_cqt_forward's own condition: the deepest level reflects about its ends
+    if (p->lib09) AMTX_REQUIRE(d.len.back() > p->pad, "amtx_cqt_track_layout: reflect padding needs a longer track (deepest level: %lld samples, pad %d)",
+                               (long long)d.len.back(), p->pad);
+    for (int l = 0; l < nl; ++l) {
+        level_len[l] = d.len[l];
+        level_stride[l] = (!p->lib09 && l == 0) ? 0 : d.stride[l];      // zero pads: level 0 is the audio, read in place
+    }
+    for (int h = 0; h < p->n_harm; ++h) rows_h[h] = d.frames_h[h];
+    *frames = d.t_out;
+    return nl;
+}
+
+extern "C" int amtx_cqt_pyramid_build(const amtx_cqt_plan* p, const float* audio, int64_t audio_elems, const int64_t* tracks_host,
+                                      const int64_t* tracks, int num_tracks, float* pyramid, int64_t pyramid_elems, float* maxima, void* stream_) {
+    AMTX_REQUIRE(p && audio && tracks_host && tracks && pyramid && maxima, "amtx_cqt_pyramid_build: null argument");
+    AMTX_REQUIRE(num_tracks > 0 && num_tracks < 65536 && audio_elems > 0 && pyramid_elems > 0, "amtx_cqt_pyramid_build: bad num_tracks / buffer sizes");
+    AMTX_REQUIRE(((uintptr_t)audio % 16) == 0 && ((uintptr_t)pyramid % 16) == 0, "amtx_cqt_pyramid_build: audio and pyramid must be 16-byte aligned");
+    const int nl = (int)p->levels.size(), cols = pyr_cols(p);
+    // the host table against the plan's own layout and the buffers: nothing below writes or reads outside what it describes
+    int64_t audio_end = 0, pyr_end = 0, rows_max = 0;
+    for (int t = 0; t < num_tracks; ++t) {
+        const int64_t* tr = tracks_host + (int64_t)t * cols;
+        int64_t len[16], stride[16], rows[16], frames = 0;
+        AMTX_REQUIRE(tr[1] > 0, "amtx_cqt_pyramid_build: track %d has no samples", t);
+        const int rc = amtx_cqt_track_layout(p, tr[1], len, stride, rows, &frames);
+        if (rc < 0) return rc;
+        AMTX_REQUIRE(tr[0] >= audio_end && tr[0] % 4 == 0 && tr[0] + tr[1] <= audio_elems, "amtx_cqt_pyramid_build: track %d: bad place in the audio buffer", t);
+        audio_end = tr[0] + tr[1];
+        int64_t rmax = 0;
+        for (int h = 0; h < p->n_harm; ++h) {
+            AMTX_REQUIRE(tr[4 + 3 * nl + h] == rows[h], "amtx_cqt_pyramid_build: track %d: rows of harmonic %d differ from the plan's", t, h);
+            rmax = std::max(rmax, rows[h]);
+        }
+        AMTX_REQUIRE(tr[2] == rmax && tr[3] == frames, "amtx_cqt_pyramid_build: track %d: frame counts differ from the plan's", t);
+        rows_max = std::max(rows_max, rmax);
+        for (int l = 0; l < nl; ++l) {
+            const int64_t* lv = tr + 4 + 3 * l;
+            AMTX_REQUIRE(lv[1] == len[l] && lv[2] == stride[l], "amtx_cqt_pyramid_build: track %d: level %d differs from the plan's layout", t, l);
+            AMTX_REQUIRE(lv[0] >= pyr_end && lv[0] % 4 == 0 && lv[0] + lv[2] <= pyramid_elems, "amtx_cqt_pyramid_build: track %d: bad place of level %d in the pyramid", t, l);
+            pyr_end = lv[0] + lv[2];
+        }
+    }
+    int rc = clips_check("amtx_cqt_pyramid_build", p, num_tracks, rows_max);
+    if (rc != AMTX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    const int zero_pads = p->lib09 ? 0 : 1;
+    AMTX_CHECK_HIP(hipMemsetAsync(maxima, 0, sizeof(float) * num_tracks * p->n_harm, s));
+    // the chain of amtx_cqt_forward on every track as a batch of one: the level signals are the whole-track forward's
+    for (int t = 0; t < num_tracks; ++t) {
+        const int64_t* tr = tracks_host + (int64_t)t * cols;
+        const float* src = audio + tr[0];
+        for (int l = 0; l < nl; ++l) {
+            const int64_t* lv = tr + 4 + 3 * l;
+            float* pyr = pyramid + lv[0];
+            if (l == 0) {
+                if (zero_pads) continue;
+                const unsigned nb = (unsigned)std::min<int64_t>((tr[1] + 255) / 256, 4096);
+                hipLaunchKernelGGL(cqt_level0_kernel, dim3(nb, 1), dim3(256), 0, s, src, tr[1], tr[1], pyr, lv[2], p->pad, 0, maxima + (int64_t)t * p->n_harm,
+                                   p->n_harm);
+            } else {
+                const bool from_audio = zero_pads && l == 1;
+                rc = amtx_launch_cqt_decimate(from_audio ? src : (const float*)(pyramid + lv[-3]), lv[-2], from_audio ? tr[1] : lv[-1], from_audio ? 0 : p->pad,
+                                              pyr, lv[1], lv[2], p->pad, p->d_tfrag, zero_pads, (float*)nullptr, p->n_harm, 1, s);
+                if (rc != AMTX_OK) return rc;
+            }
+            AMTX_CHECK_LAUNCH();
+            if (!zero_pads) {
+                hipLaunchKernelGGL(cqt_pad_kernel, dim3(8, 1), dim3(256), 0, s, pyr, lv[1], lv[2], p->pad, p->lib09);
+                AMTX_CHECK_LAUNCH();
+            }
+        }
+    }
+    // every track whole, no map: the maxima of each harmonic over its own rows
+    return clips_basis(p, audio, pyramid, tracks, nullptr, num_tracks, rows_max, nullptr, maxima, s);
+}
+
+extern "C" int amtx_cqt_power_clips(const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tracks, const int64_t* desc,
+                                    int batch, int64_t num_frames, float* power, void* stream_) {
+    AMTX_REQUIRE(p && audio && pyramid && tracks && desc && power, "amtx_cqt_power_clips: null argument");
+    const int rc = clips_check("amtx_cqt_power_clips", p, batch, num_frames);
+    if (rc != AMTX_OK) return rc;
+    return clips_basis(p, audio, pyramid, tracks, desc, batch, num_frames, power, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" size_t amtx_cqt_clips_workspace_bytes(const amtx_cqt_plan* p, int batch, int64_t num_frames) {
+    if (!p || batch <= 0 || num_frames <= 0) return 0;
+    return ((size_t)batch * p->n_harm * p->n_bins * num_frames * 4 + 255) & ~(size_t)255;
+}
+
+extern "C" int amtx_cqt_clips(const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tracks, const int64_t* desc, int batch,
+                              int64_t num_frames, const float* refs, int decibels, void* workspace, size_t workspace_bytes, float* out, void* stream_) {
+    AMTX_REQUIRE(out, "amtx_cqt_clips: null argument");
+    return clips_scaled("amtx_cqt_clips", p, audio, pyramid, tracks, desc, batch, num_frames, refs, decibels, workspace, workspace_bytes, out, nullptr, 0,
+                        stream_);
+}
+
+extern "C" int amtx_cqt_clips16(const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tracks, const int64_t* desc, int batch,
+                                int64_t num_frames, const float* refs, int decibels, void* workspace, size_t workspace_bytes, void* out16, void* stream_) {
+    AMTX_REQUIRE(out16, "amtx_cqt_clips16: null argument");
+    return clips_scaled("amtx_cqt_clips16", p, audio, pyramid, tracks, desc, batch, num_frames, refs, decibels, workspace, workspace_bytes, nullptr, out16,
+                        0, stream_);
+}
+
+extern "C" int amtx_cqt_clips16_split(const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tracks, const int64_t* desc,
+                                      int batch, int64_t num_frames, const float* refs, int decibels, void* workspace, size_t workspace_bytes,
+                                      void* out16, int64_t plane_elems, void* stream_) {
+    AMTX_REQUIRE(out16 && plane_elems > 0 && plane_elems % 8 == 0, "amtx_cqt_clips16_split: null argument / plane stride not a multiple of 8 elements");
+    return clips_scaled("amtx_cqt_clips16_split", p, audio, pyramid, tracks, desc, batch, num_frames, refs, decibels, workspace, workspace_bytes, nullptr,
+                        out16, plane_elems / 8, stream_);
 }

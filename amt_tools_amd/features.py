@@ -13,6 +13,7 @@ plus additions the reference does not have:
 
     process_batch(audio: torch.Tensor (B, N) on the GPU) -> torch.Tensor (B, C, F, T)   # batched, stays on device
     process_clips(clips: tracks.TrackClips) -> torch.Tensor (B, 1, F, T)                # frames cut from resident tracks, track-level dB
+    process_clips(clips: tracks.PyramidClips) -> torch.Tensor (B, C, F, T)              # the same for the CQT family, from resident pyramids
     frontend()  -> nn.Module for `TranscriptionModel.frontend` (models/common.py:56-57,107-120): the
                    fused seam -- features are computed on the device inside `pre_proc`.
 
@@ -485,11 +486,68 @@ class _CqtPlanOwner(object):
             _lib.call('amtx_cqt_forward16', *args, device=audio.device)
         return out
 
+    # ---- clips cut from the resident pyramids of whole tracks (amt_tools_amd/tracks.py, include/amtx_pyramid.h) ---------------
+    def _clips_args(self, clips):
+        """(plan, audio, pyramid, track table, descriptors, B, T) of a PyramidClips of this module's plan; anything else raises."""
+        from .tracks import PyramidClips
+        if not isinstance(clips, PyramidClips):
+            raise NotImplementedError(f'{type(self).__name__}: the decimation pyramid has no clip form over raw audio (clips of the CQT family '
+                                      f'come from a tracks.PyramidBank, those of a TrackBank from STFT / MelSpec)')
+        bank = clips.bank
+        if bank.module is not self and (type(bank.module) is not type(self) or bank.module._plan_key() != self._plan_key()):
+            raise ValueError('the clips come from a bank of another module: its pyramids and track maxima are those of its own plan')
+        audio = bank.audio
+        return self._get_plan(audio.device), audio, bank.pyramid, bank.table, clips.desc_dev, clips.num_clips, clips.num_frames
+
+    def _plan_key(self):
+        fmin, harmonics, truncate = self._cqt_args()
+        return (int(self.sample_rate), int(self.hop_length), float(fmin), int(self.n_bins), int(self.bins_per_octave), float(self.gamma),
+                tuple(float(h) for h in harmonics), bool(truncate), str(self.librosa_version).startswith('0.9'))
+
+    def _clips_workspace(self, plan, B, T, device):
+        need = _lib.call('amtx_cqt_clips_workspace_bytes', plan, B, T)
+        ws = self.__dict__.get('_workspace')
+        if ws is None or ws.numel() < need or ws.device != device:
+            self.__dict__['_workspace'] = None
+            ws = self.__dict__['_workspace'] = _lib.alloc_workspace(need, device)
+        return ws
+
     def power_clips(self, clips):
-        raise NotImplementedError(f'{type(self).__name__}: the decimation pyramid has no clip form (clips come from STFT / MelSpec banks)')
+        """A PyramidClips -> (power (B, H, F, T) fp32, db_ref (B, H)): column t of clip b is frame first_frame[b] + t of its track's power
+        map, bit for bit; db_ref holds the maxima of the clips' TRACKS per harmonic (PyramidBank.db_ref)."""
+        import torch
+        plan, audio, pyramid, table, desc, B, T = self._clips_args(clips)
+        H = _lib.call('amtx_cqt_num_harmonics', plan)
+        power = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=audio.device)
+        _lib.call('amtx_cqt_power_clips', plan, audio, pyramid, table, desc, B, T, power, device=audio.device)
+        return power, clips.db_ref
 
     def process_clips(self, clips, model_layout=False):
-        return self.power_clips(clips)
+        """Features of a PyramidClips on the device, (B, H, F, T) float32 (model layout: (B, H, T, F)): the slices
+        [first_frame, first_frame + num_frames) of the tracks' own feature maps, bit for bit -- each harmonic scaled against its maximum
+        over the whole track, edge frames from the track's samples (SURVEY finding F7)."""
+        import torch
+        plan, audio, pyramid, table, desc, B, T = self._clips_args(clips)
+        H = _lib.call('amtx_cqt_num_harmonics', plan)
+        ws = self._clips_workspace(plan, B, T, audio.device)
+        out = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=audio.device)
+        _lib.call('amtx_cqt_clips', plan, audio, pyramid, table, desc, B, T, clips.db_ref, int(bool(self.decibels)), ws, ws.numel(), out,
+                  device=audio.device)
+        return out.transpose(-1, -2) if model_layout else out
+
+    def process_clips16(self, clips, split=False):
+        """A PyramidClips -> (B, T, F, 8) bfloat16, or (2, B, T, F, 8) with `split`: process_batch16 of the clips' tracks, sliced on T."""
+        import torch
+        plan, audio, pyramid, table, desc, B, T = self._clips_args(clips)
+        assert _lib.call('amtx_cqt_num_harmonics', plan) <= 8
+        ws = self._clips_workspace(plan, B, T, audio.device)
+        out = torch.empty(((2,) if split else ()) + (B, T, self.n_bins, 8), dtype=torch.bfloat16, device=audio.device)
+        args = (plan, audio, pyramid, table, desc, B, T, clips.db_ref, int(bool(self.decibels)), ws, ws.numel(), out)
+        if split:
+            _lib.call('amtx_cqt_clips16_split', *args, out[0].numel(), device=audio.device)
+        else:
+            _lib.call('amtx_cqt_clips16', *args, device=audio.device)
+        return out
 
     def _process_host(self, audio):
         import torch

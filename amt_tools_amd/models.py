@@ -96,8 +96,8 @@ class TranscriptionModel(nn.Module):
         batch = tools.dict_to_device(batch, self.device)
         audio = tools.unpack_dict(batch, tools.KEY_AUDIO)
         feats = tools.unpack_dict(batch, tools.KEY_FEATS)
-        from .tracks import TrackClips
-        if isinstance(audio, TrackClips):
+        from .tracks import TrackClips, PyramidClips
+        if isinstance(audio, (TrackClips, PyramidClips)):
             # clips cut from device-resident tracks: the slices of the tracks' own feature maps (track-level dB scale)
             frontend_feats = self._clips_module(audio).process_clips(audio, model_layout=True).transpose(-1, -2)
             feats = frontend_feats if feats is None else torch.cat((feats, frontend_feats), dim=1)
@@ -108,11 +108,17 @@ class TranscriptionModel(nn.Module):
         return batch
 
     def _clips_module(self, clips):
-        """The feature module that turns a TrackClips batch entry into features: the model's ONE SpectralFrontend over an STFT / MelSpec,
-        on the device the clips' bank lives on.  Anything else raises -- clips are never silently skipped."""
-        from .features import _SpecPlanOwner, _index_of
+        """The feature module that turns a TrackClips / PyramidClips batch entry into features: the model's ONE SpectralFrontend, over an
+        STFT / MelSpec for a TrackClips and over a CQT-family module for a PyramidClips, on the device the clips' bank lives on.  Anything
+        else raises -- clips are never silently skipped."""
+        from .features import _SpecPlanOwner, _CqtPlanOwner, _index_of
+        from .tracks import PyramidClips
         module = self.frontend[0].module if len(self.frontend) == 1 and isinstance(self.frontend[0], SpectralFrontend) else None
-        if not isinstance(module, _SpecPlanOwner):
+        if isinstance(clips, PyramidClips):
+            if not isinstance(module, _CqtPlanOwner):
+                raise TypeError('a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend; clips of a PyramidBank need '
+                                'one over a CQT / VQT / HCQT / HVQT module')
+        elif not isinstance(module, _SpecPlanOwner):
             raise TypeError('a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend over an STFT / MelSpec module')
         if torch.device(self.device).type != 'cuda' or _index_of(self.device) != clips.device.index:
             raise ValueError(f'the clips live on {clips.device}, the model on {self.device}')
@@ -382,6 +388,9 @@ class PendingFeatures16(PendingFeatures):
         return self.feats16.device
 
     def materialize(self):
+        from .tracks import PyramidClips
+        if isinstance(self.audio, PyramidClips):                # clips cut from resident pyramids (OnsetsFrames._fused_features)
+            return self.module.process_clips(self.audio).transpose(-1, -2)
         return self.module.process_batch(self.audio).transpose(-1, -2)
 
 
@@ -579,7 +588,18 @@ class OnsetsFrames(TranscriptionModel):
             return None
         batch = tools.dict_to_device(batch, self.device)
         audio = batch[tools.KEY_AUDIO]
-        from .tracks import TrackClips
+        from .tracks import TrackClips, PyramidClips
+        if isinstance(audio, PyramidClips):
+            # clips cut from resident pyramids: the conv kernel's staging format straight from the clip kernels, under the conditions of
+            # an audio tensor below; anything else is the ordinary path: pre_proc -> process_clips (or its error)
+            if not cqt:
+                return None
+            module = self._clips_module(audio)                       # (raises for a bank on another device)
+            form = self._get_engine(audio.device).takes_feats16()
+            if not form or int(getattr(module, 'n_bins', -1)) != int(self.dim_in) or int(module.get_num_channels()) != int(self.in_channels):
+                return None
+            batch[tools.KEY_FEATS] = PendingFeatures16(module, module.process_clips16(audio, split=(form == 2)), audio)
+            return batch
         if isinstance(audio, TrackClips):
             # clips cut from resident tracks: the same deferred dB scale, against the TRACK's maximum (own maximum = reference = track_max)
             if cqt or not self._get_engine(audio.device).fuses_db_scale():
