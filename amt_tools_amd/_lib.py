@@ -1,5 +1,6 @@
 """
-ctypes binding of the amtx C ABI (include/amtx.h and the headers beside it, EXTRA_HEADERS and LATER_HEADERS -> amt_tools_amd/csrc/libamtx.so).
+ctypes binding of the amtx C ABI (include/amtx.h and the headers beside it, EXTRA_HEADERS, LATER_HEADERS and MORE_HEADERS ->
+amt_tools_amd/csrc/libamtx.so).
 
 The product path has NO fallback: if the shared library is missing or a call fails, an exception is
 raised.  Pointers handed to the library are raw device addresses (`tensor.data_ptr()`), the stream is
@@ -18,6 +19,9 @@ EXTRA_HEADERS = ('amtx_tracks.h',)
 # Headers added since, each pinned by a table of its own again (tests/golden/abi_signatures_pyramid.json): EXTRA_HEADERS and
 # extra_signatures() are themselves pinned, so they keep answering what they answered.
 LATER_HEADERS = ('amtx_pyramid.h',)
+# The open-ended group: every header after those, each with a pinned table of its own (tests/golden/abi_signatures_labels.json).  No test
+# holds this tuple to a fixed value, so the next header is appended HERE, not given a tuple of its own.
+MORE_HEADERS = ('amtx_labels.h',)
 
 _lib = None
 
@@ -118,12 +122,13 @@ _extra_signatures = None
 
 
 def _header_tables():
-    """({header: table} of EXTRA_HEADERS, the same of LATER_HEADERS), read once per process.  A name declared twice across headers raises."""
+    """({header: table} of EXTRA_HEADERS, the same of LATER_HEADERS, the same of MORE_HEADERS), read once per process.  A name declared twice
+    across headers raises."""
     global _extra_signatures
     if _extra_signatures is None:
         seen = set(signatures())
         both = []
-        for headers in (EXTRA_HEADERS, LATER_HEADERS):
+        for headers in (EXTRA_HEADERS, LATER_HEADERS, MORE_HEADERS):
             tables = {}
             for header in headers:
                 with open(os.path.join(os.path.dirname(HEADER_PATH), header)) as f:
@@ -147,11 +152,16 @@ def later_signatures():
     return _header_tables()[1]
 
 
+def more_signatures():
+    """{header name: parse_header of it} for MORE_HEADERS."""
+    return _header_tables()[2]
+
+
 _funcs = {}            # name -> (function, number of parameters, its return value goes through check, it ends in `void* stream`)
 
 
 def lib():
-    """Load libamtx.so (once) and give every function include/amtx.h, EXTRA_HEADERS and LATER_HEADERS declare its restype / argtypes.  Raises AmtxError when the HIP
+    """Load libamtx.so (once) and give every function include/amtx.h, EXTRA_HEADERS, LATER_HEADERS and MORE_HEADERS declare its restype / argtypes.  Raises AmtxError when the HIP
     extension has not been built, when it lacks a declared function, or when the header holds a declaration parse_header cannot map."""
     global _lib
     if _lib is None:
@@ -164,7 +174,7 @@ def lib():
         except OSError as e:
             raise AmtxError(f'cannot load {LIB_PATH}: {e}') from e
         bound = dict(signatures())
-        for table in list(extra_signatures().values()) + list(later_signatures().values()):
+        for table in list(extra_signatures().values()) + list(later_signatures().values()) + list(more_signatures().values()):
             bound.update(table)
         for name, (letters, stream) in bound.items():
             try:
@@ -188,7 +198,7 @@ def call(name, *args, device=None):
     try:
         fn, nargs, checked, stream = _funcs[name]
     except KeyError:
-        raise AmtxError(f'include/amtx.h and {", ".join(EXTRA_HEADERS + LATER_HEADERS)} declare no function {name}') from None
+        raise AmtxError(f'include/amtx.h and {", ".join(MORE_HEADERS + EXTRA_HEADERS + LATER_HEADERS)} declare no function {name}') from None
     fill_stream = stream and device is not None
     if len(args) + fill_stream != nargs:
         raise TypeError(f'{name} takes {nargs - fill_stream} arguments{" besides the stream" if fill_stream else ""} ({len(args)} given)')

@@ -14,15 +14,22 @@ bit, without ever writing that map: amtx_spec_power_clips frames each clip out o
 half-band stages need context that doubles per level -- so the bank keeps every track's decimation pyramid resident beside its audio
 (include/amtx_pyramid.h: about as many samples again) and a clip's features are basis products over windows of those resident signals.
 
-Features only: callers slice their label maps with the same first frames.  A TrackBank of raw audio serves STFT / MelSpec modules only:
-the CQT family has no clip form there.
+A TrackBank of raw audio serves STFT / MelSpec modules only: the CQT family has no clip form there.
+
+`LabelBank` is the ground truth of the same clips.  A clip's labels are an identity too: the columns [first_frame, first_frame + num_frames)
+of the track's own label maps (the reference's slice_track, amt_tools/datasets/common.py:392).  The whole-track maps are made on the
+host, where the reference's time-to-frame rule is pinned (amt_tools_amd/cache.py); their rows are piecewise constant, so the bank keeps
+them run-length encoded -- integers only (encode_rows) -- and `labels.clips(...)` decodes the clips' columns on the device
+(amtx_label_clips, include/amtx_labels.h) into the tensors the loss kernels take without a copy.  `ClipLoader` draws clips by the
+reference's rule (draw_clips) and yields complete batches: features' clips under tools.KEY_AUDIO, label tensors under their keys.
 """
 
 import numpy as np
 
 from . import _lib
 
-__all__ = ['TrackBank', 'TrackClips', 'PyramidBank', 'PyramidClips', 'clip_descriptors', 'frame_start']
+__all__ = ['TrackBank', 'TrackClips', 'PyramidBank', 'PyramidClips', 'clip_descriptors', 'frame_start',
+           'LabelBank', 'ClipLoader', 'encode_rows', 'decode_rows', 'draw_clips']
 
 
 def frame_start(sample_start, hop_length):
@@ -288,3 +295,285 @@ class PyramidBank(TrackBank):
         desc = np.ascontiguousarray(np.stack((ids, checked[:, 2], checked[:, 3]), axis=1))
         audio, db_ref = self._device_state()[:2]
         return PyramidClips(self, desc, torch.from_numpy(desc).to(audio.device), db_ref[torch.from_numpy(ids).to(audio.device)])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# ground truth: run-length encoded label rows, decoded per clip on the device
+# ------------------------------------------------------------------------------------------------------------------------------
+MAX_LABEL_KEYS = 16         # AMTX_LABEL_MAX_KEYS (include/amtx_labels.h): label maps of one dtype kind that one launch serves
+
+
+def _is_float_map(a):
+    kind = np.asarray(a).dtype.kind
+    if kind not in 'fiub':
+        raise TypeError(f'a label map holds floating, integer or bool values, not {np.asarray(a).dtype}')
+    return kind == 'f'
+
+
+def _row_patterns(label_map, what=''):
+    """The (rows, T) int32 patterns of a label map: float32 bits of a floating map, int32 values of an integer or bool map."""
+    a = np.asarray(label_map)
+    is_float = _is_float_map(a)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f'{what}a label map is (rows, frames) with at least one of each, not {a.shape}')
+    if is_float:
+        with np.errstate(over='ignore', invalid='ignore'):
+            f32 = a.astype(np.float32)
+            bad = ~((f32.astype(a.dtype) == a) | (np.isnan(a) & np.isnan(f32)))
+        if bad.any():
+            r, t = (int(i) for i in np.argwhere(bad)[0])
+            raise ValueError(f'{what}row {r}, frame {t}: float32 does not hold {a[r, t]!r} exactly')
+        return np.ascontiguousarray(f32).view(np.int32)
+    if a.dtype.kind == 'u':
+        bad = a.astype(np.uint64) > np.uint64(2 ** 31 - 1)
+    elif a.dtype.kind == 'i':
+        wide = a.astype(np.int64)
+        bad = (wide < -2 ** 31) | (wide > 2 ** 31 - 1)
+    else:
+        bad = np.zeros(a.shape, dtype=bool)
+    if bad.any():
+        r, t = (int(i) for i in np.argwhere(bad)[0])
+        raise ValueError(f'{what}row {r}, frame {t}: {int(a[r, t])} is outside int32')
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def encode_rows(label_map, what=''):
+    """Run-length encoding of a (rows, T) label map: (row_ptr int64 (rows + 1,), run_first int32 (N,), run_bits int32 (N,)).  Run j of a
+    row -- row_ptr[r] <= j < row_ptr[r + 1] -- holds the 32-bit pattern run_bits[j] from frame run_first[j] up to the next run's first
+    frame, or to the track's end; every row's first run starts at frame 0.  Runs are split where the PATTERN changes: NaN and -0.0 survive.
+
+    A floating map is stored as its float32 patterns, an integer or bool map as int32 values; ValueError, naming row and frame (after the
+    prefix `what`), for a value float32 does not represent exactly or an integer outside int32.  Pure NumPy."""
+    p = _row_patterns(label_map, what)
+    starts = np.ones(p.shape, dtype=bool)
+    starts[:, 1:] = p[:, 1:] != p[:, :-1]
+    rows, frames = np.nonzero(starts)                     # row-major: ascending frames inside ascending rows
+    row_ptr = np.concatenate(([0], np.cumsum(starts.sum(axis=1)))).astype(np.int64)
+    return row_ptr, frames.astype(np.int32), p[rows, frames]
+
+
+def decode_rows(row_ptr, run_first, run_bits, num_frames, dtype=np.float32):
+    """The inverse of encode_rows for a track of `num_frames` frames: (rows, num_frames) float32 with the stored patterns (dtype float32)
+    or the stored values as int64 (dtype int64) -- what amtx_label_clips writes for out_kind 0 / 1.  Pure NumPy: the CPU reference."""
+    row_ptr = np.asarray(row_ptr, dtype=np.int64)
+    run_first, run_bits = np.asarray(run_first, dtype=np.int32), np.asarray(run_bits, dtype=np.int32)
+    stop = np.empty(run_first.shape, dtype=np.int64)
+    stop[:-1] = run_first[1:]
+    stop[row_ptr[1:] - 1 - row_ptr[0]] = int(num_frames)             # a row's last run ends with the track
+    flat = np.repeat(run_bits, stop - run_first).reshape(len(row_ptr) - 1, int(num_frames))
+    if np.dtype(dtype) == np.float32:
+        return flat.view(np.float32)
+    if np.dtype(dtype) == np.int64:
+        return flat.astype(np.int64)
+    raise TypeError(f'label clips are float32 or int64, not {np.dtype(dtype)}')
+
+
+class LabelBank(object):
+    """The frame-aligned ground truth of whole tracks, run-length encoded (encode_rows), for clips cut on the device.
+
+    maps: one dict {key: (rows_key, T_track) array} per track -- tools.KEY_MULTIPITCH, KEY_ONSETS, KEY_OFFSETS, KEY_TABLATURE or any other
+    frame-aligned key -- consumed one track at a time (an iterator's maps can be dropped as soon as they are encoded).  All tracks carry
+    the same keys with the same row count and dtype kind per key; all keys of a track have the same width, and with `bank` (the TrackBank /
+    PyramidBank of the same tracks) that width is bank.frame_counts[i]: ValueError otherwise, naming the track.
+
+    One row_ptr / run_first / run_bits for all tracks; the global row is track * rows_total + row, the floating keys' rows first, then the
+    integer (and bool) keys'.  The device copies are created on first use, never at construction, and never pickled (the host encoding
+    is kept): a bank can be built before DataLoader workers fork, like TrackBank."""
+
+    def __init__(self, maps, bank=None, device=None):
+        self.device = device if device is not None else (bank.device if bank is not None else 'cuda')
+        self.float_keys, self.int_keys = [], []          # [(key, rows)] in the order of the first track's dict
+        counts, ptrs, firsts, bits = [], [np.zeros(1, dtype=np.int64)], [], []
+        kinds, order, runs = None, None, 0
+        for i, entry in enumerate(maps):
+            if kinds is None:
+                if not len(entry):
+                    raise ValueError('track 0 carries no label map')
+                kinds = {key: (_is_float_map(a), int(np.shape(a)[0]) if np.ndim(a) == 2 else None) for key, a in entry.items()}
+                self.float_keys = [(key, rows) for key, (is_float, rows) in kinds.items() if is_float]
+                self.int_keys = [(key, rows) for key, (is_float, rows) in kinds.items() if not is_float]
+                order = [key for key, _ in self.float_keys + self.int_keys]
+                for group in (self.float_keys, self.int_keys):
+                    if len(group) > MAX_LABEL_KEYS:
+                        raise ValueError(f'{len(group)} label maps of one dtype kind: one launch serves {MAX_LABEL_KEYS}')
+            if sorted(map(str, entry)) != sorted(map(str, kinds)):
+                raise ValueError(f'track {i} carries the keys {sorted(map(str, entry))}, track 0 {sorted(map(str, kinds))}')
+            width = None
+            for key in order:
+                a = np.asarray(entry[key])
+                if _is_float_map(a) != kinds[key][0]:
+                    raise ValueError(f"track {i}, '{key}': dtype {a.dtype}, but track 0 holds {'floating' if kinds[key][0] else 'integer'} values there")
+                if a.ndim != 2:
+                    raise ValueError(f"track {i}, '{key}': a label map is (rows, frames), not {a.shape}")
+                if a.shape[0] != kinds[key][1]:
+                    raise ValueError(f"track {i}, '{key}': shape {a.shape}, but track 0 has {kinds[key][1]} rows there")
+                if width is None:
+                    width = int(a.shape[1])
+                elif a.shape[1] != width:
+                    raise ValueError(f"track {i}: '{key}' has {a.shape[1]} frames, '{order[0]}' has {width}")
+                row_ptr, run_first, run_bits = encode_rows(a, f"track {i}, '{key}': ")
+                ptrs.append(row_ptr[1:] + runs)
+                firsts.append(run_first)
+                bits.append(run_bits)
+                runs += int(row_ptr[-1])
+            if bank is not None and (i >= len(bank) or width != int(bank.frame_counts[i])):
+                have = f'{int(bank.frame_counts[i])} frames' if i < len(bank) else f'only {len(bank)} tracks'
+                raise ValueError(f'track {i}: its label maps have {width} frames, the bank has {have}')
+            counts.append(width)
+        if kinds is None:
+            raise ValueError('maps: at least one track')
+        if bank is not None and len(counts) != len(bank):
+            raise ValueError(f'label maps of {len(counts)} tracks for a bank of {len(bank)}')
+        self.frame_counts = np.array(counts, dtype=np.int64)
+        self.rows_total = sum(rows for _, rows in self.float_keys + self.int_keys)
+        self.row_ptr = np.concatenate(ptrs)
+        self.run_first = np.concatenate(firsts)
+        self.run_bits = np.concatenate(bits)
+
+    @classmethod
+    def from_notes(cls, notes, times, profile, keys=None, ambiguity=None, bank=None, device=None):
+        """The piano recipe: notes[i] = (pitches, intervals) and times[i] = the frame grid of track i; the whole-track maps come from
+        cache.notes_to_multi_pitch / notes_to_onsets / notes_to_offsets on the host (`ambiguity` as there) and each track's maps are
+        dropped once they are encoded.  keys: of tools.KEY_MULTIPITCH, KEY_ONSETS, KEY_OFFSETS (default: all three)."""
+        from . import cache, tools
+        makers = {tools.KEY_MULTIPITCH: lambda p, i, t: cache.notes_to_multi_pitch(p, i, t, profile),
+                  tools.KEY_ONSETS: lambda p, i, t: cache.notes_to_onsets(p, i, t, profile, ambiguity),
+                  tools.KEY_OFFSETS: lambda p, i, t: cache.notes_to_offsets(p, i, t, profile, ambiguity)}
+        keys = tuple(makers) if keys is None else tuple(keys)
+        for key in keys:
+            if key not in makers:
+                raise ValueError(f"no label map '{key}' from notes: {', '.join(makers)} (tablature and other maps go in as `maps`)")
+        if len(notes) != len(times):
+            raise ValueError(f'{len(notes)} note lists for {len(times)} frame grids')
+        return cls(({key: makers[key](pitches, intervals, grid) for key in keys} for (pitches, intervals), grid in zip(notes, times)),
+                   bank=bank, device=device)
+
+    def __len__(self):
+        return len(self.frame_counts)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_dev', None)
+        return state
+
+    @property
+    def keys(self):
+        """Every label key, the floating ones first: the order of the rows inside a track."""
+        return [key for key, _ in self.float_keys + self.int_keys]
+
+    @property
+    def runs_per_track(self):
+        """(num_tracks,) runs of every track."""
+        return np.diff(self.row_ptr[::self.rows_total])
+
+    @property
+    def nbytes(self):
+        """Bytes of the three tables, on the host as on the device."""
+        return int(self.row_ptr.nbytes + self.run_first.nbytes + self.run_bits.nbytes)
+
+    def _rows_of(self, key):
+        lo = 0
+        for name, rows in self.float_keys + self.int_keys:
+            if name == key:
+                return lo, lo + rows
+            lo += rows
+        raise KeyError(key)
+
+    def host_map(self, track, key):
+        """The whole (rows_key, T_track) map of one track, decoded on the host (decode_rows): float32 or int64 as clips() gives it."""
+        lo, hi = self._rows_of(key)
+        g = int(track) * self.rows_total
+        ptr = self.row_ptr[g + lo:g + hi + 1]
+        dtype = np.float32 if key in dict(self.float_keys) else np.int64
+        return decode_rows(ptr, self.run_first[ptr[0]:ptr[-1]], self.run_bits[ptr[0]:ptr[-1]], self.frame_counts[int(track)], dtype)
+
+    def _device_state(self):
+        """(row_ptr, run_first, run_bits) on the bank's device."""
+        dev = self.__dict__.get('_dev')
+        if dev is None:
+            import torch
+            from .features import _index_of
+            device = torch.device('cuda', _index_of(self.device))
+            dev = self.__dict__['_dev'] = tuple(torch.from_numpy(a).to(device) for a in (self.row_ptr, self.run_first, self.run_bits))
+        return dev
+
+    def clips(self, track_ids, first_frames, num_frames):
+        """{key: device tensor (B, rows_key, num_frames)} -- float32 for floating keys, int64 for integer and bool keys, each contiguous:
+        the columns [first_frames[b], first_frames[b] + num_frames) of the maps of track track_ids[b].  Same signature and host validation
+        as bank.clips (clip_descriptors against this bank's own frame counts).  One amtx_label_clips launch per dtype kind; the keys of a
+        kind are views into one allocation, key-major."""
+        import torch
+        checked = clip_descriptors(np.zeros(len(self), dtype=np.int64), self.frame_counts, self.frame_counts, track_ids, first_frames, num_frames)
+        ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
+        desc = np.ascontiguousarray(np.stack((ids, checked[:, 2], checked[:, 3]), axis=1))
+        row_ptr, run_first, run_bits = self._device_state()
+        device = row_ptr.device
+        desc_dev = torch.from_numpy(desc).to(device)
+        B, T = int(desc.shape[0]), int(num_frames)
+        result, row_lo = {}, 0
+        for group, dtype, kind in ((self.float_keys, torch.float32, 0), (self.int_keys, torch.int64, 1)):
+            if not group:
+                continue
+            key_rows = np.cumsum([row_lo] + [rows for _, rows in group]).astype(np.int64)
+            row_hi = int(key_rows[-1])
+            flat = torch.empty(((row_hi - row_lo) * B * T,), dtype=dtype, device=device)
+            _lib.call('amtx_label_clips', row_ptr, run_first, run_bits, len(self), self.rows_total, row_lo, row_hi, key_rows, len(group),
+                      desc_dev, B, T, flat, kind, device=device)
+            for (key, rows), lo in zip(group, key_rows):
+                at = int(lo - row_lo) * B * T
+                result[key] = flat[at:at + rows * B * T].view(B, rows, T)
+            row_lo = row_hi
+        return result
+
+
+def draw_clips(rng, lengths, hop_length, num_frames, track_ids):
+    """First frames of one random clip per entry of `track_ids`, by the reference's rule (amt_tools/datasets/common.py:340-343):
+    seq_length = num_frames * hop_length, sample_start = rng.randint(0, length - seq_length), first frame = sample_start // hop_length --
+    drawn in the order of track_ids from `rng` (a np.random.RandomState).  lengths: the samples of every track of the bank.  ValueError
+    for an unknown track and for a track of seq_length samples or fewer (the reference pads those; the banks refuse them).  Pure host code."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    track_ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
+    seq_length = int(num_frames) * int(hop_length)
+    if int(num_frames) < 1 or int(hop_length) < 1:
+        raise ValueError(f'a clip has at least one frame of at least one sample (got {num_frames} frames, hop {hop_length})')
+    first_frames = np.empty(track_ids.shape, dtype=np.int64)
+    for b, k in enumerate(track_ids):
+        if k < 0 or k >= len(lengths):
+            raise ValueError(f'unknown track {int(k)}: the bank holds {len(lengths)} tracks')
+        if lengths[k] <= seq_length:
+            raise ValueError(f'track {int(k)} has {int(lengths[k])} samples: a clip of {int(num_frames)} frames needs more than {seq_length}')
+        first_frames[b] = frame_start(rng.randint(0, int(lengths[k]) - seq_length), hop_length)
+    return first_frames
+
+
+class ClipLoader(object):
+    """Complete training batches from a TrackBank / PyramidBank and the LabelBank of the same tracks: an iterable with __len__ that takes
+    the place of the DataLoader in the reference's train().  Every batch is {tools.KEY_AUDIO: bank.clips(...), **labels.clips(...)} with
+    the same track ids and first frames for both: one clip of `num_frames` frames per track, drawn by draw_clips.
+
+    An epoch is one permutation of the tracks from this loader's np.random.RandomState(seed), dealt into batches of `batch_size`; the
+    last, smaller batch is dropped with drop_last.  The TRACK ORDER is this loader's own: the reference's comes from the shuffle of torch's
+    DataLoader, which no NumPy generator reproduces.  The clip positions follow the reference's rule, from this loader's generator."""
+
+    def __init__(self, bank, labels, num_frames, batch_size, seed=0, drop_last=True):
+        if len(bank) != len(labels):
+            raise ValueError(f'a bank of {len(bank)} tracks and labels of {len(labels)}')
+        if int(batch_size) < 1 or int(num_frames) < 1:
+            raise ValueError(f'batch_size and num_frames are at least 1 (got {batch_size}, {num_frames})')
+        self.bank, self.labels = bank, labels
+        self.num_frames, self.batch_size, self.drop_last = int(num_frames), int(batch_size), bool(drop_last)
+        self.rng = np.random.RandomState(seed)
+
+    def __len__(self):
+        full, rest = divmod(len(self.bank), self.batch_size)
+        return full + (1 if rest and not self.drop_last else 0)
+
+    def __iter__(self):
+        from . import tools
+        order = self.rng.permutation(len(self.bank))
+        for i in range(len(self)):
+            ids = order[i * self.batch_size:(i + 1) * self.batch_size]
+            firsts = draw_clips(self.rng, self.bank.lengths, self.bank.module.hop_length, self.num_frames, ids)
+            batch = {tools.KEY_AUDIO: self.bank.clips(ids, firsts, self.num_frames)}
+            batch.update(self.labels.clips(ids, firsts, self.num_frames))
+            yield batch
