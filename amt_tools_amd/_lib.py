@@ -1,6 +1,8 @@
 """
-ctypes binding of the amtx C ABI (include/amtx.h and the headers beside it, EXTRA_HEADERS, LATER_HEADERS and MORE_HEADERS ->
-amt_tools_amd/csrc/libamtx.so).
+ctypes binding of the amtx C ABI (the headers of HEADERS under include/ -> amt_tools_amd/csrc/libamtx.so).
+
+Every header is read by parse_header, every function it declares is bound by lib() and reached through call(); header_signatures() holds
+one table per header, and a name declared in two headers is an error.  tests/golden/ pins each header's table in a file of its own.
 
 The product path has NO fallback: if the shared library is missing or a call fails, an exception is
 raised.  Pointers handed to the library are raw device addresses (`tensor.data_ptr()`), the stream is
@@ -13,15 +15,8 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMTX_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libamtx.so')      # AMTX_LIB_PATH: a debug / timing build of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'amtx.h')
-# Further headers of the same library, bound the same way.  signatures() / declared_symbols() stay the table of amtx.h alone (pinned by
-# tests/golden/abi_signatures.json); each of these has its own pinned table (tests/golden/abi_signatures_tracks.json).
-EXTRA_HEADERS = ('amtx_tracks.h',)
-# Headers added since, each pinned by a table of its own again (tests/golden/abi_signatures_pyramid.json): EXTRA_HEADERS and
-# extra_signatures() are themselves pinned, so they keep answering what they answered.
-LATER_HEADERS = ('amtx_pyramid.h',)
-# The open-ended group: every header after those, each with a pinned table of its own (tests/golden/abi_signatures_labels.json).  No test
-# holds this tuple to a fixed value, so the next header is appended HERE, not given a tuple of its own.
-MORE_HEADERS = ('amtx_labels.h',)
+# Every header of the library, bound the same way; a new header is appended here and gets a pinned table of its own under tests/golden/.
+HEADERS = ('amtx.h', 'amtx_tracks.h', 'amtx_pyramid.h', 'amtx_labels.h')
 
 _lib = None
 
@@ -104,13 +99,25 @@ def parse_header(text):
 _signatures = None
 
 
-def signatures():
-    """parse_header of include/amtx.h, read once per process."""
+def header_signatures():
+    """{header: parse_header of it} for every header of HEADERS, read once per process.  A name declared in two headers raises."""
     global _signatures
     if _signatures is None:
-        with open(HEADER_PATH) as f:
-            _signatures = parse_header(f.read())
+        tables, seen = {}, set()
+        for header in HEADERS:
+            with open(os.path.join(os.path.dirname(HEADER_PATH), header)) as f:
+                tables[header] = parse_header(f.read())
+            twice = seen & set(tables[header])
+            if twice:
+                raise AmtxError(f'{sorted(twice)[0]} is declared in {header} and in another header')
+            seen |= set(tables[header])
+        _signatures = tables
     return _signatures
+
+
+def signatures():
+    """The table of include/amtx.h alone."""
+    return header_signatures()['amtx.h']
 
 
 def declared_symbols():
@@ -118,51 +125,12 @@ def declared_symbols():
     return sorted(signatures())
 
 
-_extra_signatures = None
-
-
-def _header_tables():
-    """({header: table} of EXTRA_HEADERS, the same of LATER_HEADERS, the same of MORE_HEADERS), read once per process.  A name declared twice
-    across headers raises."""
-    global _extra_signatures
-    if _extra_signatures is None:
-        seen = set(signatures())
-        both = []
-        for headers in (EXTRA_HEADERS, LATER_HEADERS, MORE_HEADERS):
-            tables = {}
-            for header in headers:
-                with open(os.path.join(os.path.dirname(HEADER_PATH), header)) as f:
-                    tables[header] = parse_header(f.read())
-                twice = seen & set(tables[header])
-                if twice:
-                    raise AmtxError(f'{sorted(twice)[0]} is declared in {header} and in another header')
-                seen |= set(tables[header])
-            both.append(tables)
-        _extra_signatures = tuple(both)
-    return _extra_signatures
-
-
-def extra_signatures():
-    """{header name: parse_header of it} for EXTRA_HEADERS."""
-    return _header_tables()[0]
-
-
-def later_signatures():
-    """{header name: parse_header of it} for LATER_HEADERS."""
-    return _header_tables()[1]
-
-
-def more_signatures():
-    """{header name: parse_header of it} for MORE_HEADERS."""
-    return _header_tables()[2]
-
-
 _funcs = {}            # name -> (function, number of parameters, its return value goes through check, it ends in `void* stream`)
 
 
 def lib():
-    """Load libamtx.so (once) and give every function include/amtx.h, EXTRA_HEADERS, LATER_HEADERS and MORE_HEADERS declare its restype / argtypes.  Raises AmtxError when the HIP
-    extension has not been built, when it lacks a declared function, or when the header holds a declaration parse_header cannot map."""
+    """Load libamtx.so (once) and give every function the headers of HEADERS declare its restype / argtypes.  Raises AmtxError when the HIP
+    extension has not been built, when it lacks a declared function, or when a header holds a declaration parse_header cannot map."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -173,17 +141,15 @@ def lib():
             handle = C.CDLL(LIB_PATH)
         except OSError as e:
             raise AmtxError(f'cannot load {LIB_PATH}: {e}') from e
-        bound = dict(signatures())
-        for table in list(extra_signatures().values()) + list(later_signatures().values()) + list(more_signatures().values()):
-            bound.update(table)
-        for name, (letters, stream) in bound.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise AmtxError(f'{LIB_PATH} does not export {name}') from e
-            fn.restype = _CTYPES[letters[0]]
-            fn.argtypes = [_CTYPES[c] for c in letters[1:]]
-            _funcs[name] = (fn, len(letters) - 1, letters[0] in 'il', stream)
+        for table in header_signatures().values():
+            for name, (letters, stream) in table.items():
+                try:
+                    fn = getattr(handle, name)
+                except AttributeError as e:
+                    raise AmtxError(f'{LIB_PATH} does not export {name}') from e
+                fn.restype = _CTYPES[letters[0]]
+                fn.argtypes = [_CTYPES[c] for c in letters[1:]]
+                _funcs[name] = (fn, len(letters) - 1, letters[0] in 'il', stream)
         _lib = handle
     return _lib
 
@@ -198,7 +164,7 @@ def call(name, *args, device=None):
     try:
         fn, nargs, checked, stream = _funcs[name]
     except KeyError:
-        raise AmtxError(f'include/amtx.h and {", ".join(MORE_HEADERS + EXTRA_HEADERS + LATER_HEADERS)} declare no function {name}') from None
+        raise AmtxError(f'{", ".join(HEADERS)} declare no function {name}') from None
     fill_stream = stream and device is not None
     if len(args) + fill_stream != nargs:
         raise TypeError(f'{name} takes {nargs - fill_stream} arguments{" besides the stream" if fill_stream else ""} ({len(args)} given)')

@@ -174,11 +174,23 @@ def _index_of(device):
     return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
+def _bank_of(module, clips, what):
+    """The bank of `clips`, which must belong to `module` itself or to a module of the same plan (_same_plan): `what` of the bank are
+    those of its module's plan."""
+    bank = clips.bank
+    if bank.module is not module and not module._same_plan(bank.module):
+        raise ValueError(f'the clips come from a bank of another module: its {what} are those of its own plan')
+    return bank
+
+
 class _SpecPlanOwner(object):
     """Lazily created amtx_spec_plan (device tables) shared by STFT / MelSpec instances."""
 
     def _plan_args(self):
         raise NotImplementedError
+
+    def _same_plan(self, other):
+        return type(other) is type(self) and other._plan_args() == self._plan_args()
 
     def _get_plan(self, device=None):
         """The plan (device tables) for `device` (a torch.device / index; default: the module's own device).  Plans are cached per
@@ -280,10 +292,7 @@ class _SpecPlanOwner(object):
         bit the row amtx_spec_power gives for the whole track; track_max is the maximum of the clip's TRACK (TrackBank.db_ref).  The clips'
         OWN maxima, which the kernel also reduces (the ABI takes no null clip_max), are dropped on purpose: a bank exists for the track's."""
         import torch
-        bank = clips.bank
-        if bank.module is not self and (type(bank.module) is not type(self) or bank.module._plan_args() != self._plan_args()):
-            raise ValueError('the clips come from a bank of another module: its track maxima are those of its own plan')
-        audio = bank.audio
+        audio = _bank_of(self, clips, 'track maxima').audio
         B, T = clips.num_clips, clips.num_frames
         plan = self._get_plan(audio.device)
         F = _lib.call('amtx_spec_num_bins', plan)
@@ -493,9 +502,7 @@ class _CqtPlanOwner(object):
         if not isinstance(clips, PyramidClips):
             raise NotImplementedError(f'{type(self).__name__}: the decimation pyramid has no clip form over raw audio (clips of the CQT family '
                                       f'come from a tracks.PyramidBank, those of a TrackBank from STFT / MelSpec)')
-        bank = clips.bank
-        if bank.module is not self and (type(bank.module) is not type(self) or bank.module._plan_key() != self._plan_key()):
-            raise ValueError('the clips come from a bank of another module: its pyramids and track maxima are those of its own plan')
+        bank = _bank_of(self, clips, 'pyramids and track maxima')
         audio = bank.audio
         return self._get_plan(audio.device), audio, bank.pyramid, bank.table, clips.desc_dev, clips.num_clips, clips.num_frames
 
@@ -503,6 +510,9 @@ class _CqtPlanOwner(object):
         fmin, harmonics, truncate = self._cqt_args()
         return (int(self.sample_rate), int(self.hop_length), float(fmin), int(self.n_bins), int(self.bins_per_octave), float(self.gamma),
                 tuple(float(h) for h in harmonics), bool(truncate), str(self.librosa_version).startswith('0.9'))
+
+    def _same_plan(self, other):
+        return type(other) is type(self) and other._plan_key() == self._plan_key()
 
     def _clips_workspace(self, plan, B, T, device):
         need = _lib.call('amtx_cqt_clips_workspace_bytes', plan, B, T)

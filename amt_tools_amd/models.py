@@ -96,8 +96,8 @@ class TranscriptionModel(nn.Module):
         batch = tools.dict_to_device(batch, self.device)
         audio = tools.unpack_dict(batch, tools.KEY_AUDIO)
         feats = tools.unpack_dict(batch, tools.KEY_FEATS)
-        from .tracks import TrackClips, PyramidClips
-        if isinstance(audio, (TrackClips, PyramidClips)):
+        from .tracks import _Clips
+        if isinstance(audio, _Clips):
             # clips cut from device-resident tracks: the slices of the tracks' own feature maps (track-level dB scale)
             frontend_feats = self._clips_module(audio).process_clips(audio, model_layout=True).transpose(-1, -2)
             feats = frontend_feats if feats is None else torch.cat((feats, frontend_feats), dim=1)

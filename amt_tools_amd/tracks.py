@@ -22,6 +22,11 @@ host, where the reference's time-to-frame rule is pinned (amt_tools_amd/cache.py
 them run-length encoded -- integers only (encode_rows) -- and `labels.clips(...)` decodes the clips' columns on the device
 (amtx_label_clips, include/amtx_labels.h) into the tensors the loss kernels take without a copy.  `ClipLoader` draws clips by the
 reference's rule (draw_clips) and yields complete batches: features' clips under tools.KEY_AUDIO, label tensors under their keys.
+
+What the three banks share is written once: `_checked_request` validates a `clips(track_ids, first_frames, num_frames)` request against
+a bank's frame counts, `_clip_table` lays the checked request out as the int64 table a clip kernel reads (clip_descriptors adds the
+reflect rule and the 4-column form of amtx_spec_power_clips), `_Resident` is the lazy, never-pickled device state, and `_Clips` is the
+batch entry that TrackClips and PyramidClips name -- the feature modules and models choose the kernel family by that type.
 """
 
 import numpy as np
@@ -37,55 +42,67 @@ def frame_start(sample_start, hop_length):
     return int(sample_start) // int(hop_length)
 
 
+def _checked_request(frame_counts, track_ids, first_frames, num_frames):
+    """The one check of a clip request against a bank's frame counts: (track ids, first frames) as int64 1-D arrays.  ValueError for ids
+    and first frames that do not pair up, no clip, fewer than one frame, an unknown track, a negative first frame and a clip that runs
+    past its track's last frame (a track shorter than the clip included), in that order.  Pure host code."""
+    frame_counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+    ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
+    firsts = np.asarray(first_frames, dtype=np.int64).reshape(-1)
+    num_frames = int(num_frames)
+    if ids.shape != firsts.shape or ids.size == 0:
+        raise ValueError('one first frame per track id, and at least one clip')
+    if num_frames < 1:
+        raise ValueError(f'a clip has at least one frame (got {num_frames})')
+    bad = (ids < 0) | (ids >= len(frame_counts))
+    if bad.any():
+        raise ValueError(f'unknown track {int(ids[bad][0])}: the bank holds {len(frame_counts)} tracks')
+    if (firsts < 0).any():
+        raise ValueError(f'negative first frame {int(firsts[firsts < 0][0])}')
+    past = firsts + num_frames > frame_counts[ids]
+    if past.any():
+        b = int(np.argmax(past))
+        raise ValueError(f'clip {b}: frames [{int(firsts[b])}, {int(firsts[b]) + num_frames}) run past the '
+                         f'{int(frame_counts[ids[b]])} frames of track {int(ids[b])}')
+    return ids, firsts
+
+
+def _clip_table(*columns):
+    """int64 (B, len(columns)) C-contiguous table of a checked request; a scalar column (the frames of every clip) is repeated."""
+    desc = np.empty((columns[0].size, len(columns)), dtype=np.int64)
+    for c, column in enumerate(columns):
+        desc[:, c] = column
+    return desc
+
+
 def clip_descriptors(starts, lengths, frame_counts, track_ids, first_frames, num_frames, reflect_half=None):
     """The table amtx_spec_power_clips reads: int64 (B, 4) rows {track_start, track_len, first_frame, frames}, frames = num_frames, for the
     clips [first_frames[b], first_frames[b] + num_frames) of the tracks track_ids[b].  starts / lengths / frame_counts describe the bank
     (element offset, samples and frames of every track).  reflect_half: n_fft // 2 of a reflect-padded plan (librosa 0.9), else None.
 
-    Pure host code.  ValueError for an unknown track, a negative first frame, a clip that runs past its track's last frame (a track shorter
-    than the clip included) and for a reflect-padded plan over a track of n_fft / 2 samples or fewer."""
+    Pure host code.  ValueError for a request _checked_request refuses and for a reflect-padded plan over a track of n_fft / 2 samples or
+    fewer."""
     starts, lengths, frame_counts = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (starts, lengths, frame_counts))
-    track_ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
-    first_frames = np.asarray(first_frames, dtype=np.int64).reshape(-1)
-    num_frames = int(num_frames)
     if not (len(starts) == len(lengths) == len(frame_counts)):
         raise ValueError('starts, lengths and frame_counts describe the same tracks: one entry each')
-    if track_ids.shape != first_frames.shape or track_ids.size == 0:
-        raise ValueError('one first frame per track id, and at least one clip')
-    if num_frames < 1:
-        raise ValueError(f'a clip has at least one frame (got {num_frames})')
-    bad = (track_ids < 0) | (track_ids >= len(starts))
-    if bad.any():
-        raise ValueError(f'unknown track {int(track_ids[bad][0])}: the bank holds {len(starts)} tracks')
-    if (first_frames < 0).any():
-        raise ValueError(f'negative first frame {int(first_frames[first_frames < 0][0])}')
-    past = first_frames + num_frames > frame_counts[track_ids]
-    if past.any():
-        b = int(np.argmax(past))
-        raise ValueError(f'clip {b}: frames [{int(first_frames[b])}, {int(first_frames[b]) + num_frames}) run past the '
-                         f'{int(frame_counts[track_ids[b]])} frames of track {int(track_ids[b])}')
+    ids, firsts = _checked_request(frame_counts, track_ids, first_frames, num_frames)
     if reflect_half is not None:
-        short = lengths[track_ids] <= int(reflect_half)
+        short = lengths[ids] <= int(reflect_half)
         if short.any():
             b = int(np.argmax(short))
-            raise ValueError(f'track {int(track_ids[b])} has {int(lengths[track_ids[b]])} samples: reflect padding needs more than '
+            raise ValueError(f'track {int(ids[b])} has {int(lengths[ids[b]])} samples: reflect padding needs more than '
                              f'n_fft/2 = {int(reflect_half)}')
-    desc = np.empty((track_ids.size, 4), dtype=np.int64)
-    desc[:, 0] = starts[track_ids]
-    desc[:, 1] = lengths[track_ids]
-    desc[:, 2] = first_frames
-    desc[:, 3] = num_frames
-    return desc
+    return _clip_table(starts[ids], lengths[ids], firsts, int(num_frames))
 
 
 def _reflect_half(module):
     return int(module.n_fft) // 2 if module._pad_mode() == 1 else None
 
 
-class TrackClips(object):
-    """Clips of a TrackBank, as a batch entry under tools.KEY_AUDIO or an argument of process_clips / power_clips:
-    `bank`, `desc` (host int64 (B, 4), clip_descriptors), `desc_dev` (its device copy) and `db_ref` ((B,) device float32: the power
-    maxima of the clips' tracks).  No tensor subclass: tools.dict_to_device passes it through as it is."""
+class _Clips(object):
+    """Clips of a bank, as a batch entry under tools.KEY_AUDIO or an argument of process_clips / power_clips: `bank`, `desc` (the host
+    int64 table the clip kernels read, the clips' frame count in its last column), `desc_dev` (its device copy) and `db_ref` (device
+    float32: the power maxima of the clips' tracks).  No tensor subclass: tools.dict_to_device passes it through as it is."""
 
     def __init__(self, bank, desc, desc_dev, db_ref):
         self.bank, self.desc, self.desc_dev, self.db_ref = bank, desc, desc_dev, db_ref
@@ -96,14 +113,40 @@ class TrackClips(object):
 
     @property
     def num_frames(self):
-        return int(self.desc[0, 3])
+        return int(self.desc[0, -1])
 
     @property
     def device(self):
         return self.desc_dev.device
 
 
-class TrackBank(object):
+class TrackClips(_Clips):
+    """Clips of a TrackBank: desc (B, 4) = clip_descriptors, db_ref (B,)."""
+
+
+class PyramidClips(_Clips):
+    """Clips of a PyramidBank: desc (B, 3) rows {track, first_frame, frames}, db_ref (B, n_harm), per harmonic."""
+
+
+class _Resident(object):
+    """Device state that is created on first use, never at construction, and never pickled: `self.device` names the device, `_upload(device)`
+    returns the tuple of device tensors, and `_device_state()` caches it under __dict__['_dev']."""
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_dev', None)
+        return state
+
+    def _device_state(self):
+        dev = self.__dict__.get('_dev')
+        if dev is None:
+            import torch
+            from .features import _index_of
+            dev = self.__dict__['_dev'] = self._upload(torch.device('cuda', _index_of(self.device)))
+        return dev
+
+
+class TrackBank(_Resident):
     """Whole tracks (1-D float32 arrays), back to back in ONE float32 device buffer, for the STFT / MelSpec `module` whose features the
     clips will be.  Keeps `starts` / `lengths` (samples) and `frame_counts` (module.get_expected_frames) per track on the host, and
     `db_ref`: every track's power maximum -- the reference of its dB scale -- from one amtx_spec_power_clips launch that writes no map.
@@ -146,34 +189,33 @@ class TrackBank(object):
     def __len__(self):
         return len(self.lengths)
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_dev', None)
-        return state
+    def _check_frames(self, i, frames):
+        """The plan's frame count of track i must be the host bookkeeping's (module.get_expected_frames), or clips near the track's end
+        would be framed from padding, or not exist (the reference's own count differs for a module that is not centred with
+        win_length < n_fft: features/waveform.py:43-67)."""
+        if frames != int(self.frame_counts[i]):
+            raise ValueError(f'track {i} ({int(self.lengths[i])} samples): the module expects {int(self.frame_counts[i])} frames, '
+                             f'its plan computes {frames}')
 
-    def _device_state(self):
+    def _upload(self, device):
         """(audio, db_ref) on the bank's device."""
-        dev = self.__dict__.get('_dev')
-        if dev is None:
-            import torch
-            from .features import _index_of
-            device = torch.device('cuda', _index_of(self.device))
-            plan = self.module._get_plan(device)
-            # the kernel's contract counts frames as amtx_spec_num_frames does; the host bookkeeping (module.get_expected_frames) must agree,
-            # or clips near a track's end would be framed from padding (the reference's own count differs for a module that is not
-            # centred with win_length < n_fft: features/waveform.py:43-67)
-            for i, n in enumerate(self.lengths):
-                frames = int(_lib.call('amtx_spec_num_frames', plan, int(n)))
-                if frames != int(self.frame_counts[i]):
-                    raise ValueError(f'track {i} ({int(n)} samples): the module expects {int(self.frame_counts[i])} frames, its plan computes {frames}')
-            audio = torch.from_numpy(self._host).to(device)
-            desc = torch.from_numpy(self._track_desc).to(device)
-            db_ref = torch.empty((len(self),), dtype=torch.float32, device=device)
-            # power = NULL: maxima only; `frames` = each track's own count, rows per clip = the longest track's
-            _lib.call('amtx_spec_power_clips', plan, audio, desc, len(self), int(self.frame_counts.max()), None, db_ref,
-                      device=device)
-            dev = self.__dict__['_dev'] = (audio, db_ref)
-        return dev
+        import torch
+        plan = self.module._get_plan(device)
+        for i, n in enumerate(self.lengths):                       # the kernel's contract counts frames as amtx_spec_num_frames does
+            self._check_frames(i, int(_lib.call('amtx_spec_num_frames', plan, int(n))))
+        audio = torch.from_numpy(self._host).to(device)
+        desc = torch.from_numpy(self._track_desc).to(device)
+        db_ref = torch.empty((len(self),), dtype=torch.float32, device=device)
+        # power = NULL: maxima only; `frames` = each track's own count, rows per clip = the longest track's
+        _lib.call('amtx_spec_power_clips', plan, audio, desc, len(self), int(self.frame_counts.max()), None, db_ref,
+                  device=device)
+        return audio, db_ref
+
+    def _clips_of(self, kind, ids, desc):
+        """The `kind` (TrackClips / PyramidClips) of a checked request: its table on the device and the maxima of the clips' tracks."""
+        import torch
+        audio, db_ref = self._device_state()[:2]
+        return kind(self, desc, torch.from_numpy(desc).to(audio.device), db_ref[torch.from_numpy(ids).to(audio.device)])
 
     @property
     def audio(self):
@@ -188,32 +230,8 @@ class TrackBank(object):
     def clips(self, track_ids, first_frames, num_frames):
         """`num_frames` frames from first_frames[b] on of track track_ids[b], as a TrackClips.  first_frames follow the reference's rule
         (frame_start); the request is validated on the host (clip_descriptors)."""
-        import torch
         desc = clip_descriptors(self.starts, self.lengths, self.frame_counts, track_ids, first_frames, num_frames, _reflect_half(self.module))
-        audio, db_ref = self._device_state()
-        ids = torch.from_numpy(np.asarray(track_ids, dtype=np.int64).reshape(-1)).to(audio.device)
-        return TrackClips(self, desc, torch.from_numpy(desc).to(audio.device), db_ref[ids])
-
-
-class PyramidClips(object):
-    """Clips of a PyramidBank, as a batch entry under tools.KEY_AUDIO or an argument of a CQT-family module's process_clips / power_clips:
-    `bank`, `desc` (host int64 (B, 3) rows {track, first_frame, frames}), `desc_dev` (its device copy) and `db_ref` ((B, n_harm) device
-    float32: per harmonic, the power maxima of the clips' tracks)."""
-
-    def __init__(self, bank, desc, desc_dev, db_ref):
-        self.bank, self.desc, self.desc_dev, self.db_ref = bank, desc, desc_dev, db_ref
-
-    @property
-    def num_clips(self):
-        return int(self.desc.shape[0])
-
-    @property
-    def num_frames(self):
-        return int(self.desc[0, 2])
-
-    @property
-    def device(self):
-        return self.desc_dev.device
+        return self._clips_of(TrackClips, np.asarray(track_ids, dtype=np.int64).reshape(-1), desc)
 
 
 class PyramidBank(TrackBank):
@@ -228,47 +246,40 @@ class PyramidBank(TrackBank):
             raise TypeError(f'a PyramidBank takes a CQT, VQT, HCQT or HVQT of this package, not {type(module).__name__}')
         self._take(tracks, module, device, align=4)
 
-    def _device_state(self):
+    def _upload(self, device):
         """(audio, db_ref, pyramid, track table) on the bank's device."""
-        dev = self.__dict__.get('_dev')
-        if dev is None:
-            import ctypes as C
-            import torch
-            from .features import _index_of
-            device = torch.device('cuda', _index_of(self.device))
-            plan = self.module._get_plan(device)
-            cols = int(_lib.call('amtx_cqt_track_cols', plan))
-            n_harm = int(_lib.call('amtx_cqt_num_harmonics', plan))
-            table = np.zeros((len(self), cols), dtype=np.int64)
-            place = 0                                            # elements of the pyramid buffer handed out (strides are multiples of 4)
-            for i, n in enumerate(self.lengths):
-                level_len, level_stride, rows_h = ((C.c_int64 * 16)() for _ in range(3))
-                frames = C.c_int64()
-                # not through _lib.call: AMTX_ERR_UNSUPPORTED is an answer here (a plan the windowed basis kernel does not cover)
-                rc = _lib.lib().amtx_cqt_track_layout(plan, int(n), level_len, level_stride, rows_h, C.byref(frames))
-                if rc == _lib.ERR_UNSUPPORTED:
-                    raise NotImplementedError(f'{type(self.module).__name__}: {_lib.lib().amtx_last_error().decode()}')
-                try:
-                    levels = _lib.check(rc, 'amtx_cqt_track_layout')
-                except _lib.AmtxError as e:
-                    raise ValueError(f'track {i} ({int(n)} samples): {e}') from None
-                # the host bookkeeping (module.get_expected_frames) must agree with the plan, or clips near a track's end would not exist
-                if frames.value != int(self.frame_counts[i]):
-                    raise ValueError(f'track {i} ({int(n)} samples): the module expects {int(self.frame_counts[i])} frames, its plan computes {frames.value}')
-                rows = list(rows_h[:n_harm])
-                table[i, :4] = (self.starts[i], n, max(rows), frames.value)
-                for l in range(levels):
-                    table[i, 4 + 3 * l:7 + 3 * l] = (place, level_len[l], level_stride[l])
-                    place += level_stride[l]
-                table[i, 4 + 3 * levels:] = rows
-            audio = torch.from_numpy(self._host).to(device)
-            pyramid = torch.empty((max(place, 4),), dtype=torch.float32, device=device)
-            table_dev = torch.from_numpy(table).to(device)
-            db_ref = torch.empty((len(self), n_harm), dtype=torch.float32, device=device)
-            _lib.call('amtx_cqt_pyramid_build', plan, audio, audio.numel(), table, table_dev, len(self), pyramid, pyramid.numel(), db_ref,
-                      device=device)
-            dev = self.__dict__['_dev'] = (audio, db_ref, pyramid, table_dev)
-        return dev
+        import ctypes as C
+        import torch
+        plan = self.module._get_plan(device)
+        cols = int(_lib.call('amtx_cqt_track_cols', plan))
+        n_harm = int(_lib.call('amtx_cqt_num_harmonics', plan))
+        table = np.zeros((len(self), cols), dtype=np.int64)
+        place = 0                                            # elements of the pyramid buffer handed out (strides are multiples of 4)
+        for i, n in enumerate(self.lengths):
+            level_len, level_stride, rows_h = ((C.c_int64 * 16)() for _ in range(3))
+            frames = C.c_int64()
+            # not through _lib.call: AMTX_ERR_UNSUPPORTED is an answer here (a plan the windowed basis kernel does not cover)
+            rc = _lib.lib().amtx_cqt_track_layout(plan, int(n), level_len, level_stride, rows_h, C.byref(frames))
+            if rc == _lib.ERR_UNSUPPORTED:
+                raise NotImplementedError(f'{type(self.module).__name__}: {_lib.lib().amtx_last_error().decode()}')
+            try:
+                levels = _lib.check(rc, 'amtx_cqt_track_layout')
+            except _lib.AmtxError as e:
+                raise ValueError(f'track {i} ({int(n)} samples): {e}') from None
+            self._check_frames(i, frames.value)
+            rows = list(rows_h[:n_harm])
+            table[i, :4] = (self.starts[i], n, max(rows), frames.value)
+            for l in range(levels):
+                table[i, 4 + 3 * l:7 + 3 * l] = (place, level_len[l], level_stride[l])
+                place += level_stride[l]
+            table[i, 4 + 3 * levels:] = rows
+        audio = torch.from_numpy(self._host).to(device)
+        pyramid = torch.empty((max(place, 4),), dtype=torch.float32, device=device)
+        table_dev = torch.from_numpy(table).to(device)
+        db_ref = torch.empty((len(self), n_harm), dtype=torch.float32, device=device)
+        _lib.call('amtx_cqt_pyramid_build', plan, audio, audio.numel(), table, table_dev, len(self), pyramid, pyramid.numel(), db_ref,
+                  device=device)
+        return audio, db_ref, pyramid, table_dev
 
     @property
     def db_ref(self):
@@ -287,14 +298,10 @@ class PyramidBank(TrackBank):
         return self._device_state()[3]
 
     def clips(self, track_ids, first_frames, num_frames):
-        """`num_frames` frames from first_frames[b] on of track track_ids[b], as a PyramidClips; validated on the host as clip_descriptors
-        does (unknown track, negative first frame, a clip past its track's last frame, fewer than one frame)."""
-        import torch
-        checked = clip_descriptors(self.starts, self.lengths, self.frame_counts, track_ids, first_frames, num_frames)
-        ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
-        desc = np.ascontiguousarray(np.stack((ids, checked[:, 2], checked[:, 3]), axis=1))
-        audio, db_ref = self._device_state()[:2]
-        return PyramidClips(self, desc, torch.from_numpy(desc).to(audio.device), db_ref[torch.from_numpy(ids).to(audio.device)])
+        """`num_frames` frames from first_frames[b] on of track track_ids[b], as a PyramidClips; validated on the host (_checked_request:
+        unknown track, negative first frame, a clip past its track's last frame, fewer than one frame)."""
+        ids, firsts = _checked_request(self.frame_counts, track_ids, first_frames, num_frames)
+        return self._clips_of(PyramidClips, ids, _clip_table(ids, firsts, int(num_frames)))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -368,7 +375,7 @@ def decode_rows(row_ptr, run_first, run_bits, num_frames, dtype=np.float32):
     raise TypeError(f'label clips are float32 or int64, not {np.dtype(dtype)}')
 
 
-class LabelBank(object):
+class LabelBank(_Resident):
     """The frame-aligned ground truth of whole tracks, run-length encoded (encode_rows), for clips cut on the device.
 
     maps: one dict {key: (rows_key, T_track) array} per track -- tools.KEY_MULTIPITCH, KEY_ONSETS, KEY_OFFSETS, KEY_TABLATURE or any other
@@ -451,11 +458,6 @@ class LabelBank(object):
     def __len__(self):
         return len(self.frame_counts)
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_dev', None)
-        return state
-
     @property
     def keys(self):
         """Every label key, the floating ones first: the order of the rows inside a track."""
@@ -487,25 +489,18 @@ class LabelBank(object):
         dtype = np.float32 if key in dict(self.float_keys) else np.int64
         return decode_rows(ptr, self.run_first[ptr[0]:ptr[-1]], self.run_bits[ptr[0]:ptr[-1]], self.frame_counts[int(track)], dtype)
 
-    def _device_state(self):
+    def _upload(self, device):
         """(row_ptr, run_first, run_bits) on the bank's device."""
-        dev = self.__dict__.get('_dev')
-        if dev is None:
-            import torch
-            from .features import _index_of
-            device = torch.device('cuda', _index_of(self.device))
-            dev = self.__dict__['_dev'] = tuple(torch.from_numpy(a).to(device) for a in (self.row_ptr, self.run_first, self.run_bits))
-        return dev
+        import torch
+        return tuple(torch.from_numpy(a).to(device) for a in (self.row_ptr, self.run_first, self.run_bits))
 
     def clips(self, track_ids, first_frames, num_frames):
         """{key: device tensor (B, rows_key, num_frames)} -- float32 for floating keys, int64 for integer and bool keys, each contiguous:
         the columns [first_frames[b], first_frames[b] + num_frames) of the maps of track track_ids[b].  Same signature and host validation
-        as bank.clips (clip_descriptors against this bank's own frame counts).  One amtx_label_clips launch per dtype kind; the keys of a
+        as bank.clips (_checked_request against this bank's own frame counts).  One amtx_label_clips launch per dtype kind; the keys of a
         kind are views into one allocation, key-major."""
         import torch
-        checked = clip_descriptors(np.zeros(len(self), dtype=np.int64), self.frame_counts, self.frame_counts, track_ids, first_frames, num_frames)
-        ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
-        desc = np.ascontiguousarray(np.stack((ids, checked[:, 2], checked[:, 3]), axis=1))
+        desc = _clip_table(*_checked_request(self.frame_counts, track_ids, first_frames, num_frames), int(num_frames))
         row_ptr, run_first, run_bits = self._device_state()
         device = row_ptr.device
         desc_dev = torch.from_numpy(desc).to(device)

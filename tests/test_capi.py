@@ -35,6 +35,43 @@ def test_library_exports_every_declared_symbol():
     assert L.amtx_version() >= 100
 
 
+def _golden_name(header):
+    """amtx.h -> abi_signatures.json, amtx_tracks.h -> abi_signatures_tracks.json."""
+    return 'abi_signatures' + header[len('amtx'):-len('.h')] + '.json'
+
+
+@pytest.mark.parametrize('header', _lib.HEADERS)
+def test_every_header_is_bound_and_pinned_by_a_table_of_its_own(header):
+    """Each header of _lib.HEADERS goes through the same parser, duplicate check and binding loop; its table equals its own golden file
+    exactly (the notation of test_library_exports_every_declared_symbol; the file of amtx.h holds the table itself, every other file
+    {header: table}), the golden directory holds one such file per header and no other, every declared name is exported and bound, and
+    no name is declared in two headers."""
+    assert _lib.HEADERS[0] == 'amtx.h' and len(set(_lib.HEADERS)) == len(_lib.HEADERS) and list(_lib.header_signatures()) == list(_lib.HEADERS)
+    golden_dir = os.path.dirname(GOLDEN_ABI)
+    assert sorted(f for f in os.listdir(golden_dir) if f.startswith('abi_signatures')) == sorted(_golden_name(h) for h in _lib.HEADERS)
+    with open(os.path.join(golden_dir, _golden_name(header))) as f:
+        golden = json.load(f)
+    if header != 'amtx.h':
+        assert list(golden) == [header]
+        golden = golden[header]
+    table = _lib.header_signatures()[header]
+    assert {name: list(row) for name, row in table.items()} == golden and len(golden) >= 1
+    assert (table is _lib.signatures()) == (header == 'amtx.h')
+    L = _lib.lib()
+    for name in golden:
+        assert hasattr(L, name) and name in _lib._funcs, name
+        assert [h for h in _lib.HEADERS if name in _lib.header_signatures()[h]] == [header], name
+    with pytest.raises(_lib.AmtxError, match='amtx.h, amtx_tracks.h, amtx_pyramid.h, amtx_labels.h declare no function amtx_nothing'):
+        _lib.call('amtx_nothing')
+
+
+def test_a_name_declared_in_two_headers_is_refused(monkeypatch):
+    monkeypatch.setattr(_lib, 'HEADERS', ('amtx.h', 'amtx_tracks.h', 'amtx_tracks.h'))
+    monkeypatch.setattr(_lib, '_signatures', None)
+    with pytest.raises(_lib.AmtxError, match='is declared in amtx_tracks.h and in another header'):
+        _lib.header_signatures()
+
+
 def test_parse_header_on_synthetic_text():
     table = _lib.parse_header("""
         #include <stdint.h>

@@ -1,8 +1,6 @@
 """Host side of label clips cut from resident tracks (amt_tools_amd/tracks.py LabelBank / ClipLoader, include/amtx_labels.h): the
 run-length encoding round-trips every bit, the bank validates its maps, clips are drawn by the reference's rule, the loader hands the
-same clips to both banks, and the fourth header is parsed, bound and pinned beside the first three.  No GPU here."""
-import json
-import os
+same clips to both banks, and the header's entry point refuses bad arguments by name (its pinned table: tests/test_capi.py).  No GPU here."""
 import pickle
 
 import numpy as np
@@ -11,7 +9,6 @@ import pytest
 from amt_tools_amd import _lib, cache, tools
 from amt_tools_amd.tracks import ClipLoader, LabelBank, clip_descriptors, decode_rows, draw_clips, encode_rows
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 I32 = np.iinfo(np.int32)
 
 
@@ -286,30 +283,8 @@ def test_clip_loader_deals_an_epoch_and_asks_both_banks_for_the_same_clips(drop_
 # ------------------------------------------------------------------------------------------------------------------------------
 # the C ABI
 # ------------------------------------------------------------------------------------------------------------------------------
-def _table_of(name):
-    with open(os.path.join(GOLDEN, name)) as f:
-        return json.load(f)
-
-
-def _rows(tables):
-    return {header: {name: list(row) for name, row in table.items()} for header, table in tables.items()}
-
-
-def test_fourth_header_is_bound_and_pinned_beside_the_first_three():
-    golden = _table_of('abi_signatures_labels.json')
-    assert 'amtx_labels.h' in _lib.MORE_HEADERS and sorted(_lib.more_signatures()) == sorted(_lib.MORE_HEADERS)
-    assert _rows(_lib.more_signatures())['amtx_labels.h'] == golden['amtx_labels.h'] and list(golden) == ['amtx_labels.h']
-    assert _rows(_lib.later_signatures()) == _table_of('abi_signatures_pyramid.json')
-    assert _rows(_lib.extra_signatures()) == _table_of('abi_signatures_tracks.json')
-    assert {name: list(row) for name, row in _lib.signatures().items()} == _table_of('abi_signatures.json')
-    L = _lib.lib()
-    older = set(_lib.signatures())
-    for tables in (_lib.extra_signatures(), _lib.later_signatures()):
-        for table in tables.values():
-            older |= set(table)
-    for name in golden['amtx_labels.h']:
-        assert hasattr(L, name) and name in _lib._funcs and name not in older, name
-    with pytest.raises(_lib.AmtxError, match='amtx_labels.h.*amtx_tracks.h, amtx_pyramid.h declare no function amtx_nothing'):
+def test_an_undeclared_name_is_refused_with_every_header_named():
+    with pytest.raises(_lib.AmtxError, match='amtx.h, amtx_tracks.h, amtx_pyramid.h, amtx_labels.h declare no function amtx_nothing'):
         _lib.call('amtx_nothing')
 
 

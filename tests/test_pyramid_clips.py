@@ -1,8 +1,6 @@
 """Host side of CQT-family clips cut from resident pyramids (amt_tools_amd/tracks.py PyramidBank, include/amtx_pyramid.h): requests are
-validated on the host, the bank's bookkeeping needs no device, the third header is parsed, bound and pinned beside the first two, and
-every new entry point reports a null plan by name.  No GPU here."""
-import json
-import os
+validated on the host -- by one check, with one text, for the three banks --, the bank's bookkeeping needs no device, and every entry
+point of the header reports a null plan by name (the header's pinned table: tests/test_capi.py).  No GPU here."""
 import pickle
 
 import numpy as np
@@ -10,10 +8,9 @@ import pytest
 
 from amt_tools_amd import _lib
 from amt_tools_amd.features import CQT, HCQT, MelSpec
-from amt_tools_amd.tracks import PyramidBank, PyramidClips, TrackBank
+from amt_tools_amd.tracks import LabelBank, PyramidBank, PyramidClips, TrackBank, TrackClips, clip_descriptors
 
 LENGTHS = (40000, 5001, 1500)
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def _tracks():
@@ -46,7 +43,7 @@ def test_bank_bookkeeping_needs_no_gpu_and_pickles_without_device_state():
         PyramidBank([np.zeros((2, 100), dtype=np.float32)], mod)
 
 
-@pytest.mark.parametrize('track_ids,first_frames,num_frames,match', [
+INVALID_REQUESTS = [
     ([3], [0], 1, 'unknown track 3'),
     ([-1], [0], 1, 'unknown track -1'),
     ([0], [-1], 4, 'negative first frame'),
@@ -55,12 +52,47 @@ def test_bank_bookkeeping_needs_no_gpu_and_pickles_without_device_state():
     ([2], [0], 4, 'run past the 3 frames of track 2'),                              # a track shorter than the clip
     ([0], [0], 0, 'at least one frame'),
     ([0, 1], [0], 2, 'one first frame per track id'),
-])
+]
+
+
+@pytest.mark.parametrize('track_ids,first_frames,num_frames,match', INVALID_REQUESTS)
 def test_invalid_requests_raise_before_any_device_is_touched(track_ids, first_frames, num_frames, match):
     bank = PyramidBank(_tracks(), CQT(sample_rate=22050, hop_length=512, n_bins=192, bins_per_octave=24))
     with pytest.raises(ValueError, match=match):
         bank.clips(track_ids, first_frames, num_frames)
     assert '_dev' not in bank.__dict__
+
+
+class _Bank(object):
+    """What LabelBank reads of the audio bank of the same tracks."""
+    device = 'cuda:0'
+    frame_counts = np.array([79, 10, 3])
+
+    def __len__(self):
+        return 3
+
+
+def _bank(kind):
+    if kind == 'track':
+        return TrackBank(_tracks(), MelSpec(sample_rate=16000, hop_length=512))
+    if kind == 'pyramid':
+        return PyramidBank(_tracks(), CQT(sample_rate=22050, hop_length=512, n_bins=192, bins_per_octave=24))
+    return LabelBank([{'multi_pitch': np.zeros((2, T))} for T in _Bank.frame_counts], bank=_Bank())
+
+
+@pytest.mark.parametrize('kind', ['track', 'pyramid', 'label'])
+def test_every_bank_refuses_the_same_requests_with_the_same_text(kind):
+    """One request check for the three banks: every row of INVALID_REQUESTS raises from bank.clips the ValueError, word for word, that
+    clip_descriptors raises for it over the same frame counts, and no device state has been created afterwards."""
+    bank = _bank(kind)
+    np.testing.assert_array_equal(bank.frame_counts, _Bank.frame_counts)
+    for track_ids, first_frames, num_frames, match in INVALID_REQUESTS:
+        with pytest.raises(ValueError, match=match) as want:
+            clip_descriptors(np.zeros(3), bank.frame_counts, bank.frame_counts, track_ids, first_frames, num_frames)
+        with pytest.raises(ValueError, match=match) as got:
+            bank.clips(track_ids, first_frames, num_frames)
+        assert str(got.value) == str(want.value)
+        assert '_dev' not in bank.__dict__
 
 
 def test_raw_audio_bank_and_foreign_arguments_still_have_no_clip_form():
@@ -71,26 +103,11 @@ def test_raw_audio_bank_and_foreign_arguments_still_have_no_clip_form():
             with pytest.raises(NotImplementedError, match='no clip form'):
                 call(arg)
     assert PyramidClips(None, np.array([[1, 5, 33]]), None, None).num_frames == 33
+    assert TrackClips(None, np.array([[40000, 5001, 5, 33]]), None, None).num_frames == 33
 
 
-def test_third_header_is_bound_and_pinned_beside_the_first_two():
-    """include/amtx_pyramid.h goes through the parser, the duplicate check and the binding loop of the other headers; its table equals
-    tests/golden/abi_signatures_pyramid.json, and the tables of amtx.h and amtx_tracks.h and EXTRA_HEADERS are what they were."""
-    def table_of(name):
-        with open(os.path.join(GOLDEN, name)) as f:
-            return json.load(f)
-
-    def rows(tables):
-        return {header: {name: list(row) for name, row in table.items()} for header, table in tables.items()}
-    golden = table_of('abi_signatures_pyramid.json')
-    assert rows(_lib.later_signatures()) == golden and sorted(golden) == sorted(_lib.LATER_HEADERS) == ['amtx_pyramid.h']
-    assert _lib.EXTRA_HEADERS == ('amtx_tracks.h',) and rows(_lib.extra_signatures()) == table_of('abi_signatures_tracks.json')
-    assert {name: list(row) for name, row in _lib.signatures().items()} == table_of('abi_signatures.json')
-    L = _lib.lib()
-    for name in golden['amtx_pyramid.h']:
-        assert hasattr(L, name) and name in _lib._funcs and name not in _lib.signatures(), name
-        assert not any(name in table for table in _lib.extra_signatures().values()), name
-    with pytest.raises(_lib.AmtxError, match='amtx_tracks.h, amtx_pyramid.h declare no function amtx_nothing'):
+def test_an_undeclared_name_is_refused_with_every_header_named():
+    with pytest.raises(_lib.AmtxError, match='amtx.h, amtx_tracks.h, amtx_pyramid.h, amtx_labels.h declare no function amtx_nothing'):
         _lib.call('amtx_nothing')
 
 
@@ -106,7 +123,7 @@ NULL_CALLS = {
 
 
 def test_every_new_entry_point_is_covered_below():
-    assert sorted(list(NULL_CALLS) + ['amtx_cqt_clips_workspace_bytes']) == sorted(_lib.later_signatures()['amtx_pyramid.h'])
+    assert sorted(list(NULL_CALLS) + ['amtx_cqt_clips_workspace_bytes']) == sorted(_lib.header_signatures()['amtx_pyramid.h'])
 
 
 @pytest.mark.parametrize('name', sorted(NULL_CALLS))

@@ -82,22 +82,6 @@ def test_bank_bookkeeping_needs_no_gpu_and_pickles_without_device_state():
 def test_entry_point_reports_a_null_plan():
     with pytest.raises(_lib.AmtxError, match='amtx_spec_power_clips.*null argument'):
         _lib.call('amtx_spec_power_clips', None, None, None, 1, 1, None, None, None)
-
-
-def test_second_header_is_bound_and_pinned():
-    """include/amtx_tracks.h is read by the same parser as include/amtx.h and bound into the same library; its table equals
-    tests/golden/abi_signatures_tracks.json exactly (the notation of tests/golden/abi_signatures.json: return type first, then one letter
-    per parameter, then whether the function ends in `void* stream`), and the table of amtx.h is the one it was."""
-    import json
-    import os
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'abi_signatures_tracks.json')) as f:
-        golden = json.load(f)
-    parsed = {header: {name: list(row) for name, row in table.items()} for header, table in _lib.extra_signatures().items()}
-    assert parsed == golden and sorted(golden) == sorted(_lib.EXTRA_HEADERS)
-    L = _lib.lib()
-    for table in golden.values():
-        for name in table:
-            assert hasattr(L, name) and name in _lib._funcs and name not in _lib.signatures(), name
     with pytest.raises(TypeError, match='amtx_spec_power_clips takes 8'):
         _lib.call('amtx_spec_power_clips', None, None, None, 1, 1, None, None)
 
