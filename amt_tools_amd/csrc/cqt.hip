@@ -609,75 +609,165 @@ extern "C" size_t amtx_cqt_workspace_bytes(const amtx_cqt_plan* p, int batch, in
 
 namespace {
 
-// the plans, level lengths `len` and map widths `t_buf` whose basis products the windowed kernel computes; every other goes through the
-// generic GEMM
-bool basis_windowed(const amtx_cqt_plan* p, const std::vector<int64_t>& len, int64_t t_buf) {
+// The file's A/B switches, read once per process
+struct CqtSwitches {
+    bool copy_level0;      // AMTX_CQT_COPY_LEVEL0: amtx_cqt_forward copies the clip between two paddings instead of reading the audio in place
+    bool gemm_basis;       // AMTX_CQT_GEMM_BASIS: round 4's basis products (all levels in one launch of the generic fp32-A two-plane GEMM)
+};
+const CqtSwitches& cqt_switches() {
+    static const CqtSwitches sw{getenv("AMTX_CQT_COPY_LEVEL0") != nullptr, getenv("AMTX_CQT_GEMM_BASIS") != nullptr};
+    return sw;
+}
+
+struct PyrLevel { float* pyr; int64_t len, stride; };      // a level's buffer (first element of clip 0's left pad), samples, elements per clip
+// The pyramid chain of `B` equal clips of `n` samples (amtx_cqt_forward) or of one track as a batch of one (amtx_cqt_pyramid_build); level_of(l)
+// answers where level l lies.  direct0 (zero pads only): level 0 is the audio where it lies -- the first decimation and the level-0 basis
+// product read it there (out-of-clip samples read as zero: the decimator clamps, the basis kernels take a valid range), so the clip is not
+// copied between two paddings first (0.45 ms and 1.3 GB per 512 clips).  `maxbuf`: the per-(clip, harmonic) maxima the chain's first kernel
+// resets (the level-0 copy, or the decimation that reads the audio); null: nothing to reset.
+template <class LevelOf>
+int pyramid_chain(const amtx_cqt_plan* p, const float* audio, int64_t n, int64_t audio_stride, int B, bool direct0, float* maxbuf, LevelOf level_of,
+                  hipStream_t s) {
+    const int nl = (int)p->levels.size(), zero_pads = p->lib09 ? 0 : 1;
+    PyrLevel prev{}, cur{};
+    for (int l = 0; l < nl; prev = cur, ++l) {
+        cur = level_of(l);
+        if (l == 0) {
+            if (direct0) continue;
+            const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+            hipLaunchKernelGGL(cqt_level0_kernel, dim3(nb, B), dim3(256), 0, s, audio, n, audio_stride, cur.pyr, cur.stride, p->pad, zero_pads, maxbuf, p->n_harm);
+        } else {
+            const bool from_audio = direct0 && l == 1;
+            const int rc = amtx_launch_cqt_decimate(from_audio ? audio : (const float*)prev.pyr, prev.len, from_audio ? audio_stride : prev.stride,
+                                                    from_audio ? 0 : p->pad, cur.pyr, cur.len, cur.stride, p->pad, p->d_tfrag, zero_pads,
+                                                    from_audio ? maxbuf : (float*)nullptr, p->n_harm, B, s);
+            if (rc != AMTX_OK) return rc;
+        }
+        AMTX_CHECK_LAUNCH();
+        if (!zero_pads) {      // librosa 0.9: reflecting centre pad, from the level's own samples
+            hipLaunchKernelGGL(cqt_pad_kernel, dim3(8, B), dim3(256), 0, s, cur.pyr, cur.len, cur.stride, p->pad, p->lib09);
+            AMTX_CHECK_LAUNCH();
+        }
+    }
+    return AMTX_OK;
+}
+
+// The basis products' route: whether the windowed kernel computes them (every other plan goes through the generic GEMM and has no
+// clip form) and, if so, its launches, one per n_fft.  Pure: the plan's host fields and sizes in.
+struct BasisLaunch { int ks; BasisLevs ls; int slices; unsigned gx; size_t lds; };      // cqt_basis_kernel<ks> / cqt_basis_clips_kernel<ks>, grid (gx, slices)
+struct BasisRoute {
+    bool windowed;
+    int frames[BAS_MAXLEV], ft[BAS_MAXLEV], tiles_per_clip[BAS_MAXLEV];      // per level: frames per clip (0: no banks), frames per tile, tiles
+    int nlaunch;
+    BasisLaunch launch[2];
+};
+// d: the clips' level lengths and frames, or PLAN_ONLY: clips of resident tracks, whose lengths amtx_cqt_track_layout was asked about when the
+// bank was laid out -- the plan alone decides, and every level runs t_buf frames.  t_buf: frames of the power map's rows; B: clips
+constexpr const CqtDims* PLAN_ONLY = nullptr;
+BasisRoute basis_route(const amtx_cqt_plan* p, const CqtDims* d, int64_t t_buf, int B) {
+    BasisRoute r{};
     const int nl = (int)p->levels.size();
-    bool windowed = nl <= BAS_MAXLEV && p->n_harm <= 16 && (int64_t)p->n_harm * p->n_bins * t_buf < (1ll << 31);
-    for (int l = 0; l < nl && windowed; ++l) {
+    r.windowed = nl <= BAS_MAXLEV && p->n_harm <= 16 && (int64_t)p->n_harm * p->n_bins * t_buf < (1ll << 31);
+    for (int l = 0; l < nl && r.windowed; ++l) {
         const Level& L = p->levels[l];
         if (L.banks.empty()) continue;
-        windowed = (L.nfft == 128 || L.nfft == 256) && L.k_pad >= L.nfft && L.ncols <= 256 && L.ncols % 2 == 0 && L.hop >= 4 && (L.hop & (L.hop - 1)) == 0 &&
-                   (L.hop <= 512) && len[l] >= 4;
+        r.windowed = (L.nfft == 128 || L.nfft == 256) && L.k_pad >= L.nfft && L.ncols <= 256 && L.ncols % 2 == 0 && L.hop >= 4 && (L.hop & (L.hop - 1)) == 0 &&
+                     (L.hop <= 512) && (d == PLAN_ONLY || d->len[l] >= 4);
     }
-    return windowed;
-}
-
-// the plan's part of a level's BasisLevel and its tiling over `frames` frames per clip; sig / sig_gs / len / off are the caller's
-void basis_level(const Level& L, int frames, BasisLevel& bl) {
-    bl.w = L.d_w; bl.map = L.d_map; bl.n_pad = L.n_pad; bl.k_pad = L.k_pad; bl.ncols = L.ncols; bl.hop = L.hop;
-    bl.frames = frames;
-    const int hs0 = std::min(L.hop, L.nfft);
-    int ftl = std::max(16, std::min(128, ((BAS_MAXWIN - L.nfft) / hs0 + 1) / 16 * 16));
-    ftl = std::min(ftl, (bl.frames + 15) / 16 * 16);
-    bl.ft = ftl;
-    bl.tiles_per_clip = (bl.frames + ftl - 1) / ftl;
-}
-
-// one launch per n_fft over the levels of `ba`; cl: the clip form (cqt_basis_clips_kernel)
-int basis_launch(const amtx_cqt_plan* p, const BasisArgs& ba, const BasisClips* cl, hipStream_t s) {
-    const int nl = ba.nlev, B = ba.B;
+    if (!r.windowed) return r;
+    for (int l = 0; l < nl; ++l) {      // the tiling of a level over its frames
+        const Level& L = p->levels[l];
+        if (L.banks.empty()) continue;
+        r.frames[l] = (int)(d == PLAN_ONLY ? t_buf : d->frames[l]);
+        const int hs0 = std::min(L.hop, L.nfft);
+        const int ftl = std::max(16, std::min(128, ((BAS_MAXWIN - L.nfft) / hs0 + 1) / 16 * 16));
+        r.ft[l] = std::min(ftl, (r.frames[l] + 15) / 16 * 16);
+        r.tiles_per_clip[l] = (r.frames[l] + r.ft[l] - 1) / r.ft[l];
+    }
     for (int kk = 128; kk <= 256; kk *= 2) {
-        BasisLevs ls;
-        ls.n = 0;
-        size_t lds = 0;
+        BasisLaunch& bn = r.launch[r.nlaunch];
+        bn = BasisLaunch{};
+        bn.ks = kk / 32;
         for (int l = 0; l < nl; ++l) {
-            const BasisLevel& bl = ba.lev[l];
-            if (bl.frames <= 0 || p->levels[l].nfft != kk) continue;
-            const int hs = std::min(bl.hop, kk);               // frame stride of the staged copy (cqt_basis_kernel)
-            const int ws_s = (bl.ft - 1) * hs + kk;
+            if (r.frames[l] <= 0 || p->levels[l].nfft != kk) continue;
+            const int hs = std::min(p->levels[l].hop, kk);               // frame stride of the staged copy (cqt_basis_kernel)
+            const int ws_s = (r.ft[l] - 1) * hs + kk;
             const int wsp = ws_s + bas_pad(hs) * ((ws_s + hs - 1) / hs);
-            lds = std::max(lds, (size_t)((wsp + 7) & ~7) * 2 * 2 + 64);
-            ls.lev[ls.n++] = l;
+            bn.lds = std::max(bn.lds, (size_t)((wsp + 7) & ~7) * 2 * 2 + 64);
+            bn.ls.lev[bn.ls.n++] = l;
         }
-        if (!ls.n) continue;
+        if (!bn.ls.n) continue;
         // two 256-thread blocks per CU; the levels (and the second column slice of the wide ones) share the chip: 512 blocks dealt EVENLY to the
         // levels (dealing them by staged samples, by matrix work or by a mix was measured slower, 2.2 - 2.6 against 1.97 ms for the
         // front-end: the deep levels' tiles are as many as the shallow ones' and a tile's fixed costs -- barriers, a load round trip, the
         // maxima's atomics -- weigh as much as its size)
-        int slices = 1;
-        for (int i = 0; i < ls.n; ++i) slices = std::max(slices, (ba.lev[ls.lev[i]].ncols + 127) / 128);
-        ls.b0[0] = 0;
-        for (int i = 0; i < ls.n; ++i) {
-            const int64_t tiles = (int64_t)ba.lev[ls.lev[i]].tiles_per_clip * B;
-            ls.b0[i + 1] = ls.b0[i] + (int)std::min<int64_t>(std::max(8, 512 / ls.n), tiles);
+        bn.slices = 1;
+        for (int i = 0; i < bn.ls.n; ++i) bn.slices = std::max(bn.slices, (p->levels[bn.ls.lev[i]].ncols + 127) / 128);
+        bn.ls.b0[0] = 0;
+        for (int i = 0; i < bn.ls.n; ++i) {
+            const int64_t tiles = (int64_t)r.tiles_per_clip[bn.ls.lev[i]] * B;
+            bn.ls.b0[i + 1] = bn.ls.b0[i] + (int)std::min<int64_t>(std::max(8, 512 / bn.ls.n), tiles);
         }
-        const unsigned gx = (unsigned)ls.b0[ls.n];
-        if (cl && kk == 256) {
-            AMTX_GRANT_LDS(cqt_basis_clips_kernel<8>, lds);
-            hipLaunchKernelGGL(cqt_basis_clips_kernel<8>, dim3(gx, slices), dim3(256), lds, s, ba, ls, *cl);
-        } else if (cl) {
-            AMTX_GRANT_LDS(cqt_basis_clips_kernel<4>, lds);
-            hipLaunchKernelGGL(cqt_basis_clips_kernel<4>, dim3(gx, slices), dim3(256), lds, s, ba, ls, *cl);
-        } else if (kk == 256) {
-            AMTX_GRANT_LDS(cqt_basis_kernel<8>, lds);
-            hipLaunchKernelGGL(cqt_basis_kernel<8>, dim3(gx, slices), dim3(256), lds, s, ba, ls);
-        } else {
-            AMTX_GRANT_LDS(cqt_basis_kernel<4>, lds);
-            hipLaunchKernelGGL(cqt_basis_kernel<4>, dim3(gx, slices), dim3(256), lds, s, ba, ls);
-        }
-        AMTX_CHECK_LAUNCH();
+        bn.gx = (unsigned)bn.ls.b0[bn.ls.n];
+        ++r.nlaunch;
     }
+    return r;
+}
+
+// what both forms of the basis launch set alike; the level signals (sig, sig_gs, len, off) and BasisArgs.rows are the caller's
+BasisArgs basis_args(const amtx_cqt_plan* p, const BasisRoute& r, int B, float* mag, int64_t t_buf, float* maxbuf) {
+    BasisArgs ba{};
+    ba.nlev = (int)p->levels.size(); ba.B = B; ba.ntiles = 0;
+    ba.mag = mag; ba.mag_gs = (int64_t)p->n_harm * p->n_bins * t_buf; ba.mag_pitch = t_buf;
+    ba.maxbuf = maxbuf; ba.n_harm = p->n_harm;
+    for (int l = 0; l < ba.nlev; ++l) {
+        const Level& L = p->levels[l];
+        if (L.banks.empty()) continue;
+        BasisLevel& bl = ba.lev[l];
+        bl.w = L.d_w; bl.map = L.d_map; bl.n_pad = L.n_pad; bl.k_pad = L.k_pad; bl.ncols = L.ncols; bl.hop = L.hop;
+        bl.frames = r.frames[l]; bl.ft = r.ft[l]; bl.tiles_per_clip = r.tiles_per_clip[l];
+    }
+    return ba;
+}
+
+template <int KS>
+int basis_launch_ks(const BasisLaunch& bn, const BasisArgs& ba, const BasisClips* cl, hipStream_t s) {
+    if (cl) {
+        AMTX_GRANT_LDS(cqt_basis_clips_kernel<KS>, bn.lds);
+        hipLaunchKernelGGL(cqt_basis_clips_kernel<KS>, dim3(bn.gx, bn.slices), dim3(256), bn.lds, s, ba, bn.ls, *cl);
+    } else {
+        AMTX_GRANT_LDS(cqt_basis_kernel<KS>, bn.lds);
+        hipLaunchKernelGGL(cqt_basis_kernel<KS>, dim3(bn.gx, bn.slices), dim3(256), bn.lds, s, ba, bn.ls);
+    }
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
+}
+
+// the route's launches, one per n_fft; cl: the clip form (cqt_basis_clips_kernel)
+int basis_launch(const BasisRoute& r, const BasisArgs& ba, const BasisClips* cl, hipStream_t s) {
+    for (int i = 0; i < r.nlaunch; ++i) {
+        const BasisLaunch& bn = r.launch[i];
+        const int rc = bn.ks == 8 ? basis_launch_ks<8>(bn, ba, cl, s) : basis_launch_ks<4>(bn, ba, cl, s);
+        if (rc != AMTX_OK) return rc;
+    }
+    return AMTX_OK;
+}
+
+// amplitude_to_db(ref = max) -> /80 + 1 of the power map mag[B][n_harm][n_bins][t_buf], truncated to t_out frames: fp32 into `out`, or, out16 !=
+// null, [B][t_out][n_bins][8] bf16 (lo_plane != 0: and its second plane).  `fn` names the 16-bit form in its refusal.
+int scale_launch(const char* fn, const amtx_cqt_plan* p, const float* mag, const float* refs, int B, int64_t t_buf, int64_t t_out, int decibels, float* out,
+                 void* out16, int64_t lo_plane, hipStream_t s) {
+    if (out16) {
+        AMTX_REQUIRE(p->n_harm <= 8 && ((uintptr_t)out16 % 16) == 0, "%s: at most 8 harmonics, output 16-byte aligned", fn);
+        const int nbc = std::min(p->n_bins, 120);            // bins per pass: 32 x 121 x 16 bytes of LDS
+        const size_t lds = (size_t)(lo_plane ? 2 : 1) * SC16_TT * (nbc + 1) * 16 + 64;
+        AMTX_GRANT_LDS(cqt_scale16_kernel, lds);
+        hipLaunchKernelGGL(cqt_scale16_kernel, dim3((unsigned)((t_out + SC16_TT - 1) / SC16_TT), B), dim3(256), lds, s, mag, refs, p->n_harm, p->n_bins, nbc,
+                           t_buf, t_out, decibels, (uint4*)out16, lo_plane);
+    } else {
+        hipLaunchKernelGGL(cqt_scale_kernel, dim3(8, B * p->n_harm), dim3(256), 0, s, mag, refs, p->n_bins, t_buf, t_out, decibels, out);
+    }
+    AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
 
@@ -699,57 +789,29 @@ static int cqt_forward_impl(const amtx_cqt_plan* p, const float* audio, int64_t 
     float* mag = (float*)(ws + d.off_mag);
     float* maxbuf = (float*)(ws + d.off_max);
     const int zero_pads = p->lib09 ? 0 : 1;
+    const CqtSwitches& sw = cqt_switches();
 
-    // librosa >= 0.10 (zero centre padding): level 0 of the pyramid IS the caller's audio -- the first decimation and the level-0 basis
-    // product read it where it lies (out-of-clip samples read as zero: the decimator clamps, the GEMM's A loader takes a valid range), so
-    // the clip is not copied between two paddings first (0.45 ms and 1.3 GB per 512 clips).  librosa 0.9's reflecting pad keeps the copy.
-    static const bool copy_level0 = getenv("AMTX_CQT_COPY_LEVEL0") != nullptr;        // A/B switch
-    const bool direct0 = zero_pads && !copy_level0;
+    // zero centre padding: level 0 of the pyramid IS the caller's audio (pyramid_chain), unless AMTX_CQT_COPY_LEVEL0 keeps the copy for the A/B
+    const bool direct0 = zero_pads && !sw.copy_level0;
     if (direct0 && nl == 1) AMTX_CHECK_HIP(hipMemsetAsync(maxbuf, 0, sizeof(float) * B * p->n_harm, s));
-    for (int l = 0; l < nl; ++l) {
-        float* pyr = (float*)(ws + d.pyr_off[l]);
-        if (l == 0) {
-            if (direct0) continue;
-            const unsigned nb = (unsigned)std::min<int64_t>((num_samples + 255) / 256, 4096);
-            hipLaunchKernelGGL(cqt_level0_kernel, dim3(nb, B), dim3(256), 0, s, audio, num_samples, audio_stride, pyr, d.stride[0], p->pad,
-                               zero_pads, maxbuf, p->n_harm);
-        } else {
-            const bool from_audio = direct0 && l == 1;
-            int rc = amtx_launch_cqt_decimate(from_audio ? audio : (const float*)(ws + d.pyr_off[l - 1]), d.len[l - 1], from_audio ? audio_stride : d.stride[l - 1],
-                                              from_audio ? 0 : p->pad, pyr, d.len[l], d.stride[l], p->pad, p->d_tfrag, zero_pads,
-                                              from_audio ? maxbuf : (float*)nullptr, p->n_harm, B, s);
-            if (rc != AMTX_OK) return rc;
-        }
-        AMTX_CHECK_LAUNCH();
-        if (!zero_pads) {      // librosa 0.9: reflecting centre pad, from the level's own samples
-            hipLaunchKernelGGL(cqt_pad_kernel, dim3(8, B), dim3(256), 0, s, pyr, d.len[l], d.stride[l], p->pad, p->lib09);
-            AMTX_CHECK_LAUNCH();
-        }
-    }
-    // the basis products of all levels: the windowed kernel (cqt_basis_kernel), one launch per level on the same stream; AMTX_CQT_GEMM_BASIS=1
-    // keeps round 4's path (all levels in ONE launch of the generic fp32-A two-plane GEMM) for the A/B
-    static const bool gemm_basis = getenv("AMTX_CQT_GEMM_BASIS") != nullptr;
-    const bool windowed = !gemm_basis && basis_windowed(p, d.len, d.t_buf);
-    if (windowed) {
-        BasisArgs ba;
-        ba.nlev = nl; ba.B = B; ba.ntiles = 0;
-        ba.mag = mag; ba.mag_gs = (int64_t)p->n_harm * p->n_bins * d.t_buf; ba.mag_pitch = d.t_buf;
-        ba.maxbuf = maxbuf; ba.n_harm = p->n_harm;
-        for (int h = 0; h < 16; ++h) ba.rows[h] = h < p->n_harm ? d.frames_h[h] : 0;
+    int rc = pyramid_chain(p, audio, num_samples, audio_stride, B, direct0, maxbuf,
+                           [&](int l) { return PyrLevel{(float*)(ws + d.pyr_off[l]), d.len[l], d.stride[l]}; }, s);
+    if (rc != AMTX_OK) return rc;
+    // the basis products of all levels: the windowed kernel, or (AMTX_CQT_GEMM_BASIS=1: for the A/B) round 4's path
+    const BasisRoute route = basis_route(p, &d, d.t_buf, B);
+    if (route.windowed && !sw.gemm_basis) {
+        BasisArgs ba = basis_args(p, route, B, mag, d.t_buf, maxbuf);
+        for (int h = 0; h < p->n_harm; ++h) ba.rows[h] = d.frames_h[h];
         for (int l = 0; l < nl; ++l) {
-            const Level& L = p->levels[l];
             BasisLevel& bl = ba.lev[l];
-            bl = BasisLevel();
-            if (L.banks.empty()) { bl.frames = 0; continue; }
+            if (bl.frames <= 0) continue;
             if (direct0 && l == 0) { bl.sig = audio; bl.sig_gs = audio_stride; }
             else { bl.sig = (const float*)(ws + d.pyr_off[l]) + p->pad; bl.sig_gs = d.stride[l]; }
             bl.len = d.len[l];
             // librosa 0.9's reflecting pads live in the pyramid buffer on both sides of the signal: there every sample the windows touch exists
-            bl.off = 0;
             if (!zero_pads) { bl.sig -= p->pad; bl.off = p->pad; bl.len = d.stride[l]; }
-            basis_level(L, (int)d.frames[l], bl);
         }
-        const int rc = basis_launch(p, ba, nullptr, s);
+        rc = basis_launch(route, ba, nullptr, s);
         if (rc != AMTX_OK) return rc;
     } else {
     // the basis products of ALL levels in one launch (same kernel, per-level A / W / sizes; 8 launches before)
@@ -778,31 +840,18 @@ static int cqt_forward_impl(const amtx_cqt_plan* p, const float* audio, int64_t 
         for (int h = 0; h < p->n_harm && h < 16; ++h) g.pair_rows[h] = d.frames_h[h];
         g.pair_max = maxbuf; g.pair_nh = p->n_harm;       // the per-(clip, harmonic) maxima of the dB reference, kept by the epilogue
         if (ng == AMTX_GEMM_MULTI_MAX) {
-            int rc = amtx_launch_gemm_multi(gs, ng, s);
+            rc = amtx_launch_gemm_multi(gs, ng, s);
             if (rc != AMTX_OK) return rc;
             ng = 0;
         }
         gs[ng++] = g;
     }
     if (ng) {
-        int rc = amtx_launch_gemm_multi(gs, ng, s);
+        rc = amtx_launch_gemm_multi(gs, ng, s);
         if (rc != AMTX_OK) return rc;
     }
     }
-    if (out16) {
-        AMTX_REQUIRE(p->n_harm <= 8 && ((uintptr_t)out16 % 16) == 0, "amtx_cqt_forward16: at most 8 harmonics, output 16-byte aligned");
-        const int nbc = std::min(p->n_bins, 120);            // bins per pass: 32 x 121 x 16 bytes of LDS
-        const size_t lds = (size_t)(lo_plane ? 2 : 1) * SC16_TT * (nbc + 1) * 16 + 64;
-        AMTX_GRANT_LDS(cqt_scale16_kernel, lds);
-        hipLaunchKernelGGL(cqt_scale16_kernel, dim3((unsigned)((d.t_out + SC16_TT - 1) / SC16_TT), B), dim3(256), lds, s, (const float*)mag,
-                           (const float*)maxbuf, p->n_harm, p->n_bins, nbc, d.t_buf, d.t_out, decibels, (uint4*)out16, lo_plane);
-        AMTX_CHECK_LAUNCH();
-        return AMTX_OK;
-    }
-    hipLaunchKernelGGL(cqt_scale_kernel, dim3(8, B * p->n_harm), dim3(256), 0, s, (const float*)mag, (const float*)maxbuf, p->n_bins, d.t_buf,
-                       d.t_out, decibels, out);
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+    return scale_launch("amtx_cqt_forward16", p, mag, maxbuf, B, d.t_buf, d.t_out, decibels, out, out16, lo_plane, s);
 }
 
 extern "C" int amtx_cqt_forward(const amtx_cqt_plan* p, const float* audio, int64_t num_samples, int64_t audio_stride, int batch, int decibels,
@@ -833,23 +882,17 @@ namespace {
 int pyr_cols(const amtx_cqt_plan* p) { return 4 + 3 * (int)p->levels.size() + p->n_harm; }
 
 // the basis products of `B` clips of `num_frames` frames (desc) or of the table's `B` tracks whole (desc = null, num_frames = the longest's
-// rows): power maps into `mag` and / or maxima into `maxima`
-int clips_basis(const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tab, const int64_t* desc, int B, int64_t num_frames,
-                float* mag, float* maxima, hipStream_t s) {
+// rows), by the route clips_check made of the same B and num_frames: power maps into `mag` and / or maxima into `maxima`
+int clips_basis(const amtx_cqt_plan* p, const BasisRoute& route, const float* audio, const float* pyramid, const int64_t* tab, const int64_t* desc, int B,
+                int64_t num_frames, float* mag, float* maxima, hipStream_t s) {
     const int nl = (int)p->levels.size();
-    BasisArgs ba;
-    ba.nlev = nl; ba.B = B; ba.ntiles = 0;
-    ba.mag = mag; ba.mag_gs = (int64_t)p->n_harm * p->n_bins * num_frames; ba.mag_pitch = num_frames;
-    ba.maxbuf = maxima; ba.n_harm = p->n_harm;
-    for (int h = 0; h < 16; ++h) ba.rows[h] = 0;
+    BasisArgs ba = basis_args(p, route, B, mag, num_frames, maxima);
     BasisClips cl;
     cl.tab = tab; cl.desc = desc; cl.cols = pyr_cols(p); cl.rows_col = 4 + 3 * nl; cl.num_frames = (int)num_frames;
     for (int l = 0; l < nl; ++l) {
-        const Level& L = p->levels[l];
         BasisLevel& bl = ba.lev[l];
-        bl = BasisLevel();
         cl.base_col[l] = 4 + 3 * l;
-        if (L.banks.empty()) { bl.frames = 0; cl.len_col[l] = 4 + 3 * l + 1; continue; }
+        if (bl.frames <= 0) { cl.len_col[l] = 4 + 3 * l + 1; continue; }
         if (!p->lib09 && l == 0) {            // zero pads: level 0 is the audio where it lies
             bl.sig = audio; bl.off = 0;
             cl.base_col[l] = 0; cl.len_col[l] = 1;
@@ -860,14 +903,15 @@ int clips_basis(const amtx_cqt_plan* p, const float* audio, const float* pyramid
             bl.sig = pyramid; bl.off = p->pad;
             cl.len_col[l] = 4 + 3 * l + 2;
         }
-        basis_level(L, (int)num_frames, bl);
     }
-    return basis_launch(p, ba, &cl, s);
+    return basis_launch(route, ba, &cl, s);
 }
 
-int clips_check(const char* fn, const amtx_cqt_plan* p, int batch, int64_t num_frames) {
+// the request's sizes, and the route of its basis products (PLAN_ONLY: the tracks' lengths were checked where the bank was laid out)
+int clips_check(const char* fn, const amtx_cqt_plan* p, int batch, int64_t num_frames, BasisRoute& route) {
     AMTX_REQUIRE(batch > 0 && batch < 65536 && num_frames > 0 && num_frames < (1ll << 31), "%s: bad batch/num_frames", fn);
-    if (!basis_windowed(p, std::vector<int64_t>(p->levels.size(), 4), num_frames)) {
+    route = basis_route(p, PLAN_ONLY, num_frames, batch);
+    if (!route.windowed) {
         amtx_set_error("%s: this plan's basis products have no clip form (the windowed kernel does not cover it)", fn);
         return AMTX_ERR_UNSUPPORTED;
     }
@@ -878,29 +922,18 @@ int clips_scaled(const char* fn, const amtx_cqt_plan* p, const float* audio, con
                  int64_t num_frames, const float* refs, int decibels, void* workspace, size_t workspace_bytes, float* out, void* out16,
                  int64_t lo_plane, void* stream_) {
     AMTX_REQUIRE(p && audio && pyramid && tab && desc && refs && workspace && (out || out16), "%s: null argument", fn);
-    int rc = clips_check(fn, p, batch, num_frames);
+    BasisRoute route;
+    int rc = clips_check(fn, p, batch, num_frames, route);
     if (rc != AMTX_OK) return rc;
     AMTX_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", fn);
     const size_t need = amtx_cqt_clips_workspace_bytes(p, batch, num_frames);
     AMTX_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream_;
     float* mag = (float*)workspace;
-    rc = clips_basis(p, audio, pyramid, tab, desc, batch, num_frames, mag, nullptr, s);
+    rc = clips_basis(p, route, audio, pyramid, tab, desc, batch, num_frames, mag, nullptr, s);
     if (rc != AMTX_OK) return rc;
     // the whole-track scaling kernels with a clip-sized map (t_buf = t_out = num_frames) and the tracks' maxima as references
-    if (out16) {
-        AMTX_REQUIRE(p->n_harm <= 8 && ((uintptr_t)out16 % 16) == 0, "%s: at most 8 harmonics, output 16-byte aligned", fn);
-        const int nbc = std::min(p->n_bins, 120);
-        const size_t lds = (size_t)(lo_plane ? 2 : 1) * SC16_TT * (nbc + 1) * 16 + 64;
-        AMTX_GRANT_LDS(cqt_scale16_kernel, lds);
-        hipLaunchKernelGGL(cqt_scale16_kernel, dim3((unsigned)((num_frames + SC16_TT - 1) / SC16_TT), batch), dim3(256), lds, s, (const float*)mag, refs,
-                           p->n_harm, p->n_bins, nbc, num_frames, num_frames, decibels, (uint4*)out16, lo_plane);
-    } else {
-        hipLaunchKernelGGL(cqt_scale_kernel, dim3(8, batch * p->n_harm), dim3(256), 0, s, (const float*)mag, refs, p->n_bins, num_frames, num_frames,
-                           decibels, out);
-    }
-    AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+    return scale_launch(fn, p, mag, refs, batch, num_frames, num_frames, decibels, out, out16, lo_plane, s);
 }
 
 }  // namespace
@@ -916,7 +949,7 @@ extern "C" int amtx_cqt_track_layout(const amtx_cqt_plan* p, int64_t num_samples
     AMTX_REQUIRE(num_samples > 0, "amtx_cqt_track_layout: bad num_samples");
     const int nl = (int)p->levels.size();
     const CqtDims d = dims(p, 1, num_samples);
-    if (nl > 16 || !basis_windowed(p, d.len, d.t_buf)) {
+    if (nl > 16 || !basis_route(p, &d, d.t_buf, 1).windowed) {
         amtx_set_error("amtx_cqt_track_layout: no clip form: the windowed basis kernel does not cover this plan (n_fft 128 or 256 on every level; "
                        "or a pyramid level of these %lld samples has fewer than 4)", (long long)num_samples);
         return AMTX_ERR_UNSUPPORTED;
@@ -964,46 +997,31 @@ extern "C" int amtx_cqt_pyramid_build(const amtx_cqt_plan* p, const float* audio
             pyr_end = lv[0] + lv[2];
         }
     }
-    int rc = clips_check("amtx_cqt_pyramid_build", p, num_tracks, rows_max);
+    BasisRoute route;
+    int rc = clips_check("amtx_cqt_pyramid_build", p, num_tracks, rows_max, route);
     if (rc != AMTX_OK) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    const int zero_pads = p->lib09 ? 0 : 1;
+    const bool zero_pads = !p->lib09;
     AMTX_CHECK_HIP(hipMemsetAsync(maxima, 0, sizeof(float) * num_tracks * p->n_harm, s));
-    // the chain of amtx_cqt_forward on every track as a batch of one: the level signals are the whole-track forward's
+    // the chain of amtx_cqt_forward on every track as a batch of one: the level signals are the whole-track forward's.  Zero pads: level 0 is
+    // always the audio in place (a bank has no level-0 storage) and the maxima were reset above
     for (int t = 0; t < num_tracks; ++t) {
         const int64_t* tr = tracks_host + (int64_t)t * cols;
-        const float* src = audio + tr[0];
-        for (int l = 0; l < nl; ++l) {
-            const int64_t* lv = tr + 4 + 3 * l;
-            float* pyr = pyramid + lv[0];
-            if (l == 0) {
-                if (zero_pads) continue;
-                const unsigned nb = (unsigned)std::min<int64_t>((tr[1] + 255) / 256, 4096);
-                hipLaunchKernelGGL(cqt_level0_kernel, dim3(nb, 1), dim3(256), 0, s, src, tr[1], tr[1], pyr, lv[2], p->pad, 0, maxima + (int64_t)t * p->n_harm,
-                                   p->n_harm);
-            } else {
-                const bool from_audio = zero_pads && l == 1;
-                rc = amtx_launch_cqt_decimate(from_audio ? src : (const float*)(pyramid + lv[-3]), lv[-2], from_audio ? tr[1] : lv[-1], from_audio ? 0 : p->pad,
-                                              pyr, lv[1], lv[2], p->pad, p->d_tfrag, zero_pads, (float*)nullptr, p->n_harm, 1, s);
-                if (rc != AMTX_OK) return rc;
-            }
-            AMTX_CHECK_LAUNCH();
-            if (!zero_pads) {
-                hipLaunchKernelGGL(cqt_pad_kernel, dim3(8, 1), dim3(256), 0, s, pyr, lv[1], lv[2], p->pad, p->lib09);
-                AMTX_CHECK_LAUNCH();
-            }
-        }
+        rc = pyramid_chain(p, audio + tr[0], tr[1], tr[1], 1, zero_pads, zero_pads ? (float*)nullptr : maxima + (int64_t)t * p->n_harm,
+                           [&](int l) { return PyrLevel{pyramid + tr[4 + 3 * l], tr[4 + 3 * l + 1], tr[4 + 3 * l + 2]}; }, s);
+        if (rc != AMTX_OK) return rc;
     }
     // every track whole, no map: the maxima of each harmonic over its own rows
-    return clips_basis(p, audio, pyramid, tracks, nullptr, num_tracks, rows_max, nullptr, maxima, s);
+    return clips_basis(p, route, audio, pyramid, tracks, nullptr, num_tracks, rows_max, nullptr, maxima, s);
 }
 
 extern "C" int amtx_cqt_power_clips(const amtx_cqt_plan* p, const float* audio, const float* pyramid, const int64_t* tracks, const int64_t* desc,
                                     int batch, int64_t num_frames, float* power, void* stream_) {
     AMTX_REQUIRE(p && audio && pyramid && tracks && desc && power, "amtx_cqt_power_clips: null argument");
-    const int rc = clips_check("amtx_cqt_power_clips", p, batch, num_frames);
+    BasisRoute route;
+    const int rc = clips_check("amtx_cqt_power_clips", p, batch, num_frames, route);
     if (rc != AMTX_OK) return rc;
-    return clips_basis(p, audio, pyramid, tracks, desc, batch, num_frames, power, nullptr, (hipStream_t)stream_);
+    return clips_basis(p, route, audio, pyramid, tracks, desc, batch, num_frames, power, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" size_t amtx_cqt_clips_workspace_bytes(const amtx_cqt_plan* p, int batch, int64_t num_frames) {

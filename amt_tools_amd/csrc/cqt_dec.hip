@@ -364,29 +364,61 @@ __global__ __launch_bounds__(512, 1) void cqt_decimate2_kernel(const float* __re
 #endif
 }
 
+// The file's A/B and tuning switches, read once per process
+struct DecSwitches {
+    bool v1;        // AMTX_CQT_DECIM_V1: round 4's decimator
+    int blocks;     // AMTX_CQT_DECIM_BLOCKS: persistent blocks of cqt_decimate2_kernel, default 256 (one per CU); clamped to [1, 1024], and
+                    // anything that does not parse as such keeps the default
+};
+const DecSwitches& dec_switches() {
+    static const DecSwitches sw = [] {
+        DecSwitches v{getenv("AMTX_CQT_DECIM_V1") != nullptr, 256};
+        const char* e = getenv("AMTX_CQT_DECIM_BLOCKS");
+        if (e && *e) {
+            char* end = nullptr;
+            const long b = strtol(e, &end, 10);
+            if (end && *end == 0 && b >= 1 && b <= 1024) v.blocks = (int)b;
+        }
+        return v;
+    }();
+    return sw;
+}
+
+// Which decimator a level of n_in -> n_out samples of `batch` clips runs, and in which geometry.  Pure: sizes and switches in, a launch out.
+enum class DecKernel { V2, V1 };
+struct DecRoute {
+    DecKernel kernel;
+    dim3 grid;
+    unsigned block;
+    size_t lds;
+    int nb2, ntiles;      // V2: tiles per clip, tiles of the launch
+};
+DecRoute dec_route(int64_t n_in, int64_t n_out, int batch, const DecSwitches& sw) {
+    DecRoute r{};
+    const int64_t nb2 = (n_out + DEC2_MCH - 1) / DEC2_MCH;
+    if (!sw.v1 && nb2 * batch < (1ll << 30) && n_in < (1ll << 30) - DEC2_MXS) {
+        r.kernel = DecKernel::V2;
+        r.nb2 = (int)nb2; r.ntiles = (int)(nb2 * batch);
+        r.grid = dim3((unsigned)std::min(r.ntiles, sw.blocks)); r.block = 512; r.lds = DEC2_LDS;
+    } else {
+        r.kernel = DecKernel::V1;
+        r.grid = dim3((unsigned)((n_out + DEC_MCH - 1) / DEC_MCH), batch); r.block = 256; r.lds = 0;
+    }
+    return r;
+}
+
 }  // namespace
 
 int amtx_launch_cqt_decimate(const float* in, int64_t n_in, int64_t in_stride, int in_pad, float* out, int64_t n_out, int64_t out_stride, int pad,
                              const void* tfrag, int zero_pads, float* maxbuf, int n_harm, int batch, hipStream_t s) {
     AMTX_REQUIRE(in && out && tfrag && n_in >= 1 && n_out >= 1 && batch >= 1 && batch < 65536 && n_harm <= 256, "cqt decimator: bad arguments");
-    static const bool decim_v1 = getenv("AMTX_CQT_DECIM_V1") != nullptr;     // A/B switch: round 4's decimator
-    const int64_t nb2 = (n_out + DEC2_MCH - 1) / DEC2_MCH;
-    if (!decim_v1 && nb2 * batch < (1ll << 30) && n_in < (1ll << 30) - DEC2_MXS) {
-        const int ntiles = (int)(nb2 * batch);
-        // one persistent block per CU; the tuning switch is clamped to [1, 1024] and anything that does not parse as such keeps the default
-        static const int dec_blocks = [] {
-            const char* e = getenv("AMTX_CQT_DECIM_BLOCKS");
-            if (!e || !*e) return 256;
-            char* end = nullptr;
-            const long v = strtol(e, &end, 10);
-            return (end && *end == 0 && v >= 1 && v <= 1024) ? (int)v : 256;
-        }();
-        AMTX_GRANT_LDS(cqt_decimate2_kernel, DEC2_LDS);
-        hipLaunchKernelGGL(cqt_decimate2_kernel, dim3((unsigned)std::min(ntiles, dec_blocks)), dim3(512), DEC2_LDS, s, in, n_in, in_stride, in_pad, out, n_out,
-                           out_stride, pad, (const uint4*)tfrag, zero_pads, maxbuf, n_harm, (int)nb2, ntiles);
+    const DecRoute r = dec_route(n_in, n_out, batch, dec_switches());
+    if (r.kernel == DecKernel::V2) {
+        AMTX_GRANT_LDS(cqt_decimate2_kernel, r.lds);
+        hipLaunchKernelGGL(cqt_decimate2_kernel, r.grid, dim3(r.block), r.lds, s, in, n_in, in_stride, in_pad, out, n_out, out_stride, pad, (const uint4*)tfrag,
+                           zero_pads, maxbuf, n_harm, r.nb2, r.ntiles);
     } else {
-        const unsigned nb = (unsigned)((n_out + DEC_MCH - 1) / DEC_MCH);
-        hipLaunchKernelGGL(cqt_decimate_mfma_kernel, dim3(nb, batch), dim3(256), 0, s, in, n_in, in_stride, in_pad, out, n_out, out_stride, pad,
+        hipLaunchKernelGGL(cqt_decimate_mfma_kernel, r.grid, dim3(r.block), r.lds, s, in, n_in, in_stride, in_pad, out, n_out, out_stride, pad,
                            (const uint4*)tfrag, zero_pads, maxbuf, n_harm);
     }
     AMTX_CHECK_LAUNCH();

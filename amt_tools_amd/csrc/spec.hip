@@ -1022,60 +1022,94 @@ extern "C" int amtx_spec_filterbank(const amtx_spec_plan* plan, float* host_out)
     return AMTX_OK;
 }
 
-// K1 launch for either source of the clips' headers (EqualClips / ClipTable): the power-of-two kernel for n_fft != 2048, the ring kernel
-// for the BASELINE log-mel shape, the general kernel otherwise.  T = rows per clip; `what` names the entry point in messages.
+// The file's A/B switch, read once per process.  AMTX_SPEC_NATURAL_ROWS is not here: it shapes the mel tables, so build_mel_tables
+// reads it where a plan (or amtx_spec_mel_layout) is made.
+struct SpecSwitches {
+    bool no_ring;      // AMTX_SPEC_NO_RING: the general kernel for the BASELINE log-mel shape too (A/B and the bit-equality test)
+};
+static const SpecSwitches& spec_switches() {
+    static const SpecSwitches sw{getenv("AMTX_SPEC_NO_RING") != nullptr};
+    return sw;
+}
+
+// Which K1 instantiation a call runs and in which geometry.  Pure: the plan's host fields, the sizes and the switches in; no
+// device pointer is dereferenced, nothing launched, no environment read.
+enum class SpecKernel { POW2, RING, GENERAL_MEL_LDS, GENERAL_MEL, GENERAL_STFT };
+struct SpecRoute {
+    int rc;                   // AMTX_OK, or the refusal's code with its text (the launcher puts the entry point's name in front)
+    const char* refusal;
+    SpecKernel kernel;
+    int log2m, fpw, has_mel;  // geometry arguments of POW2
+    unsigned grid;            // blocks of 256 threads
+    size_t lds;
+};
+constexpr int SPEC_FPW = 8;   // frames per wave of every instantiation
+
+// the BASELINE log-mel shape: hop 512 and four mel rounds of 4 / 8 / 20 / 32 tap slots (= librosa's 229 Slaney rows at 22.05 kHz), the one
+// layout spec_power_ring_kernel<.., 4, 8, 20, 32, ..> holds in registers
+static bool ring_shape(const amtx_spec_plan& plan) {
+    const SpecDev& dv = plan.dev;
+    return plan.n_fft == NFFT && plan.hop == RING_HOP && (plan.n_mels + 63) / 64 == 4 && dv.round_max[0] == 4 && dv.round_max[1] == 8 &&
+           dv.round_max[2] == 20 && dv.round_max[3] == 32 && dv.round_off[1] == 4 && dv.round_off[2] == 12 && dv.round_off[3] == 32;
+}
+
+static SpecRoute spec_route(const amtx_spec_plan& plan, int batch, int64_t T, const SpecSwitches& sw) {
+    SpecRoute r{};
+    r.fpw = SPEC_FPW; r.has_mel = plan.n_mels > 0 ? 1 : 0;
+    const int64_t chunks = (T + SPEC_FPW * WAVES - 1) / (SPEC_FPW * WAVES);
+    if (chunks * batch >= (1ll << 31)) { r.rc = AMTX_ERR_ARG; r.refusal = "grid too large"; return r; }
+    r.grid = (unsigned)(chunks * batch);
+    if (plan.n_fft != NFFT) {
+        while ((2 << r.log2m) < plan.n_fft) ++r.log2m;
+        const int m = plan.n_fft / 2;
+        r.kernel = SpecKernel::POW2;
+        r.lds = (size_t)WAVES * m * sizeof(float2) + (size_t)WAVES * (m + 1 + 128 + 3) * sizeof(float);
+        return r;
+    }
+    // what the ring and the general kernel share: the waves' FFT and power buffers and the twiddles
+    const size_t lds_fft = WAVES * XB_ELEMS * sizeof(float2) + WAVES * PB_ELEMS * sizeof(float) + (M / 2 + 64) * sizeof(float2);
+    if (!sw.no_ring && ring_shape(plan)) {       // clip ring in LDS + mel weights in registers
+        r.kernel = SpecKernel::RING;
+        r.lds = lds_fft + 64 * 4 * sizeof(int) + RING_ELEMS * sizeof(float);
+        return r;
+    }
+    const int mel_rounds = (plan.n_mels + 63) / 64;
+    const int mel_slots = mel_rounds > 0 ? plan.dev.round_off[mel_rounds - 1] + plan.dev.round_max[mel_rounds - 1] : 0;
+    const bool mel_lds = mel_rounds > 0 && mel_slots <= MEL_LDS_MAX_SLOTS;
+    r.kernel = mel_lds ? SpecKernel::GENERAL_MEL_LDS : r.has_mel ? SpecKernel::GENERAL_MEL : SpecKernel::GENERAL_STFT;
+    r.lds = lds_fft + 2 * 64 * MAX_MEL_ROUNDS * sizeof(int) + (mel_lds ? (size_t)mel_slots * 64 * sizeof(float) : 0);
+    return r;
+}
+
+// K1 launch for either source of the clips' headers (EqualClips / ClipTable): clear the maxima, route, bind the instantiation for SRC.
+// T = rows per clip; `what` names the entry point in messages.
 template <class SRC>
 static int spec_power_launch(const amtx_spec_plan* plan, const float* audio, SRC src, int batch, int64_t T, float* power, float* clip_max,
                              hipStream_t stream, const char* what) {
     AMTX_CHECK_HIP(hipMemsetAsync(clip_max, 0, sizeof(float) * batch, stream));
-    if (plan->n_fft != NFFT) {
-        int log2m = 0;
-        while ((2 << log2m) < plan->n_fft) ++log2m;
-        const int m = plan->n_fft / 2, fpw = 8;
-        const int64_t chunks_g = (T + fpw * WAVES - 1) / (fpw * WAVES);
-        const int64_t nblocks_g = chunks_g * batch;
-        AMTX_REQUIRE(nblocks_g < (1ll << 31), "%s: grid too large", what);
-        const size_t lds_g = (size_t)WAVES * m * sizeof(float2) + (size_t)WAVES * (m + 1 + 128 + 3) * sizeof(float);
-        auto kern = spec_power_pow2_kernel<SRC>;
-        AMTX_GRANT_LDS(kern, lds_g);
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks_g), dim3(256), lds_g, stream, plan->dev, log2m, fpw, audio, src, T, power,
-                           (unsigned*)clip_max, plan->n_mels > 0 ? 1 : 0);
-        AMTX_CHECK_LAUNCH();
-        return AMTX_OK;
+    const SpecRoute r = spec_route(*plan, batch, T, spec_switches());
+    if (r.rc != AMTX_OK) {
+        amtx_set_error("%s: %s", what, r.refusal);
+        return r.rc;
     }
-    constexpr int FPW = 8;
-    constexpr int FPB = FPW * WAVES;
-    const int64_t chunks = (T + FPB - 1) / FPB;
-    const int64_t nblocks = chunks * batch;
-    AMTX_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", what);
-    const int mel_rounds = plan->n_mels > 0 ? (plan->n_mels + 63) / 64 : 0;
-    const int mel_slots = mel_rounds > 0 ? plan->dev.round_off[mel_rounds - 1] + plan->dev.round_max[mel_rounds - 1] : 0;
-    const bool mel_lds = mel_rounds > 0 && mel_slots <= MEL_LDS_MAX_SLOTS;
-    const size_t lds = WAVES * XB_ELEMS * sizeof(float2) + WAVES * PB_ELEMS * sizeof(float) + (M / 2 + 64) * sizeof(float2) +
-                       2 * 64 * MAX_MEL_ROUNDS * sizeof(int) + (mel_lds ? (size_t)mel_slots * 64 * sizeof(float) : 0);
     auto launch = [&](auto kern) -> int {
-        AMTX_GRANT_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds, stream, plan->dev, audio, src, T, power, (unsigned*)clip_max);
+        AMTX_GRANT_LDS(kern, r.lds);
+        hipLaunchKernelGGL(kern, dim3(r.grid), dim3(256), r.lds, stream, plan->dev, audio, src, T, power, (unsigned*)clip_max);
         return AMTX_OK;
     };
-    // the BASELINE log-mel shape (hop 512, four mel rounds of 4 / 8 / 20 / 32 tap slots = librosa's 229 Slaney rows at 22.05 kHz) has its own
-    // kernel: clip ring in LDS + mel weights in registers; AMTX_SPEC_NO_RING=1 keeps the general kernel (A/B and the bit-equality test)
-    static const bool no_ring = getenv("AMTX_SPEC_NO_RING") != nullptr;
-    const auto& dv = plan->dev;
-    if (!no_ring && plan->hop == RING_HOP && mel_rounds == 4 && dv.round_max[0] == 4 && dv.round_max[1] == 8 && dv.round_max[2] == 20 &&
-        dv.round_max[3] == 32 && dv.round_off[1] == 4 && dv.round_off[2] == 12 && dv.round_off[3] == 32) {
-        auto kern = spec_power_ring_kernel<FPW, 4, 8, 20, 32, SRC>;
-        const size_t lds_r = WAVES * XB_ELEMS * sizeof(float2) + WAVES * PB_ELEMS * sizeof(float) + (M / 2 + 64) * sizeof(float2) +
-                             64 * 4 * sizeof(int) + RING_ELEMS * sizeof(float);
-        AMTX_GRANT_LDS(kern, lds_r);
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_r, stream, plan->dev, audio, src, T, power, (unsigned*)clip_max);
-        AMTX_CHECK_LAUNCH();
-        return AMTX_OK;
+    int rc = AMTX_OK;
+    switch (r.kernel) {
+    case SpecKernel::POW2: {
+        auto kern = spec_power_pow2_kernel<SRC>;
+        AMTX_GRANT_LDS(kern, r.lds);
+        hipLaunchKernelGGL(kern, dim3(r.grid), dim3(256), r.lds, stream, plan->dev, r.log2m, r.fpw, audio, src, T, power, (unsigned*)clip_max, r.has_mel);
+        break;
     }
-    int rc;
-    if (mel_lds) rc = launch(spec_power_kernel<FPW, true, true, SRC>);
-    else if (plan->n_mels > 0) rc = launch(spec_power_kernel<FPW, true, false, SRC>);
-    else rc = launch(spec_power_kernel<FPW, false, false, SRC>);
+    case SpecKernel::RING: rc = launch(spec_power_ring_kernel<SPEC_FPW, 4, 8, 20, 32, SRC>); break;
+    case SpecKernel::GENERAL_MEL_LDS: rc = launch(spec_power_kernel<SPEC_FPW, true, true, SRC>); break;
+    case SpecKernel::GENERAL_MEL: rc = launch(spec_power_kernel<SPEC_FPW, true, false, SRC>); break;
+    case SpecKernel::GENERAL_STFT: rc = launch(spec_power_kernel<SPEC_FPW, false, false, SRC>); break;
+    }
     if (rc != AMTX_OK) return rc;
     AMTX_CHECK_LAUNCH();
     return AMTX_OK;

@@ -231,7 +231,9 @@ def level_lengths(n, n_levels):
 def expected_route(cfg, n):
     """'windowed128' | 'windowed256' | 'windowed128+256' | 'gemm:<reason>': the conditions of cqt_forward_impl, by hand.  Windowed needs at
     most 10 levels and 16 harmonics and, on EVERY level that holds banks: n_fft 128 or 256, at most 256 columns, a power-of-two hop in
-    4 .. 512, and at least 4 samples of signal."""
+    4 .. 512, and at least 4 samples of signal.  The independent statement of cqt.hip's basis_route: tests/test_gpu_cqt_edges.py holds the
+    kernels the profiler sees to it, and tests/golden/frontend_trace.json (tests/test_frontend_trace.py), recorded before basis_route
+    existed, holds the library's own decision for the same plans and lengths, launch by launch."""
     levels, n_levels, _ = plan_layout(cfg)
     lens = level_lengths(n, n_levels)
     if n_levels > 10 or len(cfg['harmonics']) > 16:

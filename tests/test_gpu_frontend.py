@@ -255,3 +255,51 @@ def test_ring_kernel_returns_the_bits_of_the_general_kernel(tmp_path, lv):
     for k in ring.files:
         np.testing.assert_array_equal(ring[k], general[k])
     assert ring['arr_0'].shape == (5, 625, 229) and ring['arr_0'].max() > 0
+
+
+# (module, the case of tests/golden/frontend_trace.json that names its kernel): the five routes of spec.hip's spec_route
+SPEC_ROUTES = {
+    'ring': (lambda M, S: M(sample_rate=22050, hop_length=512, n_mels=229, n_fft=2048), '22050 2048 512 229 1 0'),
+    'general_mel_lds': (lambda M, S: M(sample_rate=22050, hop_length=512, n_mels=128, n_fft=2048), '22050 2048 512 128 1 0'),
+    'general_mel': (lambda M, S: M(sample_rate=22050, hop_length=512, n_mels=64, n_fft=2048), '22050 2048 512 64 1 0'),
+    'general_stft': (lambda M, S: S(sample_rate=22050, hop_length=512, n_fft=2048), '22050 2048 512 0 1 0'),
+    'pow2': (lambda M, S: M(sample_rate=16000, hop_length=256, n_mels=80, n_fft=1024), '16000 1024 256 80 1 0'),
+}
+
+
+@pytest.mark.parametrize('route', sorted(SPEC_ROUTES))
+def test_each_call_launches_the_one_kernel_of_the_recorded_trace(route):
+    """process_batch (equal clips) and process_clips of a TrackBank of the same plan (clip table) each launch exactly one spec_power* kernel:
+    the instantiation -- template arguments and source type -- the host trace recorded for that plan (tests/test_frontend_trace.py)."""
+    import json
+    import re
+    import sys
+    from amt_tools_amd.tracks import TrackBank
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'san'))
+    import frontend_trace
+    make, plan = SPEC_ROUTES[route]
+    mod = make(*_mods())
+    n_fft, hop = int(plan.split()[1]), int(plan.split()[2])
+    n = 2 * n_fft + 3 * hop + 7
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'frontend_trace.json')) as f:
+        golden = json.load(f)
+    assert golden['cases_sha256'] == frontend_trace.cases_sha256()
+    cases, recorded_run = frontend_trace.cases(), frontend_trace.expand(golden)['']
+
+    def recorded(entry, x):                # the kernel of the run without a switch, as 'spec_power..._kernel<...>'
+        _, _, (launch,) = recorded_run[cases.index('spec %s %s 2 %d' % (entry, plan, x))]
+        return re.search(r'spec_power\w*_kernel<[^>]*>', launch).group(0)
+    tracks = [synth_clip(20 + i, num_samples=n) for i in range(2)]
+    audio = torch.from_numpy(np.stack(tracks)).to('cuda:0')
+    bank = TrackBank(tracks, mod, 'cuda:0')
+    clips = bank.clips([0, 1], [0, 0], 1 + n // hop)
+    for name, run, want in (('process_batch', lambda: mod.process_batch(audio), recorded('power', 512 * 9)),
+                            ('process_clips', lambda: mod.process_clips(clips), recorded('power_clips', 1 + 512 * 9 // hop))):
+        run()                                                         # plan creation, the bank's upload and the LDS grant stay out of the profile
+        torch.cuda.synchronize()
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            run()
+            torch.cuda.synchronize()
+        ran = [(m.group(0), e.count) for e in prof.key_averages() for m in [re.search(r'spec_power\w*_kernel<[^>]*>', e.key)] if m]
+        print(f'SPECROUTE {route} {name}: {ran}')
+        assert ran == [(want, 1)], (route, name, want, [e.key for e in prof.key_averages()])
