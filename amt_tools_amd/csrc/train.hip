@@ -795,105 +795,174 @@ __global__ __launch_bounds__(256) void conv_w_permute_kernel(const float* in, fl
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int launch_xgemm(XArgs g, int splits, hipStream_t stream) {
-    AMTX_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "matmul: empty problem");
-    const int bn = g.N <= 32 ? 32 : g.N <= 64 ? 64 : 128;
-    const int64_t ksteps = (g.K + XBK - 1) / XBK;
-    splits = (int)std::max<int64_t>(1, std::min<int64_t>(splits, ksteps));
-    g.kchunk = (ksteps + splits - 1) / splits * XBK;
-    splits = (int)((g.K + g.kchunk - 1) / g.kchunk);
-    const int64_t gm = (g.M + XBM - 1) / XBM, gn = (g.N + bn - 1) / bn;
-    AMTX_REQUIRE(gm < (1ll << 31) && gn < 65536 && splits < 65536, "matmul: grid too large");
-    dim3 grid((unsigned)gm, (unsigned)gn, (unsigned)splits);
-    if (bn == 32) hipLaunchKernelGGL(xgemm_kernel<32>, grid, dim3(256), 0, stream, g);
-    else if (bn == 64) hipLaunchKernelGGL(xgemm_kernel<64>, grid, dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL(xgemm_kernel<128>, grid, dim3(256), 0, stream, g);
-    AMTX_CHECK_LAUNCH();
-    return splits;
+// ---------------------------------------------------------------------------------------------------------------------------
+// Host side: checks -> route -> launch.  A route is a function of the arguments alone: it dereferences nothing, launches
+// nothing and reads no environment, and answers a refusal (its error text) or everything its launch site needs.  The workspace queries are the
+// same routes' answers.
+
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// C[M][N] over a contraction of K: the column tile width, the contraction splits and the grid
+struct XgemmRoute {
+    const char* error = nullptr;      // a refusal: amtx_last_error's text, with AMTX_ERR_ARG
+    int bn = 0;              // xgemm_kernel<bn>
+    int64_t gm = 0, gn = 0;  // grid x, y
+    int splits = 0;          // grid z
+    int64_t kchunk = 0;      // contraction elements per split (a multiple of 32)
+    bool reduce = false;     // the splits write partial tiles to the workspace, xreduce_kernel sums them (and adds the bias)
+    size_t ws_bytes = 0;     // what the partial tiles of the split count this problem would like take: amtx_matmul_workspace_bytes
+};
+XgemmRoute xgemm_route(int64_t M, int64_t N, int64_t K, int64_t ldc, bool has_ws, size_t ws_bytes) {
+    XgemmRoute r;
+    if (!(M > 0 && N > 0 && K > 0)) r.error = "matmul: empty problem";
+    if (r.error) return r;      // before tiles are counted: the workspace query of an empty problem answers 0
+    r.bn = N <= 32 ? 32 : N <= 64 ? 64 : 128;
+    r.gm = ceil_div(M, XBM), r.gn = ceil_div(N, r.bn);
+    const int64_t tiles = r.gm * r.gn, ksteps = ceil_div(K, XBK);
+    // splits: enough blocks to fill the chip when the output has few tiles, at least 16 k-steps per split.  ~4 blocks per CU: a block is
+    // latency-bound (two barriers and a dependent load per 32-deep step), co-resident blocks overlap
+    int64_t splits = 1;
+    if (tiles < 192 && ksteps >= 32) splits = std::max<int64_t>(1, std::min<int64_t>(ceil_div(1024, tiles), ksteps / 16));
+    if (splits > 1) r.ws_bytes = (size_t)splits * M * N * sizeof(float);
+    r.reduce = splits > 1 && ldc == N && has_ws && ws_bytes >= r.ws_bytes;      // else one launch straight into C
+    if (!r.reduce) splits = 1;
+    r.kchunk = ceil_div(ksteps, splits) * XBK;
+    r.splits = (int)ceil_div(K, r.kchunk);                                      // no empty split: whole k-steps, dealt evenly
+    if (!(r.gm < (1ll << 31) && r.gn < 65536 && r.splits < 65536)) r.error = "matmul: grid too large";
+    return r;
 }
 
-// number of contraction splits: enough blocks to fill the chip when the output has few tiles, at least 8 k-steps per split
-int pick_splits(int64_t M, int64_t N, int64_t K) {
-    const int bn = N <= 32 ? 32 : N <= 64 ? 64 : 128;
-    const int64_t tiles = ((M + XBM - 1) / XBM) * ((N + bn - 1) / bn);
-    const int64_t ksteps = (K + XBK - 1) / XBK;
-    if (tiles >= 192 || ksteps < 32) return 1;
-    // ~4 blocks per CU: a block is latency-bound (two barriers and a dependent load per 32-deep step), co-resident blocks overlap
-    return (int)std::max<int64_t>(1, std::min<int64_t>((1024 + tiles - 1) / tiles, ksteps / 16));
+// column sums of a (rows x ncols) matrix with leading dimension ld
+size_t colsum_flat_bytes(int ncols) { return (size_t)256 * ncols * sizeof(float); }      // the flat kernel's partials: [256 blocks][ncols]
+struct ColsumRoute {
+    enum Kind { FLAT, SPLIT, DIRECT } kind;      // xcolsum_flat_kernel + reduce | xcolsum_kernel over row groups + reduce | xcolsum_kernel into `out`
+    int groups;                                  // partial rows in the workspace (FLAT: blocks)
+    int64_t rows_per_group;
+};
+ColsumRoute colsum_route(int64_t ld, int64_t rows, int ncols, bool aligned, size_t ws_bytes) {
+    if (ld == ncols && 1024 % ncols == 0 && rows * ncols >= (1 << 16) && aligned && ws_bytes >= colsum_flat_bytes(ncols)) return {ColsumRoute::FLAT, 256, 0};
+    int groups = (int)std::max<int64_t>(1, std::min<int64_t>(256, rows / 256));
+    while (groups > 1 && (size_t)groups * ncols * sizeof(float) > ws_bytes) groups /= 2;
+    return {groups > 1 ? ColsumRoute::SPLIT : ColsumRoute::DIRECT, groups, ceil_div(rows, groups)};
+}
+
+// Conv2d forward / input gradient, C channels in and N out: the strip kernel (xconv_kernel) where it applies, else the generic implicit GEMM
+size_t xconv_image_bytes(int bn, int C) { return (size_t)2 * bn * (18 * C + 16); }      // xconv_wprep_kernel's image: [hi, lo][bn][9 C bf16 + 16 bytes]
+struct XconvRoute {
+    bool strip;
+    int bn, ns;              // xconv_kernel<bn, ns>
+    size_t lds;
+    int64_t blocks;
+};
+XconvRoute xconv_route(int64_t positions, int C, int N, size_t img_bytes) {
+    XconvRoute r{};
+    r.bn = N <= 32 ? 32 : 64;
+    r.ns = C == 32 ? 5 : 9;
+    const size_t image = xconv_image_bytes(r.bn, C);
+    r.lds = image + (size_t)4 * (XBM + 2) * (2 * C + 16);       // + two buffers of hi / lo strips
+    // bn 64 with C 64 would take 224 384 bytes: it runs on the generic kernel, and no xconv_kernel<64, 9> is built
+    r.strip = C % 32 == 0 && C <= 64 && N <= 64 && r.lds <= 156 * 1024 && img_bytes >= image;
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / r.lds));
+    r.blocks = std::min<int64_t>(ceil_div(positions, XBM), 256 * per_cu);
+    return r;
+}
+
+// Conv2d weight gradient: the register-resident kernel (xwgrad_kernel) where it applies, else the generic implicit GEMM
+constexpr int WG_MAX_BLOCKS = 768;
+size_t xwgrad_partial_bytes(int64_t blocks, int c_out) { return (size_t)blocks * 288 * c_out * sizeof(float); }      // [blocks][288][c_out]
+struct XwgradRoute {
+    bool resident;
+    int nt, blocks;              // xwgrad_kernel<nt>, the blocks used: none without a step
+    int64_t steps_per_block;     // 32-position steps per block
+};
+XwgradRoute xwgrad_route(int64_t positions, int c_in, int c_out, size_t rest_bytes) {
+    XwgradRoute r{};
+    const int64_t nsteps = ceil_div(positions, 32), most = std::min<int64_t>(WG_MAX_BLOCKS, nsteps);
+    r.resident = c_in == WG_C && (c_out == 32 || c_out == 64) && rest_bytes >= xwgrad_partial_bytes(most, c_out);
+    if (!r.resident) return r;
+    r.nt = c_out / 16;
+    r.steps_per_block = ceil_div(nsteps, most);
+    r.blocks = (int)ceil_div(nsteps, r.steps_per_block);
+    return r;
+}
+
+// The convolution workspace: [wt | gt | rest].  wt: the permuted weights; gt: the [(tap, ci)][co] weight gradient; rest: the strip kernel's
+// weight image, then (stream-ordered) the weight gradient's partials, then the column sum's.
+struct ConvWs {
+    float *wt, *gt;
+    void* rest;
+    size_t rest_bytes;       // 0 where the workspace ends inside wt / gt (the forward asks for wt alone)
+    static size_t w_bytes(int c_in, int c_out) { return ((size_t)9 * c_in * c_out * sizeof(float) + 255) / 256 * 256; }
+    static size_t need(int64_t positions, int c_in, int c_out) {
+        const size_t split = xgemm_route((int64_t)9 * c_in, c_out, positions, c_out, false, 0).ws_bytes;
+        const size_t image = std::max(xconv_image_bytes(64, std::max(c_in, c_out)), xwgrad_partial_bytes(WG_MAX_BLOCKS, c_out));
+        return 2 * w_bytes(c_in, c_out) + std::max(std::max(split, colsum_flat_bytes(c_out)), image) + 256;
+    }
+    ConvWs(void* ws, size_t bytes, int c_in, int c_out) {
+        char* p = static_cast<char*>(ws);
+        const size_t w = w_bytes(c_in, c_out);
+        wt = reinterpret_cast<float*>(p), gt = reinterpret_cast<float*>(p + w), rest = p + 2 * w;
+        rest_bytes = bytes > 2 * w ? bytes - 2 * w : 0;
+    }
+};
+
+// ---- launches: one binder per kernel family names the instantiation from the route's answer
+int launch_xreduce(const float* partial, int splits, int64_t count, const float* bias, int ncols, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(xreduce_kernel, dim3((unsigned)ceil_div(count, 64)), dim3(256), 0, stream, partial, splits, count, count, bias, ncols, out);
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
 }
 
 // C = op(A) op(B)^T through (optional) split partials in `ws`
 int matmul(const XOp& A, const XOp& B, const float* bias, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes,
            hipStream_t stream) {
-    XArgs g{};
-    g.A = A; g.B = B; g.M = M; g.N = N; g.K = K;
-    int splits = pick_splits(M, N, K);
-    if (splits > 1 && (ldc != N || !ws || ws_bytes < (size_t)splits * M * N * sizeof(float))) splits = 1;
-    if (splits == 1) {
-        g.bias = bias; g.C = C; g.ldc = ldc; g.c_split_stride = 0;
-        const int rc = launch_xgemm(g, 1, stream);
-        return rc < 0 ? rc : AMTX_OK;
-    }
-    g.bias = nullptr; g.C = static_cast<float*>(ws); g.ldc = N; g.c_split_stride = M * N;
-    const int used = launch_xgemm(g, splits, stream);
-    if (used < 0) return used;
-    const int64_t count = M * N;
-    hipLaunchKernelGGL(xreduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, stream, (const float*)ws, used, count, count, bias, (int)N, C);
+    const XgemmRoute r = xgemm_route(M, N, K, ldc, ws != nullptr, ws_bytes);
+    AMTX_REQUIRE(!r.error, "%s", r.error);
+    XArgs g{A, B, bias, C, ldc, M, N, K, r.kchunk, 0};
+    if (r.reduce) { g.bias = nullptr; g.C = static_cast<float*>(ws); g.ldc = N; g.c_split_stride = M * N; }
+    const dim3 grid((unsigned)r.gm, (unsigned)r.gn, (unsigned)r.splits);
+    if (r.bn == 32) hipLaunchKernelGGL(xgemm_kernel<32>, grid, dim3(256), 0, stream, g);
+    else if (r.bn == 64) hipLaunchKernelGGL(xgemm_kernel<64>, grid, dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL(xgemm_kernel<128>, grid, dim3(256), 0, stream, g);
     AMTX_CHECK_LAUNCH();
-    return AMTX_OK;
+    return r.reduce ? launch_xreduce(g.C, r.splits, M * N, bias, (int)N, C, stream) : AMTX_OK;
 }
 
 int colsum(const float* x, int64_t ld, int64_t rows, int ncols, float* out, void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (ld == ncols && 1024 % ncols == 0 && rows * ncols >= (1 << 16) && aligned16(x) && ws && ws_bytes >= (size_t)256 * ncols * sizeof(float)) {
-        const int blocks = 256;
-        hipLaunchKernelGGL(xcolsum_flat_kernel, dim3(blocks), dim3(256), 0, stream, x, rows * ncols, ncols, static_cast<float*>(ws));
-        AMTX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(xreduce_kernel, dim3((unsigned)((ncols + 63) / 64)), dim3(256), 0, stream, (const float*)ws, blocks, (int64_t)ncols, (int64_t)ncols,
-                           (const float*)nullptr, ncols, out);
-        AMTX_CHECK_LAUNCH();
-        return AMTX_OK;
-    }
-    int splits = (int)std::max<int64_t>(1, std::min<int64_t>(256, rows / 256));
-    while (splits > 1 && (size_t)splits * ncols * sizeof(float) > ws_bytes) splits /= 2;
-    const int64_t per = (rows + splits - 1) / splits;
-    float* partial = splits == 1 ? out : static_cast<float*>(ws);
-    hipLaunchKernelGGL(xcolsum_kernel, dim3((unsigned)((ncols + 63) / 64), (unsigned)splits), dim3(256), 0, stream, x, ld, rows, ncols, per, partial);
+    const ColsumRoute r = colsum_route(ld, rows, ncols, aligned16(x), ws ? ws_bytes : 0);
+    float* partial = r.kind == ColsumRoute::DIRECT ? out : static_cast<float*>(ws);
+    if (r.kind == ColsumRoute::FLAT) hipLaunchKernelGGL(xcolsum_flat_kernel, dim3(r.groups), dim3(256), 0, stream, x, rows * ncols, ncols, partial);
+    else hipLaunchKernelGGL(xcolsum_kernel, dim3((unsigned)ceil_div(ncols, 64), (unsigned)r.groups), dim3(256), 0, stream, x, ld, rows, ncols, r.rows_per_group, partial);
     AMTX_CHECK_LAUNCH();
-    if (splits > 1) {
-        hipLaunchKernelGGL(xreduce_kernel, dim3((unsigned)((ncols + 63) / 64)), dim3(256), 0, stream, (const float*)partial, splits, (int64_t)ncols, (int64_t)ncols,
-                           (const float*)nullptr, ncols, out);
-        AMTX_CHECK_LAUNCH();
-    }
+    return r.kind == ColsumRoute::DIRECT ? AMTX_OK : launch_xreduce(partial, r.groups, ncols, nullptr, ncols, out, stream);
+}
+
+template <int BN, int NS>
+int launch_xconv(const XconvRoute& r, const XConvArgs& g, hipStream_t stream) {
+    AMTX_GRANT_LDS((xconv_kernel<BN, NS>), r.lds);
+    hipLaunchKernelGGL((xconv_kernel<BN, NS>), dim3((unsigned)r.blocks), dim3(256), r.lds, stream, g);
+    AMTX_CHECK_LAUNCH();
     return AMTX_OK;
 }
 
-// strip kernel when it applies (see xconv_kernel), else the generic implicit GEMM
 int conv_rows_matmul(const float* x, const float* w_tapmajor, const float* bias, float* y, int64_t positions, int T, int F, int C, int N,
                      void* img_ws, size_t img_bytes, hipStream_t stream) {
-    const int bn = N <= 32 ? 32 : 64;
-    const size_t wimg = (size_t)2 * bn * (18 * C + 16);
-    const size_t lds = wimg + (size_t)4 * (XBM + 2) * (2 * C + 16);
-    if (C % 32 == 0 && C <= 64 && N <= 64 && lds <= 156 * 1024 && img_ws && img_bytes >= wimg) {
-        hipLaunchKernelGGL(xconv_wprep_kernel, dim3(16), dim3(256), 0, stream, w_tapmajor, N, 9 * C, bn, static_cast<char*>(img_ws));
-        AMTX_CHECK_LAUNCH();
-        XConvArgs g{x, img_ws, bias, y, positions, N, C, T, F};
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / lds));
-        const int64_t blocks = std::min<int64_t>((positions + XBM - 1) / XBM, 256 * per_cu);
-#define XCONV_LAUNCH(BN_, NS_)                                                                             \
-        do {                                                                                                  \
-            AMTX_GRANT_LDS((xconv_kernel<BN_, NS_>), lds);                                                    \
-            hipLaunchKernelGGL((xconv_kernel<BN_, NS_>), dim3((unsigned)blocks), dim3(256), lds, stream, g);  \
-        } while (0)
-        if (bn == 32 && C == 32) XCONV_LAUNCH(32, 5);
-        else if (bn == 32) XCONV_LAUNCH(32, 9);
-        else if (C == 32) XCONV_LAUNCH(64, 5);
-        else XCONV_LAUNCH(64, 9);
-#undef XCONV_LAUNCH
-        AMTX_CHECK_LAUNCH();
-        return AMTX_OK;
+    const XconvRoute r = xconv_route(positions, C, N, img_bytes);
+    if (!r.strip) {
+        XOp A{x, 0, XK_CONV_ROWS, T, F, C};
+        return matmul(A, XOp{w_tapmajor, (int64_t)9 * C, XK_ROWS, 0, 0, 0}, bias, y, N, positions, N, (int64_t)9 * C, nullptr, 0, stream);
     }
-    XOp A{x, 0, XK_CONV_ROWS, T, F, C};
-    return matmul(A, XOp{w_tapmajor, (int64_t)9 * C, XK_ROWS, 0, 0, 0}, bias, y, N, positions, N, (int64_t)9 * C, nullptr, 0, stream);
+    hipLaunchKernelGGL(xconv_wprep_kernel, dim3(16), dim3(256), 0, stream, w_tapmajor, N, 9 * C, r.bn, static_cast<char*>(img_ws));
+    AMTX_CHECK_LAUNCH();
+    const XConvArgs g{x, img_ws, bias, y, positions, N, C, T, F};
+    if (r.bn == 32) return r.ns == 5 ? launch_xconv<32, 5>(r, g, stream) : launch_xconv<32, 9>(r, g, stream);
+    return launch_xconv<64, 5>(r, g, stream);      // bn 64 is a strip route at C 32 only
+}
+
+int conv_w_permute(const float* in, float* out, int c_out, int c_in, int mode, hipStream_t stream) {
+    hipLaunchKernelGGL(conv_w_permute_kernel, dim3((unsigned)((9 * c_in * c_out + 255) / 256)), dim3(256), 0, stream, in, out, c_out, c_in, mode);
+    AMTX_CHECK_LAUNCH();
+    return AMTX_OK;
 }
 
 XOp rows_op(const float* p, int64_t ld) { return XOp{p, ld, XK_ROWS, 0, 0, 0}; }
@@ -902,10 +971,7 @@ XOp cols_op(const float* p, int64_t ld) { return XOp{p, ld, XK_COLS, 0, 0, 0}; }
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------ C ABI
-extern "C" size_t amtx_matmul_workspace_bytes(int64_t m, int64_t n, int64_t k) {
-    const int s = pick_splits(m, n, k);
-    return s > 1 ? (size_t)s * m * n * sizeof(float) : 0;
-}
+extern "C" size_t amtx_matmul_workspace_bytes(int64_t m, int64_t n, int64_t k) { return xgemm_route(m, n, k, n, false, 0).ws_bytes; }
 
 extern "C" int amtx_matmul_f32(const float* a, int64_t lda, int a_trans, const float* b, int64_t ldb, int b_trans, const float* bias, float* c,
                                int64_t ldc, int64_t m, int64_t n, int64_t k, void* workspace, size_t workspace_bytes, void* stream) {
@@ -921,9 +987,7 @@ extern "C" int amtx_linear_train_fwd(const float* x, int64_t ldx, const float* w
     return amtx_matmul_f32(x, ldx, 0, w, ldw, 0, bias, y, ldy, m, n, k, nullptr, 0, stream);
 }
 
-extern "C" size_t amtx_linear_bwd_workspace_bytes(int64_t m, int n, int k) {
-    return std::max<size_t>(amtx_matmul_workspace_bytes(n, k, m), (size_t)256 * n * sizeof(float)) + 256;
-}
+extern "C" size_t amtx_linear_bwd_workspace_bytes(int64_t m, int n, int k) { return std::max(amtx_matmul_workspace_bytes(n, k, m), colsum_flat_bytes(n)) + 256; }
 
 extern "C" int amtx_linear_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* w, int64_t ldw, float* dx, int64_t lddx,
                                float* dw, float* db, int64_t m, int n, int k, void* workspace, size_t workspace_bytes, void* stream) {
@@ -941,17 +1005,7 @@ extern "C" int amtx_linear_bwd(const float* dy, int64_t lddy, const float* x, in
     return AMTX_OK;
 }
 
-namespace {
-size_t conv_ws_w(int c_in, int c_out) { return ((size_t)9 * c_in * c_out * sizeof(float) + 255) / 256 * 256; }
-}
-
-extern "C" size_t amtx_conv3x3_train_workspace_bytes(int64_t rows, int num_bins, int c_in, int c_out) {
-    const int64_t positions = rows * num_bins;
-    const size_t split = amtx_matmul_workspace_bytes((int64_t)9 * c_in, c_out, positions);
-    const size_t image = std::max<size_t>((size_t)2 * 64 * (18 * std::max(c_in, c_out) + 16),    // weight image of the strip kernel
-                                          (size_t)768 * 288 * c_out * sizeof(float));           // partial gradients of xwgrad_kernel
-    return 2 * conv_ws_w(c_in, c_out) + std::max(std::max<size_t>(split, (size_t)256 * c_out * sizeof(float)), image) + 256;
-}
+extern "C" size_t amtx_conv3x3_train_workspace_bytes(int64_t rows, int num_bins, int c_in, int c_out) { return ConvWs::need(rows * num_bins, c_in, c_out); }
 
 extern "C" int amtx_conv3x3_train_fwd(const float* x, const float* w, const float* bias, float* y, int64_t rows, int frames_per_clip, int num_bins,
                                       int c_in, int c_out, void* workspace, size_t workspace_bytes, void* stream_) {
@@ -969,13 +1023,12 @@ extern "C" int amtx_conv3x3_train_fwd(const float* x, const float* w, const floa
         c.groups = 1; c.w_gs = 0; c.shift_gs = 0; c.out_gs = 0; c.relu = 0;
         return amtx_launch_conv1(c, stream);
     }
-    AMTX_REQUIRE(workspace && workspace_bytes >= conv_ws_w(c_in, c_out), "amtx_conv3x3_train_fwd: workspace too small");
-    float* wf = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(conv_w_permute_kernel, dim3((unsigned)((9 * c_in * c_out + 255) / 256)), dim3(256), 0, stream, w, wf, c_out, c_in, 0);
-    AMTX_CHECK_LAUNCH();
-    char* img = static_cast<char*>(workspace) + 2 * conv_ws_w(c_in, c_out);
-    const size_t img_bytes = workspace_bytes > 2 * conv_ws_w(c_in, c_out) ? workspace_bytes - 2 * conv_ws_w(c_in, c_out) : 0;
-    return conv_rows_matmul(x, wf, bias, y, rows * num_bins, frames_per_clip, num_bins, c_in, c_out, img, img_bytes, stream);
+    // the forward needs wt alone; a workspace that ends before `rest` has no room for the strip kernel's weight image (generic kernel)
+    AMTX_REQUIRE(workspace && workspace_bytes >= ConvWs::w_bytes(c_in, c_out), "amtx_conv3x3_train_fwd: workspace too small");
+    const ConvWs ws(workspace, workspace_bytes, c_in, c_out);
+    int rc;
+    if ((rc = conv_w_permute(w, ws.wt, c_out, c_in, 0, stream)) != AMTX_OK) return rc;
+    return conv_rows_matmul(x, ws.wt, bias, y, rows * num_bins, frames_per_clip, num_bins, c_in, c_out, ws.rest, ws.rest_bytes, stream);
 }
 
 extern "C" int amtx_conv3x3_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, int64_t rows, int frames_per_clip,
@@ -983,44 +1036,31 @@ extern "C" int amtx_conv3x3_bwd(const float* dy, const float* x, const float* w,
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     AMTX_REQUIRE(dy && rows > 0 && frames_per_clip > 0 && num_bins > 0 && rows % frames_per_clip == 0, "amtx_conv3x3_bwd: bad arguments");
     AMTX_REQUIRE(c_out % 4 == 0, "amtx_conv3x3_bwd: c_out must be a multiple of 4 (got %d)", c_out);
-    AMTX_REQUIRE(workspace && workspace_bytes >= amtx_conv3x3_train_workspace_bytes(rows, num_bins, c_in, c_out), "amtx_conv3x3_bwd: workspace too small");
     const int64_t positions = rows * num_bins;
+    AMTX_REQUIRE(workspace && workspace_bytes >= ConvWs::need(positions, c_in, c_out), "amtx_conv3x3_bwd: workspace too small");
     AMTX_REQUIRE(positions < (1ll << 31), "amtx_conv3x3_bwd: too many positions");
-    char* ws = static_cast<char*>(workspace);
-    float* wt = reinterpret_cast<float*>(ws);                                   // permuted weights / [(tap, ci)][co] gradient
-    float* gt = reinterpret_cast<float*>(ws + conv_ws_w(c_in, c_out));
-    void* rest = ws + 2 * conv_ws_w(c_in, c_out);
-    const size_t rest_bytes = workspace_bytes - 2 * conv_ws_w(c_in, c_out);
+    const ConvWs ws(workspace, workspace_bytes, c_in, c_out);
     int rc;
     if (dx) {   // correlation of dy with the flipped kernel: dx[pos][ci] = sum_{tap, co} dy[pos + off(tap)][co] w[co][ci][8 - tap]
         AMTX_REQUIRE(w && c_in % 4 == 0, "amtx_conv3x3_bwd: dx needs w and c_in %% 4 == 0");
-        hipLaunchKernelGGL(conv_w_permute_kernel, dim3((unsigned)((9 * c_in * c_out + 255) / 256)), dim3(256), 0, stream, w, wt, c_out, c_in, 1);
-        AMTX_CHECK_LAUNCH();
-        // the weight image lives at the start of the scratch area; the split partials of dw reuse it afterwards (stream-ordered)
-        if ((rc = conv_rows_matmul(dy, wt, nullptr, dx, positions, frames_per_clip, num_bins, c_out, c_in, rest, rest_bytes, stream)) != AMTX_OK) return rc;
+        if ((rc = conv_w_permute(w, ws.wt, c_out, c_in, 1, stream)) != AMTX_OK) return rc;
+        if ((rc = conv_rows_matmul(dy, ws.wt, nullptr, dx, positions, frames_per_clip, num_bins, c_out, c_in, ws.rest, ws.rest_bytes, stream)) != AMTX_OK) return rc;
     }
     if (dw) {   // G[(tap, ci)][co] = sum_pos x[pos + off(tap)][ci] dy[pos][co], then back to (c_out, c_in, 3, 3)
         AMTX_REQUIRE(x && (c_in == 1 || c_in % 4 == 0), "amtx_conv3x3_bwd: dw needs x and c_in = 1 or a multiple of 4");
-        const int wg_blocks = (int)std::min<int64_t>(768, (positions + 31) / 32);
-        if (c_in == WG_C && (c_out == 32 || c_out == 64) && rest_bytes >= (size_t)wg_blocks * 288 * c_out * sizeof(float)) {
-            XWgradArgs wa{x, dy, static_cast<float*>(rest), positions, frames_per_clip, num_bins, 0};
-            const int64_t nsteps = (positions + 31) / 32;
-            wa.steps_per_block = (nsteps + wg_blocks - 1) / wg_blocks;
-            const int used = (int)((nsteps + wa.steps_per_block - 1) / wa.steps_per_block);
-            if (c_out == 32) hipLaunchKernelGGL(xwgrad_kernel<2>, dim3(used), dim3(256), 0, stream, wa);
-            else hipLaunchKernelGGL(xwgrad_kernel<4>, dim3(used), dim3(256), 0, stream, wa);
+        const XwgradRoute r = xwgrad_route(positions, c_in, c_out, ws.rest_bytes);
+        if (r.resident) {
+            const XWgradArgs wa{x, dy, static_cast<float*>(ws.rest), positions, frames_per_clip, num_bins, r.steps_per_block};
+            if (r.nt == 2) hipLaunchKernelGGL(xwgrad_kernel<2>, dim3(r.blocks), dim3(256), 0, stream, wa);
+            else hipLaunchKernelGGL(xwgrad_kernel<4>, dim3(r.blocks), dim3(256), 0, stream, wa);
             AMTX_CHECK_LAUNCH();
-            const int64_t count = (int64_t)288 * c_out;
-            hipLaunchKernelGGL(xreduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, stream, (const float*)rest, used, count, count,
-                               (const float*)nullptr, c_out, gt);
-            AMTX_CHECK_LAUNCH();
+            if ((rc = launch_xreduce(wa.partial, r.blocks, (int64_t)288 * c_out, nullptr, c_out, ws.gt, stream)) != AMTX_OK) return rc;
         } else {
             XOp A{x, 0, XK_CONV_COLS, frames_per_clip, num_bins, c_in};
-            if ((rc = matmul(A, cols_op(dy, c_out), nullptr, gt, c_out, (int64_t)9 * c_in, c_out, positions, rest, rest_bytes, stream)) != AMTX_OK) return rc;
+            if ((rc = matmul(A, cols_op(dy, c_out), nullptr, ws.gt, c_out, (int64_t)9 * c_in, c_out, positions, ws.rest, ws.rest_bytes, stream)) != AMTX_OK) return rc;
         }
-        hipLaunchKernelGGL(conv_w_permute_kernel, dim3((unsigned)((9 * c_in * c_out + 255) / 256)), dim3(256), 0, stream, (const float*)gt, dw, c_out, c_in, 2);
-        AMTX_CHECK_LAUNCH();
+        if ((rc = conv_w_permute(ws.gt, dw, c_out, c_in, 2, stream)) != AMTX_OK) return rc;
     }
-    if (db) return colsum(dy, c_out, positions, c_out, db, rest, rest_bytes, stream);
+    if (db) return colsum(dy, c_out, positions, c_out, db, ws.rest, ws.rest_bytes, stream);
     return AMTX_OK;
 }

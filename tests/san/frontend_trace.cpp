@@ -11,44 +11,16 @@
 //   through pointers are printed the same way: a name, a tab, numbers).
 // Buffers the host code only takes addresses of are reserved address space (never touched, never committed); what it writes -- clip_max, the
 // maxima, the workspace's maxima and the host track table -- is real memory.
-#include "../../include/amtx.h"
+#include "trace_common.h"
 #include "../../include/amtx_pyramid.h"
 #include "../../include/amtx_tracks.h"
 
-#include <sys/mman.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <fstream>
-#include <iostream>
 #include <map>
 #include <sstream>
-#include <string>
 #include <vector>
 
-extern "C" void amtx_san_trace_begin(void);
-extern "C" const char* amtx_san_trace_take(void);
-
 namespace {
-
-// address space of `bytes` bytes, 4096-byte aligned; pages exist only where something writes
-struct Reserved {
-    void* p = nullptr;
-    size_t n = 0;
-    explicit Reserved(size_t bytes) : n(std::max<size_t>(bytes, 4096)) {
-        p = mmap(nullptr, n, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-        if (p == MAP_FAILED) { perror("mmap"); exit(2); }
-    }
-    ~Reserved() { munmap(p, n); }
-    Reserved(const Reserved&) = delete;
-    Reserved& operator=(const Reserved&) = delete;
-};
-
-void report(long long rc, bool failed, const std::string& extra = std::string()) {
-    const std::string trace = amtx_san_trace_take();
-    std::cout << "=\t" << rc << '\t' << (failed ? amtx_last_error() : "") << '\n' << extra << trace;
-}
 
 std::map<std::string, amtx_spec_plan*> spec_plans;
 std::map<std::string, amtx_cqt_plan*> cqt_plans;

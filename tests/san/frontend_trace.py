@@ -160,7 +160,8 @@ def _unfold(ids):
     return ids['of'] * ids['rep'] + ids['then'] if isinstance(ids, dict) else ids
 
 
-def compact(runs):
+def compact(runs, sha256=None):
+    """`sha256`: that of the case list the runs are of, where it is not `cases()` (tests/san/train_trace.py)."""
     tables = {'names': {}, 'launches': {}, 'outcomes': {}}
 
     def index(table, value):
@@ -175,7 +176,7 @@ def compact(runs):
     ids = {s: [outcome(o) for o in r] for s, r in runs.items()}
     base = ids['']
     out = {s: r if not s else [[i, o] for i, (o, b) in enumerate(zip(r, base)) if o != b] for s, r in ids.items()}
-    return dict({t: [json.loads(k) for k in v] for t, v in tables.items()}, cases_sha256=cases_sha256(), runs=out)
+    return dict({t: [json.loads(k) for k in v] for t, v in tables.items()}, cases_sha256=sha256 or cases_sha256(), runs=out)
 
 
 def expand(c):
@@ -194,7 +195,7 @@ def expand(c):
 
 
 def write(c, path):
-    """Valid JSON with several table rows to a line."""
+    """Valid JSON with several table rows to a line; a 'parent_commit' entry goes into the header next to the case list's hash."""
     def rows(values):
         lines, line = [], ''
         for v in (json.dumps(v, separators=(',', ':')) for v in values):
@@ -205,7 +206,7 @@ def write(c, path):
         return ',\n'.join(lines + [line])
     with open(path, 'w') as f:
         f.write('{' + ',\n'.join('"%s": [\n%s\n]' % (t, rows(c[t])) for t in ('names', 'launches', 'outcomes')) +
-                ',\n"cases_sha256": "%s",\n"runs": {\n' % c['cases_sha256'] +
+                ',\n"cases_sha256": "%s",\n' % c['cases_sha256'] + ('"parent_commit": "%s",\n' % c['parent_commit'] if 'parent_commit' in c else '') + '"runs": {\n' +
                 ',\n'.join('%s: [\n%s\n]' % (json.dumps(s), rows(r)) for s, r in c['runs'].items()) + '\n}}\n')
 
 

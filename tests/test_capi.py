@@ -211,3 +211,12 @@ def test_conv_launchers_refuse_with_the_recorded_code_and_text(entry, args, code
         out_type, b, t, f, c_in, c_out = args
         rc = L.amtx_conv1_fwd(p, f * t, 0, f, 1, p, p, p, out_type, b, t, f, c_in, c_out, None)
     assert (rc, L.amtx_last_error().decode()) == (code, text)
+
+
+def test_training_workspace_queries_answer_zero_splits_for_an_empty_problem():
+    """xgemm_route refuses an empty problem before it counts tiles: amtx_matmul_workspace_bytes of a problem without rows or columns and a long
+    contraction (32 k-steps or more) answers 0 -- it used to divide by the tile count -- and the queries built on it stay finite.  Host only."""
+    L = _lib.lib()
+    assert L.amtx_matmul_workspace_bytes(0, 64, 1024) == 0 and L.amtx_matmul_workspace_bytes(128, 0, 1024) == 0 and L.amtx_matmul_workspace_bytes(128, 64, 0) == 0
+    assert L.amtx_linear_bwd_workspace_bytes(4096, 0, 64) == 256 and L.amtx_conv3x3_train_workspace_bytes(5000, 229, 0, 32) == 768 * 288 * 32 * 4 + 256
+    assert L.amtx_matmul_workspace_bytes(1, 4, 996) == 32          # the smallest split problem still asks for its two partial tiles

@@ -535,3 +535,81 @@ def test_full_size_training_step_matches_the_oracle(of2, capsys):
         print(f'\n[config 4 full size, {"OnsetsFrames2 mc=3" if of2 else "OnsetsFrames mc=2"}] 8 clips x 625 frames: losses '
               f'{ {k: round(v, 4) for k, v in got_loss.items()} }; {n_tensors} gradient tensors, worst relative error {worst:.2e} ({worst_k}); '
               f'after one Adam step {flips} of {entries} weights moved the other way (|g_ref| inside the gradient tolerance)')
+
+
+# (call, arguments): the smallest that reach each route of train.hip.  matmul: (m, n, k, what ldc has more than n);
+# linear_db: amtx_linear_bwd's bias gradient alone at (m, n, k); conv_fwd / conv_bwd: (c_in, c_out) at rows 34, 17 frames a clip, 10 bins
+TRAIN_ROUTES = [('matmul', (37, 32, 256, 0)), ('matmul', (37, 64, 256, 0)), ('matmul', (37, 88, 256, 0)),      # the three tile widths
+                ('matmul', (88, 512, 5000, 0)), ('matmul', (88, 512, 5000, 4)),                              # split + reduce; a padded C: one launch
+                ('linear_db', (1024, 64, 176)), ('linear_db', (5000, 88, 512)), ('linear_db', (511, 64, 176)),     # flat, row groups, direct
+                ('conv_fwd', (32, 32)), ('conv_fwd', (32, 64)), ('conv_fwd', (64, 64)), ('conv_fwd', (48, 96)), ('conv_fwd', (1, 32)),   # strip x 2, generic x 2, conv1
+                ('conv_bwd', (32, 64)), ('conv_bwd', (48, 96))]                                              # <32, 9> dgrad + xwgrad_kernel<4>; generic
+
+
+@pytest.mark.parametrize('call,args', TRAIN_ROUTES, ids=lambda v: v if isinstance(v, str) else '-'.join(map(str, v)))
+def test_train_entry_points_launch_the_recorded_kernels(call, args):
+    """Each entry point launches the kernels -- instantiations and counts -- of the row that tests/golden/train_trace.json holds for the same
+    arguments (tests/test_train_trace.py: recorded on the host, before train.hip took its decisions from routes), with a workspace of exactly
+    the query's answer.  Operands are zeros: only the launches are looked at."""
+    import collections
+    import json
+    import os
+    import re
+    import sys
+    from amt_tools_amd import _lib
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.join(here, 'san'))
+    import train_trace
+    L, dev, rows, t, f = _lib.lib(), 'cuda:0', 34, 17, 10
+    stream = _lib.current_stream()
+
+    def z(*shape):
+        return torch.zeros(*shape, device=dev)
+
+    def workspace(need):
+        return torch.zeros(int(need), dtype=torch.uint8, device=dev)
+    if call == 'matmul':
+        m, n, k, pad = args
+        case = train_trace.matmul_case(m, n, k, ldc_pad=pad)
+        a, b, bias, c, ws = z(m, k), z(n, k), z(n), z(m, n + pad), workspace(L.amtx_matmul_workspace_bytes(m, n, k))
+        run = lambda: _lib.check(L.amtx_matmul_f32(_lib.ptr(a), k, 0, _lib.ptr(b), k, 0, _lib.ptr(bias), _lib.ptr(c), n + pad, m, n, k,      # noqa: E731
+                                                   _lib.ptr(ws), ws.numel(), stream), 'amtx_matmul_f32')
+    elif call == 'linear_db':
+        m, n, k = args
+        case = train_trace.linear_bwd_case(m, n, k, 4)
+        dy, db, ws = z(m, n), z(n), workspace(L.amtx_linear_bwd_workspace_bytes(m, n, k))
+        run = lambda: _lib.check(L.amtx_linear_bwd(_lib.ptr(dy), n, None, k, None, k, None, k, None, _lib.ptr(db), m, n, k,                  # noqa: E731
+                                                   _lib.ptr(ws), ws.numel(), stream), 'amtx_linear_bwd')
+    else:
+        ci, co = args
+        x, w, bias, y, ws = z(rows, f, ci), z(co, ci, 3, 3), z(co), z(rows, f, co), workspace(L.amtx_conv3x3_train_workspace_bytes(rows, f, ci, co))
+        if call == 'conv_fwd':
+            case = train_trace.conv_fwd_case(rows, t, f, ci, co)
+            run = lambda: _lib.check(L.amtx_conv3x3_train_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), rows, t, f, ci, co,     # noqa: E731
+                                                              _lib.ptr(ws), ws.numel(), stream), 'amtx_conv3x3_train_fwd')
+        else:
+            case = train_trace.conv_bwd_case(rows, t, f, ci, co, 7)
+            dx, dw = z(rows, f, ci), z(co, ci, 3, 3)
+            run = lambda: _lib.check(L.amtx_conv3x3_bwd(_lib.ptr(y), _lib.ptr(x), _lib.ptr(w), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(bias),   # noqa: E731
+                                                        rows, t, f, ci, co, _lib.ptr(ws), ws.numel(), stream), 'amtx_conv3x3_bwd')
+    with open(os.path.join(here, 'golden', 'train_trace.json')) as fh:
+        golden = json.load(fh)
+    assert golden['cases_sha256'] == train_trace.cases_sha256()
+    rc, err, recorded = train_trace.expand(golden)[train_trace.cases().index(case)]
+    assert rc == 0 and not err
+
+    def kernel(text):
+        m = re.search(r'\w+_kernel(<[^>]*>)?', text)
+        return m and m.group(0)
+    want = collections.Counter(kernel(line) for line in recorded if kernel(line))
+    run()                                                             # the LDS grant and lazy module load stay out of the profile
+    torch.cuda.synchronize()
+    with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+        run()
+        torch.cuda.synchronize()
+    ran = collections.Counter()
+    for e in prof.key_averages():
+        if kernel(e.key):
+            ran[kernel(e.key)] += e.count
+    print(f'TRAINROUTE {case!r}: {dict(ran)}')
+    assert want and ran == want, (case, [e.key for e in prof.key_averages()])
