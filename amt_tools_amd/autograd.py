@@ -12,7 +12,9 @@ the 61 ms of GPU time of a step at 8 clips x 625 frames).  Here:
   * TabCNN's window pool and grouped softmax loss: TabWindowPoolFunction, SoftmaxGroupsLossFunction (csrc/tabtrain.hip).
 Arithmetic: fp32 in / out with split-bf16 (3-MFMA) products, fp32 accumulation -- fp32-class accuracy.  No vendor BLAS / MIOpen kernel
 runs in a step; a layer whose shape the kernels do not take goes to the stock ATen op AND is recorded (`fallbacks()`,
-`training_backend()`), or raises under `AMTX_STRICT_TRAINING=1`.
+`training_backend()`), or raises under `AMTX_STRICT_TRAINING=1`.  Which layer takes which side is decided here, once per layer kind, by the
+`*_supported` / `linear_takes` predicates and `linear_layer`: DESIGN.md 5.14 has the table (rule, fallback site, recorded reason), and
+tests/test_train_dispatch.py pins it off the GPU.
 """
 import os
 
@@ -23,7 +25,8 @@ from . import _lib
 __all__ = ['bilstm', 'bilstm_multi', 'BiLSTMFunction', 'bce_logits_loss', 'BCELogitsLossFunction', 'bn_relu_pool', 'BNReLUPoolFunction',
            'matmul_f32', 'linear', 'LinearFunction', 'conv3x3', 'Conv3x3Function', 'tab_conv3x3', 'tab_window_pool', 'TabWindowPoolFunction',
            'softmax_groups_loss', 'SoftmaxGroupsLossFunction', 'training_backend', 'note_fallback', 'fallbacks', 'fallback_total',
-           'reset_fallbacks']
+           'reset_fallbacks', 'linear_takes', 'linear_supported', 'linear_layer', 'conv_module_supported', 'conv3x3_supported', 'tab_conv_supported',
+           'bilstm_supported', 'bn_relu_pool_supported', 'bce_logits_loss_supported', 'softmax_groups_loss_supported']
 
 HIDDEN_SIZES = (128, 256, 384, 512)  # hidden sizes per direction the training recurrences are built for (model_complexity 2 .. 5)
 
@@ -123,9 +126,14 @@ def _colsum(x2):
     return db
 
 
+def linear_takes(dtype, k, n):
+    """The GEMMs take a dense layer of k inputs and n outputs in `dtype`: nn.Linear, and the LSTM's input projection (n = 8 hidden)."""
+    return USE_HIP_DENSE and dtype == torch.float32 and k % 4 == 0 and n % 4 == 0
+
+
 def linear_supported(x, weight):
-    return (USE_HIP_DENSE and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.dim() == 2
-            and weight.shape[0] % 4 == 0 and weight.shape[1] % 4 == 0 and x.shape[-1] == weight.shape[1])
+    return (x.is_cuda and x.dtype == weight.dtype and weight.dim() == 2 and x.shape[-1] == weight.shape[1]
+            and linear_takes(x.dtype, weight.shape[1], weight.shape[0]))
 
 
 class LinearFunction(torch.autograd.Function):
@@ -165,17 +173,29 @@ def linear(x, weight, bias=None):
     return LinearFunction.apply(x, weight, bias)
 
 
+def linear_layer(site, x, weight, bias=None):
+    """F.linear of a training step on a GPU: on the HIP kernels where they take it, else on the stock op, recorded under `site`."""
+    if linear_supported(x, weight):
+        return linear(x, weight, bias)
+    note_fallback(site, f'Linear {weight.shape[1]} -> {weight.shape[0]}, {x.dtype}')
+    return torch.nn.functional.linear(x, weight, bias)
+
+
+def conv_module_supported(conv, padding, input_grad, dtype=None):
+    """An nn.Conv2d(3x3, stride 1, `padding` on both axes) with a bias that Conv3x3Function can run on fp32 maps (`dtype`: the map's; None:
+    the weight's); `input_grad`: whether its input needs a gradient, which the direct first-layer kernel does not produce."""
+    if not (USE_HIP_DENSE and isinstance(conv, torch.nn.Conv2d) and (conv.weight.dtype if dtype is None else dtype) == torch.float32
+            and conv.kernel_size == (3, 3) and conv.padding == padding and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.bias is not None and (padding == (0, 0) or conv.padding_mode == 'zeros')):
+        return False
+    if conv.in_channels == 1 and not input_grad:
+        return conv.out_channels % 8 == 0     # direct first-layer kernel forward, K = 9 weight-gradient GEMM
+    return conv.out_channels % 4 == 0         # c_in a multiple of 4, or padded to one with zero channels (_pad_channels)
+
+
 def conv3x3_supported(x, conv):
     """nn.Conv2d(3x3, padding 1, stride 1) on an fp32 CUDA map whose input gradient, if wanted, the kernels can produce."""
-    if not (USE_HIP_DENSE and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and isinstance(conv, torch.nn.Conv2d)):
-        return False
-    if not (conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
-            and conv.bias is not None and conv.padding_mode == 'zeros'):
-        return False
-    c_in, c_out = conv.in_channels, conv.out_channels
-    if c_in == 1 and not x.requires_grad:
-        return c_out % 8 == 0                 # direct first-layer kernel forward, K = 9 weight-gradient GEMM
-    return c_out % 4 == 0                     # c_in a multiple of 4, or padded to one with zero channels (conv3x3)
+    return x.is_cuda and x.dim() == 4 and conv_module_supported(conv, (1, 1), x.requires_grad, x.dtype)
 
 
 class Conv3x3Function(torch.autograd.Function):
@@ -211,28 +231,22 @@ class Conv3x3Function(torch.autograd.Function):
         return dx, dw, db
 
 
-def conv3x3(x, conv):
-    """`conv(x)` for an nn.Conv2d(3x3, padding 1) on the HIP kernels, differentiably.  Input channel counts the implicit GEMMs do not
-    take as they are (3 or 6 = an HCQT / multi-channel first layer, amt_tools/features/hvqt.py:107-133; 1 when the input itself needs a
-    gradient) are padded with zero channels to a multiple of 4 -- in the map and in the weights, so the products are unchanged and the
-    weight gradient of the real channels comes back through the pad's own backward (a slice)."""
+def _pad_channels(x, weight):
+    """Input channel counts the implicit GEMMs do not take as they are (3 or 6 = an HCQT / multi-channel first layer,
+    amt_tools/features/hvqt.py:107-133; 1 when the input itself needs a gradient) are padded with zero channels to a multiple of 4 -- in the
+    map and in the weights, so the products are unchanged and the weight gradient of the real channels comes back through the pad's own
+    backward (a slice)."""
     c_in = x.shape[1]
-    weight = conv.weight
     if c_in % 4 != 0 and not (c_in == 1 and not x.requires_grad):
         pad = (-c_in) % 4
         x = torch.nn.functional.pad(x, (0, 0, 0, 0, 0, pad))
         weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, pad))
-    return Conv3x3Function.apply(x, weight, conv.bias)
+    return x, weight
 
 
-def _pack(w_hh_f, w_hh_b):
-    H = w_hh_f.shape[1]
-    n = int(_lib.call('amtx_bilstm_h_packed_elems', H, 2))
-    fwd = torch.empty(n, dtype=torch.int16, device=w_hh_f.device)
-    bwd = torch.empty(n, dtype=torch.int16, device=w_hh_f.device)
-    wf, wb = w_hh_f.detach().contiguous().float(), w_hh_b.detach().contiguous().float()
-    _lib.call('amtx_bilstm_h_pack_device', wf, wb, H, 2, fwd, bwd, device=wf.device)
-    return fwd, bwd
+def conv3x3(x, conv):
+    """`conv(x)` for an nn.Conv2d(3x3, padding 1) on the HIP kernels, differentiably (any input channel count: _pad_channels)."""
+    return Conv3x3Function.apply(*_pad_channels(x, conv.weight), conv.bias)
 
 
 class BiLSTMFunction(torch.autograd.Function):
@@ -253,20 +267,19 @@ class BiLSTMFunction(torch.autograd.Function):
         xproj = torch.empty((G, B * T, 8 * H), dtype=torch.float32, device=dev)
         frag_fwd = torch.empty((G, n), dtype=torch.int16, device=dev)
         frag_bwd = torch.empty((G, n), dtype=torch.int16, device=dev)
-        saved = []
+        saved, hip_mm = [], []               # hip_mm: per group, the input projection and its gradients on the HIP GEMMs
         for g, (x, w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_b, w_hh_b, b_ih_b, b_hh_b) in enumerate(groups):
             assert x.shape[:2] == (B, T) and w_hh_f.shape[1] == H
             x2 = x.reshape(B * T, x.shape[2])
             w_ih = torch.cat([w_ih_f, w_ih_b], dim=0)                                  # (8 H, I)
             bias = torch.cat([b_ih_f + b_hh_f, b_ih_b + b_hh_b], dim=0)
-            hip_mm = USE_HIP_DENSE and x2.shape[1] % 4 == 0
-            if not hip_mm:
-                note_fallback('BiLSTM input projection', 'USE_HIP_DENSE off' if not USE_HIP_DENSE else f'input size {x2.shape[1]} is not a multiple of 4')
-            if hip_mm:
+            hip_mm.append(linear_takes(torch.float32, x2.shape[1], 8 * H))             # (x is fp32: matmul_f32 asserts it)
+            if hip_mm[g]:
                 if not _ok2d(x2):
                     x2 = x2.contiguous()
                 matmul_f32(x2, w_ih, bias=bias, out=xproj[g])                          # [B][T][2][4H]
             else:
+                note_fallback('BiLSTM input projection', 'USE_HIP_DENSE off' if not USE_HIP_DENSE else f'input size {x2.shape[1]} is not a multiple of 4')
                 torch.addmm(bias, x2, w_ih.t(), out=xproj[g])
             wf, wb = w_hh_f.detach().contiguous().float(), w_hh_b.detach().contiguous().float()
             _lib.call('amtx_bilstm_h_pack_device', wf, wb, H, 2, frag_fwd[g], frag_bwd[g], device=dev)
@@ -275,7 +288,7 @@ class BiLSTMFunction(torch.autograd.Function):
         save = torch.empty((G, B, T, 2, 5, H), dtype=torch.float32, device=dev)
         _lib.call('amtx_bilstm_h_train_fwd', xproj, frag_fwd, H, 2, out, save, B, T, G, device=dev)
         ctx.save_for_backward(out, save, frag_bwd, *saved)
-        ctx.hip_mm = [USE_HIP_DENSE and saved[2 * g].shape[1] % 4 == 0 for g in range(G)]
+        ctx.hip_mm = hip_mm
         ctx.dims = (G, B, T, H)
         ctx.need_dx = [bool(ctx.needs_input_grad[1 + 9 * g]) for g in range(G)]
         return tuple(out[g] for g in range(G))
@@ -288,7 +301,7 @@ class BiLSTMFunction(torch.autograd.Function):
         dout = torch.stack([d.contiguous().float() for d in douts], dim=0)
         dxproj = torch.empty((G, B * T, 8 * H), dtype=torch.float32, device=dev)
         _lib.call('amtx_bilstm_h_train_bwd', dout, save, frag_bwd, H, 2, dxproj, B, T, G, device=dev)
-        ones = torch.ones((1, B * T), dtype=torch.float32, device=dev)
+        ones = None if all(ctx.hip_mm) else torch.ones((1, B * T), dtype=torch.float32, device=dev)     # read by the ATen branch alone
         grads = [None]
         n = 4 * H
         for g in range(G):
@@ -322,6 +335,13 @@ def _lstm_args(x, lstm):
             lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse, lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse)
 
 
+def bilstm_supported(x, lstm, enabled=True):
+    """`lstm` on x can run on BiLSTMFunction: an fp32 CUDA input, both directions, one layer, a hidden size the recurrences are built for;
+    `enabled`: the owner's switch (LanguageModel.use_hip_autograd)."""
+    return bool(enabled and x.is_cuda and x.dtype == torch.float32 and lstm.bidirectional and lstm.num_layers == 1
+                and lstm.hidden_size in HIDDEN_SIZES)
+
+
 def bilstm(x, lstm):
     """Run `lstm` (an nn.LSTM(batch_first, bidirectional, hidden in HIDDEN_SIZES, one layer)) on x through the HIP kernels, differentiably."""
     return BiLSTMFunction.apply(1, *_lstm_args(x, lstm))[0]
@@ -330,10 +350,7 @@ def bilstm(x, lstm):
 def bilstm_multi(xs, lstms):
     """Independent LSTMs of the same hidden size on inputs of the same (B, T) in one launch each way (the onset and offset
     recurrences of OnsetsFrames2, which otherwise run one after the other with two blocks busy each)."""
-    args = []
-    for x, lstm in zip(xs, lstms):
-        args += list(_lstm_args(x, lstm))
-    return BiLSTMFunction.apply(len(xs), *args)
+    return BiLSTMFunction.apply(len(xs), *[a for x, lstm in zip(xs, lstms) for a in _lstm_args(x, lstm)])
 
 
 class BCELogitsLossFunction(torch.autograd.Function):
@@ -360,6 +377,12 @@ class BCELogitsLossFunction(torch.autograd.Function):
     def backward(ctx, g):
         saved = ctx.saved_tensors
         return (saved[0] * g if saved else None), None, None
+
+
+def bce_logits_loss_supported(logits, labels):
+    """fp32 CUDA logits (B,T,K) against labels (B,K,T)."""
+    return (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3 and labels.dim() == 3
+            and labels.shape == (logits.shape[0], logits.shape[2], logits.shape[1]))
 
 
 def bce_logits_loss(logits, labels, weight=None):
@@ -419,27 +442,15 @@ def bn_relu_pool(x, bn, pool):
 def tab_conv_supported(conv, input_grad):
     """An unpadded nn.Conv2d(3x3, stride 1) of TabCNN that tab_conv3x3 can run as a padded convolution over a whole sequence;
     `input_grad`: whether its input will need a gradient (every layer but the first)."""
-    if not (USE_HIP_DENSE and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (3, 3) and conv.padding == (0, 0)
-            and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None
-            and conv.weight.dtype == torch.float32):
-        return False
-    if conv.in_channels == 1 and not input_grad:
-        return conv.out_channels % 8 == 0     # direct first-layer kernel forward, K = 9 weight-gradient GEMM
-    return conv.out_channels % 4 == 0         # c_in a multiple of 4, or padded to one with zero channels
+    return conv_module_supported(conv, (0, 0), input_grad)
 
 
 def tab_conv3x3(x, conv):
     """TabCNN's unpadded conv as a padded ("same") one on Conv3x3Function: x is (B, c_in, cols, F) -- the sequence's columns on the
     kernels' frame axis, TabCNN's frequency rows on their bin axis -- so the weight goes in with its two spatial axes swapped (a
     differentiable transpose).  Valid output (row r, column v) is the result's (v + 1, r + 1); its border is wrong and stays unread.
-    Input channel counts the implicit GEMMs do not take are zero-padded to a multiple of 4, as conv3x3 does."""
-    weight = conv.weight.transpose(-1, -2)
-    c_in = x.shape[1]
-    if c_in % 4 != 0 and not (c_in == 1 and not x.requires_grad):
-        pad = (-c_in) % 4
-        x = torch.nn.functional.pad(x, (0, 0, 0, 0, 0, pad))
-        weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, pad))
-    return Conv3x3Function.apply(x, weight, conv.bias)
+    Any input channel count: _pad_channels, as in conv3x3."""
+    return Conv3x3Function.apply(*_pad_channels(x, conv.weight.transpose(-1, -2)), conv.bias)
 
 
 class TabWindowPoolFunction(torch.autograd.Function):
@@ -510,6 +521,12 @@ class SoftmaxGroupsLossFunction(torch.autograd.Function):
     def backward(ctx, g):
         saved = ctx.saved_tensors
         return ((saved[0] * g).to(ctx.dtype) if saved else None), None, None, None, None
+
+
+def softmax_groups_loss_supported(logits, labels, num_groups):
+    """fp32 CUDA logits (B, T, G*C) against labels (B, G, T)."""
+    return (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3
+            and tuple(labels.shape) == (logits.shape[0], num_groups, logits.shape[1]))
 
 
 def softmax_groups_loss(logits, labels, num_groups, num_classes, weight=None):

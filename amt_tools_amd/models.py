@@ -14,8 +14,7 @@ Execution paths
   (`amtx_of_forward`): conv1 -> conv3x3+BN+ReLU+pool (MFMA) -> fc1 (MFMA GEMM) -> persistent BiLSTM ->
   LogisticBank heads -> piano roll.  No fallback: a missing extension raises.
 * training mode on a GPU (autograd) -> hand-written HIP forward + backward kernels behind autograd.Functions
-  (amt_tools_amd/autograd.py): the three BiLSTM recurrences, BatchNorm(batch statistics)+ReLU+MaxPool, the
-  LogisticBank loss; `autograd.training_backend()` names what still runs on ATen.
+  (amt_tools_amd/autograd.py, which also decides per layer between them and a recorded ATen fallback: DESIGN.md 5.14).
 * CPU devices -> stock torch ops on the same parameters (ATen; the reference's own arithmetic).
 
 `precision` selects the inference engine's dense arithmetic.  `'x3'` (DEFAULT since round 6: split-bf16, three bf16 MFMAs per
@@ -35,6 +34,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib, tools
+from . import autograd
 
 __all__ = ['TranscriptionModel', 'OutputLayer', 'LogisticBank', 'AcousticModel', 'LanguageModel', 'OnsetsFrames',
            'SpectralFrontend']
@@ -166,24 +166,18 @@ class LogisticBank(OutputLayer):
         self.output_layer = nn.Linear(self.dim_in, self.dim_out)
 
     def forward(self, feats):
-        if feats.is_cuda and torch.is_grad_enabled():
-            from .autograd import linear, linear_supported, note_fallback     # training on a GPU: the HIP GEMMs, forward and backward
-            if linear_supported(feats, self.output_layer.weight):
-                return linear(feats, self.output_layer.weight, self.output_layer.bias)
-            note_fallback('LogisticBank.output_layer', f'Linear {self.dim_in} -> {self.dim_out}, {feats.dtype}')
+        if feats.is_cuda and torch.is_grad_enabled():     # training on a GPU: the HIP GEMMs, forward and backward
+            return autograd.linear_layer('LogisticBank.output_layer', feats, self.output_layer.weight, self.output_layer.bias)
         return self.output_layer(feats)
 
     def get_loss(self, estimated, reference):
         """BCE with logits; mean over frames, sum over keys, mean over the batch (common.py:541-584).
         estimated (B,T,O) logits, reference (B,O,T)."""
-        if (estimated.is_cuda and estimated.dtype == torch.float32 and estimated.dim() == 3 and reference.dim() == 3
-                and reference.shape == (estimated.shape[0], estimated.shape[2], estimated.shape[1])):
-            from .autograd import bce_logits_loss     # one HIP pass: loss + d loss / d logits
-            return bce_logits_loss(estimated, reference, self.weights)
+        if autograd.bce_logits_loss_supported(estimated, reference):
+            return autograd.bce_logits_loss(estimated, reference, self.weights)     # one HIP pass: loss + d loss / d logits
         if estimated.is_cuda and torch.is_grad_enabled() and estimated.requires_grad:
             # (a validation pass that computes a loss on logits of another dtype / layout is not a training step: nothing to record)
-            from .autograd import note_fallback
-            note_fallback('LogisticBank.get_loss', f'logits {tuple(estimated.shape)} {estimated.dtype} vs labels {tuple(reference.shape)}')
+            autograd.note_fallback('LogisticBank.get_loss', f'logits {tuple(estimated.shape)} {estimated.dtype} vs labels {tuple(reference.shape)}')
         est = estimated.transpose(-2, -1)
         weight = self.weights.unsqueeze(-1) if self.weights is not None else None
         loss = F.binary_cross_entropy_with_logits(est.float(), reference.float(), weight=weight, reduction='none')
@@ -217,29 +211,29 @@ class AcousticModel(nn.Module):
     def _stage(self, layer, x):
         """One conv stage.  Training on a GPU: the convolution is an implicit GEMM on the HIP kernels (autograd.conv3x3: forward,
         input and weight gradients), BatchNorm (batch statistics) + ReLU (+ MaxPool) run as the HIP passes of
-        amt_tools_amd/autograd.py (bn_relu_pool); the Dropout behind them is the module's own."""
+        amt_tools_amd/autograd.py (bn_relu_pool); the Dropout behind them is the module's own.  Which side each step takes: DESIGN.md 5.14."""
+        if not (self.training and x.is_cuda):
+            return layer(x)
         mods = list(layer)
-        if self.training and self.use_hip_bn and x.is_cuda and not isinstance(mods[1], nn.SyncBatchNorm):
-            from .autograd import bn_relu_pool, bn_relu_pool_supported, conv3x3, conv3x3_supported, note_fallback
-            if conv3x3_supported(x, mods[0]):
-                y = conv3x3(x, mods[0])
-            else:
-                note_fallback('AcousticModel conv', f'Conv2d {mods[0].in_channels} -> {mods[0].out_channels} on {x.dtype}')
-                y = mods[0](x)
-            if bn_relu_pool_supported(y, mods[1]):
-                pool = len(mods) > 3 and isinstance(mods[3], nn.MaxPool2d)
-                y = bn_relu_pool(y, mods[1], pool)
-                for m in mods[(4 if pool else 3):]:
-                    y = m(y)
-                return y
-            note_fallback('AcousticModel BatchNorm+ReLU+MaxPool', f'{y.shape[1]} channels, {y.dtype}, channels_last={y.is_contiguous(memory_format=torch.channels_last)}')
-            for m in mods[1:]:
-                y = m(y)
-            return y
-        if self.training and x.is_cuda:
-            from .autograd import note_fallback
-            note_fallback('AcousticModel stage', 'use_hip_bn off' if not self.use_hip_bn else 'SyncBatchNorm (stock modules by design: its statistics are a collective)')
-        return layer(x)
+        conv, bn = mods[0], mods[1]
+        if not self.use_hip_bn or isinstance(bn, nn.SyncBatchNorm):
+            autograd.note_fallback('AcousticModel stage', 'use_hip_bn off' if not self.use_hip_bn else 'SyncBatchNorm (stock modules by design: its statistics are a collective)')
+            return layer(x)
+        if autograd.conv3x3_supported(x, conv):
+            y = autograd.conv3x3(x, conv)
+        else:
+            autograd.note_fallback('AcousticModel conv', f'Conv2d {conv.in_channels} -> {conv.out_channels} on {x.dtype}')
+            y = conv(x)
+        done = 1                                   # modules of the stage that have run
+        if autograd.bn_relu_pool_supported(y, bn):
+            pool = len(mods) > 3 and isinstance(mods[3], nn.MaxPool2d)
+            y = autograd.bn_relu_pool(y, bn, pool)
+            done = 4 if pool else 3
+        else:
+            autograd.note_fallback('AcousticModel BatchNorm+ReLU+MaxPool', f'{y.shape[1]} channels, {y.dtype}, channels_last={y.is_contiguous(memory_format=torch.channels_last)}')
+        for m in mods[done:]:
+            y = m(y)
+        return y
 
     def forward(self, in_feats):
         x = self._stage(self.layer3, self._stage(self.layer2, self._stage(self.layer1, in_feats)))
@@ -251,19 +245,12 @@ class AcousticModel(nn.Module):
             lin = self.fc1[0]
             B, C, T, F = x.shape
             w = lin.weight.view(lin.out_features, C, F).transpose(1, 2).reshape(lin.out_features, F * C)
-            from .autograd import linear, linear_supported, note_fallback
-            xin = x.permute(0, 2, 3, 1).reshape(B, T, F * C)
-            if linear_supported(xin, w):
-                y = linear(xin, w, lin.bias)
-            else:
-                note_fallback('AcousticModel.fc1', f'Linear {w.shape[1]} -> {w.shape[0]}, {xin.dtype}')
-                y = torch.nn.functional.linear(xin, w, lin.bias)
+            y = autograd.linear_layer('AcousticModel.fc1', x.permute(0, 2, 3, 1).reshape(B, T, F * C), w, lin.bias)
             for m in list(self.fc1)[1:]:
                 y = m(y)
             return y
         if self.training and x.is_cuda:
-            from .autograd import note_fallback
-            note_fallback('AcousticModel.fc1', 'conv map not in channels-last layout')
+            autograd.note_fallback('AcousticModel.fc1', 'conv map not in channels-last layout')
         x = x.transpose(-3, -2).flatten(-2)
         return self.fc1(x)
 
@@ -286,15 +273,11 @@ class LanguageModel(nn.Module):
     def forward(self, in_feats):
         # differentiable path on a GPU (training, or eval outside the engine): both directions' recurrence is one persistent HIP
         # kernel forward and one backward (amt_tools_amd/autograd.py) instead of MIOpen's per-time-step LSTM
-        from .autograd import HIDDEN_SIZES
-        if (in_feats.is_cuda and in_feats.dtype == torch.float32 and self.num_directions == 2 and self.hidden_size in HIDDEN_SIZES
-                and self.mlm.num_layers == 1 and self.use_hip_autograd):
-            from .autograd import bilstm
-            return bilstm(in_feats, self.mlm)
+        if autograd.bilstm_supported(in_feats, self.mlm, self.use_hip_autograd):
+            return autograd.bilstm(in_feats, self.mlm)
         if in_feats.is_cuda and torch.is_grad_enabled():
-            from .autograd import note_fallback
-            note_fallback('LanguageModel', f'nn.LSTM hidden {self.hidden_size} x {self.num_directions} directions, {in_feats.dtype}, '
-                                           f'use_hip_autograd={self.use_hip_autograd}')
+            autograd.note_fallback('LanguageModel', f'nn.LSTM hidden {self.hidden_size} x {self.num_directions} directions, {in_feats.dtype}, '
+                                                    f'use_hip_autograd={self.use_hip_autograd}')
         return self.mlm(in_feats)[0]
 
 
@@ -666,8 +649,7 @@ class OnsetsFrames(TranscriptionModel):
         output = dict()
         fb0 = None
         if feats.is_cuda and self.training and torch.is_grad_enabled():
-            from . import autograd as _ag
-            fb0 = _ag.fallback_total()
+            fb0 = autograd.fallback_total()
         if self._overlap_heads(feats):
             # The detector heads only meet at the refinement stage (onsetsframes.py:118-134): the pitch head runs on a side stream beside the
             # recurrent heads -- acoustic model + a 625-step BiLSTM that keeps 4 of the 256 CUs busy at 8 clips; autograd replays
@@ -700,7 +682,7 @@ class OnsetsFrames(TranscriptionModel):
         joint = torch.cat(heads + [multi_pitch], -1)
         output[tools.KEY_MULTIPITCH] = self.adjoin(joint)
         if fb0 is not None:
-            self.__dict__['_fb_last_forward'] = _ag.fallback_total() - fb0     # 0: the next training forward may overlap its heads
+            self.__dict__['_fb_last_forward'] = autograd.fallback_total() - fb0    # 0: the next training forward may overlap its heads
             if self.__dict__['_fb_last_forward']:
                 self.__dict__['_overlap_latched_off'] = True                   # sticky: see _overlap_heads
         return output
@@ -718,8 +700,7 @@ class OnsetsFrames(TranscriptionModel):
             return False
         if os.environ.get('AMTX_TRAIN_OVERLAP', '1') == '0' or not self.__dict__.get('overlap_heads', True):
             return False
-        from . import autograd as ag
-        if not ag.USE_HIP_DENSE:
+        if not autograd.USE_HIP_DENSE:
             return False
         # Several ranks (round 6): on by default too.  Rounds 4 - 5 kept it off under a real process group "until an 8-GPU soak has run"; what
         # is known since: the round-1 hang needs MIOpen + hipBLASLt kernels on the two streams (none in this step); 300 steps with a one-rank
@@ -743,9 +724,8 @@ class OnsetsFrames(TranscriptionModel):
         """Onset (and offset) detector heads: (onsets, offsets or None)."""
         if self._grouped_recurrences(feats):
             # the onset and offset heads are independent: their two recurrences run as ONE grouped launch each way
-            from .autograd import bilstm_multi
             (am_on, lm_on, lb_on), (am_off, lm_off, lb_off) = self.onset_head, self.offset_head
-            l_on, l_off = bilstm_multi([am_on(feats), am_off(feats)], [lm_on.mlm, lm_off.mlm])
+            l_on, l_off = autograd.bilstm_multi([am_on(feats), am_off(feats)], [lm_on.mlm, lm_off.mlm])
             return lb_on(l_on), lb_off(l_off)
         onsets = self.onset_head(feats)
         offsets = self.offset_head(feats) if self.has_offsets else None
@@ -753,12 +733,11 @@ class OnsetsFrames(TranscriptionModel):
 
     def _grouped_recurrences(self, feats):
         """Training on a GPU with an offset head whose LSTM and the onset head's are both on the HIP autograd path."""
-        if not (self.has_offsets and feats.is_cuda and self.training and feats.dtype == torch.float32):
+        if not (self.has_offsets and self.training):
             return False
-        from .autograd import HIDDEN_SIZES
         lms = (self.onset_head[1], self.offset_head[1])
-        return all(isinstance(lm, LanguageModel) and lm.use_hip_autograd and lm.num_directions == 2 and lm.mlm.num_layers == 1
-                   and lm.hidden_size in HIDDEN_SIZES for lm in lms) and lms[0].hidden_size == lms[1].hidden_size
+        return all(isinstance(lm, LanguageModel) and autograd.bilstm_supported(feats, lm.mlm, lm.use_hip_autograd)
+                   for lm in lms) and lms[0].hidden_size == lms[1].hidden_size
 
     def post_proc(self, batch):
         """Losses (when ground truth is present) + final piano rolls (onsetsframes.py:138-196)."""
@@ -967,12 +946,8 @@ class TabCNN(TranscriptionModel):
       sequence instead of once per window (3.5x less arithmetic at dim_in 192), logits and tablature come out of the same call.
       `precision` 'x3' (default: split-bf16, fp32-class logits) or 'bf16' (the throughput mode).
     * training on a CUDA device with the window view pre_proc makes (`use_hip_train`, on by default) -> the same shared-window
-      dataflow with gradients: the three convolutions as padded 3x3 convolutions over each whole sequence on the
-      split-bf16 training GEMMs (autograd.tab_conv3x3), ReLU between them as ATen glue, conv3's ReLU + 2x2 pool of every window in one
-      kernel (autograd.TabWindowPoolFunction), the module's own Dropouts, fc and the output layer on autograd.LinearFunction, and in
-      post_proc the grouped softmax loss with its gradient (autograd.SoftmaxGroupsLossFunction).  A CUDA training forward that cannot
-      take it (a contiguous copy of the windows, an unsupported layer, `use_hip_train` off) is recorded by autograd.note_fallback
-      ('TabCNN.train') and runs stock -- or raises under AMTX_STRICT_TRAINING=1.
+      dataflow with gradients on the kernels of amt_tools_amd/autograd.py (_forward_hip_train).  A CUDA training
+      forward that cannot take it (train_unsupported; the rules: DESIGN.md 5.14) is recorded under 'TabCNN.train' and runs stock.
     * everything else (CPU, eval with grad enabled, a contiguous copy of the windows in eval mode) -> stock torch ops, unchanged.  An
       inference call the engine would take but whose configuration it does not build is recorded by autograd.note_fallback."""
 
@@ -1024,7 +999,6 @@ class TabCNN(TranscriptionModel):
             return None
         why = self.engine_unsupported()
         if why is not None:
-            from . import autograd
             autograd.note_fallback('TabCNN.forward', f'no HIP engine for {why}')
             return None
         return view
@@ -1048,7 +1022,6 @@ class TabCNN(TranscriptionModel):
 
     def train_unsupported(self, feats):
         """Why a training forward on the CUDA tensor `feats` cannot take the shared-window HIP path, or None when it can."""
-        from . import autograd
         if not self.use_hip_train:
             return 'TabCNN.use_hip_train is off'
         if not autograd.USE_HIP_DENSE:
@@ -1067,13 +1040,15 @@ class TabCNN(TranscriptionModel):
         if not isinstance(self.conv[6], nn.MaxPool2d) or self.conv[6].kernel_size not in (2, (2, 2)):
             return 'conv.6 is not MaxPool2d((2, 2))'
         fc, out = self.dense[0], self.dense[-1].output_layer
-        if fc.weight.dtype != torch.float32 or fc.in_features % 4 or fc.out_features % 4 or out.in_features % 4:
+        # the output layer runs with its rows zero-padded to a multiple of 4 (_forward_hip_train): the rule is asked about that shape, so
+        # only its input width can fail it; its dtype has never been looked at (the module is converted as a whole)
+        n_out = out.out_features + (-out.out_features) % 4
+        if not (autograd.linear_takes(fc.weight.dtype, fc.in_features, fc.out_features) and autograd.linear_takes(fc.weight.dtype, out.in_features, n_out)):
             return f'dense layers {fc.in_features} -> {fc.out_features} -> {out.out_features}'
         return None
 
     def _forward_hip_train(self, feats):
         """The training forward on shared-window sequences: returns the (B, T, G*C) logits."""
-        from . import autograd
         view = tab_window_view(feats, self.frame_width)
         B, T = feats.shape[:2]
         sb, sc, sf, st = view['strides']
@@ -1096,7 +1071,6 @@ class TabCNN(TranscriptionModel):
     def forward(self, feats):
         self.__dict__.pop('_engine_tab', None)
         if self.training and torch.is_tensor(feats) and feats.is_cuda:
-            from . import autograd
             why = self.train_unsupported(feats)
             if why is None:
                 return {tools.KEY_TABLATURE: self._forward_hip_train(feats)}
@@ -1116,10 +1090,8 @@ class TabCNN(TranscriptionModel):
         logits = output[tools.KEY_TABLATURE]
         if tools.KEY_TABLATURE in batch:
             labels = batch[tools.KEY_TABLATURE]
-            if (self.training and self.use_hip_train and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3
-                    and tuple(labels.shape) == (logits.shape[0], head.num_groups, logits.shape[1])):
-                from .autograd import softmax_groups_loss
-                loss = softmax_groups_loss(logits, labels, head.num_groups, head.num_classes, head.weights)
+            if self.training and self.use_hip_train and autograd.softmax_groups_loss_supported(logits, labels, head.num_groups):
+                loss = autograd.softmax_groups_loss(logits, labels, head.num_groups, head.num_classes, head.weights)
             else:
                 loss = head.get_loss(logits, labels)
             output[tools.KEY_LOSS] = {tools.KEY_LOSS_TOTAL: loss}

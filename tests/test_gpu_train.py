@@ -613,3 +613,44 @@ def test_train_entry_points_launch_the_recorded_kernels(call, args):
             ran[kernel(e.key)] += e.count
     print(f'TRAINROUTE {case!r}: {dict(ran)}')
     assert want and ran == want, (case, [e.key for e in prof.key_averages()])
+
+
+@pytest.mark.parametrize('case', ['of1', 'of1 87 keys', 'of1 use_hip_bn off on the pitch head'])
+def test_fallbacks_of_a_training_step_are_those_of_the_recorded_dispatch(case, monkeypatch):
+    """tests/golden/train_dispatch.json is recorded on fake CUDA tensors (tests/train_dispatch_trace.py): here one real training step of the
+    same three models (OnsetsFrames, dim_in 32, model_complexity 2, 2 clips x 16 frames; 87 keys; use_hip_bn off on the pitch head) on one
+    stream has to record the (site, reason) sequence of the golden row of the same name, and give a finite loss."""
+    import json
+    import os
+    import sys
+    from amt_tools_amd import autograd as ag
+    from amt_tools_amd.models import OnsetsFrames
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, here)
+    import train_dispatch_trace as trace
+    with open(os.path.join(here, 'golden', 'train_dispatch.json')) as fh:
+        golden = json.load(fh)
+    assert golden['cases_sha256'] == trace.cases_sha256()
+    want = [tuple(e[1:]) for e in trace.expand(golden)[golden['names'].index(case)][0] if e[0] == 'fallback']
+    assert bool(want) == (case != 'of1')
+    monkeypatch.setenv('AMTX_TRAIN_OVERLAP', '0')
+    seen, note = [], ag.note_fallback
+    monkeypatch.setattr(ag, 'note_fallback', lambda site, reason: (seen.append((site, reason)), note(site, reason))[1])
+    keys = 87 if '87' in case else 88
+    torch.manual_seed(3)
+    model = OnsetsFrames(32, tools.PianoProfile(high=107 if keys == 87 else None), 1, 2, device='cuda:0')
+    model.change_device()
+    model.train()
+    if 'use_hip_bn' in case:
+        model.pitch_head[0].use_hip_bn = False
+    batch = {tools.KEY_FEATS: torch.rand(2, 1, 32, 16), tools.KEY_MULTIPITCH: (torch.rand(2, keys, 16) < 0.05).float(),
+             tools.KEY_ONSETS: (torch.rand(2, keys, 16) < 0.02).float()}
+    try:
+        loss = model.run_on_batch(batch)[tools.KEY_LOSS][tools.KEY_LOSS_TOTAL]
+        loss.backward()
+        torch.cuda.synchronize()
+    finally:
+        ag.reset_fallbacks()
+    print(f'DISPATCH {case!r}: {seen}')
+    assert seen == want, (seen, want)
+    assert bool(torch.isfinite(loss))
