@@ -183,13 +183,24 @@ def _bank_of(module, clips, what):
     return bank
 
 
-class _SpecPlanOwner(object):
-    """Lazily created amtx_spec_plan (device tables) shared by STFT / MelSpec instances."""
+class _PlanOwner(object):
+    """Lazily created plans (device tables) of a feature module, one per device index.  A subclass names its ABI prefix (`<_ABI>_create` /
+    `_destroy`), its "no GPU visible" text, what pickling drops, and states its plan ONCE: _plan_args()."""
+
+    _ABI = None                 # 'amtx_spec_plan' / 'amtx_cqt_plan'
+    _NO_GPU = None              # the text for a process that sees no GPU
+    _TRANSIENT = ('_plans',)    # __dict__ keys that hold device pointers or tensors: never pickled (DataLoader workers, torch.save)
 
     def _plan_args(self):
+        """The plan as a tuple of plain Python values: the arguments `<_ABI>_create` is called with (_create_args) AND the identity _same_plan
+        compares -- one list, so a plan parameter cannot be in the one and not in the other."""
         raise NotImplementedError
 
+    def _create_args(self):
+        return self._plan_args()
+
     def _same_plan(self, other):
+        """What lets the clips of `other`'s bank run under this module."""
         return type(other) is type(self) and other._plan_args() == self._plan_args()
 
     def _get_plan(self, device=None):
@@ -203,9 +214,9 @@ class _SpecPlanOwner(object):
         plan = plans.get(index)
         if plan is None:
             if not torch.cuda.is_available():
-                raise _lib.AmtxError('no GPU visible: the spectral front-end has no CPU fallback')
+                raise _lib.AmtxError(self._NO_GPU)
             handle = C.c_void_p()
-            _lib.call('amtx_spec_plan_create', C.byref(handle), *self._plan_args(), device=index)
+            _lib.call(self._ABI + '_create', C.byref(handle), *self._create_args(), device=index)
             plan = plans[index] = handle
         return plan
 
@@ -216,18 +227,45 @@ class _SpecPlanOwner(object):
         """Follow the model to its device (TranscriptionModel.change_device propagates here through SpectralFrontend)."""
         self.device = device
 
-    def __getstate__(self):   # plans hold device pointers: never pickle them (DataLoader workers, torch.save)
+    def __getstate__(self):
         state = dict(self.__dict__)
-        state.pop('_plans', None)
-        state.pop('_prof_events', None)
+        for key in self._TRANSIENT:
+            state.pop(key, None)
         return state
 
     def __del__(self):
         for plan in self.__dict__.get('_plans', {}).values():
             try:
-                _lib.call('amtx_spec_plan_destroy', plan)
+                _lib.call(self._ABI + '_destroy', plan)
             except Exception:
                 pass
+
+    def _workspace_for(self, need, device):
+        """The module's one kernel workspace: kept from call to call, replaced when it is too small or lives on another device."""
+        ws = self.__dict__.get('_workspace')
+        if ws is None or ws.numel() < need or ws.device != device:
+            self.__dict__['_workspace'] = None
+            ws = self.__dict__['_workspace'] = _lib.alloc_workspace(need, device)
+        return ws
+
+    def _process_host(self, audio):
+        import torch
+        dev = torch.device('cuda', self._device_index())
+        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(dev).unsqueeze(0)
+        return self.process_batch(x)[0].cpu().numpy()
+
+    def frontend(self):
+        """nn.Module wrapper for `TranscriptionModel.frontend`: (B,1,N) audio -> (B,C,F,T) features."""
+        from .models import SpectralFrontend
+        return SpectralFrontend(self)
+
+
+class _SpecPlanOwner(_PlanOwner):
+    """The amtx_spec_plan shared by STFT / MelSpec instances."""
+
+    _ABI = 'amtx_spec_plan'
+    _NO_GPU = 'no GPU visible: the spectral front-end has no CPU fallback'
+    _TRANSIENT = ('_plans', '_prof_events')
 
     # ---- device path -------------------------------------------------------------------------
     def power_batch(self, audio):
@@ -312,17 +350,9 @@ class _SpecPlanOwner(object):
         return self.scale_batch(power, track_max, track_max, model_layout)
 
     def _process_host(self, audio, empty_rows):
-        import torch
         if audio.shape[-1] == 0:
             return np.zeros((1, empty_rows, 0))
-        dev = torch.device('cuda', self._device_index())
-        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(dev).unsqueeze(0)
-        return self.process_batch(x)[0].cpu().numpy()
-
-    def frontend(self):
-        """nn.Module wrapper for `TranscriptionModel.frontend`: (B,1,N) audio -> (B,1,F,T) features."""
-        from .models import SpectralFrontend
-        return SpectralFrontend(self)
+        return super()._process_host(audio)
 
 
 class STFT(WaveformWrapper, _SpecPlanOwner):
@@ -406,53 +436,30 @@ def _early_downsample_count(nyquist, filter_cutoff, hop_length, n_octaves):
     return min(c1, max(0, twos - n_octaves + 1))
 
 
-class _CqtPlanOwner(object):
-    """Lazily created amtx_cqt_plan shared by the VQT-family modules."""
+class _CqtPlanOwner(_PlanOwner):
+    """The amtx_cqt_plan shared by the VQT-family modules."""
 
-    def _cqt_args(self):
-        raise NotImplementedError
+    _ABI = 'amtx_cqt_plan'
+    _NO_GPU = 'no GPU visible: the CQT front-end has no CPU fallback'
+    _TRANSIENT = ('_plans', '_workspace')
+    _truncate = False           # HVQT: the harmonics are truncated to the smallest frame count
 
-    def _device_index(self):
-        return _index_of(self.device)
+    def _plan_args(self):
+        return (int(self.sample_rate), int(self.hop_length), float(self.fmin), int(self.n_bins), int(self.bins_per_octave), float(self.gamma),
+                tuple(float(h) for h in getattr(self, 'harmonics', (1.0,))), int(self._truncate), int(str(self.librosa_version).startswith('0.9')))
+
+    def _create_args(self):
+        args = self._plan_args()
+        harmonics = args[6]                                  # the ABI takes them as (const double*, count)
+        return args[:6] + ((C.c_double * len(harmonics))(*harmonics), len(harmonics)) + args[7:]
 
     def change_device(self, device):
         self.device = device
-        for m in getattr(self, 'modules', []):
+        for m in getattr(self, 'modules', []):              # HVQT / HCQT: the per-harmonic VQTs
             m.device = device
 
-    def _get_plan(self, device=None):
-        """Per-device plan cache, see _SpecPlanOwner._get_plan."""
-        import torch
-        index = self._device_index() if device is None else _index_of(device)
-        plans = self.__dict__.setdefault('_plans', {})
-        plan = plans.get(index)
-        if plan is None:
-            if not torch.cuda.is_available():
-                raise _lib.AmtxError('no GPU visible: the CQT front-end has no CPU fallback')
-            fmin, harmonics, truncate = self._cqt_args()
-            arr = (C.c_double * len(harmonics))(*[float(h) for h in harmonics])
-            handle = C.c_void_p()
-            _lib.call('amtx_cqt_plan_create', C.byref(handle), int(self.sample_rate), int(self.hop_length), float(fmin), int(self.n_bins),
-                      int(self.bins_per_octave), float(self.gamma), arr, len(harmonics), int(truncate),
-                      int(str(self.librosa_version).startswith('0.9')), device=index)
-            plan = plans[index] = handle
-        return plan
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_plans', None)
-        state.pop('_workspace', None)
-        return state
-
-    def __del__(self):
-        for plan in self.__dict__.get('_plans', {}).values():
-            try:
-                _lib.call('amtx_cqt_plan_destroy', plan)
-            except Exception:
-                pass
-
-    def process_batch(self, audio, model_layout=False):
-        """(B, N) float32 CUDA tensor -> (B, C, F, T) float32 features on the device."""
+    def _audio_args(self, audio, max_harmonics=None):
+        """Check the audio, get its device's plan, the sizes and the workspace: (plan, audio, N, row stride, B), T, H, workspace."""
         import torch
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2
         audio = audio.contiguous()
@@ -460,13 +467,27 @@ class _CqtPlanOwner(object):
         plan = self._get_plan(audio.device)
         T = _lib.call('amtx_cqt_num_frames', plan, N)
         H = _lib.call('amtx_cqt_num_harmonics', plan)
-        need = _lib.call('amtx_cqt_workspace_bytes', plan, B, N)
-        ws = self.__dict__.get('_workspace')
-        if ws is None or ws.numel() < need or ws.device != audio.device:
-            self.__dict__['_workspace'] = None
-            ws = self.__dict__['_workspace'] = _lib.alloc_workspace(need, audio.device)
-        out = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=audio.device)
-        _lib.call('amtx_cqt_forward', plan, audio, N, audio.stride(0) if B > 1 else N, B, int(bool(self.decibels)), ws, ws.numel(), out, device=audio.device)
+        assert max_harmonics is None or H <= max_harmonics
+        ws = self._workspace_for(_lib.call('amtx_cqt_workspace_bytes', plan, B, N), audio.device)
+        return (plan, audio, N, audio.stride(0) if B > 1 else N, B), T, H, ws
+
+    def _staged16(self, entry, args, B, T, split, device):
+        """The (B, T, F, 8) bfloat16 map of `entry`(*args, out), or with `split` the two planes (2, B, T, F, 8) of `entry`_split."""
+        import torch
+        out = torch.empty(((2,) if split else ()) + (B, T, self.n_bins, 8), dtype=torch.bfloat16, device=device)
+        if split:
+            _lib.call(entry + '_split', *args, out, out[0].numel(), device=device)
+        else:
+            _lib.call(entry, *args, out, device=device)
+        return out
+
+    def process_batch(self, audio, model_layout=False):
+        """(B, N) float32 CUDA tensor -> (B, C, F, T) float32 features on the device."""
+        import torch
+        args, T, H, ws = self._audio_args(audio)
+        device = args[1].device
+        out = torch.empty((args[-1], H, self.n_bins, T), dtype=torch.float32, device=device)
+        _lib.call('amtx_cqt_forward', *args, int(bool(self.decibels)), ws, ws.numel(), out, device=device)
         return out
 
     def process_batch16(self, audio, split=False):
@@ -475,61 +496,33 @@ class _CqtPlanOwner(object):
         C .. 7 zero) -- what OnsetsFrames.run_on_batch hands its engine when the model takes it (amtx_of_forward_feats16).
         split=True: (2, B, T, F, 8) -- plane 0 that map, plane 1 = bf16(feature - plane 0): the two planes the x3 engine multiplies with
         (amtx_cqt_forward16_split)."""
-        import torch
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2
-        audio = audio.contiguous()
-        B, N = audio.shape
-        plan = self._get_plan(audio.device)
-        T = _lib.call('amtx_cqt_num_frames', plan, N)
-        assert _lib.call('amtx_cqt_num_harmonics', plan) <= 8
-        need = _lib.call('amtx_cqt_workspace_bytes', plan, B, N)
-        ws = self.__dict__.get('_workspace')
-        if ws is None or ws.numel() < need or ws.device != audio.device:
-            self.__dict__['_workspace'] = None
-            ws = self.__dict__['_workspace'] = _lib.alloc_workspace(need, audio.device)
-        out = torch.empty(((2,) if split else ()) + (B, T, self.n_bins, 8), dtype=torch.bfloat16, device=audio.device)
-        args = (plan, audio, N, audio.stride(0) if B > 1 else N, B, int(bool(self.decibels)), ws, ws.numel(), out)
-        if split:
-            _lib.call('amtx_cqt_forward16_split', *args, out[0].numel(), device=audio.device)
-        else:
-            _lib.call('amtx_cqt_forward16', *args, device=audio.device)
-        return out
+        args, T, _, ws = self._audio_args(audio, max_harmonics=8)
+        return self._staged16('amtx_cqt_forward16', args + (int(bool(self.decibels)), ws, ws.numel()), args[-1], T, split, args[1].device)
 
     # ---- clips cut from the resident pyramids of whole tracks (amt_tools_amd/tracks.py, include/amtx_pyramid.h) ---------------
-    def _clips_args(self, clips):
-        """(plan, audio, pyramid, track table, descriptors, B, T) of a PyramidClips of this module's plan; anything else raises."""
+    def _clips_args(self, clips, max_harmonics=None, workspace=True):
+        """(plan, audio, pyramid, track table, descriptors, B, T) of a PyramidClips of this module's plan, H and the workspace; anything
+        else raises."""
         from .tracks import PyramidClips
         if not isinstance(clips, PyramidClips):
             raise NotImplementedError(f'{type(self).__name__}: the decimation pyramid has no clip form over raw audio (clips of the CQT family '
                                       f'come from a tracks.PyramidBank, those of a TrackBank from STFT / MelSpec)')
         bank = _bank_of(self, clips, 'pyramids and track maxima')
         audio = bank.audio
-        return self._get_plan(audio.device), audio, bank.pyramid, bank.table, clips.desc_dev, clips.num_clips, clips.num_frames
-
-    def _plan_key(self):
-        fmin, harmonics, truncate = self._cqt_args()
-        return (int(self.sample_rate), int(self.hop_length), float(fmin), int(self.n_bins), int(self.bins_per_octave), float(self.gamma),
-                tuple(float(h) for h in harmonics), bool(truncate), str(self.librosa_version).startswith('0.9'))
-
-    def _same_plan(self, other):
-        return type(other) is type(self) and other._plan_key() == self._plan_key()
-
-    def _clips_workspace(self, plan, B, T, device):
-        need = _lib.call('amtx_cqt_clips_workspace_bytes', plan, B, T)
-        ws = self.__dict__.get('_workspace')
-        if ws is None or ws.numel() < need or ws.device != device:
-            self.__dict__['_workspace'] = None
-            ws = self.__dict__['_workspace'] = _lib.alloc_workspace(need, device)
-        return ws
+        plan, B, T = self._get_plan(audio.device), clips.num_clips, clips.num_frames
+        H = _lib.call('amtx_cqt_num_harmonics', plan)
+        assert max_harmonics is None or H <= max_harmonics
+        ws = self._workspace_for(_lib.call('amtx_cqt_clips_workspace_bytes', plan, B, T), audio.device) if workspace else None
+        return (plan, audio, bank.pyramid, bank.table, clips.desc_dev, B, T), H, ws
 
     def power_clips(self, clips):
         """A PyramidClips -> (power (B, H, F, T) fp32, db_ref (B, H)): column t of clip b is frame first_frame[b] + t of its track's power
         map, bit for bit; db_ref holds the maxima of the clips' TRACKS per harmonic (PyramidBank.db_ref)."""
         import torch
-        plan, audio, pyramid, table, desc, B, T = self._clips_args(clips)
-        H = _lib.call('amtx_cqt_num_harmonics', plan)
-        power = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=audio.device)
-        _lib.call('amtx_cqt_power_clips', plan, audio, pyramid, table, desc, B, T, power, device=audio.device)
+        args, H, _ = self._clips_args(clips, workspace=False)
+        B, T, device = args[-2], args[-1], args[1].device
+        power = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=device)
+        _lib.call('amtx_cqt_power_clips', *args, power, device=device)
         return power, clips.db_ref
 
     def process_clips(self, clips, model_layout=False):
@@ -537,37 +530,17 @@ class _CqtPlanOwner(object):
         [first_frame, first_frame + num_frames) of the tracks' own feature maps, bit for bit -- each harmonic scaled against its maximum
         over the whole track, edge frames from the track's samples (SURVEY finding F7)."""
         import torch
-        plan, audio, pyramid, table, desc, B, T = self._clips_args(clips)
-        H = _lib.call('amtx_cqt_num_harmonics', plan)
-        ws = self._clips_workspace(plan, B, T, audio.device)
-        out = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=audio.device)
-        _lib.call('amtx_cqt_clips', plan, audio, pyramid, table, desc, B, T, clips.db_ref, int(bool(self.decibels)), ws, ws.numel(), out,
-                  device=audio.device)
+        args, H, ws = self._clips_args(clips)
+        B, T, device = args[-2], args[-1], args[1].device
+        out = torch.empty((B, H, self.n_bins, T), dtype=torch.float32, device=device)
+        _lib.call('amtx_cqt_clips', *args, clips.db_ref, int(bool(self.decibels)), ws, ws.numel(), out, device=device)
         return out.transpose(-1, -2) if model_layout else out
 
     def process_clips16(self, clips, split=False):
         """A PyramidClips -> (B, T, F, 8) bfloat16, or (2, B, T, F, 8) with `split`: process_batch16 of the clips' tracks, sliced on T."""
-        import torch
-        plan, audio, pyramid, table, desc, B, T = self._clips_args(clips)
-        assert _lib.call('amtx_cqt_num_harmonics', plan) <= 8
-        ws = self._clips_workspace(plan, B, T, audio.device)
-        out = torch.empty(((2,) if split else ()) + (B, T, self.n_bins, 8), dtype=torch.bfloat16, device=audio.device)
-        args = (plan, audio, pyramid, table, desc, B, T, clips.db_ref, int(bool(self.decibels)), ws, ws.numel(), out)
-        if split:
-            _lib.call('amtx_cqt_clips16_split', *args, out[0].numel(), device=audio.device)
-        else:
-            _lib.call('amtx_cqt_clips16', *args, device=audio.device)
-        return out
-
-    def _process_host(self, audio):
-        import torch
-        dev = torch.device('cuda', self._device_index())
-        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(dev).unsqueeze(0)
-        return self.process_batch(x)[0].cpu().numpy()
-
-    def frontend(self):
-        from .models import SpectralFrontend
-        return SpectralFrontend(self)
+        args, _, ws = self._clips_args(clips, max_harmonics=8)
+        return self._staged16('amtx_cqt_clips16', args + (clips.db_ref, int(bool(self.decibels)), ws, ws.numel()), args[-2], args[-1], split,
+                              args[1].device)
 
 
 class VQT(FeatureModule, _CqtPlanOwner):
@@ -586,9 +559,6 @@ class VQT(FeatureModule, _CqtPlanOwner):
         self.n_octs = int(np.ceil(float(self.n_bins) / self.bins_per_octave))
         self.librosa_version = str(librosa_version)
         self.device = device
-
-    def _cqt_args(self):
-        return self.fmin, [1.0], False
 
     def get_early_ds_count(self):
         fmax = self.fmin * 2.0 ** ((self.n_bins - 1) / self.bins_per_octave)
@@ -656,8 +626,7 @@ class HVQT(FeatureModule, _CqtPlanOwner):
         self.librosa_version = str(librosa_version)
         self.device = device
 
-    def _cqt_args(self):
-        return self.fmin, self.harmonics, True
+    _truncate = True
 
     def get_expected_frames(self, audio):
         return min(module.get_expected_frames(audio) for module in self.modules)

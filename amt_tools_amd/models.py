@@ -24,6 +24,7 @@ config 2 names: 2.8x the frames/s, sigmoid outputs within 7e-3, 1.4e-3 of the th
 tests/test_gpu_model.py print both) -- opt in with `precision='bf16'`.  `'f16'` exists only in a library built with AMTX_BUILD_F16=1.
 """
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -58,6 +59,7 @@ class TranscriptionModel(nn.Module):
     # ---- engine management (device handles never enter state_dict / pickles, SURVEY finding F11) ----
     _engine_class = None           # the subclass's _EngineBase
     _transient = ('_engine',)      # __dict__ keys that live only between calls on one device: subclasses extend, __getstate__ drops them
+    _engine_stages = False         # the engine's first kernel can stage the features itself: the deferred forms of feature_route exist
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -92,37 +94,47 @@ class TranscriptionModel(nn.Module):
 
     def pre_proc(self, batch):
         """To-device copy (the caller's dict is not modified) + optional front-end on the raw audio
-        (models/common.py:83-122)."""
+        (models/common.py:83-122).  What is staged from the audio, and by which method of the front-end's module, is feature_route's answer
+        (DESIGN.md 5.15); a deferred form (PendingFeatures) goes under KEY_FEATS as it is."""
         batch = tools.dict_to_device(batch, self.device)
         audio = tools.unpack_dict(batch, tools.KEY_AUDIO)
         feats = tools.unpack_dict(batch, tools.KEY_FEATS)
-        from .tracks import _Clips
-        if isinstance(audio, _Clips):
-            # clips cut from device-resident tracks: the slices of the tracks' own feature maps (track-level dB scale, SURVEY F7)
-            frontend_feats = self._clips_module(audio).process_clips(audio, model_layout=True).transpose(-1, -2)
-            feats = frontend_feats if feats is None else torch.cat((feats, frontend_feats), dim=1)
-        elif audio is not None and len(self.frontend):
-            frontend_feats = self.frontend(audio.unsqueeze(-2))
-            feats = frontend_feats if feats is None else torch.cat((feats, frontend_feats), dim=1)
+        route = self._feature_route(batch, audio)
+        if route.source is not None:
+            staged = self._stage_features(route, audio)
+            feats = staged if feats is None else torch.cat((feats, staged), dim=1)
         batch[tools.KEY_FEATS] = feats
         return batch
 
-    def _clips_module(self, clips):
-        """The feature module that turns a TrackClips / PyramidClips batch entry into features: the model's ONE SpectralFrontend, over an
-        STFT / MelSpec for a TrackClips and over a CQT-family module for a PyramidClips, on the device the clips' bank lives on.  Anything
-        else raises -- clips are never silently skipped."""
-        from .features import _SpecPlanOwner, _CqtPlanOwner, _index_of
-        from .tracks import PyramidClips
-        module = self.frontend[0].module if len(self.frontend) == 1 and isinstance(self.frontend[0], SpectralFrontend) else None
-        if isinstance(clips, PyramidClips):
-            if not isinstance(module, _CqtPlanOwner):
-                raise TypeError('a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend; clips of a PyramidBank need '
-                                'one over a CQT / VQT / HCQT / HVQT module')
-        elif not isinstance(module, _SpecPlanOwner):
-            raise TypeError('a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend over an STFT / MelSpec module')
-        if torch.device(self.device).type != 'cuda' or _index_of(self.device) != clips.device.index:
-            raise ValueError(f'the clips live on {clips.device}, the model on {self.device}')
-        return module
+    def _feature_route(self, batch, audio):
+        """feature_route of this model and batch: the facts are gathered here, the rules are there.  The two switches are read per call."""
+        from .tracks import _Clips, PyramidClips
+        clips = isinstance(audio, _Clips)
+        one = len(self.frontend) == 1 and isinstance(self.frontend[0], SpectralFrontend)
+        return feature_route(
+            training=self.training, inside=self._engine_stages and bool(self.__dict__.get('_in_run_on_batch')), n_frontends=len(self.frontend),
+            module=self.frontend[0].module if one else None, defer_db_scale=os.environ.get('AMTX_DEFER_DB_SCALE', '1') != '0',
+            cqt_feats16=os.environ.get('AMTX_CQT_FEATS16', '1') != '0',
+            source=None if audio is None else 'audio' if not clips else 'pyramid_clips' if isinstance(audio, PyramidClips) else 'track_clips',
+            audio_dims=audio.dim() if torch.is_tensor(audio) else None, has_feats=tools.query_dict(batch, tools.KEY_FEATS), device=self.device,
+            clips_device=audio.device if clips else None, dim_in=self.dim_in, in_channels=self.in_channels,
+            engine=lambda question: getattr(self._get_engine(audio.device), question)())
+
+    def _stage_features(self, route, audio):
+        """What `route` makes of `audio`: the (B,C,F,T) feature map, or the PendingFeatures of a deferred form."""
+        source, form, module = route
+        if (source, form) == ('audio', 'feats'):
+            return self.frontend(audio.unsqueeze(-2))       # any nn.Sequential; a SpectralFrontend calls STAGING's process_batch
+        stage = getattr(module, STAGING[source, form])
+        if form == 'feats':
+            # clips cut from device-resident tracks: the slices of the tracks' own feature maps (track-level dB scale, SURVEY F7)
+            return stage(audio, model_layout=True).transpose(-1, -2)
+        if source == 'audio':
+            audio = audio.float()
+        if form == 'power':
+            # (clips: their own maximum = the reference = the TRACK's maximum)
+            return PendingFeatures(module, *stage(audio))
+        return PendingFeatures16(module, stage(audio, split=(form == 'feats16_split')), audio, source=source)
 
     def forward(self, feats):
         raise NotImplementedError
@@ -340,15 +352,84 @@ def _pick_side_stream(device, candidates=6, spins=20, spin_cycles=20000):
     return first or torch.cuda.Stream(device=device)
 
 
+FeatureRoute = collections.namedtuple('FeatureRoute', 'source form module')
+
+# (source, form) -> the method of the front-end's module that stages it.  ('audio', 'feats') is reached through
+# `model.frontend` itself, which may hold anything; the 'feats' rows are also what a deferred form materializes through.
+STAGING = {('audio', 'feats'): 'process_batch', ('audio', 'power'): 'power_batch',
+           ('audio', 'feats16'): 'process_batch16', ('audio', 'feats16_split'): 'process_batch16',
+           ('track_clips', 'feats'): 'process_clips', ('track_clips', 'power'): 'power_clips',
+           ('pyramid_clips', 'feats'): 'process_clips', ('pyramid_clips', 'feats16'): 'process_clips16', ('pyramid_clips', 'feats16_split'): 'process_clips16'}
+# form -> the engine entry point that takes it (_OFEngine.forward)
+ENTRY_POINTS = {'feats': 'amtx_of_forward', 'power': 'amtx_of_forward_power', 'feats16': 'amtx_of_forward_feats16', 'feats16_split': 'amtx_of_forward_feats16'}
+_CLIPS_FAMILY = {'track_clips': 'spec', 'pyramid_clips': 'cqt'}
+_CLIPS_NEED = {'track_clips': 'a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend over an STFT / MelSpec module',
+               'pyramid_clips': 'a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend; clips of a PyramidBank need '
+                                'one over a CQT / VQT / HCQT / HVQT module'}
+
+
+def feature_route(*, training, inside, n_frontends, module, defer_db_scale, cqt_feats16, source, audio_dims, has_feats, device, clips_device,
+                  dim_in, in_channels, engine):
+    """How a batch's audio entry becomes the model's features: FeatureRoute(source, form, module).  A pure function of plain facts.
+      training, inside       the model's mode; inside run_on_batch or not
+      n_frontends, module    len(model.frontend); the module of its ONE SpectralFrontend, or None when it is anything else
+      defer_db_scale, cqt_feats16   the switches AMTX_DEFER_DB_SCALE / AMTX_CQT_FEATS16 (False = set to 0)
+      source, audio_dims     what the batch holds under KEY_AUDIO: 'audio' (audio_dims: dim() of a tensor, else None) | 'track_clips' |
+                             'pyramid_clips' | None
+      has_feats              KEY_FEATS is in the batch too
+      device, clips_device   the model's device; the device the clips' bank lives on
+      dim_in, in_channels    the model's
+      engine                 engine('fuses_db_scale') / engine('takes_feats16'): asked only where a deferred form hangs on the answer, so the
+                             engine is created exactly there.
+    source: what is staged (None: nothing -- no audio, or a tensor and no front-end).  form: 'feats' = the ordinary (B,C,F,T) map;
+    'power' = a dB-scaled STFT / MelSpec stops after its power kernel and the engine's first conv scales (PendingFeatures); 'feats16' /
+    'feats16_split' = a CQT-family module writes the conv kernel's own staging format, one plane or the two of x3 (PendingFeatures16).
+    The deferred forms exist inside run_on_batch in eval mode on a GPU, for audio alone, as a 2-D tensor or as clips of the module's family.
+    Clips need the ONE SpectralFrontend over a module of their family, on the device their bank lives on: anything else raises -- clips are
+    never silently skipped.  A PyramidClips is checked before the engine is asked, a TrackClips after: which error a wrong batch gets, and
+    whether an engine exists by then, is part of the behaviour (tests/golden/feature_handoff.json)."""
+    from .features import _SpecPlanOwner, _CqtPlanOwner, _index_of
+    family = 'cqt' if isinstance(module, _CqtPlanOwner) else 'spec' if isinstance(module, _SpecPlanOwner) else None
+    clips = source in _CLIPS_FAMILY
+    on_gpu = torch.device(device).type == 'cuda'
+
+    def check_clips():
+        if family != _CLIPS_FAMILY[source]:
+            raise TypeError(_CLIPS_NEED[source])
+        if not on_gpu or _index_of(device) != clips_device.index:
+            raise ValueError(f'the clips live on {clips_device}, the model on {device}')
+
+    form = 'feats'
+    if (inside and not training and defer_db_scale and not has_feats and on_gpu
+            and (cqt_feats16 if family == 'cqt' else family == 'spec' and getattr(module, 'decibels', False))
+            and (family == _CLIPS_FAMILY[source] if clips else audio_dims == 2)):
+        if family == 'cqt':
+            if clips:
+                check_clips()
+            planes = engine('takes_feats16')
+            # amtx_of_forward_feats16 takes a bare (B,T,F,8) pointer and indexes it with the MODEL's dim_in / in_channels: a front-end of
+            # another shape goes through the ordinary path, whose strides and shapes are explicit (and which raises on a mismatch)
+            if planes and int(getattr(module, 'n_bins', -1)) == int(dim_in) and int(module.get_num_channels()) == int(in_channels):
+                form = 'feats16_split' if planes == 2 else 'feats16'
+        elif engine('fuses_db_scale'):
+            form = 'power'
+    if clips:
+        check_clips()
+    elif not n_frontends:
+        source = None
+    return FeatureRoute(source, form, module)
+
+
 class PendingFeatures(object):
-    """What OnsetsFrames.pre_proc puts under KEY_FEATS inside run_on_batch when the dB scaling of the front-end is deferred into the
-    engine's first conv kernel (amtx_of_forward_power): the raw power mel spectrogram (B,T,F), the clips' own maxima (B,) and the
-    FeatureModule that would finish them.  `materialize()` is the ordinary feature tensor (B,1,T,F), bit-identical to what the conv
-    kernel stages."""
+    """What pre_proc puts under KEY_FEATS for a deferred form of feature_route: its `form`, what the engine reads and the FeatureModule
+    (`module`) that would finish it.  This class is form 'power' -- the dB scaling of the front-end is deferred into the engine's first conv
+    kernel (amtx_of_forward_power): the raw power mel spectrogram (B,T,F), the clips' own maxima (B,) and, optionally, (B,) reference powers
+    for the dB scale (track-level reference; None = each clip's own maximum).  `materialize()` is the ordinary feature tensor
+    (B,1,T,F), bit-identical to what the conv kernel stages."""
 
     def __init__(self, module, power, clip_max, ref=None):
-        # ref: optional (B,) reference powers for the dB scale (track-level reference, SURVEY F7); None = each clip's own maximum
-        self.module, self.power, self.clip_max, self.ref = module, power, clip_max, ref
+        self.module, self.form = module, 'power'
+        self.power, self.clip_max, self.ref = power, clip_max, ref
 
     @property
     def device(self):
@@ -359,22 +440,21 @@ class PendingFeatures(object):
 
 
 class PendingFeatures16(PendingFeatures):
-    """What OnsetsFrames.pre_proc puts under KEY_FEATS inside run_on_batch when a CQT-family front-end has written its features in the
-    first conv kernel's own staging format (FeatureModule.process_batch16 -> amtx_of_forward_feats16): (B,T,F,8) bfloat16, the harmonics
-    of a position side by side.  `materialize()` is the ordinary fp32 feature tensor as a (B,C,T,F) view, computed from the audio."""
+    """Forms 'feats16' / 'feats16_split': a CQT-family front-end has written its features in the first conv kernel's own staging format
+    (process_batch16 / process_clips16 -> amtx_of_forward_feats16): (B,T,F,8) bfloat16, the harmonics of a position side by side, or the two
+    planes (2,B,T,F,8) of the x3 engine.  `audio` is what they were computed from, a tensor or a PyramidClips (`source`); `materialize()` is
+    the ordinary fp32 feature tensor as a (B,C,T,F) view, computed from it."""
 
-    def __init__(self, module, feats16, audio):
-        self.module, self.feats16, self.audio = module, feats16, audio
+    def __init__(self, module, feats16, audio, source='audio'):
+        self.module, self.form = module, 'feats16_split' if feats16.dim() == 5 else 'feats16'
+        self.feats16, self.audio, self.source = feats16, audio, source
 
     @property
     def device(self):
         return self.feats16.device
 
     def materialize(self):
-        from .tracks import PyramidClips
-        if isinstance(self.audio, PyramidClips):                # clips cut from resident pyramids (OnsetsFrames._fused_features)
-            return self.module.process_clips(self.audio).transpose(-1, -2)
-        return self.module.process_batch(self.audio).transpose(-1, -2)
+        return getattr(self.module, STAGING[self.source, 'feats'])(self.audio).transpose(-1, -2)
 
 
 class _EngineBase(object):
@@ -471,16 +551,21 @@ class _OFEngine(_EngineBase):
         return bool(_lib.call('amtx_of_conv_stack_fused', self.handle, int(batch), int(num_frames)))
 
     def forward(self, feats, want_logits=True):
-        """feats: (B,C,T,F) fp32 CUDA tensor (any strides), or PendingFeatures.  Returns binary maps + raw logits."""
-        pending = feats if isinstance(feats, PendingFeatures) else None
-        pending16 = isinstance(pending, PendingFeatures16)
-        if pending16:
-            feats = pending.feats16                         # (B,T,F,8) or two planes (2,B,T,F,8): shape and device only
+        """feats: (B,C,T,F) fp32 CUDA tensor (any strides), or PendingFeatures.  Returns binary maps + raw logits.  The form says which entry
+        point runs (ENTRY_POINTS), where B and T are read and which strides go with the pointer."""
+        form = feats.form if isinstance(feats, PendingFeatures) else 'feats'
+        if form == 'feats':
+            B, _, T, _ = feats.shape
+            lead = (feats, *feats.stride(), B, T)
+        elif form == 'power':
+            clip_max, ref, feats = feats.clip_max, feats.ref, feats.power.unsqueeze(1)
+            B, _, T, _ = feats.shape
+            sb, _, st, sf = feats.stride()
+            lead = (feats, sb, st, sf, clip_max, ref, B, T)
+        else:
+            feats = feats.feats16                           # (B,T,F,8) or two planes (2,B,T,F,8): a bare pointer, shape and device only
             B, T = feats.shape[-4], feats.shape[-3]
-        elif pending is not None:
-            feats = pending.power.unsqueeze(1)
-        if not pending16:
-            B, Cc, T, Fd = feats.shape
+            lead = (feats, B, T)
         self._grow_workspace(_lib.call('amtx_of_workspace_bytes', self.handle, B, T), feats.device)
         n_out = self.n_out
         opts = dict(dtype=torch.float32, device=feats.device)
@@ -489,15 +574,8 @@ class _OFEngine(_EngineBase):
         lo = torch.empty((B, T, n_out), **opts) if want_logits else None
         lm = torch.empty((B, T, n_out), **opts) if want_logits else None
         lp = torch.empty((B, T, n_out), **opts) if want_logits else None
-        sb, sc, st, sf = (0, 0, 0, 0) if pending16 else feats.stride()
-        ws, outs = self.workspace, (onsets, multi_pitch, lo, lm, lp)
-        if pending16:
-            _lib.call('amtx_of_forward_feats16', self.handle, feats, B, T, ws, ws.numel(), *outs, device=feats.device)
-        elif pending is not None:
-            _lib.call('amtx_of_forward_power', self.handle, feats, sb, st, sf, pending.clip_max, pending.ref, B, T, ws, ws.numel(), *outs,
-                      device=feats.device)
-        else:
-            _lib.call('amtx_of_forward', self.handle, feats, sb, sc, st, sf, B, T, ws, ws.numel(), *outs, device=feats.device)
+        ws = self.workspace
+        _lib.call(ENTRY_POINTS[form], self.handle, *lead, ws, ws.numel(), onsets, multi_pitch, lo, lm, lp, device=feats.device)
         self._last = (B, T)
         return onsets, multi_pitch, lo, lm, lp
 
@@ -533,80 +611,15 @@ class OnsetsFrames(TranscriptionModel):
         self.adjoin = nn.Sequential(LanguageModel(self.dim_aj, self.dim_lm), LogisticBank(self.dim_lm, dim_out))
 
     _engine_class = _OFEngine
+    _engine_stages = True
     _transient = TranscriptionModel._transient + ('_engine_out', '_engine_offsets', '_side_stream', '_overlap_armed', '_fb_last_forward',
                                                   '_overlap_latched_off')
 
     def pre_proc(self, batch):
-        pending = self._deferred_scale(batch) if self.__dict__.get('_in_run_on_batch') else None
-        if pending is not None:
-            return pending
         batch = super().pre_proc(batch)
-        # frequency <-> time (onsetsframes.py:90); a view, the engine takes strides
-        batch[tools.KEY_FEATS] = batch[tools.KEY_FEATS].transpose(-1, -2)
-        return batch
-
-    def _deferred_scale(self, batch):
-        """Inside run_on_batch, eval mode, raw audio only, a front-end of this package on the GPU and an engine whose first conv stages the
-        features itself.  dB-scaled log-mel / STFT: the front-end stops after its power kernel and the dB scaling happens inside the conv
-        kernel (PendingFeatures; one kernel launch and one write + read of the feature tensor less per batch).  CQT family (HCQT / HVQT: one
-        channel per harmonic): the front-end writes its map in the conv kernel's own staging format (PendingFeatures16: one 16-bit plane for
-        the bf16 engine, the two planes of the split for x3).
-        Returns the pre-processed batch, or None when none of that holds (the ordinary path then runs)."""
-        if self.training or len(self.frontend) != 1 or not isinstance(self.frontend[0], SpectralFrontend):
-            return None
-        if os.environ.get('AMTX_DEFER_DB_SCALE', '1') == '0':     # A/B switch: front-end writes finished features (amtx_spec_scale)
-            return None
-        from .features import _SpecPlanOwner, _CqtPlanOwner
-        module = self.frontend[0].module
-        cqt = isinstance(module, _CqtPlanOwner)
-        if cqt:
-            # CQT family (HCQT: one channel per harmonic): the front-end writes the features in the conv kernel's staging format
-            if os.environ.get('AMTX_CQT_FEATS16', '1') == '0':     # A/B switch: fp32 (B,C,F,T) features, converted by the conv kernel
-                return None
-        elif not isinstance(module, _SpecPlanOwner) or not getattr(module, 'decibels', False):
-            return None
-        if tools.query_dict(batch, tools.KEY_FEATS) or not tools.query_dict(batch, tools.KEY_AUDIO):
-            return None
-        if torch.device(self.device).type != 'cuda':
-            return None
-        batch = tools.dict_to_device(batch, self.device)
-        audio = batch[tools.KEY_AUDIO]
-        from .tracks import TrackClips, PyramidClips
-        if isinstance(audio, PyramidClips):
-            # clips cut from resident pyramids: the conv kernel's staging format straight from the clip kernels, under the conditions of
-            # an audio tensor below; anything else is the ordinary path: pre_proc -> process_clips (or its error)
-            if not cqt:
-                return None
-            module = self._clips_module(audio)                       # (raises for a bank on another device)
-            form = self._get_engine(audio.device).takes_feats16()
-            if not form or int(getattr(module, 'n_bins', -1)) != int(self.dim_in) or int(module.get_num_channels()) != int(self.in_channels):
-                return None
-            batch[tools.KEY_FEATS] = PendingFeatures16(module, module.process_clips16(audio, split=(form == 2)), audio)
-            return batch
-        if isinstance(audio, TrackClips):
-            # clips cut from resident tracks: the same deferred dB scale, against the TRACK's maximum (own maximum = reference = track_max)
-            if cqt or not self._get_engine(audio.device).fuses_db_scale():
-                return None                                          # the ordinary path: pre_proc -> process_clips (or its error)
-            power, track_max = self._clips_module(audio).power_clips(audio)
-            batch[tools.KEY_FEATS] = PendingFeatures(module, power, clip_max=track_max)
-            return batch
-        if not (torch.is_tensor(audio) and audio.is_cuda and audio.dim() == 2):
-            return None
-        if cqt:
-            form = self._get_engine(audio.device).takes_feats16()
-            if not form:
-                return None
-            # amtx_of_forward_feats16 takes a bare (B,T,F,8) pointer and indexes it with the MODEL's dim_in / in_channels: a front-end of
-            # another shape goes through the ordinary path, whose strides and shapes are explicit (and which raises on a mismatch)
-            if int(getattr(module, 'n_bins', -1)) != int(self.dim_in) or int(module.get_num_channels()) != int(self.in_channels):
-                return None
-            audio = audio.float()
-            batch[tools.KEY_FEATS] = PendingFeatures16(module, module.process_batch16(audio, split=(form == 2)), audio)
-            return batch
-        if not self._get_engine(audio.device).fuses_db_scale():
-            return None
-        power, clip_max = module.power_batch(audio.float())
-        batch[tools.KEY_FEATS] = PendingFeatures(module, power, clip_max)
+        if not isinstance(batch[tools.KEY_FEATS], PendingFeatures):
+            # frequency <-> time (onsetsframes.py:90); a view, the engine takes strides
+            batch[tools.KEY_FEATS] = batch[tools.KEY_FEATS].transpose(-1, -2)
         return batch
 
     def run_on_batch(self, batch):
