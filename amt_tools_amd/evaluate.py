@@ -8,7 +8,7 @@ Every evaluator is split in two:
 * counting -- `counts(estimated, reference)` on host arrays (the reference's own float64 expressions, evaluate.py:815-829, :1246-1281,
   :1331-1334) or `counts_batch(estimated, reference)` on device tensors (ONE C-ABI call into csrc/eval.hip, a whole batch), and
 * `results_from_counts(counts)` -- the arithmetic from those few numbers to precision / recall / f-measure / tdr / accuracy.  Both paths end
-  in it, so they cannot disagree on the arithmetic.
+  in it, so they cannot disagree on the arithmetic.  (stage_batch / enqueue_batch / results_batch: its part in validate_batched.)
 
 Note matching restates mir_eval.transcription.match_notes (mir_eval is not required): see `note_edges`.  UNPINNED: the rules -- non-strict
 comparisons, 0.05 s onset tolerance, 50 cents, 0.05 s minimum offset tolerance, distances rounded to N_DECIMALS before they are compared --
@@ -20,6 +20,7 @@ import json
 import os
 import sys
 import warnings
+from collections import namedtuple
 from copy import deepcopy
 
 import numpy as np
@@ -268,6 +269,21 @@ class Evaluator(object):
     def process_track(self, estimated, reference, track=None):
         return self.track_results(self.evaluate(*self.unpack(estimated, reference)), track)
 
+    # The three moments of a batch in validate_batched (`batch`: its _Batch).  Here: what the map and tablature evaluators share
+    reference_dtype = np.float32
+
+    def stage_batch(self, refs, batch):
+        """The clips' unpacked references on their way to the device; what comes back is handed to the other two as `staged`."""
+        return batch.upload(np.stack([np.asarray(r) for r in refs]).astype(self.reference_dtype))
+
+    def enqueue_batch(self, staged, batch):
+        """Enqueue the counting on the model's stream -> tuple of device tensors to bring to the host."""
+        raise NotImplementedError(f'{type(self).__name__} has no batched counting')
+
+    def results_batch(self, staged, counts, batch):
+        """What enqueue_batch returned, as host arrays -> one results dictionary per clip."""
+        return [self.results_from_counts(c) for c in counts[0]]
+
     def finalize(self, writer, step=0):
         log_results(self.average_results(), writer, step, patterns=self.patterns, tag=tools.VAL)
         self.reset_results()
@@ -329,6 +345,17 @@ class LossWrapper(Evaluator):
     def evaluate(self, estimated, reference=None):
         return estimated
 
+    # an eval-mode batch carries no loss: nothing to stage or count, unpack()'s warning and an empty dictionary per clip
+    def stage_batch(self, refs, batch):
+        return None
+
+    def enqueue_batch(self, staged, batch):
+        return ()
+
+    def results_batch(self, staged, counts, batch):
+        warnings.warn(f'Entry for key \'{self.unpack_key}\' not found in estimates.', category=RuntimeWarning)
+        return [dict() for _ in batch.idx]
+
 
 class StackedEvaluator(Evaluator):
     def __init__(self, average_slices=False, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
@@ -372,6 +399,9 @@ class StackedMultipitchEvaluator(StackedEvaluator):
         counts = torch.empty((B, S, 3), dtype=torch.int64, device=est.device)
         _lib.call('amtx_eval_multipitch_counts', est, ref, B, S, K, T, counts, device=est.device)
         return counts
+
+    def enqueue_batch(self, staged, batch):
+        return (self.counts_batch(batch.est_map(self.unpack_key, stacked=staged.dim() == 4), staged),)
 
     def results_from_counts(self, counts):
         """(S, 3) counts of one clip -> its results dictionary."""
@@ -470,12 +500,42 @@ class StackedNoteEvaluator(StackedEvaluator):
     def evaluate(self, estimated, reference):
         return self.results_from_counts(self.counts(estimated, reference), list(estimated.keys())[:len(reference)])
 
+    stacked = True                 # the references are stacked notes (a tablature model's); NoteEvaluator: batched notes
+
+    def stage_batch(self, refs, batch):
+        """Notes as one (pitch, onset)-sorted row array plus offsets, a group per clip (stacked: per clip and slice); on the device only
+        when every pitch is one the kernel takes."""
+        groups = [g for r in refs for g in (_stacked_rows(r) if self.stacked else [r])]
+        rows, offsets, ok = _pack_groups(groups)
+        return _NoteRefs(rows, offsets, (batch.upload(rows), batch.upload(offsets)) if ok else None, len(groups) // max(len(refs), 1),
+                         [list(r.keys()) for r in refs] if self.stacked else None)
+
+    def enqueue_batch(self, staged, batch):
+        assert self.stacked == (batch.notes.strings is not None), 'NoteEvaluator scores batched notes, StackedNoteEvaluator the stacked notes of a tablature model'
+        assert staged.per_clip == (batch.notes.strings or 1), 'one reference note group per string'
+        # the decoder's rows as they are on the device, before result()'s host ordering, which the matcher does not need
+        return self.match_batch(batch.dev_rows, staged.dev) if staged.dev is not None and batch.dev_rows is not None else ()
+
+    def results_batch(self, staged, counts, batch):
+        from . import _lib
+        counts, status = counts if counts else (None, None)
+        if counts is not None and not batch.overflow and int(status[0]) == -1:
+            raise _lib.AmtxError('amtx_eval_notes_match: an estimated note with a fractional pitch')
+        # the host matcher takes the whole batch when the references' pitches are fractional, when the decoder overflowed (the
+        # matcher ran on a truncated buffer; the batch is decoded again for the host) or when a group is beyond the window bound
+        if counts is None or batch.overflow or int(status[0]) != 0:
+            counts = _host_note_counts(self, *batch.est_rows_host(), staged.rows, staged.offsets)
+        n = staged.per_clip
+        return [self.results_from_counts(counts[j * n:(j + 1) * n], staged.keys[j] if staged.keys else None) for j in range(len(batch.idx))]
+
 
 class NoteEvaluator(StackedNoteEvaluator):
     """The same for one list of batched notes (N, 3) (amt_tools/evaluate.py:990-1037)."""
 
     def __init__(self, offset_ratio=None, unpack_key=None, results_key=None, save_dir=None, patterns=None, verbose=False):
         super().__init__(offset_ratio, True, unpack_key, results_key, save_dir, patterns, verbose)
+
+    stacked = False
 
     def evaluate(self, estimated, reference):
         estimated, reference = np.asarray(estimated), np.asarray(reference)
@@ -538,6 +598,11 @@ class TablatureEvaluator(Evaluator):
     def counts_batch(self, estimated, reference):
         return _TabCounts.counts_batch(estimated, reference, self.profile)
 
+    reference_dtype = np.int64
+
+    def enqueue_batch(self, staged, batch):
+        return (self.counts_batch(batch.preds[tools.KEY_TABLATURE].long(), staged),)
+
     def results_from_counts(self, counts):
         counts = np.asarray(counts, dtype=np.float64)
         num_predicted, num_ground_truth, num_correct_tablature, num_correct_multi_pitch = counts[0], counts[1], counts[2], counts[3]
@@ -562,6 +627,8 @@ class SoftmaxAccuracy(Evaluator):
 
     def counts_batch(self, estimated, reference):
         return _TabCounts.counts_batch(estimated, reference, None)
+
+    reference_dtype, enqueue_batch = np.int64, TablatureEvaluator.enqueue_batch
 
     def results_from_counts(self, counts):
         counts = np.asarray(counts)
@@ -594,31 +661,9 @@ def _pack_groups(groups):
     return np.ascontiguousarray(rows), offsets, ok
 
 
-class _Staged(object):
-    """One batch's references on their way to the device, per evaluator."""
-
-    def __init__(self, leaves, references, idx, device, on_gpu):
-        import torch
-        self.items = []
-        for e in leaves:
-            refs = [tools.unpack_dict(references[i], e.unpack_key) for i in idx]
-            if isinstance(e, LossWrapper):
-                self.items.append(None)
-            elif isinstance(e, StackedNoteEvaluator):
-                stacked = not isinstance(e, NoteEvaluator)
-                groups = [g for r in refs for g in (_stacked_rows(r) if stacked else [r])]
-                per_clip = len(groups) // max(len(refs), 1)
-                rows, offsets, ok = _pack_groups(groups)
-                dev = None
-                if on_gpu and ok:
-                    dev = (torch.from_numpy(rows).pin_memory().to(device, non_blocking=True), torch.from_numpy(offsets).pin_memory().to(device, non_blocking=True))
-                self.items.append(dict(kind='notes', rows=rows, offsets=offsets, dev=dev, per_clip=per_clip, keys=[list(r.keys()) for r in refs] if stacked else None))
-            elif isinstance(e, (TablatureEvaluator, SoftmaxAccuracy)):
-                host = np.stack([np.asarray(r) for r in refs]).astype(np.int64)
-                self.items.append(dict(kind='tab', host=host, dev=torch.from_numpy(host).pin_memory().to(device, non_blocking=True) if on_gpu else None))
-            else:
-                host = np.stack([np.asarray(r) for r in refs]).astype(np.float32)
-                self.items.append(dict(kind='map', host=host, dev=torch.from_numpy(host).pin_memory().to(device, non_blocking=True) if on_gpu else None))
+# a note evaluator's staged references: _pack_groups' host arrays, the pair on the device (None: a pitch the kernel does not take), groups
+# per clip, and per clip the keys of its stacked notes (None: batched notes)
+_NoteRefs = namedtuple('_NoteRefs', 'rows offsets dev per_clip keys')
 
 
 def _host_note_counts(e, est_rows, est_off, ref_rows, ref_off):
@@ -631,25 +676,56 @@ def _host_note_counts(e, est_rows, est_off, ref_rows, ref_off):
     return out
 
 
+class _Batch(object):
+    """One batch of validate_batched on its way through inference._batched: made while the batch is staged (idx, uploads, staged: what
+    every leaf's stage_batch returned), filled behind the model (preds, notes: the decoder's handle or None, dev_rows: its
+    device_rows(), work: what every leaf's enqueue_batch returned, done: the event behind all of it) and read when it is finished
+    (overflow: the decoder's first buffer was too small)."""
+
+    def __init__(self, idx, model, device):
+        self.idx, self.model, self.device, self.uploads, self._est_host = idx, model, device, [], None
+
+    def upload(self, array):
+        """A host array of references to the device, from pinned memory on the current (copy) stream; enqueue record_stream()s them all."""
+        import torch
+        self.uploads.append(torch.from_numpy(array).pin_memory().to(self.device, non_blocking=True))
+        return self.uploads[-1]
+
+    def est_map(self, key, stacked):
+        """The model's map under `key`; a tablature model's multi-pitch map is expanded from its tablature (amtx_tab_expand)."""
+        est = self.preds.get(key)
+        if est is None and key == tools.KEY_MULTIPITCH and tools.KEY_TABLATURE in self.preds:
+            est = tools.tab_expand(self.preds[tools.KEY_TABLATURE], self.model.profile, stacked=stacked, collapsed=not stacked)[0 if stacked else 1]
+        if est is None:
+            raise KeyError(f'the model output has no entry \'{key}\'')
+        return est
+
+    def est_rows_host(self):
+        """(rows, offsets) of the estimated notes on the host, fetched once: only a batch that takes the host matcher asks."""
+        if self._est_host is None:
+            if self.dev_rows is not None:
+                self._est_host = self.notes.fetch()[:2]      # decodes once more when the first buffer was too small
+            else:                                             # CPU tablature decoder
+                self._est_host = _pack_groups([g for clip in self.notes.result() for g in _stacked_rows(clip)])[:2]
+        return self._est_host
+
+
 def validate_batched(clips, references, model, evaluator, times=None, batch_size=256, rank=0, world=1):
     """Score a partition without bringing a map to the host.  `clips` as for run_offline_batched; `references`: one ground-truth dictionary
     per clip with the keys the evaluators unpack (KEY_MULTIPITCH / KEY_ONSETS / KEY_OFFSETS maps, KEY_NOTES as batched notes -- stacked
-    notes for tablature models --, KEY_TABLATURE).  Per batch: audio and references are uploaded on a copy stream under the previous batch's
-    kernels, the model runs, notes are decoded on the device when the evaluator tree holds a note evaluator and the decoder's row arrays go
-    straight to amtx_eval_notes_match, every evaluator's counts_batch is enqueued, and only the count tensors (and the decoder's offsets
-    table) come back, on the side stream of transcribe._D2H_STREAMS, while the next batch runs.  Every clip's results are appended to the
-    evaluator in clip order, exactly as process_track would have.  Returns evaluator.average_results() for the clips this rank owns."""
+    notes for tablature models --, KEY_TABLATURE).  The loop is run_offline_batched's (inference._batched), with every evaluator's
+    stage_batch / enqueue_batch / results_batch as its hooks: a batch's references are uploaded beside its audio; behind the model, notes
+    are decoded on the device when the evaluator tree holds a note evaluator and the decoder's row arrays go straight to
+    amtx_eval_notes_match; only the count tensors (and the decoder's offsets table) come back, on transcribe's side stream, while the next
+    batch runs.  Every clip's results are appended to the evaluator in clip order, exactly as process_track would have.  Returns
+    evaluator.average_results() for the clips this rank owns."""
     import torch
-    from . import _lib, transcribe
-    from .dp import shard_indices
-    from .inference import _frame_times, run_offline_batched
-    clips = torch.as_tensor(np.asarray(clips) if not torch.is_tensor(clips) else clips)
-    assert len(references) == clips.shape[0], (len(references), clips.shape[0])
-    mine = [int(i) for i in shard_indices(clips.shape[0], rank, world)]
+    from . import transcribe
+    from .inference import _batched, _model_device, run_offline_batched
+    assert len(references) == len(clips), (len(references), len(clips))
     leaves = _leaves(evaluator)
     need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
-    device = torch.device(f'cuda:{model.device}' if isinstance(model.device, int) else model.device)
-    on_gpu = device.type == 'cuda' and torch.cuda.is_available()
+    device, on_gpu = _model_device(model)
 
     def track(results, i):
         evaluator.track_results(results if isinstance(evaluator, ComboEvaluator) else results[0], i)
@@ -657,133 +733,39 @@ def validate_batched(clips, references, model, evaluator, times=None, batch_size
     if not on_gpu:
         # a CPU model: the host evaluators on run_offline_batched's output, clip by clip
         out = run_offline_batched(clips, model, times=times, batch_size=batch_size, rank=rank, world=world, decode_notes=need_notes)
-        for i in mine:
-            track([e.evaluate(*e.unpack(out[i], references[i])) for e in leaves], i)
+        for i, preds in out.items():
+            track([e.evaluate(*e.unpack(preds, references[i])) for e in leaves], i)
         return evaluator.average_results()
 
-    key = tools.KEY_AUDIO if clips.dim() == 2 else tools.KEY_FEATS
-    pcm16 = key == tools.KEY_AUDIO and clips.dtype == torch.int16
-    copy_stream = torch.cuda.Stream(device)
-    side = transcribe._D2H_STREAMS.get(str(device))
-    if side is None:
-        side = transcribe._D2H_STREAMS[str(device)] = torch.cuda.Stream(device)
+    side = transcribe._side_stream(device)
 
-    def stage(idx):
-        with torch.cuda.stream(copy_stream):
-            sel = clips[torch.as_tensor(idx)]
-            if not pcm16:
-                sel = sel.float()
-            data = sel.pin_memory().to(device, non_blocking=True)
-            if pcm16:
-                data = data.to(torch.float32).mul_(1.0 / 32768.0)
-            staged = _Staged(leaves, references, idx, device, True)
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        return data, staged, ev
+    def stage_extra(idx):
+        batch = _Batch(idx, model, device)
+        batch.staged = [e.stage_batch([tools.unpack_dict(references[i], e.unpack_key) for i in idx], batch) for e in leaves]
+        return batch
 
-    def est_maps(e, preds, stacked):
-        est = preds.get(e.unpack_key)
-        if est is None and e.unpack_key == tools.KEY_MULTIPITCH and tools.KEY_TABLATURE in preds:
-            st, co = tools.tab_expand(preds[tools.KEY_TABLATURE], model.profile, stacked=stacked, collapsed=not stacked)
-            est = st if stacked else co
-        if est is None:
-            raise KeyError(f'the model output has no entry \'{e.unpack_key}\'')
-        return est
+    def enqueue(idx, preds, batch):
+        """Everything of one batch that runs on the device."""
+        stream = torch.cuda.current_stream(device)
+        for t in batch.uploads:
+            t.record_stream(stream)
+        batch.preds = preds
+        batch.notes = transcribe.decode_notes_for(preds, model, times) if need_notes else None
+        batch.dev_rows = batch.notes.device_rows() if need_notes else None      # None: the CPU tablature decoder
+        batch.work = [e.enqueue_batch(staged, batch) for e, staged in zip(leaves, batch.staged)]
+        batch.done = torch.cuda.Event()
+        batch.done.record(stream)
+        return batch
 
-    def enqueue(idx, preds, staged):
-        """Everything of one batch that runs on the device; returns what finish() needs."""
-        main = torch.cuda.current_stream(device)
-        handle, tab_model = None, tools.KEY_MULTIPITCH not in preds and tools.KEY_TABLATURE in preds
-        if need_notes:
-            T = preds[tools.KEY_TABLATURE if tab_model else tools.KEY_MULTIPITCH].shape[-1]
-            t = times if times is not None else _frame_times(model, T)
-            if tab_model:
-                handle = transcribe.decode_tab_notes_batch_async(preds[tools.KEY_TABLATURE], t, model.profile)
-            else:
-                handle = transcribe.decode_notes_batch_async(preds[tools.KEY_ONSETS], preds[tools.KEY_MULTIPITCH], t, model.profile.low)
-        dev_rows = handle.device_rows() if handle is not None else None      # None: the CPU tablature decoder
-        work = []
-        for e, item in zip(leaves, staged.items):
-            if item is None:
-                work.append(None)
-                continue
-            for v in (item['dev'] if isinstance(item['dev'], tuple) else (item['dev'],)):
-                if v is not None:
-                    v.record_stream(main)
-            if item['kind'] == 'notes':
-                stacked = not isinstance(e, NoteEvaluator)
-                assert stacked == tab_model, 'NoteEvaluator scores batched notes, StackedNoteEvaluator the stacked notes of a tablature model'
-                assert item['per_clip'] == (preds[tools.KEY_TABLATURE].shape[1] if tab_model else 1), 'one reference note group per string'
-                work.append(e.match_batch(dev_rows[:2], item['dev']) if item['dev'] is not None and dev_rows is not None else None)
-            elif item['kind'] == 'tab':
-                work.append(e.counts_batch(preds[tools.KEY_TABLATURE].long(), item['dev']))
-            else:
-                work.append(e.counts_batch(est_maps(e, preds, item['host'].ndim == 4), item['dev']))
-        done = torch.cuda.Event()
-        done.record(main)
-        return idx, staged, handle, dev_rows, work, done
-
-    def finish(pending):
-        idx, staged, handle, dev_rows, work, done = pending
-        side.wait_event(done)
+    def finish(batch):
+        side.wait_event(batch.done)
         with torch.cuda.stream(side):
-            # a note evaluator's work is (counts, status word); everything else one count tensor
-            host = [None if w is None else tuple(v.cpu().numpy() for v in w) if isinstance(w, tuple) else w.cpu().numpy() for w in work]
-            est_off = dev_rows[1].cpu().numpy() if dev_rows is not None else None
-        overflow = est_off is not None and int(est_off[-1]) > dev_rows[0].shape[0]      # the decoder's first buffer was too small
-        est_host = None                 # the estimated notes on the host: only when a batch has to take the host matcher
-
-        def est_rows_host():
-            nonlocal est_host
-            if est_host is None:
-                if dev_rows is not None:
-                    with torch.cuda.stream(side):
-                        total = int(est_off[-1])
-                        rows, offsets = dev_rows[2](total) if overflow else dev_rows[:2]
-                        est_host = (rows[:total].cpu().numpy(), offsets.cpu().numpy())
-                else:                    # CPU tablature decoder
-                    groups = [g for clip in handle.result() for g in _stacked_rows(clip)]
-                    est_host = _pack_groups(groups)[:2]
-            return est_host
-
-        per_eval = []
-        for e, item, counts in zip(leaves, staged.items, host):
-            if item is None:
-                warnings.warn(f'Entry for key \'{e.unpack_key}\' not found in estimates.', category=RuntimeWarning)
-                per_eval.append([dict() for _ in idx])
-            elif item['kind'] == 'notes':
-                counts, status = counts if counts is not None else (None, None)
-                if counts is not None and not overflow and int(status[0]) == -1:
-                    raise _lib.AmtxError('amtx_eval_notes_match: an estimated note with a fractional pitch')
-                # the host matcher takes the whole batch when the references' pitches are fractional, when the decoder overflowed (the
-                # matcher ran on a truncated buffer; the batch is decoded again for the host) or when a group is beyond the window bound
-                if counts is None or overflow or int(status[0]) != 0:
-                    rows, off = est_rows_host()
-                    counts = _host_note_counts(e, rows, off, item['rows'], item['offsets'])
-                n = item['per_clip']
-                per_eval.append([e.results_from_counts(counts[j * n:(j + 1) * n], item['keys'][j] if item['keys'] else None) for j in range(len(idx))])
-            else:
-                per_eval.append([e.results_from_counts(counts[j]) for j in range(len(idx))])
-        for j, i in enumerate(idx):
+            host = [tuple(t.cpu().numpy() for t in work) for work in batch.work]
+            est_off = batch.dev_rows[1].cpu().numpy() if batch.dev_rows is not None else None
+        batch.overflow = est_off is not None and int(est_off[-1]) > batch.dev_rows[0].shape[0]
+        per_eval = [e.results_batch(staged, counts, batch) for e, staged, counts in zip(leaves, batch.staged, host)]
+        for j, i in enumerate(batch.idx):
             track([r[j] for r in per_eval], i)
 
-    with torch.no_grad():
-        starts = list(range(0, len(mine), batch_size))
-        nxt = stage(mine[starts[0]:starts[0] + batch_size]) if starts else None
-        pending = None
-        for n, s in enumerate(starts):
-            idx = mine[s:s + batch_size]
-            data, staged, ev = nxt
-            main = torch.cuda.current_stream(device)
-            main.wait_event(ev)
-            data.record_stream(main)
-            if n + 1 < len(starts):
-                nxt = stage(mine[starts[n + 1]:starts[n + 1] + batch_size])
-            preds = model.run_on_batch({key: data})
-            now = enqueue(idx, preds, staged)
-            if pending is not None:
-                finish(pending)
-            pending = now
-        if pending is not None:
-            finish(pending)
+    _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra)
     return evaluator.average_results()

@@ -6,6 +6,7 @@ Inference drivers.
   optional estimator.  (Without the reference's four whole-dict deep copies.)
 * `run_offline_batched(...)` -- new (BASELINE config 5): many equally long clips per launch, clips sharded
   over ranks round-robin (`i % world`), no collective on the data path; per-clip results equal `run_offline`'s.
+* `_batched(...)` -- the loop under it and under `evaluate.validate_batched`: a partition through the model, batch by batch.
 """
 
 import numpy as np
@@ -37,17 +38,25 @@ def _frame_times(model, num_frames):
     raise ValueError('decode_notes=True needs `times` when the model has no front-end module to take hop_length / sample_rate from')
 
 
-@torch.no_grad()
-def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=1, decode_notes=False, keep=None):
-    """clips: (num_clips, N) float32 -- or int16 PCM -- array / CPU tensor of equally long clips (the model needs a front-end in
-    `model.frontend`) or (num_clips, C, F, T) features.  Returns {clip index: predictions dict} for the clips
-    this rank owns.  With decode_notes=True the note lists are decoded on the device (amtx_notes_decode; a model whose output is a
-    tablature, TabCNN: stacked notes {string: (pitches, intervals)} from amtx_tab_notes, and `keep` may name KEY_MULTIPITCH for the
-    collapsed pitch map of the tablature).
-    `keep`: keys of the model output to bring back to the host (default: every array; () = notes only).
+def _model_device(model):
+    """(the model's torch.device, whether the batched drivers take their GPU path for it)."""
+    device = torch.device(f'cuda:{model.device}' if isinstance(model.device, int) else model.device)
+    return device, device.type == 'cuda' and torch.cuda.is_available()
 
-    On a GPU model the loop is a three-stage pipeline: batch i+1 is uploaded on a copy stream (from pinned memory) while batch
-    i's kernels run, and batch i-1's results are brought to the host / assembled into note arrays while the GPU is busy."""
+
+@torch.no_grad()
+def _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra=None):
+    """The clips this rank owns through `model.run_on_batch`, `batch_size` at a time.  `clips` as for run_offline_batched.  Per batch,
+    with idx the list of its clip indices:
+
+      extra = stage_extra(idx)              (optional) while the batch is staged, BEFORE the batch before it runs
+      pending = enqueue(idx, preds, extra)  right behind run_on_batch; anything but None
+      finish(pending)                       after the NEXT batch's enqueue (the last batch: after the loop)
+
+    On a GPU model this is a three-stage pipeline: batch n+1 is uploaded on a copy stream (from pinned memory) while batch n's kernels
+    run, and batch n-1 is finished on the host while the GPU is busy.  stage_extra runs inside the copy stream's context, before the
+    event the model's stream waits for is recorded: what it uploads rides the same event (but has to be record_stream()ed by its reader).
+    On a CPU model there are no streams; the calls come in the same order."""
     clips = torch.as_tensor(np.asarray(clips) if not torch.is_tensor(clips) else clips)
     mine = shard_indices(clips.shape[0], rank, world)
     key = tools.KEY_AUDIO if clips.dim() == 2 else tools.KEY_FEATS
@@ -56,19 +65,8 @@ def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=
     # float32 array on the device: sample * 2^-15 is exact.  Host-to-host transcription is bound by the upload (2 KB per frame as float32)
     pcm16 = key == tools.KEY_AUDIO and clips.dtype == torch.int16
     wire = torch.int16 if pcm16 else torch.float32
-    device = torch.device(f'cuda:{model.device}' if isinstance(model.device, int) else model.device)
-    on_gpu = device.type == 'cuda' and torch.cuda.is_available()
-    out = {}
-
-    def finish(pending):
-        idx, preds, handle = pending
-        notes = handle.result() if handle is not None else None
-        host = tools.dict_to_array({k: v for k, v in preds.items() if keep is None or k in keep})
-        for j, i in enumerate(idx):
-            out[i] = {k: v[j] for k, v in host.items() if isinstance(v, np.ndarray)}
-            if notes is not None:
-                out[i][tools.KEY_NOTES] = notes[j]
-
+    device, on_gpu = _model_device(model)
+    copy_stream = torch.cuda.Stream(device) if on_gpu else None
     staging = [None, None]            # pinned staging buffers (ring of two) + the event of the copy that last read them
     stage_count = [0]
 
@@ -77,7 +75,7 @@ def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=
         contiguous = hi - lo == len(idx)
         if not on_gpu:
             sel = (clips[lo:hi] if contiguous else clips[torch.as_tensor(idx)]).float()
-            return (sel * (1.0 / 32768.0) if pcm16 else sel), None
+            return (sel * (1.0 / 32768.0) if pcm16 else sel), (stage_extra(idx) if stage_extra else None), None
         with torch.cuda.stream(copy_stream):
             zero_copy = contiguous and clips.is_pinned() and clips.dtype == wire
             if zero_copy:
@@ -98,61 +96,68 @@ def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=
             dev = src.to(device, non_blocking=True)
             if pcm16:
                 dev = dev.to(torch.float32).mul_(1.0 / 32768.0)   # on the copy stream, behind the DMA: the model's stream sees float32 audio
+            extra = stage_extra(idx) if stage_extra else None
             ev = torch.cuda.Event()
             ev.record(copy_stream)
             if not zero_copy:
                 staging[slot][1] = ev
-        return dev, (ev, src)
+        return dev, extra, ev
 
-    copy_stream = torch.cuda.Stream(device) if on_gpu else None
-    starts = list(range(0, len(mine), batch_size))
-    nxt = stage(mine[starts[0]:starts[0] + batch_size]) if starts else None
+    batches = [mine[s:s + batch_size] for s in range(0, len(mine), batch_size)]
+    nxt = stage(batches[0]) if batches else None
     pending = None
-    for n, s in enumerate(starts):
-        idx = mine[s:s + batch_size]
-        data, sync = nxt
-        if sync is not None:
+    for n, idx in enumerate(batches):
+        data, extra, uploaded = nxt
+        if uploaded is not None:
             main = torch.cuda.current_stream(device)
-            main.wait_event(sync[0])
+            main.wait_event(uploaded)
             # `data` was allocated from the copy stream's pool: tell the allocator that the main stream reads it, or the block
             # could be handed to the upload of batch n+2 (and overwritten by DMA) while this batch's first kernel still reads it
             data.record_stream(main)
-        if n + 1 < len(starts):
-            nxt = stage(mine[starts[n + 1]:starts[n + 1] + batch_size])
-        preds = model.run_on_batch({key: data})
-        handle = None
-        if decode_notes and tools.KEY_MULTIPITCH not in preds and tools.KEY_TABLATURE in preds:
-            # tablature models (TabCNN): stacked notes per string straight from the tablature (amtx_tab_notes), the collapsed multi-pitch
-            # map only on request (amtx_tab_expand: 44 pitch rows per 6 tablature rows); CPU tablatures take the host estimators
-            from . import transcribe
-            tab = preds[tools.KEY_TABLATURE]
-            t = times if times is not None else _frame_times(model, tab.shape[-1])
-            handle = transcribe.decode_tab_notes_batch_async(tab, t, model.profile)
-            if keep is not None and tools.KEY_MULTIPITCH in keep:
-                if tab.is_cuda:
-                    preds[tools.KEY_MULTIPITCH] = tools.tab_expand(tab, model.profile, stacked=False, collapsed=True)[1]
-                else:
-                    preds[tools.KEY_MULTIPITCH] = tools.stacked_multi_pitch_to_multi_pitch(tools.tablature_to_stacked_multi_pitch(tab, model.profile))
-        elif decode_notes:
-            T = preds[tools.KEY_MULTIPITCH].shape[-1]
-            t = times if times is not None else _frame_times(model, T)
-            if preds[tools.KEY_MULTIPITCH].is_cuda:
-                from .transcribe import decode_notes_batch_async
-                handle = decode_notes_batch_async(preds[tools.KEY_ONSETS], preds[tools.KEY_MULTIPITCH], t, model.profile.low)
-            else:
-                from .transcribe import multi_pitch_to_notes
-
-                class _Host(object):
-                    def __init__(self, p):
-                        self.p = p
-
-                    def result(self):
-                        mp, on = self.p[tools.KEY_MULTIPITCH].numpy(), self.p[tools.KEY_ONSETS].numpy()
-                        return [multi_pitch_to_notes(mp[b], t if np.ndim(t) == 1 else t[b], model.profile.low, on[b]) for b in range(mp.shape[0])]
-                handle = _Host(preds)
+        if n + 1 < len(batches):
+            nxt = stage(batches[n + 1])
+        now = enqueue(idx, model.run_on_batch({key: data}), extra)
         if pending is not None:
             finish(pending)                                       # the GPU is busy with this batch meanwhile
-        pending = (idx, preds, handle)
+        pending = now
     if pending is not None:
         finish(pending)
+
+
+def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=1, decode_notes=False, keep=None):
+    """clips: (num_clips, N) float32 -- or int16 PCM -- array / CPU tensor of equally long clips (the model needs a front-end in
+    `model.frontend`) or (num_clips, C, F, T) features.  Returns {clip index: predictions dict} for the clips
+    this rank owns.  With decode_notes=True the note lists are decoded on the device (amtx_notes_decode; a model whose output is a
+    tablature, TabCNN: stacked notes {string: (pitches, intervals)} from amtx_tab_notes, and `keep` may name KEY_MULTIPITCH for the
+    collapsed pitch map of the tablature).
+    `keep`: keys of the model output to bring back to the host (default: every array; () = notes only).
+
+    The loop is `_batched`'s: on a GPU model batch i+1 is uploaded while batch i's kernels run, and batch i-1's results are brought to
+    the host / assembled into note arrays while the GPU is busy."""
+    out = {}
+
+    def enqueue(idx, preds, _):
+        if not decode_notes:
+            return idx, preds, None
+        from . import transcribe
+        handle = transcribe.decode_notes_for(preds, model, times)
+        if handle.strings is not None and keep is not None and tools.KEY_MULTIPITCH in keep:
+            # a tablature model: the collapsed multi-pitch map only on request (amtx_tab_expand: 44 pitch rows per 6 tablature rows)
+            tab = preds[tools.KEY_TABLATURE]
+            if tab.is_cuda:
+                preds[tools.KEY_MULTIPITCH] = tools.tab_expand(tab, model.profile, stacked=False, collapsed=True)[1]
+            else:
+                preds[tools.KEY_MULTIPITCH] = tools.stacked_multi_pitch_to_multi_pitch(tools.tablature_to_stacked_multi_pitch(tab, model.profile))
+        return idx, preds, handle
+
+    def finish(pending):
+        idx, preds, handle = pending
+        notes = handle.result() if handle is not None else None
+        host = tools.dict_to_array({k: v for k, v in preds.items() if keep is None or k in keep})
+        for j, i in enumerate(idx):
+            out[i] = {k: v[j] for k, v in host.items() if isinstance(v, np.ndarray)}
+            if notes is not None:
+                out[i][tools.KEY_NOTES] = notes[j]
+
+    _batched(clips, model, batch_size, rank, world, enqueue, finish)
     return out

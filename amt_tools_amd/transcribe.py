@@ -134,8 +134,23 @@ def multi_pitch_to_notes(multi_pitch, times, low=tools.DEFAULT_PIANO_LOWEST_PITC
 from ._order_pool import order_batch, reference_order as _reference_order     # noqa: E402  (the reference's three unstable argsorts)
 
 
-_GRIDS = {}        # (device, shape, bytes) -> the extended time grid on the device
+_GRIDS = {}        # (grid dtype, shape, digest, device) -> the extended time grid / release table on the device
+_RELEASE = {}      # (grid dtype, shape, digest, window) -> int32 release table of amtx_tab_notes
 _D2H_STREAMS = {}  # device -> the stream note rows are copied to the host on
+
+
+def _digest_cached(cache, array, extra, make):
+    """cache[dtype, shape and digest of `array`, + extra], made by make(array) on a miss; at 16 entries the oldest ONE goes.  Keyed on a
+    digest, not on the bytes themselves (a (B, T) grid is megabytes per batch)."""
+    import hashlib
+    array = np.ascontiguousarray(array)
+    key = (array.dtype.str, array.shape, hashlib.blake2b(array.view(np.uint8).reshape(-1), digest_size=16).digest()) + extra
+    value = cache.get(key)
+    if value is None:
+        if len(cache) >= 16:
+            cache.pop(next(iter(cache)))
+        value = cache[key] = make(array)
+    return value
 
 
 def _grid_on_device(ext, dev):
@@ -143,61 +158,92 @@ def _grid_on_device(ext, dev):
     current stream: it returns only when every kernel enqueued before it has finished, so one upload per batch made the batched driver wait
     for its own model forward before it could go on to the previous batch's host work (4 x 8 ms per 2048 clips; config 5's host-to-host
     rate went from 14 to 25 M frames/s with the grid cached)."""
-    import hashlib
     import torch
-    # keyed on a digest, not on the bytes themselves (a (B, T) grid is megabytes per batch)
-    key = (str(dev), ext.shape, ext.dtype.str, hashlib.blake2b(np.ascontiguousarray(ext).view(np.uint8).reshape(-1), digest_size=16).digest())
-    t = _GRIDS.get(key)
-    if t is None:
-        if len(_GRIDS) >= 16:
-            _GRIDS.pop(next(iter(_GRIDS)))         # the oldest ONE; its memory is only reused behind the streams recorded below
-        t = _GRIDS[key] = torch.from_numpy(ext).to(dev)
+    t = _digest_cached(_GRIDS, ext, (str(dev),), lambda a: torch.from_numpy(a).to(dev))
     # the decoder's kernels read the grid on the caller's current stream, which need not be the stream it was allocated on: tell the
-    # caching allocator, so that an evicted grid is not handed out again while those kernels are still queued
+    # caching allocator, so that an evicted grid (its memory is only reused behind the streams recorded here) is not handed out again
+    # while those kernels are still queued
     t.record_stream(torch.cuda.current_stream(t.device))
     return t
 
 
-class _PendingNotes(object):
-    """Device half of the decoder already enqueued (amtx_notes_decode + amtx_notes_rows: one dense (E,3) float64 array of note rows in
-    np.nonzero order per clip, its onset column and the per-clip offsets); `result()` copies them to the host and applies the
-    reference's row order clip by clip.  Lets a caller enqueue the next batch's kernels before paying for this batch's host work."""
+def _extended_grid(times, T):
+    """One (T,) grid or a (B, T) array of grids -> (the grid(s) plus one more frame in float64, the row stride the kernels take: 0 = one
+    grid shared by the batch).  float32 grids (run_offline) convert exactly, as in the reference's float64 rows."""
+    times = np.asarray(times)
+    ext = (_extend_times(times) if times.ndim == 1 else np.stack([_extend_times(t) for t in times])).astype(np.float64)
+    assert ext.shape[-1] == T + 1
+    return np.ascontiguousarray(ext), 0 if times.ndim == 1 else ext.shape[1]
 
-    def __init__(self, rows, onset_col, offsets, B, retry):
-        self._rows, self._onset, self._offsets, self._B, self._retry = rows, onset_col, offsets, B, retry
+
+def _side_stream(device):
+    """The stream of `device` that results are copied to the host on, behind an event of the work they wait for: on the caller's stream
+    the copies would queue behind whatever the caller has enqueued since (the batched drivers: the NEXT batch's whole forward pass)."""
+    import torch
+    side = _D2H_STREAMS.get(str(device))
+    if side is None:
+        side = _D2H_STREAMS[str(device)] = torch.cuda.Stream(device)
+    return side
+
+
+class _PendingRows(object):
+    """Device half of a decoder already enqueued: one dense (E, 3) float64 array of note rows, the per-group offsets into it, for the
+    piano decoder the rows' onset column.  Lets a caller enqueue the next batch's kernels before paying for this batch's host work.
+    `strings`: note groups per clip of a tablature decoder, None for batched notes."""
+
+    def __init__(self, rows, offsets, retry, onset_col=None, strings=None):
+        self._rows, self._offsets, self._retry, self._onset, self.strings = rows, offsets, retry, onset_col, strings
         import torch
         self._done = torch.cuda.Event()
         self._done.record(torch.cuda.current_stream(rows.device))
 
     def device_rows(self):
-        """(rows (E, 3) float64, offsets int32, retry): the dense note rows and the offsets table as the decoder left them on the device,
-        before result()'s host work.  offsets[-1] > len(rows) means the first buffer was too small; retry(total) then decodes once more
-        into a buffer of `total` rows and returns the new (rows, offsets)."""
-        def retry(total):
-            again = self._retry(total)
-            return again._rows, again._offsets
-        return self._rows, self._offsets, retry
+        """(rows (E, 3) float64, offsets int32): the dense note rows and the offsets table as the decoder left them on the device, before
+        result()'s host work.  offsets[-1] > len(rows) means the first buffer was too small: the rows beyond it were not written, and
+        fetch() decodes once more into a buffer of the exact size."""
+        return self._rows, self._offsets
 
-    def result(self):
+    def fetch(self):
+        """(rows (total, 3), offsets, onset column or None) on the host, copied on the side stream behind the decoder's event."""
         import torch
-        # The copies to the host run on their own stream behind this batch's event: on the caller's stream they would queue behind
-        # whatever the caller has enqueued since (the batched driver: the NEXT batch's whole forward pass)
-        dev = self._rows.device
-        side = _D2H_STREAMS.get(str(dev))
-        if side is None:
-            side = _D2H_STREAMS[str(dev)] = torch.cuda.Stream(dev)
+        side = _side_stream(self._rows.device)
         side.wait_event(self._done)
         with torch.cuda.stream(side):
             off = self._offsets.cpu().numpy()
             total = int(off[-1])
             if total > self._rows.shape[0]:             # more notes than the first buffer held: once more with the exact size
                 again = self._retry(total)              # enqueued on this side stream, behind the decoder's event
-                self._rows, self._onset, off = again._rows, again._onset, again._offsets.cpu().numpy()
+                self._rows, self._offsets, self._onset, off = again._rows, again._offsets, again._onset, again._offsets.cpu().numpy()
             rows = self._rows[:total].cpu().numpy()
-            onset = self._onset[:total].cpu().numpy()
+            onset = self._onset[:total].cpu().numpy() if self._onset is not None else None
+        return rows, off, onset
+
+
+class _PendingNotes(_PendingRows):
+    """amtx_notes_decode + amtx_notes_rows: rows in np.nonzero order per clip; `result()` brings them to the host and applies the
+    reference's row order clip by clip."""
+
+    def result(self):
+        rows, off, onset = self.fetch()
         # the reference's row order per clip: NumPy's own argsort, three times (amt_tools_amd/_order_pool.py: a few helper processes for
         # whole batches, in-process for small ones)
-        return order_batch(rows, onset, off, self._B)
+        return order_batch(rows, onset, off, len(off) - 1)
+
+
+class _HostNotes(object):
+    """The same handle for notes that are decoded on the host, `result()` does it all.  Here: piano rolls of a CPU model, clip by clip."""
+
+    def __init__(self, *args, strings=None):
+        self._args, self.strings = args, strings
+
+    def device_rows(self):
+        """None: this handle has no rows on the device."""
+        return None
+
+    def result(self):
+        onsets, multi_pitch, t, low = self._args
+        mp, on = multi_pitch.numpy(), onsets.numpy()
+        return [multi_pitch_to_notes(mp[b], t if np.ndim(t) == 1 else t[b], low, on[b]) for b in range(mp.shape[0])]
 
 
 def decode_notes_batch_async(onsets, multi_pitch, times, low=tools.DEFAULT_PIANO_LOWEST_PITCH, rows_capacity=None):
@@ -211,15 +257,8 @@ def decode_notes_batch_async(onsets, multi_pitch, times, low=tools.DEFAULT_PIANO
     multi_pitch = multi_pitch.contiguous().float()
     if onsets is not None:
         onsets = onsets.contiguous().float()
-    times = np.asarray(times)
-    if times.ndim == 1:
-        ext = _extend_times(times).astype(np.float64)                  # float32 grids (run_offline) convert exactly, as in the reference's float64 rows
-        stride = 0
-    else:
-        ext = np.stack([_extend_times(t) for t in times]).astype(np.float64)
-        stride = ext.shape[1]
-    assert ext.shape[-1] == T + 1
-    ext_d = _grid_on_device(np.ascontiguousarray(ext), dev)
+    ext, stride = _extended_grid(times, T)
+    ext_d = _grid_on_device(ext, dev)
     cap = T // 2 + 2
     pairs = torch.empty((B * K, cap, 2), dtype=torch.int32, device=dev)
     counts = torch.empty((B * K,), dtype=torch.int32, device=dev)
@@ -230,7 +269,7 @@ def decode_notes_batch_async(onsets, multi_pitch, times, low=tools.DEFAULT_PIANO
         onset_col = torch.empty((capacity,), dtype=torch.float64, device=dev)
         offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
         _lib.call('amtx_notes_rows', pairs, counts, B, K, cap, ext_d, stride, int(low), rows, onset_col, capacity, offsets, device=dev)
-        return _PendingNotes(rows, onset_col, offsets, B, rows_pass)
+        return _PendingNotes(rows, offsets, rows_pass, onset_col)
 
     # 1024 notes per clip on average covers any realistic transcription (the synthetic bench clips decode to ~400); a denser batch is
     # caught in result() through the total the device reports and decoded again into a buffer of the exact size
@@ -397,74 +436,28 @@ def _tab_to_stacked_notes_host(tablature, times, profile, inhibition_window=None
     return StackedNoteTranscriber(profile, inhibition_window, minimum_duration).estimate(raw)
 
 
-_RELEASE = {}      # (grid dtype, grid digest, window) -> int32 release table of amtx_tab_notes
-
-
 def _release_table(times, window):
     """release[t] = first frame after t outside the inhibition window of an onset at frame t: the expression of inhibit_activations above,
     evaluated once per frame of the grid (NumPy scalars and all: the grid's dtype decides how `time + window` rounds), then the same
     max(release, t + 1).  Computed once per distinct (grid, window)."""
-    import hashlib
-    times = np.ascontiguousarray(times)
-    key = (times.dtype.str, times.shape, hashlib.blake2b(times.view(np.uint8).reshape(-1), digest_size=16).digest(), repr(window))
-    table = _RELEASE.get(key)
-    if table is None:
-        if len(_RELEASE) >= 16:
-            _RELEASE.pop(next(iter(_RELEASE)))
-        one = lambda g: np.array([max(int(np.searchsorted(g, g[t] + window, side='left')), t + 1) for t in range(len(g))], dtype=np.int32)   # noqa: E731
-        table = _RELEASE[key] = one(times) if times.ndim == 1 else np.stack([one(g) for g in times])
-    return table
+    one = lambda g: np.array([max(int(np.searchsorted(g, g[t] + window, side='left')), t + 1) for t in range(len(g))], dtype=np.int32)   # noqa: E731
+    return _digest_cached(_RELEASE, times, (repr(window),), lambda grid: one(grid) if grid.ndim == 1 else np.stack([one(g) for g in grid]))
 
 
-class _PendingTabNotes(object):
-    """Device half of the tablature decoder already enqueued (amtx_tab_notes: one dense (E, 3) float64 array of note rows, dense over
-    (clip, string), and its offsets table); `result()` copies both to the host -- on the side stream of _PendingNotes -- and slices them
-    into B stacked-notes dicts.  No sort: onsets of one string are distinct and already ascending."""
-
-    def __init__(self, rows, offsets, B, S, retry):
-        self._rows, self._offsets, self._B, self._S, self._retry = rows, offsets, B, S, retry
-        import torch
-        self._done = torch.cuda.Event()
-        self._done.record(torch.cuda.current_stream(rows.device))
-
-    def device_rows(self):
-        """(rows (E, 3) float64, offsets int32, retry): the dense note rows and the offsets table as the decoder left them on the device,
-        before result()'s host work.  offsets[-1] > len(rows) means the first buffer was too small; retry(total) then decodes once more
-        into a buffer of `total` rows and returns the new (rows, offsets)."""
-        def retry(total):
-            again = self._retry(total)
-            return again._rows, again._offsets
-        return self._rows, self._offsets, retry
+class _PendingTabNotes(_PendingRows):
+    """amtx_tab_notes: rows dense over (clip, string); `result()` brings them to the host and slices them into stacked-notes dicts, one
+    per clip.  No sort: onsets of one string are distinct and already ascending."""
 
     def result(self):
-        import torch
-        dev = self._rows.device
-        side = _D2H_STREAMS.get(str(dev))
-        if side is None:
-            side = _D2H_STREAMS[str(dev)] = torch.cuda.Stream(dev)
-        side.wait_event(self._done)
-        with torch.cuda.stream(side):
-            off = self._offsets.cpu().numpy()
-            total = int(off[-1])
-            if total > self._rows.shape[0]:             # more notes than the first buffer held: once more with the exact size
-                again = self._retry(total)              # enqueued on this side stream, behind the decoder's event
-                self._rows, off = again._rows, again._offsets.cpu().numpy()
-            rows = self._rows[:total].cpu().numpy()
-        S = self._S
+        rows, off, _ = self.fetch()
+        S = self.strings
         return [{s: (rows[off[b * S + s]:off[b * S + s + 1], 2], rows[off[b * S + s]:off[b * S + s + 1], :2]) for s in range(S)}
-                for b in range(self._B)]
+                for b in range((len(off) - 1) // S)]
 
 
-class _HostTabNotes(object):
+class _HostTabNotes(_HostNotes):
     """The same handle for what the kernel does not build (more than 64 classes under an inhibition window, more than 16 strings) and for
     CPU tablatures: the host classes, track by track."""
-
-    def __init__(self, tablature, times, profile, inhibition_window, minimum_duration):
-        self._args = (tablature, times, profile, inhibition_window, minimum_duration)
-
-    def device_rows(self):
-        """None: this handle has no rows on the device."""
-        return None
 
     def result(self):
         tablature, times, profile, window, min_dur = self._args
@@ -488,19 +481,13 @@ def decode_tab_notes_batch_async(tablature, times, profile, inhibition_window=No
     tuning = np.ascontiguousarray(profile.get_midi_tuning(), dtype=np.int32)
     assert len(tuning) == S, (len(tuning), S)
     times = np.asarray(times)
-    assert times.shape[-1] == T
-    if times.ndim == 1:
-        ext = _extend_times(times).astype(np.float64)                  # float32 grids convert exactly, as in the reference's float64 rows
-        stride = 0
-    else:
-        ext = np.stack([_extend_times(t) for t in times]).astype(np.float64)
-        stride = ext.shape[1]
+    ext, stride = _extended_grid(times, T)
     if not tablature.is_cuda or S > TAB_MAX_STRINGS or (inhibition_window is not None and num_classes > TAB_NOTES_MAX_CLASSES):
-        return _HostTabNotes(tablature, times, profile, inhibition_window, minimum_duration)
+        return _HostTabNotes(tablature, times, profile, inhibition_window, minimum_duration, strings=S)
     assert tablature.dtype == torch.int64
     dev = tablature.device
     tablature = tablature.contiguous()
-    ext_d = _grid_on_device(np.ascontiguousarray(ext), dev)
+    ext_d = _grid_on_device(ext, dev)
     rel_d, rel_stride = None, 0
     if inhibition_window is not None:
         rel_d = _grid_on_device(_release_table(times, inhibition_window), dev)
@@ -512,7 +499,7 @@ def decode_tab_notes_batch_async(tablature, times, profile, inhibition_window=No
         offsets = torch.empty((B * S + 1,), dtype=torch.int32, device=dev)
         _lib.call('amtx_tab_notes', tablature, B, S, T, tuning, num_classes, ext_d, stride, rel_d, rel_stride, int(has_min),
                   float(minimum_duration) if has_min else 0.0, rows, capacity, offsets, device=dev)
-        return _PendingTabNotes(rows, offsets, B, S, rows_pass)
+        return _PendingTabNotes(rows, offsets, rows_pass, strings=S)
 
     # a string holds at most one note per frame; 128 notes per string on average is far above any real tablature (a denser batch is caught
     # in result() through the total the device reports and decoded again into a buffer of the exact size)
@@ -521,3 +508,20 @@ def decode_tab_notes_batch_async(tablature, times, profile, inhibition_window=No
 
 def decode_tab_notes_batch(tablature, times, profile, inhibition_window=None, minimum_duration=None):
     return decode_tab_notes_batch_async(tablature, times, profile, inhibition_window, minimum_duration).result()
+
+
+def decode_notes_for(preds, model, times=None):
+    """The note decoder of one batch of `model`'s output, enqueued -- the offline drivers' one route.  Returns a handle:
+    `result()` -> the batch's note lists on the host ((K, 3) batched notes per clip; a tablature model: stacked notes per clip),
+    `device_rows()` -> _PendingRows.device_rows, or None when the notes are decoded on the host, `strings` -> note groups per clip of a
+    tablature model, else None.  The grid is `times`, or the frame grid of the model's front-end when `times` is None."""
+    from .inference import _frame_times
+    tab_model = tools.KEY_MULTIPITCH not in preds and tools.KEY_TABLATURE in preds
+    est = preds[tools.KEY_TABLATURE if tab_model else tools.KEY_MULTIPITCH]
+    if times is None:
+        times = _frame_times(model, est.shape[-1])
+    if tab_model:
+        return decode_tab_notes_batch_async(est, times, model.profile)
+    if est.is_cuda:
+        return decode_notes_batch_async(preds[tools.KEY_ONSETS], est, times, model.profile.low)
+    return _HostNotes(preds[tools.KEY_ONSETS], est, times, model.profile.low)

@@ -351,3 +351,132 @@ def test_validate_batched_equals_the_host_evaluators_on_tabcnn():
         average = ev.validate_batched(feats, references, model, combo, times=times, batch_size=batch_size)
         assert average == want.average_results()
         assert 0 < average[tools.KEY_TABLATURE][tools.KEY_F1] < 1 and list(average[tools.KEY_NOTES]) == list(range(6))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# validate_batched: the branches a batch takes only now and then
+# ------------------------------------------------------------------------------------------------------------------------------
+def assert_same_results(combo, want, clips=5):
+    """Per clip, in clip order: what every leaf has tracked equals the host evaluators' record."""
+    def same(got, want):
+        assert list(got) == list(want)
+        for k in want:
+            if isinstance(want[k], dict):
+                same(got[k], want[k])
+            else:
+                assert np.array_equal(np.asarray(got[k]), np.asarray(want[k])) and len(got[k]) == clips, k
+    for got_e, want_e in zip(combo.evaluators, want.evaluators):
+        same(got_e.results, want_e.results)
+
+
+def spy(monkeypatch, module, name, **forced):
+    """Replace module.name by a wrapper that counts its calls, keeps what they returned and forces the given keyword arguments."""
+    real, seen = getattr(module, name), []
+
+    def wrapper(*args, **kwargs):
+        seen.append(real(*args, **dict(kwargs, **forced)))
+        return seen[-1]
+    monkeypatch.setattr(module, name, wrapper)
+    return seen
+
+
+@functools.lru_cache(maxsize=None)
+def tab_setup():
+    """The model, clips and ground truth of test_validate_batched_equals_the_host_evaluators_on_tabcnn."""
+    from amt_tools_amd.models import TabCNN
+    from amt_tools_amd.synth import synth_tabcnn_state_dict
+    model = TabCNN(192, PROFILE, 1, 1, device=DEV)
+    sd = synth_tabcnn_state_dict(5, dim_in=192, in_channels=1, model_complexity=1, num_groups=6, num_classes=21)
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    model.change_device()
+    model.eval()
+    T = 40
+    feats = np.random.default_rng(3).random((5, 1, 192, T)).astype(np.float32)
+    times = np.arange(T) * 512 / 22050.0
+    out = run_offline_batched(feats, model, times=times, batch_size=3, decode_notes=True, keep=(tools.KEY_TABLATURE,))
+    references = []
+    for i in range(5):
+        rng = np.random.default_rng(50 + i)
+        tab = np.where(rng.random((6, T)) < 0.5, out[i][tools.KEY_TABLATURE], np.repeat(rng.integers(-1, 20, size=(6, T // 4)), 4, axis=-1))
+        references.append({tools.KEY_TABLATURE: tab, tools.KEY_NOTES: transcribe._tab_to_stacked_notes_host(tab, times, PROFILE)})
+    return model, feats, times, references, out
+
+
+def tab_combo():
+    return ev.ComboEvaluator([ev.TablatureEvaluator(PROFILE), ev.SoftmaxAccuracy(results_key='accuracy'),
+                              ev.StackedNoteEvaluator(offset_ratio=0.2), ev.StackedNoteEvaluator(average_slices=True, results_key='notes-avg')])
+
+
+def test_validate_batched_takes_the_host_matcher_when_the_decoder_overflows(monkeypatch):
+    """A first row buffer of ONE row: the device matcher runs on the truncated buffer (its group offsets are clamped to the buffer), the
+    batch is decoded again into a buffer of the exact size, and the host matcher scores it -- every batch, both note evaluators."""
+    model, clips, times, references, out = of_setup()
+    want, _ = host_scores(of_combo, out, references, range(5))
+    decoded = spy(monkeypatch, transcribe, 'decode_notes_batch_async', rows_capacity=1)
+    on_host = spy(monkeypatch, ev, '_host_note_counts')
+    combo = of_combo()
+    average = ev.validate_batched(clips, references, model, combo, times=times, batch_size=2)
+    assert len(decoded) == 3 and len(on_host) == 6
+    assert average == want.average_results()
+    assert_same_results(combo, want)
+
+
+def test_validate_batched_takes_the_host_matcher_when_the_tablature_decoder_overflows(monkeypatch):
+    model, feats, times, references, out = tab_setup()
+    want, _ = host_scores(tab_combo, out, references, range(5))
+    decoded = spy(monkeypatch, transcribe, 'decode_tab_notes_batch_async', rows_capacity=1)
+    on_host = spy(monkeypatch, ev, '_host_note_counts')
+    combo = tab_combo()
+    average = ev.validate_batched(feats, references, model, combo, times=times, batch_size=2)
+    assert len(decoded) == 3 and len(on_host) == 6 and all(isinstance(h, transcribe._PendingTabNotes) for h in decoded)
+    assert average == want.average_results()
+    assert_same_results(combo, want)
+
+
+def test_validate_batched_takes_the_host_matcher_for_a_fractional_reference_pitch(monkeypatch):
+    """One reference pitch of clip 1 moved by half a semitone: the device matcher takes integral pitches only, so the batch that holds
+    the clip goes to the host matcher as a whole (both note evaluators: 2 calls), the other batches stay on the device."""
+    model, clips, times, references, out = of_setup()
+    references = [dict(r) for r in references]
+    notes = np.array(references[1][tools.KEY_NOTES])
+    assert len(notes) > 0
+    notes[0, 2] += 0.5
+    references[1][tools.KEY_NOTES] = notes
+    want, _ = host_scores(of_combo, out, references, range(5))
+    on_host = spy(monkeypatch, ev, '_host_note_counts')
+    combo = of_combo()
+    average = ev.validate_batched(clips, references, model, combo, times=times, batch_size=2)
+    assert len(on_host) == 2
+    assert average == want.average_results()
+    assert_same_results(combo, want)
+
+
+def test_validate_batched_with_the_cpu_tablature_decoder_under_a_gpu_model(monkeypatch):
+    """No string count the kernel takes: the handle is the host classes' (no rows on the device), the note evaluators take the host
+    matcher, and the results are those of the unpatched run."""
+    model, feats, times, references, out = tab_setup()
+    want, _ = host_scores(tab_combo, out, references, range(5))
+    monkeypatch.setattr(transcribe, 'TAB_MAX_STRINGS', 0)
+    decoded = spy(monkeypatch, transcribe, 'decode_tab_notes_batch_async')
+    combo = tab_combo()
+    average = ev.validate_batched(feats, references, model, combo, times=times, batch_size=2)
+    assert len(decoded) == 3 and all(isinstance(h, transcribe._HostTabNotes) and h.device_rows() is None for h in decoded)
+    assert average == want.average_results()
+    assert_same_results(combo, want)
+
+
+def test_validate_batched_with_a_loss_wrapper_in_the_combo():
+    """The model's eval output has no loss: the LossWrapper leaf warns as its own unpack() does and tracks an empty dictionary per clip;
+    the leaves around it score as without it."""
+    import re
+    model, clips, times, references, out = of_setup()
+    make = lambda: ev.ComboEvaluator([ev.MultipitchEvaluator(), ev.NoteEvaluator()])                       # noqa: E731
+    want, _ = host_scores(make, out, references, range(5))
+    loss = ev.LossWrapper()
+    combo = ev.ComboEvaluator([ev.MultipitchEvaluator(), loss, ev.NoteEvaluator()])
+    with pytest.warns(RuntimeWarning, match=re.escape(f'Entry for key \'{tools.KEY_LOSS}\' not found in estimates.')):
+        average = ev.validate_batched(clips, references, model, combo, times=times, batch_size=2)
+    assert loss.results == {} and average == dict(want.average_results(), **{tools.KEY_LOSS: {}})
+    assert list(average) == [tools.KEY_MULTIPITCH, tools.KEY_LOSS, tools.KEY_NOTES]
+    combo.evaluators.remove(loss)
+    assert_same_results(combo, want)
