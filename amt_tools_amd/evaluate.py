@@ -1,7 +1,8 @@
 """
 Evaluation: the evaluator classes of amt_tools/evaluate.py (constructor arguments, result-dictionary layout and keys; `train()` takes them
 unchanged: process_track / average_results / reset_results / finalize(writer, step) / set_save_dir / set_patterns / set_verbose), and a
-batched validation loop that scores a partition on the device.
+batched validation loop that scores a partition on the device: validate_batched for host clips and references, validate_clips for clips
+of device-resident tracks (tracks.TrackBank / PyramidBank, LabelBank, NoteBank).
 
 Every evaluator is split in two:
 
@@ -28,7 +29,8 @@ import numpy as np
 from . import tools
 from .inference import run_offline
 
-__all__ = ['validate', 'validate_batched', 'average_results', 'append_results', 'log_results', 'write_results', 'pattern_match', 'Evaluator',
+__all__ = ['validate', 'validate_batched', 'validate_clips', 'average_results', 'append_results', 'log_results', 'write_results', 'pattern_match',
+           'Evaluator',
            'ComboEvaluator', 'LossWrapper', 'StackedMultipitchEvaluator', 'MultipitchEvaluator', 'StackedNoteEvaluator', 'NoteEvaluator',
            'TablatureEvaluator', 'SoftmaxAccuracy', 'note_edges', 'match_notes_count', 'N_DECIMALS']
 
@@ -719,9 +721,7 @@ def validate_batched(clips, references, model, evaluator, times=None, batch_size
     amtx_eval_notes_match; only the count tensors (and the decoder's offsets table) come back, on transcribe's side stream, while the next
     batch runs.  Every clip's results are appended to the evaluator in clip order, exactly as process_track would have.  Returns
     evaluator.average_results() for the clips this rank owns."""
-    import torch
-    from . import transcribe
-    from .inference import _batched, _model_device, run_offline_batched
+    from .inference import _model_device, run_offline_batched
     assert len(references) == len(clips), (len(references), len(clips))
     leaves = _leaves(evaluator)
     need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
@@ -737,11 +737,102 @@ def validate_batched(clips, references, model, evaluator, times=None, batch_size
             track([e.evaluate(*e.unpack(preds, references[i])) for e in leaves], i)
         return evaluator.average_results()
 
+    def stage(idx, batch):
+        return [e.stage_batch([tools.unpack_dict(references[i], e.unpack_key) for i in idx], batch) for e in leaves]
+
+    _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world)
+    return evaluator.average_results()
+
+
+class _BankNoteRefs(object):
+    """_NoteRefs of a batch whose references a tracks.NoteBank sliced on the device: `dev` is its (rows, offsets) pair (None: the bank
+    holds a pitch the device matcher does not take), and `rows` / `offsets` -- read only by a batch that takes the host matcher -- are
+    notes.host_clips of the same request, packed when first asked for."""
+
+    def __init__(self, notes, request, dev):
+        self.dev, self.per_clip = dev, notes.slices
+        self.keys = [list(notes.keys)] * len(request[0]) if notes.stacked else None
+        self._notes, self._request, self._host = notes, request, None
+
+    def _packed(self):
+        if self._host is None:
+            self._host = _pack_groups(self._notes.host_clips(*self._request))[:2]
+        return self._host
+
+    rows = property(lambda self: self._packed()[0])
+    offsets = property(lambda self: self._packed()[1])
+
+
+def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frames, num_frames, times=None, batch_size=256, rank=0, world=1):
+    """validate_batched for clips of resident tracks: clip i is `num_frames` frames from first_frames[i] on of track track_ids[i] (a request
+    as bank.clips takes it; tracks.cover_clips names the clips that cover whole tracks).  `bank`: the tracks.TrackBank / PyramidBank the
+    model's front-end reads; `labels`: the LabelBank of the same tracks, with every key a map or tablature evaluator unpacks (None: no
+    such evaluator); `notes`: their NoteBank with relative_times (None: no note evaluator).  ValueError, before anything is launched,
+    for an evaluator whose bank is missing or does not hold its key, and for a request the banks refuse.
+
+    The loop is validate_batched's (inference._batched over an inference.BankClips): per batch the model gets
+    {tools.KEY_AUDIO: bank.clips(...)}, the references are labels.clips(...) and notes.clips(...) -- device tensors in the layouts
+    stage_batch would have uploaded -- and only clip descriptors go to the device and count tensors come back.  The host matcher runs
+    on notes.host_clips(...) where results_batch falls back: the matcher's status word asks for it, the decoder overflowed, or
+    notes.integral is false.  A LossWrapper warns and contributes an empty dictionary, as in validate_batched.  Every clip's results are
+    appended in clip order; returns evaluator.average_results() for the clips this rank owns."""
+    from .inference import BankClips, _model_device
+    leaves = _leaves(evaluator)
+    for e in leaves:
+        if isinstance(e, LossWrapper):
+            continue
+        if isinstance(e, StackedNoteEvaluator):
+            if notes is None:
+                raise ValueError(f'{type(e).__name__} scores notes: validate_clips needs a NoteBank for it')
+            if e.stacked != notes.stacked:
+                raise ValueError(f'{type(e).__name__} scores {"stacked" if e.stacked else "batched"} notes, the NoteBank holds '
+                                 f'{"stacked" if notes.stacked else "batched"} notes')
+            if not notes.relative_times:
+                raise ValueError('the NoteBank holds absolute times: a clip is decoded on a grid that starts at its own first frame (relative_times=True)')
+        elif labels is None:
+            raise ValueError(f'{type(e).__name__} scores the label map \'{e.unpack_key}\': validate_clips needs a LabelBank for it')
+        elif e.unpack_key not in labels.keys:
+            raise ValueError(f'{type(e).__name__} scores the label map \'{e.unpack_key}\', the LabelBank holds {labels.keys}')
+    for other, what in ((labels, 'LabelBank'), (notes, 'NoteBank')):
+        if other is not None and len(other) != len(bank):
+            raise ValueError(f'a bank of {len(bank)} tracks and a {what} of {len(other)}')
+    source = BankClips(bank, track_ids, first_frames, num_frames)
+    if not _model_device(model)[1]:
+        raise ValueError('validate_clips scores clips of device-resident tracks: the model has to be on a GPU')
+    need_maps = any(not isinstance(e, (LossWrapper, StackedNoteEvaluator)) for e in leaves)
+    need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
+
+    def stage(idx, batch):
+        request = source.of(idx) + (source.num_frames,)
+        maps = labels.clips(*request) if need_maps else None
+        refs = None
+        if need_notes:
+            sliced = notes.clips(*request) if notes.integral else None
+            refs = _BankNoteRefs(notes, request, (sliced.rows, sliced.offsets) if sliced is not None else None)
+        return [None if isinstance(e, LossWrapper) else refs if isinstance(e, StackedNoteEvaluator) else maps[e.unpack_key] for e in leaves]
+
+    _score_on_device(source, stage, model, evaluator, times, batch_size, rank, world)
+    return evaluator.average_results()
+
+
+def _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world):
+    """What validate_batched and validate_clips share on a GPU model: inference._batched over `clips` (host clips or a BankClips) with
+    every leaf's enqueue_batch / results_batch as its hooks.  stage(idx, batch) -> what each leaf gets as `staged`: the references of the
+    clips idx on the device (or on their way there through batch.upload)."""
+    import torch
+    from . import transcribe
+    from .inference import _batched, _model_device
+    leaves = _leaves(evaluator)
+    need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
+    device = _model_device(model)[0]
     side = transcribe._side_stream(device)
+
+    def track(results, i):
+        evaluator.track_results(results if isinstance(evaluator, ComboEvaluator) else results[0], i)
 
     def stage_extra(idx):
         batch = _Batch(idx, model, device)
-        batch.staged = [e.stage_batch([tools.unpack_dict(references[i], e.unpack_key) for i in idx], batch) for e in leaves]
+        batch.staged = stage(idx, batch)
         return batch
 
     def enqueue(idx, preds, batch):
@@ -768,4 +859,3 @@ def validate_batched(clips, references, model, evaluator, times=None, batch_size
             track([r[j] for r in per_eval], i)
 
     _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra)
-    return evaluator.average_results()

@@ -6,7 +6,9 @@ Inference drivers.
   optional estimator.  (Without the reference's four whole-dict deep copies.)
 * `run_offline_batched(...)` -- new (BASELINE config 5): many equally long clips per launch, clips sharded
   over ranks round-robin (`i % world`), no collective on the data path; per-clip results equal `run_offline`'s.
-* `_batched(...)` -- the loop under it and under `evaluate.validate_batched`: a partition through the model, batch by batch.
+* `_batched(...)` -- the loop under it, under `evaluate.validate_batched` and under `evaluate.validate_clips`: a partition through the
+  model, batch by batch.  Its batches come from one of two sources: host clips that are uploaded, or `BankClips` -- clips named as
+  (track, first frame) of a tracks.TrackBank / PyramidBank, whose model input the bank makes on the device.
 """
 
 import numpy as np
@@ -44,10 +46,32 @@ def _model_device(model):
     return device, device.type == 'cuda' and torch.cuda.is_available()
 
 
+class BankClips(object):
+    """A batch source of `_batched`: clip i is `num_frames` frames from first_frames[i] on of track track_ids[i] of `bank` (a
+    tracks.TrackBank or PyramidBank).  The whole request is checked once, here, with the banks' own check and ValueError texts;
+    `batch(idx)` is bank.clips of those clips -- the entry the models take under tools.KEY_AUDIO -- made on the current stream."""
+
+    def __init__(self, bank, track_ids, first_frames, num_frames):
+        from .tracks import _checked_request
+        self.bank, self.num_frames = bank, int(num_frames)
+        self.track_ids, self.first_frames = _checked_request(bank.frame_counts, track_ids, first_frames, num_frames)
+
+    def __len__(self):
+        return int(self.track_ids.size)
+
+    def of(self, idx):
+        """(track ids, first frames) of the clips `idx`."""
+        idx = np.asarray(idx, dtype=np.int64)
+        return self.track_ids[idx], self.first_frames[idx]
+
+    def batch(self, idx):
+        return self.bank.clips(*self.of(idx), self.num_frames)
+
+
 @torch.no_grad()
 def _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra=None):
-    """The clips this rank owns through `model.run_on_batch`, `batch_size` at a time.  `clips` as for run_offline_batched.  Per batch,
-    with idx the list of its clip indices:
+    """The clips this rank owns through `model.run_on_batch`, `batch_size` at a time.  `clips` as for run_offline_batched, or a BankClips.
+    Per batch, with idx the list of its clip indices:
 
       extra = stage_extra(idx)              (optional) while the batch is staged, BEFORE the batch before it runs
       pending = enqueue(idx, preds, extra)  right behind run_on_batch; anything but None
@@ -56,21 +80,29 @@ def _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra
     On a GPU model this is a three-stage pipeline: batch n+1 is uploaded on a copy stream (from pinned memory) while batch n's kernels
     run, and batch n-1 is finished on the host while the GPU is busy.  stage_extra runs inside the copy stream's context, before the
     event the model's stream waits for is recorded: what it uploads rides the same event (but has to be record_stream()ed by its reader).
-    On a CPU model there are no streams; the calls come in the same order."""
-    clips = torch.as_tensor(np.asarray(clips) if not torch.is_tensor(clips) else clips)
-    mine = shard_indices(clips.shape[0], rank, world)
-    key = tools.KEY_AUDIO if clips.dim() == 2 else tools.KEY_FEATS
+    On a CPU model there are no streams; the calls come in the same order.
+
+    A BankClips source has nothing to upload: its batch is made by the bank on the model's own stream (a descriptor table goes up, the
+    audio is resident), so there is no pinned staging, no copy stream and no event for it, and stage_extra runs on the model's stream
+    too.  The order of the calls is the same."""
+    from_bank = isinstance(clips, BankClips)
+    if not from_bank:
+        clips = torch.as_tensor(np.asarray(clips) if not torch.is_tensor(clips) else clips)
+    mine = shard_indices(len(clips) if from_bank else clips.shape[0], rank, world)
+    key = tools.KEY_AUDIO if from_bank or clips.dim() == 2 else tools.KEY_FEATS
     # 16-bit PCM hand-over (round 6): int16 clips travel over PCIe as they are -- half the bytes of the float32 array the reference's loader makes
     # of the same file (amt_tools/tools/io.py:80-82: librosa / soundfile return sample / 32768 for 16-bit files) -- and become exactly that
     # float32 array on the device: sample * 2^-15 is exact.  Host-to-host transcription is bound by the upload (2 KB per frame as float32)
-    pcm16 = key == tools.KEY_AUDIO and clips.dtype == torch.int16
+    pcm16 = not from_bank and key == tools.KEY_AUDIO and clips.dtype == torch.int16
     wire = torch.int16 if pcm16 else torch.float32
     device, on_gpu = _model_device(model)
-    copy_stream = torch.cuda.Stream(device) if on_gpu else None
+    copy_stream = torch.cuda.Stream(device) if on_gpu and not from_bank else None
     staging = [None, None]            # pinned staging buffers (ring of two) + the event of the copy that last read them
     stage_count = [0]
 
     def stage(idx):
+        if from_bank:
+            return clips.batch(idx), (stage_extra(idx) if stage_extra else None), None
         lo, hi = int(idx[0]), int(idx[-1]) + 1
         contiguous = hi - lo == len(idx)
         if not on_gpu:

@@ -23,7 +23,11 @@ them run-length encoded -- integers only (encode_rows) -- and `labels.clips(...)
 (amtx_label_clips, include/amtx_labels.h) into the tensors the loss kernels take without a copy.  `ClipLoader` draws clips by the
 reference's rule (draw_clips) and yields complete batches: features' clips under tools.KEY_AUDIO, label tensors under their keys.
 
-What the three banks share is written once: `_checked_request` validates a `clips(track_ids, first_frames, num_frames)` request against
+`NoteBank` is the note ground truth of the same clips, for validation: the reference's slice_batched_notes of a clip's time window
+(amt_tools/tools/utils.py:322-361), computed per (clip, slice) on the device (amtx_note_clips, include/amtx_noteclips.h) into the
+(rows, offsets) pair the device note matcher reads.  `cover_clips` names the consecutive clips that cover whole tracks.
+
+What the banks share is written once: `_checked_request` validates a `clips(track_ids, first_frames, num_frames)` request against
 a bank's frame counts, `_clip_table` lays the checked request out as the int64 table a clip kernel reads (clip_descriptors adds the
 reflect rule and the 4-column form of amtx_spec_power_clips), `_Resident` is the lazy, never-pickled device state, and `_Clips` is the
 batch entry that TrackClips and PyramidClips name -- the feature modules and models choose the kernel family by that type.
@@ -34,7 +38,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ['TrackBank', 'TrackClips', 'PyramidBank', 'PyramidClips', 'clip_descriptors', 'frame_start',
-           'LabelBank', 'ClipLoader', 'encode_rows', 'decode_rows', 'draw_clips']
+           'LabelBank', 'ClipLoader', 'encode_rows', 'decode_rows', 'draw_clips', 'NoteBank', 'NoteClips', 'cover_clips', 'clip_windows']
 
 
 def frame_start(sample_start, hop_length):
@@ -572,3 +576,219 @@ class ClipLoader(object):
             batch = {tools.KEY_AUDIO: self.bank.clips(ids, firsts, self.num_frames)}
             batch.update(self.labels.clips(ids, firsts, self.num_frames))
             yield batch
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# ground truth: the notes of a clip, sliced on the device
+# ------------------------------------------------------------------------------------------------------------------------------
+def cover_clips(frame_counts, num_frames):
+    """(track_ids, first_frames, frames_left_out): consecutive, non-overlapping clips of `num_frames` frames that cover every track from
+    frame 0 -- track i gives frame_counts[i] // num_frames clips -- and the number of frames no clip holds: every track's tail shorter
+    than a clip, which is the whole of a track shorter than a clip.  Nothing is padded, nothing is counted twice.  Pure host code."""
+    frame_counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+    num_frames = int(num_frames)
+    if num_frames < 1:
+        raise ValueError(f'a clip has at least one frame (got {num_frames})')
+    if (frame_counts < 0).any():
+        raise ValueError(f'track {int(np.argmax(frame_counts < 0))} has a negative frame count')
+    per_track = frame_counts // num_frames
+    track_ids = np.repeat(np.arange(len(frame_counts), dtype=np.int64), per_track)
+    first_frames = (np.arange(len(track_ids), dtype=np.int64) - np.repeat(np.cumsum(per_track) - per_track, per_track)) * num_frames
+    return track_ids, first_frames, int((frame_counts - per_track * num_frames).sum())
+
+
+def clip_windows(module, first_frames, num_frames):
+    """(B, 2) float64 {sec_start, sec_stop} of the clips of `num_frames` frames that start at `first_frames`, by the reference's rule
+    (amt_tools/datasets/common.py:343-358 with snap_to_frame): sample_start = first_frame * hop_length, seq_length =
+    max(module.get_sample_range(num_frames)) (datasets/common.py:116: 319 999 samples for 625 frames at hop 512, not num_frames * hop_length),
+    sec_start = sample_start / sample_rate, sec_stop = (sample_start + seq_length) / sample_rate -- Python floats, made here: the device
+    never divides.  Pure host code."""
+    hop, rate = int(module.hop_length), module.sample_rate
+    seq_length = int(max(module.get_sample_range(int(num_frames))))
+    windows = np.empty((len(first_frames), 2), dtype=np.float64)
+    for b, first in enumerate(first_frames):
+        sample_start = int(first) * hop
+        windows[b] = sample_start / rate, (sample_start + seq_length) / rate
+    return windows
+
+
+def _note_order(rows):
+    """Note rows in (pitch, onset) order: evaluate._sort_rows, the order amtx_eval_notes_match reads (a stable sort)."""
+    return rows[np.lexsort((rows[:, 0], rows[:, 2]))]
+
+
+class NoteClips(object):
+    """What NoteBank.clips returns: `rows` (capacity, 3) float64 and `offsets` (batch * slices + 1,) int32 device tensors -- group
+    clip * slices + slice owns rows[offsets[g]:offsets[g + 1]], the pair StackedNoteEvaluator.match_batch takes as `reference` --, `slices`
+    (note groups per clip), `keys` (the stacked notes' keys; None for batched notes) and `total`: the rows of all groups as the host
+    counted them (None when the caller set the capacity; offsets[-1] holds the kernel's total either way)."""
+
+    def __init__(self, rows, offsets, slices, keys, total):
+        self.rows, self.offsets, self.slices, self.keys, self.total = rows, offsets, slices, keys, total
+
+
+class NoteBank(_Resident):
+    """The note ground truth of whole tracks, for clips sliced on the device (amtx_note_clips, include/amtx_noteclips.h).
+
+    notes[i]: the notes of track i, either a batched-notes array (N, 3) of rows [onset_s, offset_s, pitch] or a stacked-notes dictionary
+    {key: (pitches, intervals)} (a tablature track: one entry per string).  All tracks are of one kind; stacked tracks carry the same keys
+    in the same order (remembered as `keys`).  ValueError, naming track and row, for a NaN or infinite time and for offset < onset; with
+    `bank` (the TrackBank / PyramidBank of the same tracks) for another track count.  `bank` also gives the clips their time windows
+    (its module's hop length, sample rate and get_sample_range) and their frame counts; without it only window_clips / host_window_clips
+    answer.
+
+    One `rows` float64 (N, 3) table for all tracks and `group_ptr` int64 (num_tracks * slices + 1,): group track * slices + slice owns
+    rows[group_ptr[g]:group_ptr[g + 1]], in (pitch, onset) order.  A time of -0.0 is stored as 0.0.  `integral`: every pitch is an integer
+    in [0, 128), what the device matcher takes.  relative_times: whether a clip's times count from its own start (True: what a decoder
+    whose grid starts at 0 needs) or stay absolute (False: what the reference's dataset returns).  The device copies are created on
+    first use, never at construction, and never pickled."""
+
+    def __init__(self, notes, bank=None, relative_times=True, device=None):
+        self.device = device if device is not None else (bank.device if bank is not None else 'cuda')
+        self.module = bank.module if bank is not None else None
+        self.relative_times = bool(relative_times)
+        self.keys, stacked, groups = None, None, []
+        for i, entry in enumerate(notes):
+            is_dict = isinstance(entry, dict)
+            if stacked is None:
+                stacked = is_dict
+                self.keys = list(entry.keys()) if is_dict else None
+                if is_dict and not self.keys:
+                    raise ValueError('track 0 carries no stacked notes')
+            if is_dict != stacked:
+                raise ValueError(f'track {i} holds {"stacked" if is_dict else "batched"} notes, track 0 {"stacked" if stacked else "batched"} notes')
+            if is_dict and list(entry.keys()) != self.keys:
+                raise ValueError(f'track {i} carries the keys {list(entry.keys())}, track 0 {self.keys}')
+            for key in (self.keys if is_dict else [None]):
+                what = f'track {i}' + ('' if key is None else f', {key!r}')
+                if is_dict:
+                    pitches, intervals = entry[key]
+                    pitches = np.asarray(pitches, dtype=np.float64).reshape(-1)
+                    intervals = np.asarray(intervals, dtype=np.float64).reshape(-1, 2)
+                    if len(pitches) != len(intervals):
+                        raise ValueError(f'{what}: {len(pitches)} pitches for {len(intervals)} intervals')
+                    rows = np.concatenate([intervals, pitches[:, None]], axis=-1)
+                else:
+                    rows = np.array(entry, dtype=np.float64)
+                    if rows.size == 0:
+                        rows = rows.reshape(0, 3)
+                    if rows.ndim != 2 or rows.shape[1] != 3:
+                        raise ValueError(f'{what}: batched notes are (N, 3) rows [onset, offset, pitch], not {rows.shape}')
+                bad = ~np.isfinite(rows[:, :2]).all(axis=1)
+                if bad.any():
+                    raise ValueError(f'{what}, row {int(np.argmax(bad))}: a note time is NaN or infinite')
+                bad = rows[:, 1] < rows[:, 0]
+                if bad.any():
+                    r = int(np.argmax(bad))
+                    raise ValueError(f'{what}, row {r}: offset {float(rows[r, 1])!r} < onset {float(rows[r, 0])!r}')
+                rows[:, :2] += 0.0                                 # -0.0 -> 0.0: max / min against a window then have one answer
+                groups.append(_note_order(rows))
+        if stacked is None:
+            raise ValueError('notes: at least one track')
+        self.slices = len(self.keys) if stacked else 1
+        num_tracks = len(groups) // self.slices
+        if bank is not None and num_tracks != len(bank):
+            raise ValueError(f'notes of {num_tracks} tracks for a bank of {len(bank)}')
+        self.frame_counts = None if bank is None else np.array(bank.frame_counts, dtype=np.int64)
+        self.group_ptr = np.concatenate(([0], np.cumsum([len(g) for g in groups]))).astype(np.int64)
+        self.rows = np.ascontiguousarray(np.concatenate(groups + [np.zeros((0, 3))], axis=0))
+        pitch = self.rows[:, 2]
+        self.integral = bool(np.all((pitch == np.floor(pitch)) & (pitch >= 0) & (pitch < 128)))
+        # per group, its onsets and its offsets in ascending order: the host counts a clip's rows with two binary searches per group
+        self._onsets = [np.sort(g[:, 0]) for g in groups]
+        self._offsets = [np.sort(g[:, 1]) for g in groups]
+
+    def __len__(self):
+        return (len(self.group_ptr) - 1) // self.slices
+
+    @property
+    def stacked(self):
+        return self.keys is not None
+
+    @property
+    def nbytes(self):
+        """Bytes of the two tables, on the host as on the device."""
+        return int(self.rows.nbytes + self.group_ptr.nbytes)
+
+    def _upload(self, device):
+        """(rows, group_ptr) on the bank's device; a bank without a note still uploads one (unread) row."""
+        import torch
+        rows = self.rows if len(self.rows) else np.zeros((1, 3))
+        return torch.from_numpy(rows).to(device), torch.from_numpy(self.group_ptr).to(device)
+
+    def _request(self, track_ids, first_frames, num_frames):
+        """A checked clips(...) request -> (track ids, windows)."""
+        if self.frame_counts is None:
+            raise ValueError('a NoteBank built without a bank has no frame grid: name the clips by their windows (window_clips)')
+        ids, firsts = _checked_request(self.frame_counts, track_ids, first_frames, num_frames)
+        return ids, clip_windows(self.module, firsts, num_frames)
+
+    def _checked_windows(self, track_ids, windows):
+        ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
+        windows = np.ascontiguousarray(windows, dtype=np.float64).reshape(-1, 2)
+        if len(ids) != len(windows) or ids.size == 0:
+            raise ValueError('one (start_time, stop_time) per track id, and at least one clip')
+        bad = (ids < 0) | (ids >= len(self))
+        if bad.any():
+            raise ValueError(f'unknown track {int(ids[bad][0])}: the bank holds {len(self)} tracks')
+        bad = ~(windows[:, 0] <= windows[:, 1]) | ~np.isfinite(windows).all(axis=1) | (windows[:, 0] < 0)
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError(f'clip {b}: the window [{float(windows[b, 0])!r}, {float(windows[b, 1])!r}] is not 0 <= start_time <= stop_time, both finite')
+        return ids, windows + 0.0
+
+    def count_clips(self, track_ids, windows):
+        """(batch * slices,) int64: the rows every group of window_clips holds, from two binary searches per group.  A row is dropped for
+        offset <= start_time or for onset > stop_time, never for both (onset <= offset, start_time <= stop_time).  Pure host code."""
+        ids, windows = self._checked_windows(track_ids, windows)
+        counts = np.empty(len(ids) * self.slices, dtype=np.int64)
+        for b, (track, (start, stop)) in enumerate(zip(ids, windows)):
+            for s in range(self.slices):
+                g = int(track) * self.slices + s
+                counts[b * self.slices + s] = np.searchsorted(self._onsets[g], stop, side='right') - np.searchsorted(self._offsets[g], start, side='right')
+        return counts
+
+    def host_window_clips(self, track_ids, windows):
+        """window_clips answered with NumPy: one (n, 3) float64 array per group clip * slices + slice, the reference's slice_batched_notes
+        (amt_tools/tools/utils.py:345-359) statement by statement.  The CPU restatement of the kernel."""
+        ids, windows = self._checked_windows(track_ids, windows)
+        out = []
+        for track, (start, stop) in zip(ids, windows):
+            for s in range(self.slices):
+                g = int(track) * self.slices + s
+                rows = self.rows[self.group_ptr[g]:self.group_ptr[g + 1]]
+                rows = rows[rows[:, 1] > start]
+                rows = rows[rows[:, 0] <= stop]
+                rows[:, 0] = np.maximum(rows[:, 0], start)
+                rows[:, 1] = np.minimum(rows[:, 1], stop)
+                if self.relative_times:
+                    rows[:, :2] -= start
+                out.append(rows)
+        return out
+
+    def window_clips(self, track_ids, windows, rows_capacity=None):
+        """The notes of the clips (track_ids[b], windows[b] = (start_time, stop_time)) as a NoteClips: one amtx_note_clips call.
+        rows_capacity None: the buffer holds exactly the rows count_clips counts, so nothing is cut; a given capacity may be too
+        small, and then offsets[-1] still holds the true total and the rows past the capacity are not written."""
+        import torch
+        ids, windows = self._checked_windows(track_ids, windows)
+        total = int(self.count_clips(ids, windows).sum()) if rows_capacity is None else None
+        capacity = max(total, 1) if rows_capacity is None else int(rows_capacity)
+        rows, group_ptr = self._device_state()
+        device = rows.device
+        batch = len(ids)
+        rows_out = torch.empty((capacity, 3), dtype=torch.float64, device=device)
+        offsets = torch.empty((batch * self.slices + 1,), dtype=torch.int32, device=device)
+        ws = _lib.alloc_workspace(int(_lib.call('amtx_note_clips_workspace_bytes', batch, self.slices)), device)
+        _lib.call('amtx_note_clips', rows, group_ptr, len(self), self.slices, torch.from_numpy(ids).to(device),
+                  torch.from_numpy(windows).to(device), batch, int(self.relative_times), rows_out, capacity, offsets, ws, ws.numel(), device=device)
+        return NoteClips(rows_out, offsets, self.slices, self.keys, total)
+
+    def clips(self, track_ids, first_frames, num_frames, rows_capacity=None):
+        """The notes of the clips [first_frames[b], first_frames[b] + num_frames) of the tracks track_ids[b], as a NoteClips.  Same signature
+        and host validation as bank.clips (_checked_request against the bank's frame counts); the windows are clip_windows'."""
+        return self.window_clips(*self._request(track_ids, first_frames, num_frames), rows_capacity=rows_capacity)
+
+    def host_clips(self, track_ids, first_frames, num_frames):
+        """The same request answered with NumPy (host_window_clips): the fallback for pitches the device matcher does not take."""
+        return self.host_window_clips(*self._request(track_ids, first_frames, num_frames))
