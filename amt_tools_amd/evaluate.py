@@ -2,7 +2,8 @@
 Evaluation: the evaluator classes of amt_tools/evaluate.py (constructor arguments, result-dictionary layout and keys; `train()` takes them
 unchanged: process_track / average_results / reset_results / finalize(writer, step) / set_save_dir / set_patterns / set_verbose), and a
 batched validation loop that scores a partition on the device: validate_batched for host clips and references, validate_clips for clips
-of device-resident tracks (tracks.TrackBank / PyramidBank, LabelBank, NoteBank).
+of device-resident tracks (tracks.TrackBank / PyramidBank, LabelBank, NoteBank), validate_tracks for those tracks whole, one result per
+track, stitched from overlapped clips.
 
 Every evaluator is split in two:
 
@@ -29,7 +30,7 @@ import numpy as np
 from . import tools
 from .inference import run_offline
 
-__all__ = ['validate', 'validate_batched', 'validate_clips', 'average_results', 'append_results', 'log_results', 'write_results', 'pattern_match',
+__all__ = ['validate', 'validate_batched', 'validate_clips', 'validate_tracks', 'average_results', 'append_results', 'log_results', 'write_results', 'pattern_match',
            'Evaluator',
            'ComboEvaluator', 'LossWrapper', 'StackedMultipitchEvaluator', 'MultipitchEvaluator', 'StackedNoteEvaluator', 'NoteEvaluator',
            'TablatureEvaluator', 'SoftmaxAccuracy', 'note_edges', 'match_notes_count', 'N_DECIMALS']
@@ -749,18 +750,43 @@ class _BankNoteRefs(object):
     holds a pitch the device matcher does not take), and `rows` / `offsets` -- read only by a batch that takes the host matcher -- are
     notes.host_clips of the same request, packed when first asked for."""
 
-    def __init__(self, notes, request, dev):
+    def __init__(self, notes, request, dev, whole=False):
+        """request: (track ids, first frames, num_frames) of notes.clips; with `whole`, (track ids,) of notes.whole."""
         self.dev, self.per_clip = dev, notes.slices
         self.keys = [list(notes.keys)] * len(request[0]) if notes.stacked else None
-        self._notes, self._request, self._host = notes, request, None
+        self._notes, self._request, self._host, self._whole = notes, request, None, whole
 
     def _packed(self):
         if self._host is None:
-            self._host = _pack_groups(self._notes.host_clips(*self._request))[:2]
+            groups = self._notes.host_whole(*self._request) if self._whole else self._notes.host_clips(*self._request)
+            self._host = _pack_groups(groups)[:2]
         return self._host
 
     rows = property(lambda self: self._packed()[0])
     offsets = property(lambda self: self._packed()[1])
+
+
+def _check_banks(who, leaves, bank, labels, notes, relative_times):
+    """What validate_clips and validate_tracks refuse before anything is launched: an evaluator whose bank is missing or does not hold
+    its key, stacked against batched notes, (relative_times: a NoteBank with absolute times,) and banks of different track counts."""
+    for e in leaves:
+        if isinstance(e, LossWrapper):
+            continue
+        if isinstance(e, StackedNoteEvaluator):
+            if notes is None:
+                raise ValueError(f'{type(e).__name__} scores notes: {who} needs a NoteBank for it')
+            if e.stacked != notes.stacked:
+                raise ValueError(f'{type(e).__name__} scores {"stacked" if e.stacked else "batched"} notes, the NoteBank holds '
+                                 f'{"stacked" if notes.stacked else "batched"} notes')
+            if relative_times and not notes.relative_times:
+                raise ValueError('the NoteBank holds absolute times: a clip is decoded on a grid that starts at its own first frame (relative_times=True)')
+        elif labels is None:
+            raise ValueError(f'{type(e).__name__} scores the label map \'{e.unpack_key}\': {who} needs a LabelBank for it')
+        elif e.unpack_key not in labels.keys:
+            raise ValueError(f'{type(e).__name__} scores the label map \'{e.unpack_key}\', the LabelBank holds {labels.keys}')
+    for other, what in ((labels, 'LabelBank'), (notes, 'NoteBank')):
+        if other is not None and len(other) != len(bank):
+            raise ValueError(f'a bank of {len(bank)} tracks and a {what} of {len(other)}')
 
 
 def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frames, num_frames, times=None, batch_size=256, rank=0, world=1):
@@ -778,24 +804,7 @@ def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frame
     appended in clip order; returns evaluator.average_results() for the clips this rank owns."""
     from .inference import BankClips, _model_device
     leaves = _leaves(evaluator)
-    for e in leaves:
-        if isinstance(e, LossWrapper):
-            continue
-        if isinstance(e, StackedNoteEvaluator):
-            if notes is None:
-                raise ValueError(f'{type(e).__name__} scores notes: validate_clips needs a NoteBank for it')
-            if e.stacked != notes.stacked:
-                raise ValueError(f'{type(e).__name__} scores {"stacked" if e.stacked else "batched"} notes, the NoteBank holds '
-                                 f'{"stacked" if notes.stacked else "batched"} notes')
-            if not notes.relative_times:
-                raise ValueError('the NoteBank holds absolute times: a clip is decoded on a grid that starts at its own first frame (relative_times=True)')
-        elif labels is None:
-            raise ValueError(f'{type(e).__name__} scores the label map \'{e.unpack_key}\': validate_clips needs a LabelBank for it')
-        elif e.unpack_key not in labels.keys:
-            raise ValueError(f'{type(e).__name__} scores the label map \'{e.unpack_key}\', the LabelBank holds {labels.keys}')
-    for other, what in ((labels, 'LabelBank'), (notes, 'NoteBank')):
-        if other is not None and len(other) != len(bank):
-            raise ValueError(f'a bank of {len(bank)} tracks and a {what} of {len(other)}')
+    _check_banks('validate_clips', leaves, bank, labels, notes, relative_times=True)
     source = BankClips(bank, track_ids, first_frames, num_frames)
     if not _model_device(model)[1]:
         raise ValueError('validate_clips scores clips of device-resident tracks: the model has to be on a GPU')
@@ -815,13 +824,15 @@ def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frame
     return evaluator.average_results()
 
 
-def _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world):
-    """What validate_batched and validate_clips share on a GPU model: inference._batched over `clips` (host clips or a BankClips) with
-    every leaf's enqueue_batch / results_batch as its hooks.  stage(idx, batch) -> what each leaf gets as `staged`: the references of the
-    clips idx on the device (or on their way there through batch.upload)."""
+def _batch_scorer(stage, model, evaluator, times):
+    """The part of the device validation loops that scores ONE batch of predictions, as the three hooks inference._batched calls:
+    (stage_extra, enqueue, finish).  stage(idx, batch) -> what each leaf gets as `staged`: the references of the clips idx on the device
+    (or on their way there through batch.upload).  enqueue(idx, preds, batch) decodes the notes of `preds` when the evaluator tree holds a
+    note evaluator (grid: `times`, None for the model's own grid of the maps' length) and enqueues every leaf's counting on the current
+    stream; finish(batch) brings the counts back on transcribe's side stream and appends every clip's results under its index."""
     import torch
     from . import transcribe
-    from .inference import _batched, _model_device
+    from .inference import _model_device
     leaves = _leaves(evaluator)
     need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
     device = _model_device(model)[0]
@@ -858,4 +869,58 @@ def _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, wo
         for j, i in enumerate(batch.idx):
             track([r[j] for r in per_eval], i)
 
+    return stage_extra, enqueue, finish
+
+
+def _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world):
+    """What validate_batched and validate_clips share on a GPU model: inference._batched over `clips` (host clips or a BankClips) with
+    _batch_scorer's hooks."""
+    from .inference import _batched
+    stage_extra, enqueue, finish = _batch_scorer(stage, model, evaluator, times)
     _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra)
+
+
+def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1):
+    """Score WHOLE resident tracks, one result per track, as the reference's validate does -- from equally long overlapped clips.  The
+    tracks (`track_ids`, default every track of `bank`; position j belongs to rank j % world) go through inference.run_tracks' stitching
+    pass: clips of `num_frames` frames by tracks.seam_clips, of each only the frames at least `margin` frames from a clip edge that is
+    not a track edge, written into whole-track maps on the device.  Then, track by track, the stitched views are the predictions of a
+    batch of one, labels.clips([t], [0], L_t) and notes.whole([t]) its references, and both go through the hooks validate_clips scores a
+    batch with: notes are decoded on the track's own grid, only count tensors come back, and the host matcher (on notes.host_whole)
+    takes over where validate_clips falls back.  Every track's results are tracked under its id, in request order; returns
+    evaluator.average_results() for the tracks this rank owns.
+
+    Segment-wise inference (inference.run_tracks): exact for TabCNN from margin 4 on and for tracks that fit one clip, an approximation
+    for the BiLSTMs of Onsets & Frames; `margin` has no default.  ValueError before anything is launched as in validate_clips (a missing
+    bank or key, stacked against batched notes, a model that is not on a GPU), and for what tracks.seam_clips refuses.  A NoteBank with
+    absolute times is as good as one with relative times: a whole track starts at time 0.  A LossWrapper warns and contributes an
+    empty dictionary."""
+    import torch
+    from .inference import _model_device, _stitch_tracks
+    leaves = _leaves(evaluator)
+    _check_banks('validate_tracks', leaves, bank, labels, notes, relative_times=False)
+    if not _model_device(model)[1]:
+        raise ValueError('validate_tracks scores device-resident tracks: the model has to be on a GPU')
+    need_maps = any(not isinstance(e, (LossWrapper, StackedNoteEvaluator)) for e in leaves)
+    need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
+    with torch.no_grad():
+        mine, stitched = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world)
+
+        def stage(idx, batch):
+            maps = labels.clips(idx, [0], int(bank.frame_counts[idx[0]])) if need_maps else None
+            refs = None
+            if need_notes:
+                whole = notes.whole(idx) if notes.integral else None
+                refs = _BankNoteRefs(notes, (idx,), (whole.rows, whole.offsets) if whole is not None else None, whole=True)
+            return [None if isinstance(e, LossWrapper) else refs if isinstance(e, StackedNoteEvaluator) else maps[e.unpack_key] for e in leaves]
+
+        stage_extra, enqueue, finish = _batch_scorer(stage, model, evaluator, None)
+        pending = None
+        for j, t in enumerate(mine.tolist()):
+            now = enqueue([t], {key: stitched.track(j, key) for key in stitched.keys}, stage_extra([t]))
+            if pending is not None:
+                finish(pending)                                   # the GPU scores track j meanwhile
+            pending = now
+        if pending is not None:
+            finish(pending)
+    return evaluator.average_results()

@@ -9,6 +9,10 @@ Inference drivers.
 * `_batched(...)` -- the loop under it, under `evaluate.validate_batched` and under `evaluate.validate_clips`: a partition through the
   model, batch by batch.  Its batches come from one of two sources: host clips that are uploaded, or `BankClips` -- clips named as
   (track, first frame) of a tracks.TrackBank / PyramidBank, whose model input the bank makes on the device.
+* `run_tracks(...)` -- WHOLE resident tracks, one result per track, from equally long overlapped clips (tracks.seam_clips) through the same
+  loop: behind every batch the kept columns of every output tensor are written into whole-track maps on the device (tracks.TrackMaps,
+  amtx_stitch_clips); `_stitch_tracks` is that pass, shared with `evaluate.validate_tracks`.  Segment-wise inference: exact for TabCNN
+  (margin >= 4) and for tracks that fit one clip, an approximation for the BiLSTMs of Onsets & Frames.
 """
 
 import numpy as np
@@ -17,7 +21,7 @@ import torch
 from . import tools
 from .dp import shard_indices
 
-__all__ = ['run_offline', 'run_offline_batched']
+__all__ = ['run_offline', 'run_offline_batched', 'run_tracks']
 
 
 def run_offline(track_data, model, estimator=None):
@@ -192,4 +196,101 @@ def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=
                 out[i][tools.KEY_NOTES] = notes[j]
 
     _batched(clips, model, batch_size, rank, world, enqueue, finish)
+    return out
+
+
+def _stitch_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1, wanted=None):
+    """The stitching pass of run_tracks and evaluate.validate_tracks -> (the track ids this rank owns, in request order; the
+    tracks.TrackMaps of their whole-track outputs, slot j = the j-th of those ids, or None when the rank owns no track).
+
+    Ranks share TRACKS: position j of the request (default: every track of the bank) belongs to rank j % world.  The rank's tracks are
+    covered by tracks.seam_clips(num_frames, margin); the clips run through `_batched` over a BankClips, unsharded, and the enqueue hook
+    writes the kept columns of every output tensor (`wanted`: the keys to keep, default all) into the maps right behind run_on_batch, on
+    the model's stream -- an output that lives in the engine's workspace is read before the next batch overwrites it.  Tracks shorter
+    than a clip follow, each whole as one clip of its own length: one more pass per distinct length, through the same hook.
+
+    ValueError before anything is launched: what seam_clips refuses (for the whole request, whichever rank owns the track) and a model
+    that is not on a GPU."""
+    from .tracks import TrackMaps, seam_clips
+    seam_clips(bank.frame_counts, num_frames, margin, track_ids)                      # the whole request, checked once
+    device, on_gpu = _model_device(model)
+    if not on_gpu:
+        raise ValueError('whole tracks are stitched from clips of device-resident tracks: the model has to be on a GPU')
+    ids = np.arange(len(bank), dtype=np.int64) if track_ids is None else np.asarray(track_ids, dtype=np.int64).reshape(-1)
+    mine = ids[shard_indices(len(ids), rank, world)]
+    if mine.size == 0:
+        return mine, None
+    counts = np.asarray(bank.frame_counts, dtype=np.int64)[mine]
+    plan = seam_clips(counts, num_frames, margin)                                      # over SLOTS: a track named twice has two maps
+    maps = TrackMaps(counts, device)
+    passes = [(int(num_frames), plan.track_ids, plan.first_frames, plan.kept)] if len(plan.track_ids) else []
+    for length in sorted(set(counts[plan.short].tolist())):
+        slots = plan.short[counts[plan.short] == length]
+        passes.append((length, slots, np.zeros(len(slots), dtype=np.int64), np.tile(np.array([[0, 0, length]], dtype=np.int64), (len(slots), 1))))
+    for frames, slots, firsts, kept in passes:
+        tables = {}                        # rows of a map -> its descriptor table, on the host and on the device: uploaded once per pass
+
+        def enqueue(idx, preds, _):
+            lo, hi = int(idx[0]), int(idx[-1]) + 1                                     # unsharded: a batch is a run of clips
+            for key, value in preds.items():
+                if not torch.is_tensor(value) or (wanted is not None and key not in wanted):
+                    continue
+                if value.dim() < 2 or value.shape[0] != hi - lo or value.shape[-1] != frames:
+                    raise ValueError(f"the model output '{key}' is no (batch, rows..., num_frames) map: {tuple(value.shape)} for {hi - lo} clips of {frames} frames")
+                if key not in maps.keys:
+                    maps.add(key, value.shape[1:-1], value.dtype)
+                rows = maps.rows(key)
+                if rows not in tables:
+                    desc = maps.descriptors(key, slots, kept)
+                    tables[rows] = desc, torch.from_numpy(desc).to(device)
+                desc, desc_dev = tables[rows]
+                maps.stitch(key, value, desc[lo:hi], desc_dev[lo:hi])
+            return idx
+
+        _batched(BankClips(bank, mine[slots], firsts, frames), model, batch_size, 0, 1, enqueue, lambda pending: None)
+    return mine, maps
+
+
+@torch.no_grad()
+def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, keep=None, decode_notes=False, times=None, rank=0, world=1):
+    """Transcribe WHOLE tracks of `bank` (a tracks.TrackBank / PyramidBank) from overlapped clips of `num_frames` frames: returns
+    {track id: predictions} for the tracks this rank owns (position j of `track_ids`, default every track, belongs to rank j % world).
+    A track's predictions are host arrays (rows..., L_t) per output key, L_t the track's own frame count, and with decode_notes=True its
+    notes under tools.KEY_NOTES, decoded on the device from the track's stitched maps alone with the frame grid of its own length
+    (`times`: None for the grid of the model's front-end, else indexed by track id: times[t] is the (L_t,) grid of track t).
+    `keep` as for run_offline_batched (default: every array; () = notes only; KEY_MULTIPITCH of a tablature model on request).
+
+    Of each clip only the frames at least `margin` frames from a clip edge that is not a track edge are kept (tracks.seam_clips), so this
+    is SEGMENT-WISE inference.  For TabCNN, whose frames see 9 frames of features, margin >= 4 gives the whole-track result.  For
+    Onsets & Frames the convolutions are exact from margin 3 on in exact arithmetic, but every BiLSTM starts anew at each clip edge and
+    sees `margin` frames of context instead of the whole track: an approximation, measured in README; a track that fits one clip is run
+    whole and is exact.  `margin` has no default."""
+    from . import transcribe
+    decoder_keys = (tools.KEY_ONSETS, tools.KEY_MULTIPITCH, tools.KEY_TABLATURE)
+    wanted = None if keep is None else set(keep) | (set(decoder_keys) if decode_notes else set())
+    if keep is not None and tools.KEY_MULTIPITCH in keep:
+        wanted.add(tools.KEY_TABLATURE)                        # a tablature model's pitch map is expanded from its stitched tablature
+    mine, maps = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, wanted)
+    out = {}
+    if maps is None:
+        return out
+    host = {key: maps.host(key) for key in maps.keys if keep is None or key in keep}
+    want_pitch = keep is not None and tools.KEY_MULTIPITCH in keep and tools.KEY_MULTIPITCH not in maps.keys and tools.KEY_TABLATURE in maps.keys
+
+    def collect(j, handle):
+        out[int(mine[j])][tools.KEY_NOTES] = handle.result()[0]
+
+    pending = None
+    for j, t in enumerate(mine.tolist()):
+        out[t] = {key: arrays[j] for key, arrays in host.items()}
+        if want_pitch:                                         # the collapsed pitch map of a tablature (amtx_tab_expand), as run_offline_batched
+            out[t][tools.KEY_MULTIPITCH] = tools.tab_expand(maps.track(j, tools.KEY_TABLATURE), model.profile, stacked=False, collapsed=True)[1][0].cpu().numpy()
+        if decode_notes:
+            preds = {key: maps.track(j, key) for key in maps.keys}
+            handle = transcribe.decode_notes_for(preds, model, None if times is None else times[t])
+            if pending is not None:
+                collect(*pending)                              # the GPU decodes track j meanwhile
+            pending = j, handle
+    if pending is not None:
+        collect(*pending)
     return out

@@ -27,18 +27,26 @@ reference's rule (draw_clips) and yields complete batches: features' clips under
 (amt_tools/tools/utils.py:322-361), computed per (clip, slice) on the device (amtx_note_clips, include/amtx_noteclips.h) into the
 (rows, offsets) pair the device note matcher reads.  `cover_clips` names the consecutive clips that cover whole tracks.
 
+Whole tracks come from the same clips: `seam_clips` covers every track with equally long, overlapping clips and names the frames each
+clip keeps, `TrackMaps` holds the whole-track outputs on the device, every track's map contiguous with its own width, and
+amtx_stitch_clips (include/amtx_stitch.h; `stitch_host` is its NumPy restatement) writes a batch's kept columns into them.
+`NoteBank.whole` is the unsliced note ground truth of whole tracks.  inference.run_tracks and evaluate.validate_tracks are the drivers.
+
 What the banks share is written once: `_checked_request` validates a `clips(track_ids, first_frames, num_frames)` request against
 a bank's frame counts, `_clip_table` lays the checked request out as the int64 table a clip kernel reads (clip_descriptors adds the
 reflect rule and the 4-column form of amtx_spec_power_clips), `_Resident` is the lazy, never-pickled device state, and `_Clips` is the
 batch entry that TrackClips and PyramidClips name -- the feature modules and models choose the kernel family by that type.
 """
 
+from collections import namedtuple
+
 import numpy as np
 
 from . import _lib
 
 __all__ = ['TrackBank', 'TrackClips', 'PyramidBank', 'PyramidClips', 'clip_descriptors', 'frame_start',
-           'LabelBank', 'ClipLoader', 'encode_rows', 'decode_rows', 'draw_clips', 'NoteBank', 'NoteClips', 'cover_clips', 'clip_windows']
+           'LabelBank', 'ClipLoader', 'encode_rows', 'decode_rows', 'draw_clips', 'NoteBank', 'NoteClips', 'cover_clips', 'clip_windows',
+           'SeamPlan', 'seam_clips', 'stitch_host', 'stitch_clips', 'TrackMaps']
 
 
 def frame_start(sample_start, hop_length):
@@ -792,3 +800,222 @@ class NoteBank(_Resident):
     def host_clips(self, track_ids, first_frames, num_frames):
         """The same request answered with NumPy (host_window_clips): the fallback for pitches the device matcher does not take."""
         return self.host_window_clips(*self._request(track_ids, first_frames, num_frames))
+
+    def _checked_tracks(self, track_ids):
+        ids = np.asarray(track_ids, dtype=np.int64).reshape(-1)
+        if ids.size == 0:
+            raise ValueError('at least one track')
+        bad = (ids < 0) | (ids >= len(self))
+        if bad.any():
+            raise ValueError(f'unknown track {int(ids[bad][0])}: the bank holds {len(self)} tracks')
+        return ids
+
+    def host_whole(self, track_ids):
+        """The unsliced notes of whole tracks with NumPy: one (n, 3) float64 array per group track * slices + slice, in the bank's
+        (pitch, onset) order, times as the constructor took them.  Nothing is clamped and nothing is dropped: a note with offset == 0,
+        which every window that starts at 0 drops (offset <= start_time), is still there."""
+        out = []
+        for track in self._checked_tracks(track_ids):
+            for g in range(int(track) * self.slices, (int(track) + 1) * self.slices):
+                out.append(self.rows[self.group_ptr[g]:self.group_ptr[g + 1]].copy())
+        return out
+
+    def whole(self, track_ids):
+        """The unsliced notes of whole tracks as a NoteClips -- host_whole on the device: `rows` and int32 `offsets` of the tracks' groups,
+        taken from the resident table by index arithmetic.  Consecutive tracks give a view of the table, anything else one gather; no
+        kernel of this library runs.  A whole track starts at time 0, so relative and absolute times are the same."""
+        import torch
+        ids = self._checked_tracks(track_ids)
+        rows, _ = self._device_state()
+        lo, hi = self.group_ptr[ids * self.slices], self.group_ptr[(ids + 1) * self.slices]
+        # per group its size, in request order
+        sizes = np.concatenate([np.diff(self.group_ptr[int(t) * self.slices:(int(t) + 1) * self.slices + 1]) for t in ids])
+        offsets = np.concatenate(([0], np.cumsum(sizes)))
+        total = int(offsets[-1])
+        if total >= 2 ** 31:
+            raise ValueError(f'{total} notes: the offsets of a NoteClips are int32')
+        if total == 0:
+            out = rows[:1]                                   # the (unread) row every NoteClips holds at least
+        elif (np.diff(ids) == 1).all():
+            out = rows[int(lo[0]):int(hi[-1])]
+        else:
+            index = np.concatenate([np.arange(a, b, dtype=np.int64) for a, b in zip(lo, hi)])
+            out = rows[torch.from_numpy(index).to(rows.device)]
+        return NoteClips(out, torch.from_numpy(offsets.astype(np.int32)).to(rows.device), self.slices, self.keys, total)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# whole tracks from overlapped clips
+# ------------------------------------------------------------------------------------------------------------------------------
+# What seam_clips returns.  track_ids / first_frames: the clips, (n,) int64 each, in track order; kept: (n, 3) int64 rows
+# {dst_first_frame, src_first_col, count} -- clip j keeps its columns [src_first_col, src_first_col + count), which are the frames
+# [dst_first_frame, dst_first_frame + count) of its track; short: (m,) int64, the requested tracks shorter than a clip, in request order.
+SeamPlan = namedtuple('SeamPlan', 'track_ids first_frames kept short')
+
+
+def seam_clips(frame_counts, num_frames, margin, track_ids=None):
+    """Equally long, overlapping clips that cover whole tracks, and the frames each clip keeps: a SeamPlan.  Of a clip only frames at
+    least `margin` frames away from a clip edge that is not a track edge are kept.  With stride = num_frames - 2 * margin, a track of
+    L >= num_frames frames gives the clips at 0, stride, 2 * stride, ... while first + num_frames < L, then one last clip at
+    L - num_frames (its right edge is the track's own end).  The seams are 0, the middle first_{j+1} + (first_j + num_frames -
+    first_{j+1}) // 2 of every overlap, and L; clip j keeps the track's frames [seam_j, seam_{j+1}).  Every frame is kept exactly once.
+
+    track_ids: the tracks to cover, in this order (default: every track).  A track with L < num_frames gives no clip and is named in
+    `short`: it fits one clip of its own length.  ValueError for margin < 0, num_frames - 2 * margin < 1 and an unknown track.
+    Pure host code."""
+    frame_counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+    num_frames, margin = int(num_frames), int(margin)
+    if margin < 0:
+        raise ValueError(f'margin={margin}: the frames left out at a clip edge cannot be negative')
+    stride = num_frames - 2 * margin
+    if stride < 1:
+        raise ValueError(f'num_frames={num_frames} with margin={margin}: a clip keeps num_frames - 2 * margin frames, at least one')
+    ids = np.arange(len(frame_counts), dtype=np.int64) if track_ids is None else np.asarray(track_ids, dtype=np.int64).reshape(-1)
+    bad = (ids < 0) | (ids >= len(frame_counts))
+    if bad.any():
+        raise ValueError(f'unknown track {int(ids[bad][0])}: the bank holds {len(frame_counts)} tracks')
+    tracks, firsts, kept, short = [], [], [], []
+    for t in ids.tolist():
+        L = int(frame_counts[t])
+        if L < num_frames:
+            short.append(t)
+            continue
+        first = list(range(0, L - num_frames, stride)) + [L - num_frames]
+        seams = [0] + [b + (a + num_frames - b) // 2 for a, b in zip(first[:-1], first[1:])] + [L]
+        for j, f in enumerate(first):
+            tracks.append(t)
+            firsts.append(f)
+            kept.append((seams[j], seams[j] - f, seams[j + 1] - seams[j]))
+    return SeamPlan(np.array(tracks, dtype=np.int64), np.array(firsts, dtype=np.int64), np.array(kept, dtype=np.int64).reshape(-1, 3),
+                    np.array(short, dtype=np.int64))
+
+
+def _stitch_args(dst, src, desc, is_tensor):
+    """What stitch_host and stitch_clips check alike -> (batch, rows, num_frames) of src."""
+    if src.ndim < 2 or src.shape[0] < 1 or src.shape[-1] < 1 or int(np.prod(src.shape)) == 0:
+        raise ValueError(f'src is (batch, rows..., num_frames) with at least one of each, not {tuple(src.shape)}')
+    if dst.ndim != 1 or not (dst.is_contiguous() if is_tensor else dst.flags.c_contiguous):
+        raise ValueError('dst is one flat, contiguous buffer')
+    if src.dtype != dst.dtype:
+        raise TypeError(f'src holds {src.dtype}, dst {dst.dtype}')
+    if desc.ndim != 2 or desc.shape != (src.shape[0], 5):
+        raise ValueError(f'one descriptor row {{base, L, dst_first, src_first, count}} per clip: ({src.shape[0]}, 5), not {desc.shape}')
+    batch, num_frames = int(src.shape[0]), int(src.shape[-1])
+    return batch, int(np.prod(src.shape)) // (batch * num_frames), num_frames
+
+
+def stitch_host(dst, src, desc):
+    """amtx_stitch_clips with NumPy (include/amtx_stitch.h): dst[base_b + r * L_b + dst_first_b + i] = src[b][r][src_first_b + i] for every
+    row {base, L, dst_first, src_first, count} of `desc`, in place; returns dst.  src: (batch, rows..., num_frames); dst: a flat array of
+    the same dtype.  ValueError for a row the entry point refuses.  The CPU restatement of the kernel."""
+    src, desc = np.asarray(src), np.asarray(desc, dtype=np.int64)
+    batch, rows, num_frames = _stitch_args(dst, src, desc, False)
+    for b, (base, L, dst_first, src_first, count) in enumerate(desc.tolist()):
+        if min(base, L, dst_first, src_first, count) < 0 or src_first + count > num_frames or dst_first + count > L or base + rows * L > dst.size:
+            raise ValueError(f'clip {b}: the row {(base, L, dst_first, src_first, count)} leaves the clip, the track or dst')
+    flat = src.reshape(batch, rows, num_frames)
+    for b, (base, L, dst_first, src_first, count) in enumerate(desc.tolist()):
+        dst[base:base + rows * L].reshape(rows, L)[:, dst_first:dst_first + count] = flat[b, :, src_first:src_first + count]
+    return dst
+
+
+STITCH_DTYPES = ('torch.float32', 'torch.int64')       # 4-byte maps (piano rolls, offset probabilities) and the 8-byte tablature
+
+
+def stitch_clips(dst, src, desc, desc_dev=None):
+    """One amtx_stitch_clips launch on the current stream: the kept columns of every clip of the device tensor `src` (batch, rows...,
+    num_frames) into the flat device tensor `dst`, by the int64 (batch, 5) host table `desc` (stitch_host's).  desc_dev: its device copy,
+    when the caller has uploaded it already.  float32 and int64 are taken, as bit patterns.  Shapes, dtypes and devices are checked
+    here, before the library is entered; the rows of `desc` by the entry point, before anything is launched."""
+    import torch
+    if not (torch.is_tensor(src) and torch.is_tensor(dst)):
+        raise TypeError('src and dst are device tensors (stitch_host takes arrays)')
+    if not src.is_cuda or dst.device != src.device:
+        raise ValueError(f'src ({src.device}) and dst ({dst.device}) are on one GPU')
+    if str(src.dtype) not in STITCH_DTYPES:
+        raise TypeError(f'a stitched map holds float32 or int64 elements, not {src.dtype}')
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    batch, rows, num_frames = _stitch_args(dst, src, desc, True)
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(desc).to(src.device)
+    elif desc_dev.device != src.device or desc_dev.dtype != torch.int64 or tuple(desc_dev.shape) != desc.shape or not desc_dev.is_contiguous():
+        raise ValueError('desc_dev is the contiguous int64 copy of desc on the GPU of src')
+    _lib.call('amtx_stitch_clips', src.contiguous(), src.element_size(), batch, rows, num_frames, desc, desc_dev, dst, dst.numel(), device=src.device)
+    return dst
+
+
+class TrackMaps(object):
+    """The whole-track outputs of a set of tracks on the device: per key ONE flat allocation that holds every track's (rows..., L_t) map
+    back to back, each contiguous with its own width.  `frame_counts`: (n,) frames of the tracks, in the order of the slots 0 .. n - 1;
+    `base[key]`: (n,) int64, the element at which every slot's map starts.  Nothing downstream sees padding: `track(j, key)` is the
+    (1, rows..., L_j) view the decoders and evaluators take as a batch of one.
+
+    A key is added with the shape and dtype of its maps (`add`); the drivers do that when the first batch shows them.  The memory is
+    not initialised: a plan that keeps every frame exactly once (seam_clips) writes all of it."""
+
+    def __init__(self, frame_counts, device):
+        self.frame_counts = np.array(frame_counts, dtype=np.int64).reshape(-1)
+        if self.frame_counts.size == 0 or (self.frame_counts < 1).any():
+            raise ValueError('frame_counts: at least one track, at least one frame each')
+        self.device = device
+        self._first = np.concatenate(([0], np.cumsum(self.frame_counts)))         # frames in front of every slot, and of the end
+        self.base, self._flat, self._shape = {}, {}, {}
+
+    def __len__(self):
+        return len(self.frame_counts)
+
+    @property
+    def keys(self):
+        return list(self._flat)
+
+    @property
+    def nbytes(self):
+        """Bytes of all allocations."""
+        return int(sum(t.numel() * t.element_size() for t in self._flat.values()))
+
+    def add(self, key, shape, dtype):
+        """Allocate the maps under `key`: `shape` is a map's shape without its frame axis ((88,) for a piano roll, (6,) for a tablature),
+        dtype torch.float32 or torch.int64."""
+        import torch
+        if key in self._flat:
+            raise ValueError(f"the maps already hold '{key}'")
+        if str(dtype) not in STITCH_DTYPES:
+            raise TypeError(f"'{key}': a stitched map holds float32 or int64 elements, not {dtype}")
+        shape = tuple(int(s) for s in shape)
+        rows = int(np.prod(shape)) if shape else 1
+        if rows < 1:
+            raise ValueError(f"'{key}': a map has at least one row, not the shape {shape}")
+        self._shape[key], self.base[key] = shape, self._first[:-1] * rows
+        self._flat[key] = torch.empty((int(self._first[-1]) * rows,), dtype=dtype, device=self.device)
+
+    def rows(self, key):
+        return int(np.prod(self._shape[key])) if self._shape[key] else 1
+
+    def flat(self, key):
+        """The allocation under `key`: 1-D, slot j at [base[key][j], base[key][j] + rows * frame_counts[j])."""
+        return self._flat[key]
+
+    def track(self, j, key):
+        """The map of slot j under `key` as a batch of one: a contiguous (1, rows..., L_j) view."""
+        at, L = int(self.base[key][j]), int(self.frame_counts[j])
+        return self._flat[key][at:at + self.rows(key) * L].view((1,) + self._shape[key] + (L,))
+
+    def descriptors(self, key, slots, kept):
+        """The (n, 5) int64 table {base, L, dst_first, src_first, count} of clips whose tracks are the slots `slots` and whose kept
+        columns are the (n, 3) rows `kept` of a SeamPlan.  ValueError for an unknown slot."""
+        slots, kept = np.asarray(slots, dtype=np.int64).reshape(-1), np.asarray(kept, dtype=np.int64).reshape(-1, 3)
+        if len(slots) != len(kept) or ((slots < 0) | (slots >= len(self))).any():
+            raise ValueError(f'one slot below {len(self)} per row of kept columns')
+        return _clip_table(self.base[key][slots], self.frame_counts[slots], kept[:, 0], kept[:, 1], kept[:, 2])
+
+    def stitch(self, key, src, desc, desc_dev=None):
+        """stitch_clips of one batch tensor into the maps under `key`; its shape between batch and frames is the maps'."""
+        if tuple(src.shape[1:-1]) != self._shape[key]:
+            raise ValueError(f"'{key}': a batch of {tuple(src.shape[1:-1])} maps for maps of {self._shape[key]}")
+        stitch_clips(self._flat[key], src, desc, desc_dev)
+
+    def host(self, key):
+        """Every slot's map on the host, (rows..., L_j) each: one copy of the allocation, sliced."""
+        flat = self._flat[key].cpu().numpy()
+        rows = self.rows(key)
+        return [flat[int(at):int(at) + rows * int(L)].reshape(self._shape[key] + (int(L),)) for at, L in zip(self.base[key], self.frame_counts)]
