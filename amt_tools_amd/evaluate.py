@@ -348,16 +348,30 @@ class LossWrapper(Evaluator):
     def evaluate(self, estimated, reference=None):
         return estimated
 
-    # an eval-mode batch carries no loss: nothing to stage or count, unpack()'s warning and an empty dictionary per clip
+    # By default an eval-mode batch carries no loss: nothing to stage or count, unpack()'s warning and an empty dictionary per clip.
+    # With losses=True the loops run the model labelled with tools.KEY_LOSS_FRAMES: its per-clip float64 sums (batch.preds) are the
+    # "counts" that come back, and a clip's dictionary is {loss key: sum / frames} -- the loss of that clip as a batch of one.
+    # validate_tracks adds the sums up per track itself and hands over finished dictionaries (batch.loss_results).
     def stage_batch(self, refs, batch):
         return None
 
     def enqueue_batch(self, staged, batch):
-        return ()
+        if batch.loss_counts is None:
+            return ()
+        loss = tools.unpack_dict(batch.preds, self.unpack_key)
+        if not isinstance(loss, dict):
+            raise KeyError(f'the model output has no per-clip losses under \'{self.unpack_key}\'')
+        batch.loss_keys = list(loss.keys())
+        return tuple(loss.values())
 
     def results_batch(self, staged, counts, batch):
-        warnings.warn(f'Entry for key \'{self.unpack_key}\' not found in estimates.', category=RuntimeWarning)
-        return [dict() for _ in batch.idx]
+        if batch.loss_results is not None:
+            return batch.loss_results
+        if batch.loss_counts is None:
+            warnings.warn(f'Entry for key \'{self.unpack_key}\' not found in estimates.', category=RuntimeWarning)
+            return [dict() for _ in batch.idx]
+        frames = np.asarray(batch.loss_counts, dtype=np.float64)
+        return [{key: np.float64(sums[j]) / frames[j] for key, sums in zip(batch.loss_keys, counts)} for j in range(len(batch.idx))]
 
 
 class StackedEvaluator(Evaluator):
@@ -687,6 +701,9 @@ class _Batch(object):
 
     def __init__(self, idx, model, device):
         self.idx, self.model, self.device, self.uploads, self._est_host = idx, model, device, [], None
+        # losses=True: model_entries, the ground truth (and tools.KEY_LOSS_FRAMES) the model's batch carries; loss_counts, the frames each
+        # clip's sums run over; loss_results, finished loss dictionaries (validate_tracks).  All None: a LossWrapper warns as ever
+        self.model_entries = self.loss_counts = self.loss_results = None
 
     def upload(self, array):
         """A host array of references to the device, from pinned memory on the current (copy) stream; enqueue record_stream()s them all."""
@@ -713,7 +730,25 @@ class _Batch(object):
         return self._est_host
 
 
-def validate_batched(clips, references, model, evaluator, times=None, batch_size=256, rank=0, world=1):
+def _check_losses(who, leaves, model, labels=None, banks=False):
+    """What losses=True needs, checked before anything is launched -> the model's loss_label_keys.  ValueError without a LossWrapper
+    among the evaluators, for a model without a per-clip loss and, in the bank loops, without a LabelBank or for a LabelBank that lacks
+    one of those keys: all of them, for a map derived at a clip's edge (onsets from multi_pitch) would differ from the track's."""
+    if not any(isinstance(e, LossWrapper) for e in leaves):
+        raise ValueError(f'{who}: losses=True scores the loss through a LossWrapper: the evaluator holds none')
+    keys = getattr(model, 'loss_label_keys', None)
+    if keys is None:
+        raise ValueError(f'{who}: losses=True needs a model with per-clip losses (loss_label_keys): {type(model).__name__} has none')
+    if banks:
+        if labels is None:
+            raise ValueError(f'{who}: losses=True needs a LabelBank with the label maps {tuple(keys)} of {type(model).__name__}')
+        for key in keys:
+            if key not in labels.keys:
+                raise ValueError(f'{who}: losses=True needs the label map \'{key}\' of {type(model).__name__}, the LabelBank holds {labels.keys}')
+    return tuple(keys)
+
+
+def validate_batched(clips, references, model, evaluator, times=None, batch_size=256, rank=0, world=1, losses=False):
     """Score a partition without bringing a map to the host.  `clips` as for run_offline_batched; `references`: one ground-truth dictionary
     per clip with the keys the evaluators unpack (KEY_MULTIPITCH / KEY_ONSETS / KEY_OFFSETS maps, KEY_NOTES as batched notes -- stacked
     notes for tablature models --, KEY_TABLATURE).  The loop is run_offline_batched's (inference._batched), with every evaluator's
@@ -721,16 +756,31 @@ def validate_batched(clips, references, model, evaluator, times=None, batch_size
     are decoded on the device when the evaluator tree holds a note evaluator and the decoder's row arrays go straight to
     amtx_eval_notes_match; only the count tensors (and the decoder's offsets table) come back, on transcribe's side stream, while the next
     batch runs.  Every clip's results are appended to the evaluator in clip order, exactly as process_track would have.  Returns
-    evaluator.average_results() for the clips this rank owns."""
+    evaluator.average_results() for the clips this rank owns.
+
+    A LossWrapper among the evaluators warns and contributes an empty dictionary per clip -- an eval-mode batch carries no loss -- unless
+    `losses` is set.  With losses=True (a GPU model) the references' own maps under the model's loss_label_keys are uploaded beside the
+    audio (a key a map evaluator reads too goes up twice), the model runs labelled with tools.KEY_LOSS_FRAMES = None and returns per-clip
+    float64 sums (amt_tools_amd/cliploss.py); the LossWrapper tracks {loss key: sum / frames} per clip, the reference's loss of that clip
+    as a batch of one, so average_results()[KEY_LOSS] is the mean over clips; nothing warns, and only the sum tensors come back beside
+    the counts.  ValueError before anything is launched: no LossWrapper, a model whose loss_label_keys is None, a model that is not on
+    a GPU, a reference without the first of those keys (the others are derived by the model where its post_proc derives them)."""
     from .inference import _model_device, run_offline_batched
     assert len(references) == len(clips), (len(references), len(clips))
     leaves = _leaves(evaluator)
+    loss_keys = _check_losses('validate_batched', leaves, model) if losses else None
     need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
     device, on_gpu = _model_device(model)
 
     def track(results, i):
         evaluator.track_results(results if isinstance(evaluator, ComboEvaluator) else results[0], i)
 
+    if losses:
+        for i, ref in enumerate(references):
+            if not tools.query_dict(ref, loss_keys[0]):
+                raise ValueError(f'validate_batched: losses=True needs the label map \'{loss_keys[0]}\' of every clip: the reference of clip {i} has none')
+        if not on_gpu:
+            raise ValueError('validate_batched: losses=True is part of the device loop: the model has to be on a GPU')
     if not on_gpu:
         # a CPU model: the host evaluators on run_offline_batched's output, clip by clip
         out = run_offline_batched(clips, model, times=times, batch_size=batch_size, rank=rank, world=world, decode_notes=need_notes)
@@ -739,9 +789,15 @@ def validate_batched(clips, references, model, evaluator, times=None, batch_size
         return evaluator.average_results()
 
     def stage(idx, batch):
+        if losses:
+            given = [k for k in loss_keys if all(tools.query_dict(references[i], k) for i in idx)]
+            batch.model_entries = {k: batch.upload(np.stack([np.asarray(references[i][k]) for i in idx]).astype(np.int64 if k == tools.KEY_TABLATURE else np.float32))
+                                   for k in given}
+            batch.model_entries[tools.KEY_LOSS_FRAMES] = None
+            batch.loss_counts = np.full(len(idx), batch.model_entries[loss_keys[0]].shape[-1], dtype=np.int64)
         return [e.stage_batch([tools.unpack_dict(references[i], e.unpack_key) for i in idx], batch) for e in leaves]
 
-    _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world)
+    _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world, losses)
     return evaluator.average_results()
 
 
@@ -789,7 +845,8 @@ def _check_banks(who, leaves, bank, labels, notes, relative_times):
             raise ValueError(f'a bank of {len(bank)} tracks and a {what} of {len(other)}')
 
 
-def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frames, num_frames, times=None, batch_size=256, rank=0, world=1):
+def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frames, num_frames, times=None, batch_size=256, rank=0, world=1,
+                   losses=False):
     """validate_batched for clips of resident tracks: clip i is `num_frames` frames from first_frames[i] on of track track_ids[i] (a request
     as bank.clips takes it; tracks.cover_clips names the clips that cover whole tracks).  `bank`: the tracks.TrackBank / PyramidBank the
     model's front-end reads; `labels`: the LabelBank of the same tracks, with every key a map or tablature evaluator unpacks (None: no
@@ -800,11 +857,16 @@ def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frame
     {tools.KEY_AUDIO: bank.clips(...)}, the references are labels.clips(...) and notes.clips(...) -- device tensors in the layouts
     stage_batch would have uploaded -- and only clip descriptors go to the device and count tensors come back.  The host matcher runs
     on notes.host_clips(...) where results_batch falls back: the matcher's status word asks for it, the decoder overflowed, or
-    notes.integral is false.  A LossWrapper warns and contributes an empty dictionary, as in validate_batched.  Every clip's results are
-    appended in clip order; returns evaluator.average_results() for the clips this rank owns."""
+    notes.integral is false.  A LossWrapper warns and contributes an empty dictionary, as in validate_batched, unless `losses` is set.
+    Every clip's results are appended in clip order; returns evaluator.average_results() for the clips this rank owns.
+
+    losses=True: as in validate_batched, with labels.clips(...) of the batch's request as the model's ground truth -- made once per
+    batch and shared with the map evaluators.  ValueError before anything is launched also for labels=None and for a LabelBank that
+    lacks one of the model's loss_label_keys: all are required here, for a map derived at a clip's edge would differ from the track's."""
     from .inference import BankClips, _model_device
     leaves = _leaves(evaluator)
     _check_banks('validate_clips', leaves, bank, labels, notes, relative_times=True)
+    loss_keys = _check_losses('validate_clips', leaves, model, labels, banks=True) if losses else None
     source = BankClips(bank, track_ids, first_frames, num_frames)
     if not _model_device(model)[1]:
         raise ValueError('validate_clips scores clips of device-resident tracks: the model has to be on a GPU')
@@ -813,14 +875,17 @@ def validate_clips(bank, labels, notes, model, evaluator, track_ids, first_frame
 
     def stage(idx, batch):
         request = source.of(idx) + (source.num_frames,)
-        maps = labels.clips(*request) if need_maps else None
+        maps = labels.clips(*request) if need_maps or losses else None
+        if losses:
+            batch.model_entries = {**{k: maps[k] for k in loss_keys}, tools.KEY_LOSS_FRAMES: None}
+            batch.loss_counts = np.full(len(idx), source.num_frames, dtype=np.int64)
         refs = None
         if need_notes:
             sliced = notes.clips(*request) if notes.integral else None
             refs = _BankNoteRefs(notes, request, (sliced.rows, sliced.offsets) if sliced is not None else None)
         return [None if isinstance(e, LossWrapper) else refs if isinstance(e, StackedNoteEvaluator) else maps[e.unpack_key] for e in leaves]
 
-    _score_on_device(source, stage, model, evaluator, times, batch_size, rank, world)
+    _score_on_device(source, stage, model, evaluator, times, batch_size, rank, world, losses)
     return evaluator.average_results()
 
 
@@ -872,15 +937,15 @@ def _batch_scorer(stage, model, evaluator, times):
     return stage_extra, enqueue, finish
 
 
-def _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world):
+def _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, world, losses=False):
     """What validate_batched and validate_clips share on a GPU model: inference._batched over `clips` (host clips or a BankClips) with
-    _batch_scorer's hooks."""
+    _batch_scorer's hooks.  With `losses` the model's batch also carries what stage left in batch.model_entries."""
     from .inference import _batched
     stage_extra, enqueue, finish = _batch_scorer(stage, model, evaluator, times)
-    _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra)
+    _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra, (lambda batch: batch.model_entries) if losses else None)
 
 
-def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1):
+def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1, losses=False):
     """Score WHOLE resident tracks, one result per track, as the reference's validate does -- from equally long overlapped clips.  The
     tracks (`track_ids`, default every track of `bank`; position j belongs to rank j % world) go through inference.run_tracks' stitching
     pass: clips of `num_frames` frames by tracks.seam_clips, of each only the frames at least `margin` frames from a clip edge that is
@@ -894,17 +959,49 @@ def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, t
     for the BiLSTMs of Onsets & Frames; `margin` has no default.  ValueError before anything is launched as in validate_clips (a missing
     bank or key, stacked against batched notes, a model that is not on a GPU), and for what tracks.seam_clips refuses.  A NoteBank with
     absolute times is as good as one with relative times: a whole track starts at time 0.  A LossWrapper warns and contributes an
-    empty dictionary."""
+    empty dictionary unless `losses` is set.
+
+    losses=True: every clip of the stitching pass runs labelled -- labels.clips(...) of its request under the model's loss_label_keys --
+    with tools.KEY_LOSS_FRAMES = the columns it keeps, {src_first, count} = plan.kept[:, 1:3] (a short track, run whole: {0, L_t}), so
+    the model returns, per clip, float64 sums over exactly the frames that are stitched.  Every frame of a track is kept once, hence
+        loss(track) = sum_k mean_t = (1 / L_t) * sum over the track's clips of their sums,
+    added up in plan order in float64 on the host; the LossWrapper tracks that dictionary with the track's other results.  No logits are
+    stitched.  This is the loss of the SEGMENT-WISE logits, the same approximation as the predictions: exact for tracks that fit one
+    clip, for TabCNN from margin 4 on the whole track's loss, an approximation for Onsets & Frames.  ValueError as in validate_clips."""
     import torch
+    from . import cliploss
     from .inference import _model_device, _stitch_tracks
     leaves = _leaves(evaluator)
     _check_banks('validate_tracks', leaves, bank, labels, notes, relative_times=False)
+    loss_keys = _check_losses('validate_tracks', leaves, model, labels, banks=True) if losses else None
     if not _model_device(model)[1]:
         raise ValueError('validate_tracks scores device-resident tracks: the model has to be on a GPU')
     need_maps = any(not isinstance(e, (LossWrapper, StackedNoteEvaluator)) for e in leaves)
     need_notes = any(isinstance(e, StackedNoteEvaluator) for e in leaves)
+    device = _model_device(model)[0]
+    collected = []                         # per batch of the stitching pass: (the slot of each clip, the model's per-clip sums)
+
+    def model_entries(ids, firsts, frames, windows):
+        maps = labels.clips(ids, firsts, frames)
+        table = np.ascontiguousarray(windows, dtype=np.int32)
+        return {**{k: maps[k] for k in loss_keys}, tools.KEY_LOSS_FRAMES: cliploss.Windows(table, torch.from_numpy(table).to(device))}
+
     with torch.no_grad():
-        mine, stitched = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world)
+        if losses:
+            mine, stitched = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, model_entries=model_entries,
+                                            collect=lambda slots, preds: collected.append((np.asarray(slots), preds[tools.KEY_LOSS])))
+        else:
+            mine, stitched = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world)
+        track_losses = None
+        if collected:
+            # the only transfer of the losses: the sum tensors.  np.add.at adds in index order: a track's clips in plan order
+            slots = np.concatenate([s for s, _ in collected])
+            lengths = np.asarray(bank.frame_counts, dtype=np.float64)[mine]
+            totals = {}
+            for key in collected[0][1]:
+                totals[key] = np.zeros(len(mine), dtype=np.float64)
+                np.add.at(totals[key], slots, torch.cat([sums[key] for _, sums in collected]).cpu().numpy())
+            track_losses = [{key: total[j] / lengths[j] for key, total in totals.items()} for j in range(len(mine))]
 
         def stage(idx, batch):
             maps = labels.clips(idx, [0], int(bank.frame_counts[idx[0]])) if need_maps else None
@@ -917,7 +1014,10 @@ def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, t
         stage_extra, enqueue, finish = _batch_scorer(stage, model, evaluator, None)
         pending = None
         for j, t in enumerate(mine.tolist()):
-            now = enqueue([t], {key: stitched.track(j, key) for key in stitched.keys}, stage_extra([t]))
+            batch = stage_extra([t])
+            if track_losses is not None:
+                batch.loss_results = [track_losses[j]]
+            now = enqueue([t], {key: stitched.track(j, key) for key in stitched.keys}, batch)
             if pending is not None:
                 finish(pending)                                   # the GPU scores track j meanwhile
             pending = now

@@ -73,13 +73,16 @@ class BankClips(object):
 
 
 @torch.no_grad()
-def _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra=None):
+def _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra=None, model_extra=None):
     """The clips this rank owns through `model.run_on_batch`, `batch_size` at a time.  `clips` as for run_offline_batched, or a BankClips.
     Per batch, with idx the list of its clip indices:
 
       extra = stage_extra(idx)              (optional) while the batch is staged, BEFORE the batch before it runs
       pending = enqueue(idx, preds, extra)  right behind run_on_batch; anything but None
       finish(pending)                       after the NEXT batch's enqueue (the last batch: after the loop)
+
+    model_extra(extra) (optional) -> a dictionary of further entries of the batch the model gets beside its audio or features, made from
+    what stage_extra staged: ground truth for a labelled run.  Without it the model's batch is the one entry, as before.
 
     On a GPU model this is a three-stage pipeline: batch n+1 is uploaded on a copy stream (from pinned memory) while batch n's kernels
     run, and batch n-1 is finished on the host while the GPU is busy.  stage_extra runs inside the copy stream's context, before the
@@ -152,7 +155,7 @@ def _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra
             data.record_stream(main)
         if n + 1 < len(batches):
             nxt = stage(batches[n + 1])
-        now = enqueue(idx, model.run_on_batch({key: data}), extra)
+        now = enqueue(idx, model.run_on_batch({key: data, **model_extra(extra)} if model_extra else {key: data}), extra)
         if pending is not None:
             finish(pending)                                       # the GPU is busy with this batch meanwhile
         pending = now
@@ -199,7 +202,7 @@ def run_offline_batched(clips, model, times=None, batch_size=256, rank=0, world=
     return out
 
 
-def _stitch_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1, wanted=None):
+def _stitch_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1, wanted=None, model_entries=None, collect=None):
     """The stitching pass of run_tracks and evaluate.validate_tracks -> (the track ids this rank owns, in request order; the
     tracks.TrackMaps of their whole-track outputs, slot j = the j-th of those ids, or None when the rank owns no track).
 
@@ -208,6 +211,11 @@ def _stitch_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=2
     writes the kept columns of every output tensor (`wanted`: the keys to keep, default all) into the maps right behind run_on_batch, on
     the model's stream -- an output that lives in the engine's workspace is read before the next batch overwrites it.  Tracks shorter
     than a clip follow, each whole as one clip of its own length: one more pass per distinct length, through the same hook.
+
+    The hook of a labelled pass (evaluate.validate_tracks with losses): model_entries(track ids, first frames, frames per clip, windows)
+    -> further entries of the model's batch for the clips of one batch, `windows` being the (clips, 2) table {src_first, count} of the
+    columns each clip keeps (seam clips: plan.kept[:, 1:3]; a short track: {0, L_t}); collect(slots, preds) is called behind every
+    batch with the slot of each of its clips and the model's output.  Entries of the output that are no tensors are not stitched.
 
     ValueError before anything is launched: what seam_clips refuses (for the whole request, whichever rank owns the track) and a model
     that is not on a GPU."""
@@ -245,9 +253,16 @@ def _stitch_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=2
                     tables[rows] = desc, torch.from_numpy(desc).to(device)
                 desc, desc_dev = tables[rows]
                 maps.stitch(key, value, desc[lo:hi], desc_dev[lo:hi])
+            if collect is not None:
+                collect(slots[lo:hi], preds)
             return idx
 
-        _batched(BankClips(bank, mine[slots], firsts, frames), model, batch_size, 0, 1, enqueue, lambda pending: None)
+        def stage_extra(idx):
+            lo, hi = int(idx[0]), int(idx[-1]) + 1
+            return model_entries(mine[slots[lo:hi]], firsts[lo:hi], frames, kept[lo:hi, 1:3])
+
+        _batched(BankClips(bank, mine[slots], firsts, frames), model, batch_size, 0, 1, enqueue, lambda pending: None,
+                 stage_extra if model_entries else None, (lambda entries: entries) if model_entries else None)
     return mine, maps
 
 

@@ -35,7 +35,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib, tools
-from . import autograd
+from . import autograd, cliploss
 
 __all__ = ['TranscriptionModel', 'OutputLayer', 'LogisticBank', 'AcousticModel', 'LanguageModel', 'OnsetsFrames',
            'SpectralFrontend']
@@ -142,8 +142,37 @@ class TranscriptionModel(nn.Module):
     def post_proc(self, batch):
         raise NotImplementedError
 
+    # The label keys a per-clip loss needs (tools.KEY_LOSS_FRAMES below), the first one being the key that makes a batch labelled; None:
+    # the model has no per-clip loss.
+    loss_label_keys = None
+
+    def _take_loss_frames(self, batch):
+        """(the batch without tools.KEY_LOSS_FRAMES, whether it carried the key, its value as cliploss takes it).  The key is taken out
+        before pre_proc -- a window table is no tensor to move to the model's device and nothing for a front-end -- and put back for
+        post_proc.  ValueError for a model without a per-clip loss and in training mode: no gradient goes through the sums."""
+        if not tools.query_dict(batch, tools.KEY_LOSS_FRAMES):
+            return batch, False, None
+        if self.loss_label_keys is None:
+            raise ValueError(f'{type(self).__name__} has no per-clip loss: the batch may not carry \'{tools.KEY_LOSS_FRAMES}\'')
+        if self.training:
+            raise ValueError(f'\'{tools.KEY_LOSS_FRAMES}\' asks for per-clip loss sums, which carry no gradient: eval mode only')
+        batch = dict(batch)
+        frames = batch.pop(tools.KEY_LOSS_FRAMES)
+        if frames is not None and not isinstance(frames, cliploss.Windows):
+            frames = np.asarray(frames.detach().cpu() if torch.is_tensor(frames) else frames)
+            if frames.dtype.kind == 'f' and np.array_equal(frames, np.rint(frames)):
+                frames = frames.astype(np.int64)              # a table that went through a dict_to_dtype(float32) with the audio
+        return batch, True, frames
+
     def run_on_batch(self, batch):
+        """pre_proc -> forward -> post_proc.  In eval mode a labelled batch that carries tools.KEY_LOSS_FRAMES -- a (B, 2) integer table
+        {first, count} per clip, or None for whole clips -- gets under tools.KEY_LOSS, instead of 0-d batch means, (B,) float64 SUMS per
+        loss key: over the named frames of each clip, without the mean over frames (amt_tools_amd/cliploss.py).  sums / count is the
+        loss of that clip as a batch of one."""
+        batch, per_clip, frames = self._take_loss_frames(batch)
         batch = self.pre_proc(batch)
+        if per_clip:
+            batch[tools.KEY_LOSS_FRAMES] = frames
         batch[tools.KEY_OUTPUT] = self(batch[tools.KEY_FEATS])
         output = self.post_proc(batch)
         if tools.query_dict(batch, tools.KEY_TIMES):
@@ -194,6 +223,10 @@ class LogisticBank(OutputLayer):
         weight = self.weights.unsqueeze(-1) if self.weights is not None else None
         loss = F.binary_cross_entropy_with_logits(est.float(), reference.float(), weight=weight, reduction='none')
         return loss.mean(dim=-1).sum(dim=-1).mean()
+
+    def get_loss_sums(self, estimated, reference, frames=None):
+        """get_loss without its means: (B,) float64, per clip the sum over keys and over the frames `frames` names (cliploss.bce_sums)."""
+        return cliploss.bce_sums(estimated, reference, self.weights, frames)
 
     def finalize_output(self, raw_output, threshold=None):
         """sigmoid -> (B,O,T) -> optional threshold (common.py:586-620)."""
@@ -612,6 +645,7 @@ class OnsetsFrames(TranscriptionModel):
 
     _engine_class = _OFEngine
     _engine_stages = True
+    loss_label_keys = (tools.KEY_MULTIPITCH, tools.KEY_ONSETS)
     _transient = TranscriptionModel._transient + ('_engine_out', '_engine_offsets', '_side_stream', '_overlap_armed', '_fb_last_forward',
                                                   '_overlap_latched_off')
 
@@ -760,13 +794,19 @@ class OnsetsFrames(TranscriptionModel):
         if tools.KEY_MULTIPITCH in batch.keys():
             loss = dict()
             multi_pitch_ref = batch[tools.KEY_MULTIPITCH]
-            loss[tools.KEY_LOSS_PITCH] = pitch_layer.get_loss(multi_pitch_est, multi_pitch_ref)
+            if tools.KEY_LOSS_FRAMES in batch:
+                # per-clip sums over a frame window (run_on_batch): the same label rules, get_loss_sums for get_loss
+                frames = batch[tools.KEY_LOSS_FRAMES]
+                get_loss = lambda layer, est, ref: layer.get_loss_sums(est, ref, frames)
+            else:
+                get_loss = lambda layer, est, ref: layer.get_loss(est, ref)
+            loss[tools.KEY_LOSS_PITCH] = get_loss(pitch_layer, multi_pitch_est, multi_pitch_ref)
             if tools.KEY_ONSETS in batch.keys():
                 onsets_ref = batch[tools.KEY_ONSETS]
             else:
                 # intended behaviour of onsetsframes.py:176-178 (the reference's NumPy helper fails on tensors)
                 onsets_ref = tools.multi_pitch_to_onsets(multi_pitch_ref)
-            loss[tools.KEY_LOSS_ONSETS] = onset_layer.get_loss(onsets_est, onsets_ref)
+            loss[tools.KEY_LOSS_ONSETS] = get_loss(onset_layer, onsets_est, onsets_ref)
             loss[tools.KEY_LOSS_TOTAL] = loss[tools.KEY_LOSS_PITCH] + loss[tools.KEY_LOSS_ONSETS]
             output[tools.KEY_LOSS] = loss
         cached = self.__dict__.pop('_engine_out', None)
@@ -793,6 +833,7 @@ class OnsetsFrames2(OnsetsFrames):
     mode on a GPU -- it never falls back."""
 
     has_offsets = True
+    loss_label_keys = OnsetsFrames.loss_label_keys + (tools.KEY_OFFSETS,)
 
     def __init__(self, dim_in, profile, in_channels=1, model_complexity=3, detach_heads=True, device='cpu', precision='x3'):
         super().__init__(dim_in, profile, in_channels, model_complexity, detach_heads, device, precision)
@@ -812,7 +853,10 @@ class OnsetsFrames2(OnsetsFrames):
             else:
                 offsets_ref = tools.multi_pitch_to_offsets(batch[tools.KEY_MULTIPITCH])
             loss = output[tools.KEY_LOSS]
-            offsets_loss = offset_layer.get_loss(offsets_est, offsets_ref)
+            if tools.KEY_LOSS_FRAMES in batch:
+                offsets_loss = offset_layer.get_loss_sums(offsets_est, offsets_ref, batch[tools.KEY_LOSS_FRAMES])
+            else:
+                offsets_loss = offset_layer.get_loss(offsets_est, offsets_ref)
             loss[tools.KEY_LOSS_OFFSETS] = offsets_loss
             loss[tools.KEY_LOSS_TOTAL] += offsets_loss
             output[tools.KEY_LOSS] = loss
@@ -860,6 +904,11 @@ class SoftmaxGroups(OutputLayer):
             group_idx = torch.arange(self.num_groups, device=nll.device).expand_as(target)
             nll = nll * per_class[group_idx, target]
         return nll.sum(dim=-1).mean(dim=-1).mean()
+
+    def get_loss_sums(self, estimated, reference, frames=None):
+        """get_loss without its means: (B,) float64, per clip the sum over groups and over the frames `frames` names
+        (cliploss.softmax_groups_sums)."""
+        return cliploss.softmax_groups_sums(estimated, reference, self.num_groups, self.num_classes, self.weights, frames)
 
     def finalize_output(self, raw_output, last_negative=True):
         """Most likely class per group and frame as (B, G, T) indices; the inactive class becomes -1 when `last_negative`."""
@@ -986,6 +1035,7 @@ class TabCNN(TranscriptionModel):
 
     _engine_class = _TabEngine
     _transient = TranscriptionModel._transient + ('_engine_tab',)
+    loss_label_keys = (tools.KEY_TABLATURE,)
 
     def engine_unsupported(self):
         """Why the HIP engine does not build this configuration, or None when it does."""
@@ -1103,7 +1153,9 @@ class TabCNN(TranscriptionModel):
         logits = output[tools.KEY_TABLATURE]
         if tools.KEY_TABLATURE in batch:
             labels = batch[tools.KEY_TABLATURE]
-            if self.training and self.use_hip_train and autograd.softmax_groups_loss_supported(logits, labels, head.num_groups):
+            if tools.KEY_LOSS_FRAMES in batch:
+                loss = head.get_loss_sums(logits, labels, batch[tools.KEY_LOSS_FRAMES])      # per-clip sums (run_on_batch)
+            elif self.training and self.use_hip_train and autograd.softmax_groups_loss_supported(logits, labels, head.num_groups):
                 loss = autograd.softmax_groups_loss(logits, labels, head.num_groups, head.num_classes, head.weights)
             else:
                 loss = head.get_loss(logits, labels)

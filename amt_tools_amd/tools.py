@@ -31,6 +31,7 @@ KEY_LOSS_TOTAL = 'loss_total'
 KEY_LOSS_ONSETS = 'loss_onsets'
 KEY_LOSS_OFFSETS = 'loss_offsets'
 KEY_LOSS_PITCH = 'loss_pitch'
+KEY_LOSS_FRAMES = 'loss_frames'     # not the reference's: per-clip loss sums over a frame window of each clip (models.TranscriptionModel.run_on_batch)
 KEY_ACCURACY = 'accuracy'
 KEY_PRECISION = 'precision'
 KEY_RECALL = 'recall'
