@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMTX_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libamtx.so')      # AMTX_LIB_PATH: a debug / timing build of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'amtx.h')
 # Every header of the library, bound the same way; a new header is appended here and gets a pinned table of its own under tests/golden/.
-HEADERS = ('amtx.h', 'amtx_tracks.h', 'amtx_pyramid.h', 'amtx_labels.h', 'amtx_optim.h', 'amtx_noteclips.h', 'amtx_stitch.h', 'amtx_cliploss.h')
+HEADERS = ('amtx.h', 'amtx_tracks.h', 'amtx_pyramid.h', 'amtx_labels.h', 'amtx_optim.h', 'amtx_noteclips.h', 'amtx_stitch.h', 'amtx_cliploss.h',
+           'amtx_ofseq.h')
 _PINNED_HEADERS = 4        # call()'s "declare no function" text lists these four in this order (pinned by tests/test_capi.py); later headers go in front
 
 _lib = None

@@ -139,6 +139,14 @@ struct LstmArgs {
     float* save = nullptr;                               // training only: [groups][B][T][2][5][hidden] post-activation i,f,g,o and c
 };
 
+// The same recurrence over PACKED sequences: the rows of S sequences of different lengths back to back, xproj [groups][R][2][4 hidden] and
+// out [groups][R][2 hidden].  Of `l`, B and T are not read, x_gs / out_gs are R rows, save stays null.
+struct LstmSeqArgs {
+    LstmArgs l;
+    const int64_t* seqs;                                 // DEVICE [S][2] = {row0, len}; slot order = table order (longest first: a block's slots finish together)
+    int S;
+};
+
 // ---------------------------------------------------------------- the kernels and packers behind these structs, once per 16-bit operand format
 namespace amtx_bf16 {
 #include "amtx_kernels_fmt.h"
@@ -160,6 +168,15 @@ int amtx_launch_bce_loss(const float* logits, int64_t ld, const float* labels, c
 int amtx_launch_loss_reduce(const float* partial, int64_t n, float inv_bt, float* loss, hipStream_t stream);
 int amtx_launch_pianoroll(const float* logits, int64_t ld, int col0, int B, int T, int keys, float threshold, float* out,
                           hipStream_t stream);
+
+// ---- seqrows.hip: packed rows (include/amtx_ofseq.h).  The check every entry point that takes a sequence table makes of its HOST copy
+// (AMTX_ERR_ARG naming the row; *max_len: the longest sequence); the launchers behind amtx_rows_gather / amtx_pianoroll_seq
+int amtx_check_seq_table(const char* who, const int64_t* seqs_host, int num_seqs, int64_t total_rows, int64_t* max_len);
+int amtx_launch_rows_gather(const void* src, int batch, int64_t num_frames, int64_t width_bytes, int planes, int64_t src_plane_bytes,
+                            const int64_t* table_host, const int64_t* table_dev, void* dst, int64_t total_rows, int64_t dst_plane_bytes,
+                            hipStream_t stream);
+int amtx_launch_pianoroll_seq(const float* logits, int64_t ld, int col0, const int64_t* seqs_dev, int num_seqs, int64_t max_len, int keys,
+                              float threshold, float* out, hipStream_t stream);
 
 int amtx_launch_cvt_pad_bf16(const float* src, int64_t ld_src, int n_src, bf16_t* dst, int ld_dst, int64_t rows, hipStream_t stream,
                              bool f16 = false /* IEEE half instead of bf16 (AMTX_PREC_F16) */);

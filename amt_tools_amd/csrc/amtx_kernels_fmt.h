@@ -44,6 +44,7 @@ bool amtx_conv3x3_gen_can_fuse1(int c_in, int c_mid, int c_out, int planes);
 
 // ---------------------------------------------------------------- lstm.hip: hidden = 128, 256, 384 or 512 per direction
 int amtx_launch_bilstm(const LstmArgs& l, hipStream_t stream);
+int amtx_launch_bilstm_seq(const LstmSeqArgs& l, hipStream_t stream);   // packed sequences: (1 plane, 16-bit rows) or (2 planes, fp32 rows)
 size_t amtx_bilstm_wfrag_elems(int hidden, int planes);  // per LSTM (both directions)
 void amtx_bilstm_pack_host(const float* whh_fwd, const float* whh_bwd, int hidden, int planes, bf16_t* out);   // each (4 hidden, hidden)
 // training: device-side packing of fp32 W_hh into forward + transposed (backward) fragments; backward recurrence -> dL/d(xproj) of

@@ -420,6 +420,77 @@ __global__ __launch_bounds__(LTHREADS) void bilstm4_kernel(LstmArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Packed sequences (amtx_launch_bilstm_seq): the rows of S sequences of different lengths lie back to back, a.seqs names {row0, len} of each.
+// Slot j of a block is sequence blockIdx.x * SLOTS + j of the table: the lane reads its own row0 and len where the kernels above compute
+// b * T and read a.T, and the block runs to the largest len of its slots -- a slot that is through repeats its last row with stores
+// masked, exactly as the steps past T above.  A slot past the table's end walks row 0 of sequence 0 the same way.  The step helpers, operand
+// packing and k order are the kernels' above, so a sequence gets the bits it gets from them as B = 1, T = len.
+struct SeqSlot { int64_t row0; int len; bool ok; };
+__device__ __forceinline__ SeqSlot seq_slot(const LstmSeqArgs& a, int slot) {
+    const bool ok = slot < a.S;
+    const int64_t* e = a.seqs + 2 * (int64_t)(ok ? slot : 0);
+    return {e[0], ok ? (int)e[1] : 1, ok};
+}
+template <int SLOTS>
+__device__ __forceinline__ int seq_block_steps(const LstmSeqArgs& a) {
+    int steps = 1;
+    for (int j = 0; j < SLOTS; ++j) {
+        const int slot = blockIdx.x * SLOTS + j;
+        if (slot < a.S) steps = max(steps, (int)a.seqs[2 * (int64_t)slot + 1]);
+    }
+    return steps;
+}
+
+// hidden 128, four sequences per block: bilstm4_kernel<.., 1>'s mapping (lane = one cell of slot lane >> 4) over lstm4_step
+template <int NS, int X_TYPE, int OUT_TYPE>
+__global__ __launch_bounds__(LTHREADS) void bilstm4_seq_kernel(LstmSeqArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 bufs][NS planes][16][HP] bf16, rows 0/4/8/12 used
+    constexpr bool FAST = true;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int unit = 16 * wave + (lane & 15), cg = lane >> 4;
+    const int dir = blockIdx.y, grp = blockIdx.z;
+    const SeqSlot sq = seq_slot(a, blockIdx.x * 4 + cg);
+    const int T = sq.len, steps = seq_block_steps<4>(a);
+
+    uint4 wf[4][4][NS];
+    {
+        const uint4* w = reinterpret_cast<const uint4*>(a.l.whh + (int64_t)grp * a.l.w_gs) + lane;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int p = 0; p < NS; ++p) wf[q][ks][p] = w[(((((dir * LWAVES + wave) * 4 + q) * 4 + ks) * NS) + p) * 64];
+    }
+    for (int i = tid; i < 2 * NS * HBUF_BYTES / 16; i += LTHREADS) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0, 0, 0, 0);
+
+    float c[1] = {0.f};
+    const bool clip_ok[1] = {sq.ok};
+    const char* const xbase[1] = {reinterpret_cast<const char*>(a.l.xproj) +
+                                  ((int64_t)grp * a.l.x_gs + sq.row0 * 1024 + dir * 512 + (X_TYPE == AMTX_T_BF16 ? (unit & ~1) : unit)) *
+                                      (X_TYPE == AMTX_T_BF16 ? 2 : 4)};
+    char* const obase[1] = {reinterpret_cast<char*>(a.l.out) +
+                            ((int64_t)grp * a.l.out_gs + sq.row0 * 256 + dir * 128 + unit) * (OUT_TYPE == AMTX_T_BF16 ? 2 : 4)};
+    const int hwoff[1] = {(4 * cg * HP + unit) * 2};
+
+    typename XScalar<X_TYPE>::type x0[1][4], x1[1][4], x2[1][4], x3[1][4];
+    auto tidx = [&](int s) { return (int64_t)step_frame(s, T, dir); };
+    load_x4<X_TYPE>(xbase[0], tidx(0) * 1024, x0[0]);
+    load_x4<X_TYPE>(xbase[0], tidx(1) * 1024, x1[0]);
+    load_x4<X_TYPE>(xbase[0], tidx(2) * 1024, x2[0]);
+    __syncthreads();
+
+    for (int s = 0; s < steps; s += 4) {
+        // straight-line body, stores of the steps past this slot's own len masked (see bilstm_kernel)
+        const bool ok0[1] = {clip_ok[0] && s < T}, ok1[1] = {clip_ok[0] && s + 1 < T}, ok2[1] = {clip_ok[0] && s + 2 < T}, ok3[1] = {clip_ok[0] && s + 3 < T};
+        lstm4_step<NS, X_TYPE, OUT_TYPE, FAST, 1>(smem, 0, wf, x0, x3, c, xbase, obase, (int)tidx(s), (int)tidx(s + 3), lane, hwoff, ok0, nullptr);
+        lstm4_step<NS, X_TYPE, OUT_TYPE, FAST, 1>(smem, 1, wf, x1, x0, c, xbase, obase, (int)tidx(s + 1), (int)tidx(s + 4), lane, hwoff, ok1, nullptr);
+        lstm4_step<NS, X_TYPE, OUT_TYPE, FAST, 1>(smem, 0, wf, x2, x1, c, xbase, obase, (int)tidx(s + 2), (int)tidx(s + 5), lane, hwoff, ok2, nullptr);
+        lstm4_step<NS, X_TYPE, OUT_TYPE, FAST, 1>(smem, 1, wf, x3, x2, c, xbase, obase, (int)tidx(s + 3), (int)tidx(s + 6), lane, hwoff, ok3, nullptr);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Training: backward recurrence of the BiLSTM (the reference trains with nn.LSTM, amt_tools/train.py:126-141; MIOpen's
 // LSTM takes 46 of the 61 ms of GPU time of a training step at 8 clips x 625 frames and keeps the host launch-bound).
 // Given dL/dh for every step and the saved post-activation gates / cell states of the forward pass, one persistent
@@ -777,6 +848,198 @@ __global__ __launch_bounds__(512) void bilstm_stream_kernel(LstmArgs a) {
     }
 }
 
+
+// Packed sequences, sixteen per block (see bilstm4_seq_kernel): bilstm_stream_kernel with lane & 15 as the slot, the slot's own {row0, len} for b T
+// and a.T, and the block's longest len as the trip count.  A copy, not a shared body: called from a second kernel, the body above compiles
+// to other instructions in bilstm_stream_kernel itself (a handful more per instantiation), and that kernel stays what it was.  What the two share
+// -- FragStream, the cell helpers, split16 / store16, step_frame -- is shared; the inference path of the body is line by line the one above.
+template <int HH, int NS, int X_TYPE, int OUT_TYPE>
+__global__ __launch_bounds__(512) void bilstm_stream_seq_kernel(LstmSeqArgs q) {
+    const LstmArgs& a = q.l;
+    constexpr int NU = HH / 16, UPW = NU / 8, KSN = HH / 32;
+    constexpr int SGK = NS == 2 ? 2 : 4;          // k-steps per streamed group: 16 VGPRs per group in either precision
+    constexpr int NSUB = KSN / SGK;               // groups per (unit tile, gate)
+    constexpr int NG = UPW * 4 * NSUB;            // groups per step and wave
+    constexpr int HPG = HH + 8;
+    constexpr int HBG = 16 * HPG * 2;
+    constexpr bool FAST = true;
+    constexpr int RS = 4;                         // ring slots: RS - 1 streamed groups (4 KiB each per wave) in flight (8 slots: no faster,
+                                                  // the stream is bound by the 64 B/clk a CU's vector memory path takes, not by latency)
+    // HH = 256, bf16: of every four consecutive groups of a wave, group 0 is held in registers and group 1 in LDS for the whole launch
+    // (64 spare VGPRs, 128 KiB of LDS per block), the other two are streamed: half the bytes per step.  HH = 384, bf16: 36 groups per
+    // wave, no spare registers; every ninth group (4 per wave, again 128 KiB per block) sits in LDS, 32 are streamed.
+    constexpr bool PIN = NS == 1 && HH == 256;    // register + LDS pinning, period 4
+    constexpr bool PINL = NS == 1 && HH == 384;   // LDS pinning only: four groups per wave, period PER = 9 (HH = 512: the 128 KiB of pinned groups
+                                                  // and the two h tiles are 512 bytes more than a CU's LDS: everything streamed)
+    constexpr int PER = NG / 4;
+    constexpr int NPIN = PIN ? NG / 4 : (PINL ? 4 : 0);   // groups pinned per kind and wave
+    constexpr int NSG = NG - (PIN ? 2 : (PINL ? 1 : 0)) * NPIN;   // streamed groups per step and wave
+    static_assert(NU % 8 == 0 && KSN % SGK == 0 && NG % 4 == 0 && NSG % RS == 0, "hidden size must be a multiple of 128");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 bufs][NS planes][16][HPG] bf16
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int clip = lane & 15, g = lane >> 4;
+    const int b0 = blockIdx.x * 16, dir = blockIdx.y, grp = blockIdx.z;
+    const int b = b0 + clip;                      // the slot
+    const SeqSlot sq = seq_slot(q, b);
+    const bool clip_ok = sq.ok;
+    const int T = sq.len, steps = seq_block_steps<16>(q);
+    constexpr int XES = X_TYPE == AMTX_T_BF16 ? 2 : 4, OES = OUT_TYPE == AMTX_T_BF16 ? 2 : 4;
+
+    for (int i = tid; i < 2 * NS * HBG / 16; i += 512) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0, 0, 0, 0);
+
+    // fragment (u, q, ks, p) of direction dir: uint4 index ((((dir * NU + u) * 4 + q) * KSN + ks) * NS + p) * 64 + lane
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const char* wbase = reinterpret_cast<const char*>(a.whh + (int64_t)grp * a.w_gs) + ((int64_t)(dir * NU + wave_u * UPW) * 4 * KSN * NS) * 1024;
+    FragStream<SGK, NS> ws(wbase, lane);
+    const char* xbase = reinterpret_cast<const char*>(a.xproj) +
+                        ((int64_t)grp * a.x_gs + sq.row0 * 8 * HH + dir * 4 * HH + 16 * UPW * wave + 4 * g) * XES;
+    char* obase = reinterpret_cast<char*>(a.out) +
+                  ((int64_t)grp * a.out_gs + sq.row0 * 2 * HH + dir * HH + 16 * UPW * wave + 4 * g) * OES;
+
+    float c[UPW][4];
+#pragma unroll
+    for (int ub = 0; ub < UPW; ++ub)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c[ub][r] = 0.f;
+
+    typedef typename XRaw<X_TYPE>::type xraw_t;
+    auto tidx = [&](int s) { return (int64_t)step_frame(s, T, dir); };
+    auto load_xrow = [&](int64_t t, xraw_t (&dst)[UPW][4]) {
+#pragma unroll
+        for (int ub = 0; ub < UPW; ++ub)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                dst[ub][q] = *reinterpret_cast<const xraw_t*>(xbase + (t * 8 * HH + q * HH + 16 * ub) * XES);
+    };
+    uint4 w[RS][SGK][NS];                         // ring: streamed group si lives in slot si % RS, RS - 1 groups in flight
+    uint4 wpin[PIN ? NPIN : 1][SGK][NS];          // register-resident groups
+    // group gi -> kind (0 registers, 1 LDS, 2 streamed) and index within its kind: see kind_of / sidx_of / gi_of_sidx below
+    char* wlds = smem + 2 * NS * HBG + wave * (NPIN * SGK * NS * 1024);      // this wave's LDS-resident groups
+    if constexpr (PIN || PINL) {
+        static_for<0, NG>([&](auto ic) {
+            constexpr int gi = decltype(ic)::value;
+            constexpr int kind = PIN ? ((gi & 3) == 0 ? 0 : ((gi & 3) == 1 ? 1 : 2)) : (gi % PER == 0 ? 1 : 2);
+            constexpr int pidx = PIN ? gi >> 2 : gi / PER;
+            if constexpr (kind < 2) {
+                static_for<0, SGK>([&](auto kc) {
+                    constexpr int k = decltype(kc)::value;
+                    static_for<0, NS>([&](auto pc) {
+                        constexpr int p = decltype(pc)::value;
+                        const uint4 v = ws.load(gi, k, p);
+                        if constexpr (kind == 0) wpin[pidx][k][p] = v;
+                        else *reinterpret_cast<uint4*>(wlds + ((pidx * SGK + k) * NS + p) * 1024 + ws.wlane) = v;
+                    });
+                });
+            }
+        });
+    }
+
+    xraw_t xn[UPW][4];
+    load_xrow(tidx(0), xn);
+    static_for<0, RS - 1>([&](auto sc) {
+        constexpr int si = decltype(sc)::value;
+        constexpr int gi = PIN ? (si >> 1) * 4 + 2 + (si & 1) : (PINL ? si + si / (PER - 1) + 1 : si);
+        ws.load_group(gi, w[si % RS]);
+    });
+    __syncthreads();
+
+    int cur = 0;
+    for (int s = 0; s < steps; ++s) {
+        ws.rewind();
+        const char* hb = smem + cur * NS * HBG;
+        // the h fragments of a step: in registers while they are at most 64 (HH = 384 in two planes would be 96: read at their use)
+        constexpr bool HF_REG = KSN * NS <= 16;
+        uint4 hf[HF_REG ? KSN : 1][NS];
+        if constexpr (HF_REG) {
+#pragma unroll
+            for (int ks = 0; ks < KSN; ++ks)
+#pragma unroll
+                for (int p = 0; p < NS; ++p) hf[ks][p] = *reinterpret_cast<const uint4*>(hb + p * HBG + (clip * HPG + 32 * ks + 8 * g) * 2);
+        }
+
+        f32x4_t acc[UPW][4];
+#pragma unroll
+        for (int ub = 0; ub < UPW; ++ub)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[ub][q] = unpack_x(xn[ub][q]);
+        load_xrow(tidx(s + 1), xn);
+        __builtin_amdgcn_sched_barrier(0);
+
+        static_for<0, NG>([&](auto ic) {
+            constexpr int gi = decltype(ic)::value;
+            constexpr int ub = gi / (4 * NSUB), q = (gi / NSUB) & 3, sub = gi % NSUB;
+            constexpr int kind = PIN ? ((gi & 3) == 0 ? 0 : ((gi & 3) == 1 ? 1 : 2)) : (PINL ? (gi % PER == 0 ? 1 : 2) : 2);     // 0 registers, 1 LDS, 2 streamed
+            constexpr int pidx = PIN ? gi >> 2 : gi / PER;                                      // index among the pinned groups of its kind
+            constexpr int si = PIN ? (gi >> 2) * 2 + (gi & 3) - 2 : (PINL ? gi - gi / PER - 1 : gi);   // index among the streamed groups
+            if constexpr (kind == 2) {
+                // behind the last RS - 1 streamed groups: the first ones of the next step
+                constexpr int sn = (si + RS - 1) % NSG;
+                constexpr int gn = PIN ? (sn >> 1) * 4 + 2 + (sn & 1) : (PINL ? sn + sn / (PER - 1) + 1 : sn);
+                ws.load_group(gn, w[sn % RS]);
+            }
+            f32x4_t d = acc[ub][q];
+            static_for<0, SGK>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                constexpr int ks = sub * SGK + k;
+                uint4 w0, w1;
+                if constexpr (kind == 0) {
+                    w0 = wpin[pidx][k][0]; w1 = wpin[pidx][k][NS - 1];
+                } else if constexpr (kind == 1) {
+                    w0 = *reinterpret_cast<const uint4*>(wlds + ((pidx * SGK + k) * NS + 0) * 1024 + ws.wlane);
+                    w1 = w0;
+                } else {
+                    w0 = w[si % RS][k][0]; w1 = w[si % RS][k][NS - 1];
+                }
+                uint4 h0, h1;
+                if constexpr (HF_REG) {
+                    h0 = hf[ks][0]; h1 = hf[ks][NS - 1];
+                } else {
+                    h0 = *reinterpret_cast<const uint4*>(hb + (clip * HPG + 32 * ks + 8 * g) * 2);
+                    h1 = *reinterpret_cast<const uint4*>(hb + (NS - 1) * HBG + (clip * HPG + 32 * ks + 8 * g) * 2);
+                }
+                d = mfma16(w0, h0, d);
+                if constexpr (NS == 2) {
+                    d = mfma16(w0, h1, d);
+                    d = mfma16(w1, h0, d);
+                }
+            });
+            acc[ub][q] = d;
+            __builtin_amdgcn_sched_barrier(0);   // keep the ring as deep as written: no hoisting of later loads above this group
+        });
+
+        char* hn = smem + (cur ^ 1) * NS * HBG;
+        const int64_t t = tidx(s);
+#pragma unroll
+        for (int ub = 0; ub < UPW; ++ub) {
+            float h[4], sv[4][4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const Gates z = lstm_gates<FAST>(acc[ub][0][r], acc[ub][1][r], acc[ub][2][r], acc[ub][3][r]);
+                h[r] = lstm_cell<FAST>(z, c[ub][r]);
+                sv[0][r] = z.i; sv[1][r] = z.f; sv[2][r] = z.g; sv[3][r] = z.o;
+            }
+            if (a.save && clip_ok) {                          // (never: a.save is null here.  Kept with the body: without it hipcc fuses the cell
+                                                              // update's multiply-adds differently and the bits are no longer bilstm_stream_kernel's)
+                float* sp = a.save + ((((int64_t)grp * a.B + b) * T + t) * 2 + dir) * (5 * HH) + 16 * UPW * wave + 16 * ub + 4 * g;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(sp + q * HH) = make_float4(sv[q][0], sv[q][1], sv[q][2], sv[q][3]);
+                *reinterpret_cast<float4*>(sp + 4 * HH) = make_float4(c[ub][0], c[ub][1], c[ub][2], c[ub][3]);
+            }
+            uint2 hiw, low;
+            split16<NS>(h, hiw, low);
+            store16<NS>(hn, HBG, (clip * HPG + 16 * UPW * wave + 16 * ub + 4 * g) * 2, hiw, low);
+            if (clip_ok && s < T) {                               // a lane whose own T steps are done repeats its last row, stores masked
+                const int64_t e = t * 2 * HH + 16 * ub;
+                if (OUT_TYPE == AMTX_T_BF16) *reinterpret_cast<uint2*>(obase + e * 2) = hiw;
+                else *reinterpret_cast<float4*>(obase + e * 4) = make_float4(h[0], h[1], h[2], h[3]);
+            }
+        }
+        cur ^= 1;
+        lds_barrier();
+    }
+}
+
+
 // ---------------------------------------------------------------------------------------------------------------
 // Backward recurrence for any hidden size HH = 128 k (training at model_complexity 3): dout [B][T][2 HH], the forward's saved
 // gates / cell states -> dxproj [B][T][2][4 HH].  Lane mapping of bilstm4_bwd_kernel (four clips per block in rows 0/4/8/12 of the
@@ -1010,9 +1273,43 @@ int launch_routed(const LstmRouted& r, const LstmArgs& a, hipStream_t stream) {
     return AMTX_ERR_UNSUPPORTED;
 }
 
+// Packed sequences: slots per block, grid and dynamic LDS.  Pure: a function of (S, hidden, planes, groups) alone.  The chain of dependent
+// steps is as long as the longest sequence whatever the mapping, and the sequences of a pass are the few tracks of a validation set: hidden 128
+// always takes the four-slot mapping (one cell per lane, the shortest step; ceil(S / 4) x 2 x groups blocks), the streaming sizes the
+// sixteen-slot mapping, the only one their kernel has.  LDS as lstm_route sizes it for the same kernels' bodies.
+struct LstmSeqRouted { int slots; dim3 grid; size_t lds; };
+LstmSeqRouted lstm_seq_route(int S, int hidden, int planes, int groups) {
+    const int slots = hidden == H ? 4 : 16;
+    const size_t lds = hidden == H ? 2 * (size_t)planes * HBUF_BYTES
+                                   : 2 * (size_t)planes * 16 * (hidden + 8) * 2 + (planes == 1 && hidden <= 384 ? (size_t)8 * 4 * 4096 : 0);
+    return {slots, dim3((unsigned)((S + slots - 1) / slots), 2, (unsigned)groups), lds};
+}
+
+template <int NS, int XT>
+int launch_seq(const LstmSeqArgs& a, hipStream_t stream) {
+    const LstmSeqRouted r = lstm_seq_route(a.S, a.l.hidden, NS, a.l.groups);
+    if (a.l.hidden == H) return launch_kernel(bilstm4_seq_kernel<NS, XT, XT>, r.grid, r.lds, stream, a);
+    return with_hidden(a.l.hidden, [&](auto hh) { return launch_kernel(bilstm_stream_seq_kernel<decltype(hh)::value, NS, XT, XT>, r.grid, r.lds, stream, a); });
+}
+
 }  // namespace
 
 namespace AMTX_FMT_NS {
+
+// One plane with 16-bit xproj / out, or two planes with fp32 xproj / out (the engine's two precisions); the table a.seqs is the caller's
+// to have checked (amtx_bilstm_seq_fwd does)
+int amtx_launch_bilstm_seq(const LstmSeqArgs& a, hipStream_t stream) {
+    AMTX_REQUIRE(a.l.xproj && a.l.whh && a.l.out && a.seqs, "bilstm_seq: null pointer");
+    AMTX_REQUIRE(a.S > 0 && a.l.groups > 0, "bilstm_seq: bad sizes");
+    if (a.l.hidden != H && a.l.hidden != 256 && a.l.hidden != 384 && a.l.hidden != 512) {
+        amtx_set_error("bilstm_seq: unsupported hidden size %d (128, 256, 384 and 512 are built)", a.l.hidden);
+        return AMTX_ERR_UNSUPPORTED;
+    }
+    if (a.l.planes == 1 && a.l.x_type == AMTX_T_BF16 && a.l.out_type == AMTX_T_BF16) return launch_seq<1, AMTX_T_BF16>(a, stream);
+    if (a.l.planes == 2 && a.l.x_type == AMTX_T_F32 && a.l.out_type == AMTX_T_F32) return launch_seq<2, AMTX_T_F32>(a, stream);
+    amtx_set_error("bilstm_seq: unsupported precision/type combination (one plane with 16-bit rows, two planes with fp32 rows; hidden %d)", a.l.hidden);
+    return AMTX_ERR_UNSUPPORTED;
+}
 
 size_t amtx_bilstm_wfrag_elems(int hidden, int planes) { return (size_t)2 * 4 * hidden * hidden * planes; }
 

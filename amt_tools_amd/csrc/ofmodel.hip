@@ -17,6 +17,7 @@
 #include "amtx_kernels.h"
 #include "amtx_model_common.h"
 #include "amtx_pack_layouts.h"
+#include "../../include/amtx_ofseq.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -33,7 +34,7 @@ struct LinearPack { DevBuf w, b; int N = 0, K = 0, n_pad = 0, k_pad = 0, groups 
     X(ns, pack_linear_host) X(ns, bilstm_pack_host) X(ns, conv1_pack_host) X(ns, conv1g_pack_host) X(ns, conv3x3_pack_host)     \
     X(ns, conv3x3_gen_pack_host) X(ns, pack_conv1_dev) X(ns, pack_conv1g_dev) X(ns, pack_conv3x3_dev) X(ns, pack_conv_gen_dev)    \
     X(ns, pack_linear_dev) X(ns, launch_bilstm_pack_dev) X(ns, launch_conv1) X(ns, launch_conv3x3) X(ns, launch_conv3x3_gen)    \
-    X(ns, launch_conv_stack) X(ns, launch_gemm) X(ns, launch_bilstm)
+    X(ns, launch_conv_stack) X(ns, launch_gemm) X(ns, launch_bilstm) X(ns, launch_bilstm_seq)
 #define AMTX_KERNEL_FIELD(ns, name) decltype(&ns::amtx_##name) name;
 #define AMTX_KERNEL_ENTRY(ns, name) &ns::amtx_##name,
 struct KernelSet { AMTX_FMT_KERNELS(AMTX_KERNEL_FIELD, amtx_bf16) };
@@ -795,6 +796,176 @@ extern "C" int amtx_of_offsets(const amtx_of_model* m, void* workspace, size_t w
     const size_t row = (size_t)m->n_out * sizeof(float);
     if (logits_offsets)
         AMTX_CHECK_HIP(hipMemcpy2DAsync(logits_offsets, row, w.joint + row, (size_t)m->dim_aj * 4, row, BT, hipMemcpyDeviceToDevice, s));
+    return AMTX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The engine in two phases (include/amtx_ofseq.h): exact whole-track inference.  Past the convolutions every stage of of_forward_impl is
+// row-wise except the recurrences, so the acoustic half runs on overlapped clips and hands the rows each clip keeps to the language half,
+// which runs the rest once over whole tracks: the same launches on M = total_rows packed rows, with the packed-sequence recurrence
+// (lstm.hip) and piano rolls (seqrows.hip) in place of the (B, T) ones.  The roll and copy16 epilogues of the LogisticBank GEMMs stay
+// off in both phases: they transpose by (B, T).
+namespace {
+
+struct LanguageWorkspace { char *xp, *l1, *joint, *joint16, *xp2, *l2, *mp; size_t total; };
+
+// the rows of `carve` from xp on, per packed row
+LanguageWorkspace carve_language(const amtx_of_model* m, int64_t R, char* base) {
+    LanguageWorkspace w;
+    const size_t es = amtx_tsize(m->act_type), M = (size_t)R;
+    WorkspaceCarver ws{base};
+    w.xp = ws.take(M * m->xw * es * m->n_rec);
+    w.l1 = ws.take(M * m->dim_lm * es * m->n_rec);
+    w.joint = ws.take(M * m->dim_aj * sizeof(float));
+    w.joint16 = ws.take(M * (size_t)((m->dim_aj + 63) / 64 * 64) * 2 * (m->plan.two_plane_acts ? 2 : 1));
+    w.xp2 = ws.take(M * m->xw * es);
+    w.l2 = ws.take(M * m->dim_lm * es);
+    w.mp = ws.take(M * m->n_out * sizeof(float));
+    w.total = ws.off;
+    return w;
+}
+
+int of_acoustic_rows_impl(const amtx_of_model* m, const FeatsIn& in, int B, int T, void* workspace, size_t workspace_bytes, const int64_t* table_host,
+                          const int64_t* table_dev, int64_t R, void* rows_e, float* rows_pitch, void* stream_) {
+    AMTX_REQUIRE(m && m->finalized, "amtx_of_acoustic_rows: model not finalized");
+    AMTX_REQUIRE(!in.clip_max || m->plan.fuses_db_scale, "amtx_of_acoustic_rows_power: this model does not stage its features in the conv kernel");
+    AMTX_REQUIRE(!in.feats16 || m->plan.takes_feats16, "amtx_of_acoustic_rows_feats16: this model does not stage 16-bit channels-last features");
+    AMTX_REQUIRE((in.feats || in.feats16) && workspace && table_host && table_dev && rows_e && rows_pitch, "amtx_of_acoustic_rows: null pointer");
+    AMTX_REQUIRE(B > 0 && T > 0 && R > 0, "amtx_of_acoustic_rows: bad batch/num_frames/total_rows");
+    Workspace w = carve(m, B, T, (char*)workspace);
+    AMTX_REQUIRE(workspace_bytes >= w.total, "amtx_of_acoustic_rows: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+    AMTX_REQUIRE(((uintptr_t)workspace % 256) == 0, "amtx_of_acoustic_rows: workspace must be 256-byte aligned");
+    for (int b = 0; b < B; ++b) {        // before anything is launched; amtx_launch_rows_gather checks the same rows again behind the GEMMs
+        const int64_t* d = table_host + 3 * (int64_t)b;
+        AMTX_REQUIRE(d[0] >= 0 && d[1] >= 0 && d[2] >= 0 && d[1] <= T && d[0] <= T - d[1] && d[1] <= R && d[2] <= R - d[1],
+                     "amtx_of_acoustic_rows: clip %d: the row {%lld, %lld, %lld} leaves the clip's %d frames or the %lld packed rows", b, (long long)d[0],
+                     (long long)d[1], (long long)d[2], T, (long long)R);
+    }
+    hipStream_t s = (hipStream_t)stream_;
+    const int64_t BT = (int64_t)B * T;
+    const int at = m->act_type, pl = m->planes;
+    const KernelSet* k = m->k;
+    int rc;
+    const ConvCall call = resolve_conv(m, B, T, in.feats16 != nullptr);
+    if ((rc = run_convs(m, call, in, w, B, T, s, [] {})) != AMTX_OK) return rc;
+    const bool sp = m->plan.two_plane_acts;
+    const int64_t a3_split = BT * m->kfc_pad * m->n_heads, e_split = BT * m->dim_am * m->n_heads;
+    const int at_d = sp ? AMTX_T_SPLIT : at;
+    GemmArgs g = gemm_args(w.a3, m->kfc_pad, at_d, m->fc1, pl, w.e, m->dim_am, at_d, BT, m->n_rec, BT * m->kfc_pad, BT * m->dim_am);
+    g.a_plane = call.a3_plane; g.a_split = a3_split; g.c_split = e_split;
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
+    // the pitch head's folded GEMM into dense fp32 logits [B T][n_out]: w.mp, which nothing else of this phase uses
+    GemmArgs gp = gemm_args(w.a3 + (size_t)(m->n_heads - 1) * BT * m->kfc_pad * (sp ? 2 : amtx_tsize(at)), m->kfc_pad, at_d, m->pitch_out, pl, w.mp,
+                            m->n_out, AMTX_T_F32, BT, 1, 0, 0);
+    gp.a_plane = call.a3_plane; gp.a_split = a3_split;
+    if ((rc = k->launch_gemm(gp, s)) != AMTX_OK) return rc;
+    // kept rows -> packed rows: head by head (a two-plane map: both planes per launch)
+    const size_t es = sp ? 2 : amtx_tsize(at);
+    for (int h = 0; h < m->n_rec; ++h)
+        if ((rc = amtx_launch_rows_gather(w.e + (size_t)h * BT * m->dim_am * es, B, T, (int64_t)m->dim_am * es, sp ? 2 : 1, e_split * 2, table_host, table_dev,
+                                          (char*)rows_e + (size_t)h * R * m->dim_am * es, R, (int64_t)m->n_rec * R * m->dim_am * 2, s)) != AMTX_OK)
+            return rc;
+    return amtx_launch_rows_gather(w.mp, B, T, (int64_t)m->n_out * 4, 1, 0, table_host, table_dev, rows_pitch, R, 0, s);
+}
+
+}  // namespace
+
+extern "C" size_t amtx_of_rows_e_bytes(const amtx_of_model* m, int64_t total_rows) {
+    return m && total_rows > 0 ? (size_t)total_rows * m->dim_am * amtx_tsize(m->act_type) * m->n_rec : 0;
+}
+
+extern "C" int amtx_of_acoustic_rows(const amtx_of_model* m, const float* feats, int64_t stride_b, int64_t stride_c, int64_t stride_t, int64_t stride_f,
+                                     int batch, int num_frames, void* workspace, size_t workspace_bytes, const int64_t* table_host,
+                                     const int64_t* table_dev, int64_t total_rows, void* rows_e, float* rows_pitch, void* stream) {
+    return of_acoustic_rows_impl(m, {feats, nullptr, stride_b, stride_c, stride_t, stride_f, nullptr, nullptr}, batch, num_frames, workspace, workspace_bytes,
+                                 table_host, table_dev, total_rows, rows_e, rows_pitch, stream);
+}
+
+extern "C" int amtx_of_acoustic_rows_power(const amtx_of_model* m, const float* power, int64_t stride_b, int64_t stride_t, int64_t stride_f,
+                                           const float* clip_max, const float* ref, int batch, int num_frames, void* workspace, size_t workspace_bytes,
+                                           const int64_t* table_host, const int64_t* table_dev, int64_t total_rows, void* rows_e, float* rows_pitch,
+                                           void* stream) {
+    AMTX_REQUIRE(clip_max, "amtx_of_acoustic_rows_power: clip_max is null");
+    return of_acoustic_rows_impl(m, {power, nullptr, stride_b, 0, stride_t, stride_f, clip_max, ref}, batch, num_frames, workspace, workspace_bytes, table_host,
+                                 table_dev, total_rows, rows_e, rows_pitch, stream);
+}
+
+extern "C" int amtx_of_acoustic_rows_feats16(const amtx_of_model* m, const void* feats16, int batch, int num_frames, void* workspace,
+                                             size_t workspace_bytes, const int64_t* table_host, const int64_t* table_dev, int64_t total_rows,
+                                             void* rows_e, float* rows_pitch, void* stream) {
+    AMTX_REQUIRE(feats16, "amtx_of_acoustic_rows_feats16: feats16 is null");
+    return of_acoustic_rows_impl(m, {nullptr, feats16, 0, 0, 0, 0, nullptr, nullptr}, batch, num_frames, workspace, workspace_bytes, table_host, table_dev,
+                                 total_rows, rows_e, rows_pitch, stream);
+}
+
+extern "C" size_t amtx_of_language_workspace_bytes(const amtx_of_model* m, int64_t total_rows) {
+    if (!m || total_rows <= 0) return 0;
+    return carve_language(m, total_rows, nullptr).total;
+}
+
+extern "C" int amtx_of_language_rows(const amtx_of_model* m, const void* rows_e, const float* rows_pitch, const int64_t* seqs_host,
+                                     const int64_t* seqs_dev, int num_seqs, int64_t total_rows, void* workspace, size_t workspace_bytes,
+                                     float* out_onsets, float* out_multi_pitch, float* out_offsets, float* logits_onsets, float* logits_multi_pitch,
+                                     float* logits_offsets, void* stream_) {
+    AMTX_REQUIRE(m && m->finalized, "amtx_of_language_rows: model not finalized");
+    AMTX_REQUIRE(rows_e && rows_pitch && seqs_dev && workspace, "amtx_of_language_rows: null pointer");
+    AMTX_REQUIRE(m->has_offsets || (!out_offsets && !logits_offsets), "amtx_of_language_rows: the model has no offset head");
+    int64_t max_len = 0;
+    int rc = amtx_check_seq_table("amtx_of_language_rows", seqs_host, num_seqs, total_rows, &max_len);
+    if (rc != AMTX_OK) return rc;
+    const int64_t R = total_rows;
+    LanguageWorkspace w = carve_language(m, R, (char*)workspace);
+    AMTX_REQUIRE(workspace_bytes >= w.total, "amtx_of_language_rows: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+    AMTX_REQUIRE(((uintptr_t)workspace % 256) == 0, "amtx_of_language_rows: workspace must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream_;
+    const int at = m->act_type, pl = m->planes;
+    const KernelSet* k = m->k;
+    const bool sp = m->plan.two_plane_acts;
+    const int at_d = sp ? AMTX_T_SPLIT : at;
+
+    // recurrent heads: x-projection, packed recurrence, LogisticBank -> joint[:, r n_out : (r + 1) n_out]
+    GemmArgs g = gemm_args(rows_e, m->dim_am, at_d, m->rec_ih, pl, w.xp, m->xw, at, R, m->n_rec, R * m->dim_am, R * m->xw);
+    g.a_split = R * m->dim_am * m->n_rec;
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
+    LstmSeqArgs l;
+    l.l.xproj = w.xp; l.l.x_type = at; l.l.whh = (const bf16_t*)m->rec_hh.p; l.l.planes = pl; l.l.out = w.l1; l.l.out_type = at;
+    l.l.B = num_seqs; l.l.T = 0; l.l.groups = m->n_rec; l.l.x_gs = R * m->xw; l.l.w_gs = (int64_t)m->hh_elems; l.l.out_gs = R * m->dim_lm;
+    l.l.hidden = m->hid;
+    l.seqs = seqs_dev; l.S = num_seqs;
+    if ((rc = k->launch_bilstm_seq(l, s)) != AMTX_OK) return rc;
+    g = gemm_args(w.l1, m->dim_lm, at, m->rec_out, pl, w.joint, m->dim_aj, AMTX_T_F32, R, m->n_rec, R * m->dim_lm, m->n_out);
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
+    // the pitch head's columns, computed by the acoustic phase
+    const size_t row = (size_t)m->n_out * sizeof(float);
+    AMTX_CHECK_HIP(hipMemcpy2DAsync(w.joint + (size_t)m->n_rec * row, (size_t)m->dim_aj * 4, rows_pitch, row, row, R, hipMemcpyDeviceToDevice, s));
+
+    // refinement stage
+    const int kp = (m->dim_aj + 63) / 64 * 64;
+    if (pl == 1) {
+        if ((rc = amtx_launch_cvt_pad_bf16((const float*)w.joint, m->dim_aj, m->dim_aj, (bf16_t*)w.joint16, kp, R, s, m->f16)) != AMTX_OK) return rc;
+        g = gemm_args(w.joint16, kp, AMTX_T_BF16, m->adj_ih, pl, w.xp2, m->xw, at, R, 1, 0, 0);
+        g.K = kp;
+    } else if (sp) {
+        if ((rc = amtx_launch_cvt_split((const float*)w.joint, m->dim_aj, m->dim_aj, (bf16_t*)w.joint16, kp, R * kp, R, s)) != AMTX_OK) return rc;
+        g = gemm_args(w.joint16, kp, AMTX_T_SPLIT, m->adj_ih, pl, w.xp2, m->xw, at, R, 1, 0, 0);
+        g.K = kp; g.a_split = R * kp;
+    } else {
+        g = gemm_args(w.joint, m->dim_aj, AMTX_T_F32, m->adj_ih, pl, w.xp2, m->xw, at, R, 1, 0, 0);
+    }
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
+    l.l.xproj = w.xp2; l.l.whh = (const bf16_t*)m->adj_hh.p; l.l.out = w.l2; l.l.groups = 1;
+    if ((rc = k->launch_bilstm_seq(l, s)) != AMTX_OK) return rc;
+    g = gemm_args(w.l2, m->dim_lm, at, m->adj_out, pl, w.mp, m->n_out, AMTX_T_F32, R, 1, 0, 0);
+    if ((rc = k->launch_gemm(g, s)) != AMTX_OK) return rc;
+
+    // piano rolls, every track's (n_out, L_t) map contiguous at element n_out row0_t
+    if (out_onsets && (rc = amtx_launch_pianoroll_seq((const float*)w.joint, m->dim_aj, 0, seqs_dev, num_seqs, max_len, m->n_out, 0.5f, out_onsets, s)) != AMTX_OK) return rc;
+    if (out_offsets && (rc = amtx_launch_pianoroll_seq((const float*)w.joint, m->dim_aj, m->n_out, seqs_dev, num_seqs, max_len, m->n_out, -1.0f, out_offsets, s)) != AMTX_OK) return rc;
+    if (out_multi_pitch && (rc = amtx_launch_pianoroll_seq((const float*)w.mp, m->n_out, 0, seqs_dev, num_seqs, max_len, m->n_out, 0.5f, out_multi_pitch, s)) != AMTX_OK) return rc;
+    // optional raw logits, packed (R, n_out)
+    if (logits_onsets) AMTX_CHECK_HIP(hipMemcpy2DAsync(logits_onsets, row, w.joint, (size_t)m->dim_aj * 4, row, R, hipMemcpyDeviceToDevice, s));
+    if (logits_offsets) AMTX_CHECK_HIP(hipMemcpy2DAsync(logits_offsets, row, w.joint + row, (size_t)m->dim_aj * 4, row, R, hipMemcpyDeviceToDevice, s));
+    if (logits_multi_pitch) AMTX_CHECK_HIP(hipMemcpyAsync(logits_multi_pitch, w.mp, row * R, hipMemcpyDeviceToDevice, s));
     return AMTX_OK;
 }
 

@@ -945,7 +945,7 @@ def _score_on_device(clips, stage, model, evaluator, times, batch_size, rank, wo
     _batched(clips, model, batch_size, rank, world, enqueue, finish, stage_extra, (lambda batch: batch.model_entries) if losses else None)
 
 
-def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1, losses=False):
+def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1, exact=False, losses=False):
     """Score WHOLE resident tracks, one result per track, as the reference's validate does -- from equally long overlapped clips.  The
     tracks (`track_ids`, default every track of `bank`; position j belongs to rank j % world) go through inference.run_tracks' stitching
     pass: clips of `num_frames` frames by tracks.seam_clips, of each only the frames at least `margin` frames from a clip edge that is
@@ -967,10 +967,17 @@ def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, t
         loss(track) = sum_k mean_t = (1 / L_t) * sum over the track's clips of their sums,
     added up in plan order in float64 on the host; the LossWrapper tracks that dictionary with the track's other results.  No logits are
     stitched.  This is the loss of the SEGMENT-WISE logits, the same approximation as the predictions: exact for tracks that fit one
-    clip, for TabCNN from margin 4 on the whole track's loss, an approximation for Onsets & Frames.  ValueError as in validate_clips."""
+    clip, for TabCNN from margin 4 on the whole track's loss, an approximation for Onsets & Frames.  ValueError as in validate_clips.
+
+    exact=True: inference.run_tracks' exact route (inference._exact_tracks; OnsetsFrames / OnsetsFrames2 in eval mode, margin >= 3) makes
+    the maps -- whole-track inference, scored as above.  With losses=True its language passes also return the packed logits, and a
+    track's sums are model.loss_sums on the track's (1, L_t, n_out) logits against labels.clips([t], [0], L_t) over the frames [0, L_t):
+    loss(track) = sums / L_t is the loss of the WHOLE-TRACK logits, what the model gives for the track as a batch of one."""
     import torch
     from . import cliploss
-    from .inference import _model_device, _stitch_tracks
+    from .inference import _check_exact, _exact_tracks, _model_device, _stitch_tracks
+    if exact:
+        _check_exact(model, margin)
     leaves = _leaves(evaluator)
     _check_banks('validate_tracks', leaves, bank, labels, notes, relative_times=False)
     loss_keys = _check_losses('validate_tracks', leaves, model, labels, banks=True) if losses else None
@@ -987,12 +994,23 @@ def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, t
         return {**{k: maps[k] for k in loss_keys}, tools.KEY_LOSS_FRAMES: cliploss.Windows(table, torch.from_numpy(table).to(device))}
 
     with torch.no_grad():
-        if losses:
+        track_losses = None
+        if exact:
+            mine, stitched, *rest = _exact_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, want_logits=losses)
+            if losses and stitched is not None:
+                sums = []
+                for j, t in enumerate(mine.tolist()):
+                    L = int(bank.frame_counts[t])
+                    maps = labels.clips([t], [0], L)
+                    table = np.array([[0, L]], dtype=np.int32)
+                    sums.append(model.loss_sums(rest[0][j], {k: maps[k] for k in loss_keys}, cliploss.Windows(table, torch.from_numpy(table).to(device))))
+                host = {key: torch.cat([d[key] for d in sums]).cpu().numpy() for key in sums[0]}       # the only transfer of the losses
+                track_losses = [{key: host[key][j] / float(bank.frame_counts[t]) for key in host} for j, t in enumerate(mine.tolist())]
+        elif losses:
             mine, stitched = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, model_entries=model_entries,
                                             collect=lambda slots, preds: collected.append((np.asarray(slots), preds[tools.KEY_LOSS])))
         else:
             mine, stitched = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world)
-        track_losses = None
         if collected:
             # the only transfer of the losses: the sum tensors.  np.add.at adds in index order: a track's clips in plan order
             slots = np.concatenate([s for s, _ in collected])

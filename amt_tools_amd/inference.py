@@ -13,6 +13,8 @@ Inference drivers.
   loop: behind every batch the kept columns of every output tensor are written into whole-track maps on the device (tracks.TrackMaps,
   amtx_stitch_clips); `_stitch_tracks` is that pass, shared with `evaluate.validate_tracks`.  Segment-wise inference: exact for TabCNN
   (margin >= 4) and for tracks that fit one clip, an approximation for the BiLSTMs of Onsets & Frames.
+  With exact=True `_exact_tracks` runs instead: the acoustic half of the Onsets & Frames engine on the same clips, both recurrences once
+  over whole tracks -- whole-track inference.
 """
 
 import numpy as np
@@ -22,6 +24,8 @@ from . import tools
 from .dp import shard_indices
 
 __all__ = ['run_offline', 'run_offline_batched', 'run_tracks']
+
+KEY_LOGITS = 'logits'      # run_tracks(exact=True, keep=(..., KEY_LOGITS)): a track's raw logits
 
 
 def run_offline(track_data, model, estimator=None):
@@ -266,8 +270,93 @@ def _stitch_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=2
     return mine, maps
 
 
+def _check_exact(model, margin):
+    """What exact=True asks of the model and the margin: ValueError / NotImplementedError before anything is launched."""
+    from .models import OnsetsFrames, TabCNN
+    if isinstance(model, TabCNN):
+        raise ValueError('exact=True is for the BiLSTMs of Onsets & Frames: TabCNN has no recurrence, margin 4 is already exact for it')
+    if not isinstance(model, OnsetsFrames):
+        raise ValueError(f'exact=True runs the two-phase Onsets & Frames engine: OnsetsFrames / OnsetsFrames2, not {type(model).__name__}')
+    if model.training:
+        raise ValueError('exact=True runs the inference engine: the model has to be in eval mode')
+    if int(margin) < 3:
+        raise ValueError(f'margin={int(margin)}: the convolutions of Onsets & Frames reach 3 frames, exact=True needs margin >= 3')
+
+
+class _AcousticPhase(object):
+    """What `_batched` takes for a model in the exact route: run_on_batch is the engine's acoustic phase on the batch, gathering into the
+    packed buffers of the current language pass (`aim`)."""
+
+    def __init__(self, model):
+        self.model, self.device = model, model.device
+        self.aim = None                      # (the pass's gather table on the host, on the device, total rows, rows_e, rows_pitch)
+        self.at = 0                          # the pass's clips so far: _batched's batches are runs of clips
+
+    def run_on_batch(self, batch):
+        table, table_dev, total_rows, rows_e, rows_pitch = self.aim
+        n = batch[tools.KEY_AUDIO].num_clips
+        self.model.acoustic_rows_on_batch(batch, table[self.at:self.at + n], table_dev[self.at:self.at + n], total_rows, rows_e, rows_pitch)
+        self.at += n
+        return n
+
+
+def _exact_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, rank=0, world=1, want_logits=False, max_rows=1 << 18):
+    """The pass of run_tracks(exact=True) and evaluate.validate_tracks(exact=True): _stitch_tracks' return contract, (the track ids this
+    rank owns, in request order; the tracks.TrackMaps of their whole-track outputs) -- and, with want_logits, a third value: per slot
+    {key: the track's (1, L_t, n_out) logits}.
+
+    The plan is tracks.seam_clips, as for _stitch_tracks, and short tracks run as clips of their own length with the whole clip kept.  But
+    the clips run only the engine's ACOUSTIC phase (convolutions, fc1, the pitch head), whose kept rows are gathered into packed rows; both
+    BiLSTM recurrences then run once over the whole tracks of a LANGUAGE pass, which writes the piano rolls straight into the maps.  From
+    margin 3 on the kept rows are the track's own, so this is whole-track inference.  A language pass holds tracks in request order until the
+    next would bring it above `max_rows` rows (a memory knob); a longer track runs alone and is never split.
+
+    ValueError before anything is launched: _check_exact's, what seam_clips refuses and a model that is not on a GPU."""
+    from .tracks import TrackMaps, gather_table, seam_clips, sequence_table, track_groups
+    _check_exact(model, margin)
+    seam_clips(bank.frame_counts, num_frames, margin, track_ids)                      # the whole request, checked once
+    device, on_gpu = _model_device(model)
+    if not on_gpu:
+        raise ValueError('whole tracks are run from clips of device-resident tracks: the model has to be on a GPU')
+    ids = np.arange(len(bank), dtype=np.int64) if track_ids is None else np.asarray(track_ids, dtype=np.int64).reshape(-1)
+    mine = ids[shard_indices(len(ids), rank, world)]
+    if mine.size == 0:
+        return (mine, None, None) if want_logits else (mine, None)
+    counts = np.asarray(bank.frame_counts, dtype=np.int64)[mine]
+    engine = model._get_engine(device)
+    n_out = engine.n_out
+    keys = [tools.KEY_ONSETS, tools.KEY_MULTIPITCH] + ([tools.KEY_OFFSETS] if model.has_offsets else [])
+    maps = TrackMaps(counts, device)
+    for key in keys:
+        maps.add(key, (n_out,), torch.float32)
+    phase = _AcousticPhase(model)
+    logits = [None] * len(mine)
+    for lo, hi in track_groups(counts, max_rows):
+        row0, seqs = sequence_table(counts[lo:hi])
+        total = int(counts[lo:hi].sum())
+        rows_e = torch.empty(engine.rows_e_bytes(total), dtype=torch.uint8, device=device)
+        rows_pitch = torch.empty((total, n_out), dtype=torch.float32, device=device)
+        plan = seam_clips(counts[lo:hi], num_frames, margin)                           # over the SLOTS of this pass
+        passes = [(int(num_frames), plan.track_ids, plan.first_frames, plan.kept)] if len(plan.track_ids) else []
+        for length in sorted(set(counts[lo:hi][plan.short].tolist())):
+            slots = plan.short[counts[lo:hi][plan.short] == length]
+            passes.append((length, slots, np.zeros(len(slots), dtype=np.int64), np.tile(np.array([[0, 0, length]], dtype=np.int64), (len(slots), 1))))
+        for frames, slots, firsts, kept in passes:
+            table = gather_table(row0, slots, kept)
+            phase.aim, phase.at = (table, torch.from_numpy(table).to(device), total, rows_e, rows_pitch), 0
+            _batched(BankClips(bank, mine[lo + slots], firsts, frames), phase, batch_size, 0, 1, lambda idx, done, _: done, lambda pending: None)
+        first = int(maps.base[keys[0]][lo])                                            # n_out * the rows in front of this pass
+        out = {key: maps.flat(key)[first:first + n_out * total] for key in keys}
+        packed = engine.language_rows(rows_e, rows_pitch, seqs, torch.from_numpy(seqs).to(device), total, out, want_logits=want_logits)
+        if want_logits:
+            for j in range(lo, hi):
+                at, L = int(row0[j - lo]), int(counts[j])
+                logits[j] = {key: rows[at:at + L].unsqueeze(0) for key, rows in packed.items()}
+    return (mine, maps, logits) if want_logits else (mine, maps)
+
+
 @torch.no_grad()
-def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, keep=None, decode_notes=False, times=None, rank=0, world=1):
+def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, keep=None, decode_notes=False, times=None, rank=0, world=1, exact=False):
     """Transcribe WHOLE tracks of `bank` (a tracks.TrackBank / PyramidBank) from overlapped clips of `num_frames` frames: returns
     {track id: predictions} for the tracks this rank owns (position j of `track_ids`, default every track, belongs to rank j % world).
     A track's predictions are host arrays (rows..., L_t) per output key, L_t the track's own frame count, and with decode_notes=True its
@@ -279,13 +368,23 @@ def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, 
     is SEGMENT-WISE inference.  For TabCNN, whose frames see 9 frames of features, margin >= 4 gives the whole-track result.  For
     Onsets & Frames the convolutions are exact from margin 3 on in exact arithmetic, but every BiLSTM starts anew at each clip edge and
     sees `margin` frames of context instead of the whole track: an approximation, measured in README; a track that fits one clip is run
-    whole and is exact.  `margin` has no default."""
+    whole and is exact.  `margin` has no default.
+
+    exact=True (OnsetsFrames / OnsetsFrames2 in eval mode on a GPU, margin >= 3): WHOLE-TRACK inference -- the clips run the engine's
+    acoustic phase only, both BiLSTMs run once over every whole track (`_exact_tracks`).  `keep` may then also name 'logits': the
+    track's raw logits {key: (L_t, n_out)} come back under that key."""
     from . import transcribe
     decoder_keys = (tools.KEY_ONSETS, tools.KEY_MULTIPITCH, tools.KEY_TABLATURE)
     wanted = None if keep is None else set(keep) | (set(decoder_keys) if decode_notes else set())
     if keep is not None and tools.KEY_MULTIPITCH in keep:
         wanted.add(tools.KEY_TABLATURE)                        # a tablature model's pitch map is expanded from its stitched tablature
-    mine, maps = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, wanted)
+    logits = None
+    if exact:
+        want_logits = keep is not None and KEY_LOGITS in keep
+        mine, maps, *rest = _exact_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, want_logits)
+        logits = rest[0] if want_logits else None
+    else:
+        mine, maps = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, wanted)
     out = {}
     if maps is None:
         return out
@@ -298,6 +397,8 @@ def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, 
     pending = None
     for j, t in enumerate(mine.tolist()):
         out[t] = {key: arrays[j] for key, arrays in host.items()}
+        if logits is not None:
+            out[t][KEY_LOGITS] = {key: value[0].cpu().numpy() for key, value in logits[j].items()}
         if want_pitch:                                         # the collapsed pitch map of a tablature (amtx_tab_expand), as run_offline_batched
             out[t][tools.KEY_MULTIPITCH] = tools.tab_expand(maps.track(j, tools.KEY_TABLATURE), model.profile, stacked=False, collapsed=True)[1][0].cpu().numpy()
         if decode_notes:

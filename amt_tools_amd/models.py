@@ -395,6 +395,9 @@ STAGING = {('audio', 'feats'): 'process_batch', ('audio', 'power'): 'power_batch
            ('pyramid_clips', 'feats'): 'process_clips', ('pyramid_clips', 'feats16'): 'process_clips16', ('pyramid_clips', 'feats16_split'): 'process_clips16'}
 # form -> the engine entry point that takes it (_OFEngine.forward)
 ENTRY_POINTS = {'feats': 'amtx_of_forward', 'power': 'amtx_of_forward_power', 'feats16': 'amtx_of_forward_feats16', 'feats16_split': 'amtx_of_forward_feats16'}
+# form -> the acoustic phase's entry point (_OFEngine.acoustic_rows)
+ACOUSTIC_ROWS_ENTRY_POINTS = {'feats': 'amtx_of_acoustic_rows', 'power': 'amtx_of_acoustic_rows_power', 'feats16': 'amtx_of_acoustic_rows_feats16',
+                              'feats16_split': 'amtx_of_acoustic_rows_feats16'}
 _CLIPS_FAMILY = {'track_clips': 'spec', 'pyramid_clips': 'cqt'}
 _CLIPS_NEED = {'track_clips': 'a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend over an STFT / MelSpec module',
                'pyramid_clips': 'a TrackClips batch needs a model whose frontend is exactly one SpectralFrontend; clips of a PyramidBank need '
@@ -546,6 +549,8 @@ class _OFEngine(_EngineBase):
                          int(model.has_offsets), {'bf16': 0, 'x3': 1, 'f16': 2}[model.precision])
         self.device_sync = os.environ.get('AMTX_HOST_WEIGHT_SYNC') is None     # A/B switch: always pack on the host
         self.device_syncs = 0                            # re-syncs that stayed on the GPU (tests)
+        self.model_complexity = int(model.model_complexity)
+        self.language_workspace = None                   # the language phase's own (language_rows)
 
     def _resync_on_device(self, items):
         # A RE-sync (validate() inside train() pays one at every checkpoint) stays on the GPU where the library can pack there: the
@@ -583,9 +588,10 @@ class _OFEngine(_EngineBase):
         """True when a forward pass of this shape runs the three convolution layers as one kernel (csrc/convf.hip)."""
         return bool(_lib.call('amtx_of_conv_stack_fused', self.handle, int(batch), int(num_frames)))
 
-    def forward(self, feats, want_logits=True):
-        """feats: (B,C,T,F) fp32 CUDA tensor (any strides), or PendingFeatures.  Returns binary maps + raw logits.  The form says which entry
-        point runs (ENTRY_POINTS), where B and T are read and which strides go with the pointer."""
+    @staticmethod
+    def _input(feats):
+        """(form, the tensor whose device counts, the leading arguments of the form's entry point, B, T) of (B,C,T,F) fp32 features or a
+        PendingFeatures: the form says where B and T are read and which strides go with the pointer."""
         form = feats.form if isinstance(feats, PendingFeatures) else 'feats'
         if form == 'feats':
             B, _, T, _ = feats.shape
@@ -599,6 +605,12 @@ class _OFEngine(_EngineBase):
             feats = feats.feats16                           # (B,T,F,8) or two planes (2,B,T,F,8): a bare pointer, shape and device only
             B, T = feats.shape[-4], feats.shape[-3]
             lead = (feats, B, T)
+        return form, feats, lead, B, T
+
+    def forward(self, feats, want_logits=True):
+        """feats: (B,C,T,F) fp32 CUDA tensor (any strides), or PendingFeatures.  Returns binary maps + raw logits.  The form says which entry
+        point runs (ENTRY_POINTS)."""
+        form, feats, lead, B, T = self._input(feats)
         self._grow_workspace(_lib.call('amtx_of_workspace_bytes', self.handle, B, T), feats.device)
         n_out = self.n_out
         opts = dict(dtype=torch.float32, device=feats.device)
@@ -611,6 +623,45 @@ class _OFEngine(_EngineBase):
         _lib.call(ENTRY_POINTS[form], self.handle, *lead, ws, ws.numel(), onsets, multi_pitch, lo, lm, lp, device=feats.device)
         self._last = (B, T)
         return onsets, multi_pitch, lo, lm, lp
+
+    # ---- the two phases of exact whole-track inference (include/amtx_ofseq.h, inference._exact_tracks) ----
+    def rows_e_bytes(self, total_rows):
+        return int(_lib.call('amtx_of_rows_e_bytes', self.handle, int(total_rows)))
+
+    def acoustic_rows(self, feats, table, table_dev, total_rows, rows_e, rows_pitch):
+        """The acoustic phase on a clip batch (`feats` as for forward): the rows the (B, 3) int64 gather table {src_first, count, dst_row}
+        keeps -- `table` on the host, `table_dev` its device copy -- go into the packed buffers rows_e (rows_e_bytes(total_rows) bytes) and
+        rows_pitch (total_rows, n_out) float32."""
+        form, feats, lead, B, T = self._input(feats)
+        table = np.ascontiguousarray(table, dtype=np.int64)
+        if table.shape != (B, 3) or tuple(table_dev.shape) != (B, 3) or table_dev.dtype != torch.int64 or not table_dev.is_contiguous():
+            raise ValueError(f'one gather row {{src_first, count, dst_row}} per clip, on the host and on the device: ({B}, 3) int64')
+        self._grow_workspace(_lib.call('amtx_of_workspace_bytes', self.handle, B, T), feats.device)
+        ws = self.workspace
+        _lib.call(ACOUSTIC_ROWS_ENTRY_POINTS[form], self.handle, *lead, ws, ws.numel(), table, table_dev, int(total_rows), rows_e, rows_pitch, device=feats.device)
+
+    def language_rows(self, rows_e, rows_pitch, seqs, seqs_dev, total_rows, out, want_logits=False):
+        """The language phase on total_rows packed rows holding the whole tracks of the (S, 2) int64 sequence table {row0, len} (`seqs` on the
+        host, `seqs_dev` its device copy).  `out`: {key: flat float32 tensor of n_out * total_rows elements} for KEY_ONSETS, KEY_MULTIPITCH and
+        (offset head) KEY_OFFSETS -- track t's (n_out, L_t) map lands at element n_out * row0_t.  Returns {key: (total_rows, n_out) logits}
+        with want_logits, else {}."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int64)
+        R, device = int(total_rows), rows_pitch.device
+        need = _lib.call('amtx_of_language_workspace_bytes', self.handle, R)
+        if self.language_workspace is None or self.language_workspace.numel() < need:
+            self.language_workspace = None
+            self.language_workspace = _lib.alloc_workspace(need, device)
+        keys = (tools.KEY_ONSETS, tools.KEY_MULTIPITCH, tools.KEY_OFFSETS)
+        logits = {k: torch.empty((R, self.n_out), dtype=torch.float32, device=device) for k in keys if want_logits and k in out}
+        ws = self.language_workspace
+        try:
+            _lib.call('amtx_of_language_rows', self.handle, rows_e, rows_pitch, seqs, seqs_dev, len(seqs), R, ws, ws.numel(),
+                      *(out.get(k) for k in keys), *(logits.get(k) for k in keys), device=device)
+        except _lib.AmtxError as e:
+            if f'({_lib.ERR_UNSUPPORTED})' in str(e):
+                raise NotImplementedError(f'model_complexity={self.model_complexity}: no packed-sequence recurrence is built for this size and precision ({e})') from e
+            raise
+        return logits
 
     def offsets(self, device, want_logits=True):
         """OnsetsFrames2: offset probabilities (B,O,T) [+ raw logits (B,T,O)] of the last forward."""
@@ -668,6 +719,19 @@ class OnsetsFrames(TranscriptionModel):
         finally:
             self.__dict__.pop('_logits_wanted', None)
             self.__dict__.pop('_in_run_on_batch', None)
+
+    def acoustic_rows_on_batch(self, batch, table, table_dev, total_rows, rows_e, rows_pitch):
+        """The engine's acoustic phase (_OFEngine.acoustic_rows) on a batch whose features are staged exactly as run_on_batch stages them in
+        eval mode on a GPU (feature_route, deferred forms included).  inference._exact_tracks is the caller."""
+        self.__dict__['_in_run_on_batch'] = True
+        try:
+            feats = self.pre_proc(batch)[tools.KEY_FEATS]
+        finally:
+            self.__dict__.pop('_in_run_on_batch', None)
+        pending = isinstance(feats, PendingFeatures)
+        if not pending and feats.dtype != torch.float32:
+            feats = feats.float()
+        self._get_engine(feats.device).acoustic_rows(feats if pending else feats.detach(), table, table_dev, total_rows, rows_e, rows_pitch)
 
     def forward(self, feats):
         """feats (B,C,T,F) -> dict of raw logits (B,T,O) under 'onsets' and 'multi_pitch'."""
@@ -786,29 +850,40 @@ class OnsetsFrames(TranscriptionModel):
         return all(isinstance(lm, LanguageModel) and autograd.bilstm_supported(feats, lm.mlm, lm.use_hip_autograd)
                    for lm in lms) and lms[0].hidden_size == lms[1].hidden_size
 
+    def _loss_dict(self, output, batch):
+        """The losses of the raw logits `output` against the ground truth of `batch` (onsetsframes.py:158-184): the label rules post_proc
+        and loss_sums share.  With tools.KEY_LOSS_FRAMES in the batch, per-clip sums over a frame window (run_on_batch): get_loss_sums
+        for get_loss."""
+        onset_layer, pitch_layer = self.onset_head[-1], self.adjoin[-1]
+        loss = dict()
+        multi_pitch_ref = batch[tools.KEY_MULTIPITCH]
+        if tools.KEY_LOSS_FRAMES in batch:
+            frames = batch[tools.KEY_LOSS_FRAMES]
+            get_loss = lambda layer, est, ref: layer.get_loss_sums(est, ref, frames)
+        else:
+            get_loss = lambda layer, est, ref: layer.get_loss(est, ref)
+        loss[tools.KEY_LOSS_PITCH] = get_loss(pitch_layer, output[tools.KEY_MULTIPITCH], multi_pitch_ref)
+        if tools.KEY_ONSETS in batch.keys():
+            onsets_ref = batch[tools.KEY_ONSETS]
+        else:
+            # intended behaviour of onsetsframes.py:176-178 (the reference's NumPy helper fails on tensors)
+            onsets_ref = tools.multi_pitch_to_onsets(multi_pitch_ref)
+        loss[tools.KEY_LOSS_ONSETS] = get_loss(onset_layer, output[tools.KEY_ONSETS], onsets_ref)
+        loss[tools.KEY_LOSS_TOTAL] = loss[tools.KEY_LOSS_PITCH] + loss[tools.KEY_LOSS_ONSETS]
+        return loss
+
+    def loss_sums(self, logits, labels, frames):
+        """Per-clip loss sums of raw logits {key: (B, T, n_out)} against the label maps `labels` over the frame windows `frames` (what
+        tools.KEY_LOSS_FRAMES carries): the get_loss_sums calls post_proc makes, without a forward pass."""
+        return self._loss_dict(logits, {**labels, tools.KEY_LOSS_FRAMES: frames})
+
     def post_proc(self, batch):
         """Losses (when ground truth is present) + final piano rolls (onsetsframes.py:138-196)."""
         output = batch[tools.KEY_OUTPUT]
         onset_layer, pitch_layer = self.onset_head[-1], self.adjoin[-1]
         onsets_est, multi_pitch_est = output[tools.KEY_ONSETS], output[tools.KEY_MULTIPITCH]
         if tools.KEY_MULTIPITCH in batch.keys():
-            loss = dict()
-            multi_pitch_ref = batch[tools.KEY_MULTIPITCH]
-            if tools.KEY_LOSS_FRAMES in batch:
-                # per-clip sums over a frame window (run_on_batch): the same label rules, get_loss_sums for get_loss
-                frames = batch[tools.KEY_LOSS_FRAMES]
-                get_loss = lambda layer, est, ref: layer.get_loss_sums(est, ref, frames)
-            else:
-                get_loss = lambda layer, est, ref: layer.get_loss(est, ref)
-            loss[tools.KEY_LOSS_PITCH] = get_loss(pitch_layer, multi_pitch_est, multi_pitch_ref)
-            if tools.KEY_ONSETS in batch.keys():
-                onsets_ref = batch[tools.KEY_ONSETS]
-            else:
-                # intended behaviour of onsetsframes.py:176-178 (the reference's NumPy helper fails on tensors)
-                onsets_ref = tools.multi_pitch_to_onsets(multi_pitch_ref)
-            loss[tools.KEY_LOSS_ONSETS] = get_loss(onset_layer, onsets_est, onsets_ref)
-            loss[tools.KEY_LOSS_TOTAL] = loss[tools.KEY_LOSS_PITCH] + loss[tools.KEY_LOSS_ONSETS]
-            output[tools.KEY_LOSS] = loss
+            output[tools.KEY_LOSS] = self._loss_dict(output, batch)
         cached = self.__dict__.pop('_engine_out', None)
         if cached is not None and cached[0] is onsets_est and cached[1] is multi_pitch_est:
             output[tools.KEY_ONSETS], output[tools.KEY_MULTIPITCH] = cached[2], cached[3]
@@ -843,23 +918,25 @@ class OnsetsFrames2(OnsetsFrames):
         self.dim_aj += dim_out
         self.adjoin[0] = LanguageModel(self.dim_aj, self.dim_lm)
 
+    def _loss_dict(self, output, batch):
+        loss = super()._loss_dict(output, batch)
+        offset_layer, offsets_est = self.offset_head[-1], output[tools.KEY_OFFSETS]
+        if tools.KEY_OFFSETS in batch.keys():
+            offsets_ref = batch[tools.KEY_OFFSETS]
+        else:
+            offsets_ref = tools.multi_pitch_to_offsets(batch[tools.KEY_MULTIPITCH])
+        if tools.KEY_LOSS_FRAMES in batch:
+            offsets_loss = offset_layer.get_loss_sums(offsets_est, offsets_ref, batch[tools.KEY_LOSS_FRAMES])
+        else:
+            offsets_loss = offset_layer.get_loss(offsets_est, offsets_ref)
+        loss[tools.KEY_LOSS_OFFSETS] = offsets_loss
+        loss[tools.KEY_LOSS_TOTAL] += offsets_loss
+        return loss
+
     def post_proc(self, batch):
         output = super().post_proc(batch)
         offset_layer = self.offset_head[-1]
         offsets_est = output[tools.KEY_OFFSETS]
-        if tools.KEY_LOSS in output.keys():
-            if tools.KEY_OFFSETS in batch.keys():
-                offsets_ref = batch[tools.KEY_OFFSETS]
-            else:
-                offsets_ref = tools.multi_pitch_to_offsets(batch[tools.KEY_MULTIPITCH])
-            loss = output[tools.KEY_LOSS]
-            if tools.KEY_LOSS_FRAMES in batch:
-                offsets_loss = offset_layer.get_loss_sums(offsets_est, offsets_ref, batch[tools.KEY_LOSS_FRAMES])
-            else:
-                offsets_loss = offset_layer.get_loss(offsets_est, offsets_ref)
-            loss[tools.KEY_LOSS_OFFSETS] = offsets_loss
-            loss[tools.KEY_LOSS_TOTAL] += offsets_loss
-            output[tools.KEY_LOSS] = loss
         cached = self.__dict__.pop('_engine_offsets', None)
         if cached is not None and cached[0] is offsets_est:
             output[tools.KEY_OFFSETS] = cached[1]

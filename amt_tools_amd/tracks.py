@@ -1019,3 +1019,62 @@ class TrackMaps(object):
         flat = self._flat[key].cpu().numpy()
         rows = self.rows(key)
         return [flat[int(at):int(at) + rows * int(L)].reshape(self._shape[key] + (int(L),)) for at, L in zip(self.base[key], self.frame_counts)]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# exact whole tracks: packed rows (include/amtx_ofseq.h, inference._exact_tracks)
+# ------------------------------------------------------------------------------------------------------------------------------
+def track_groups(frame_counts, max_rows):
+    """The language passes of a request: [(lo, hi)] ranges of its slots, in request order.  Tracks are taken until the next would bring a
+    pass above `max_rows` packed rows; a track longer than max_rows runs alone and is never split.  Pure host code."""
+    counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+    if int(max_rows) < 1:
+        raise ValueError(f'max_rows={max_rows}: a language pass holds at least one row')
+    groups, lo, rows = [], 0, 0
+    for j, L in enumerate(counts.tolist()):
+        if j > lo and rows + L > int(max_rows):
+            groups.append((lo, j))
+            lo, rows = j, 0
+        rows += L
+    if len(counts):
+        groups.append((lo, len(counts)))
+    return groups
+
+
+def sequence_table(frame_counts):
+    """(row0, table) of tracks whose rows are packed back to back in slot order: row0 (n,) int64, the packed row at which slot j starts,
+    and the (n, 2) int64 sequence table {row0, len} the packed-sequence kernels take, listed LONGEST FIRST (ties in slot order) -- a
+    block's slots are consecutive rows of the table, so they finish together.  Rows are addressed through row0: no data moves for it."""
+    counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+    if counts.size == 0 or (counts < 1).any():
+        raise ValueError('frame_counts: at least one track, at least one frame each')
+    row0 = np.concatenate(([0], np.cumsum(counts)[:-1])).astype(np.int64)
+    order = np.argsort(-counts, kind='stable')
+    return row0, _clip_table(row0[order], counts[order])
+
+
+def gather_table(row0, slots, kept):
+    """The (n, 3) int64 table {src_first, count, dst_row} of amtx_rows_gather for clips whose tracks are the slots `slots` and whose kept
+    columns are the (n, 3) rows {dst_first_frame, src_first_col, count} of a SeamPlan: the kept rows of clip j land at packed row
+    row0[slot_j] + dst_first_frame_j."""
+    row0, slots, kept = np.asarray(row0, dtype=np.int64), np.asarray(slots, dtype=np.int64).reshape(-1), np.asarray(kept, dtype=np.int64).reshape(-1, 3)
+    if len(slots) != len(kept) or ((slots < 0) | (slots >= len(row0))).any():
+        raise ValueError(f'one slot below {len(row0)} per row of kept columns')
+    return _clip_table(kept[:, 1], kept[:, 2], row0[slots] + kept[:, 0])
+
+
+def gather_rows_host(dst, src, table):
+    """amtx_rows_gather with NumPy: dst[dst_row_b + i] = src[b][src_first_b + i] for every row {src_first, count, dst_row} of `table` and
+    i < count, in place; returns dst.  src: (batch, num_frames, width...), dst: (total_rows, width...) of the same dtype.  ValueError for a
+    row the entry point refuses.  The CPU restatement of the kernel."""
+    src, table = np.asarray(src), np.asarray(table, dtype=np.int64)
+    if src.ndim < 2 or dst.ndim != src.ndim - 1 or dst.shape[1:] != src.shape[2:] or dst.dtype != src.dtype:
+        raise ValueError(f'src is (batch, num_frames, width...), dst (total_rows, width...) of one dtype: {src.shape} {src.dtype}, {dst.shape} {dst.dtype}')
+    if table.shape != (src.shape[0], 3):
+        raise ValueError(f'one row {{src_first, count, dst_row}} per clip: ({src.shape[0]}, 3), not {table.shape}')
+    for b, (first, count, row) in enumerate(table.tolist()):
+        if min(first, count, row) < 0 or first + count > src.shape[1] or row + count > dst.shape[0]:
+            raise ValueError(f'clip {b}: the row {(first, count, row)} leaves the clip or the packed rows')
+    for b, (first, count, row) in enumerate(table.tolist()):
+        dst[row:row + count] = src[b, first:first + count]
+    return dst
