@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get('AMTX_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libam
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'amtx.h')
 # Every header of the library, bound the same way; a new header is appended here and gets a pinned table of its own under tests/golden/.
 HEADERS = ('amtx.h', 'amtx_tracks.h', 'amtx_pyramid.h', 'amtx_labels.h', 'amtx_optim.h', 'amtx_noteclips.h', 'amtx_stitch.h', 'amtx_cliploss.h',
-           'amtx_ofseq.h')
+           'amtx_ofseq.h', 'amtx_thrgrid.h')
 _PINNED_HEADERS = 4        # call()'s "declare no function" text lists these four in this order (pinned by tests/test_capi.py); later headers go in front
 
 _lib = None

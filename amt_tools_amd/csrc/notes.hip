@@ -9,9 +9,11 @@
 // prefix count.  HBM-bound: reads 2 x 4 B per cell once, writes 8 B per note.
 
 #include "amtx_kernels.h"
+#include "amtx_notes_walk.h"
 
 namespace {
 
+// the walk itself (stops, event slots, the carried state) is notes_walk_chunk: shared with the threshold-grid decoder (thrgrid.hip)
 __global__ __launch_bounds__(256) void notes_kernel(const float* __restrict__ onsets, const float* __restrict__ mp, int rows, int T,
                                                     int use_onsets, int cap, int2* __restrict__ pairs, int* __restrict__ counts) {
     const int lane = threadIdx.x & 63;
@@ -20,8 +22,7 @@ __global__ __launch_bounds__(256) void notes_kernel(const float* __restrict__ on
     const float* on = (use_onsets ? onsets : mp) + (int64_t)row * T;
     const float* act = mp + (int64_t)row * T;
     int2* out = pairs + (int64_t)row * cap;
-    int next_stop = T;          // first stop frame strictly after the current chunk
-    int n = 0;                  // events written so far (descending frame order)
+    NotesWalk w = notes_walk_begin(T);
     const int nchunks = (T + 63) >> 6;
     for (int ch = nchunks - 1; ch >= 0; --ch) {
         const int t = ch * 64 + lane;
@@ -31,21 +32,9 @@ __global__ __launch_bounds__(256) void notes_kernel(const float* __restrict__ on
         const bool imp = valid && ((t == 0) ? (o > 0.f) : (o - oprev > 0.f));
         // onsets given: activity = onsets OR multi_pitch; derived onsets: activity = multi_pitch (utils.py:403-411)
         const bool active = valid && ((act[t] != 0.f) || (use_onsets && o != 0.f));
-        const bool stop = valid && (!active || imp);
-        const unsigned long long smask = __ballot(stop);
-        const unsigned long long above = (lane == 63) ? 0ull : (smask >> (lane + 1));
-        const int my_next = above ? (t + 1 + __builtin_ctzll(above)) : next_stop;
-        const unsigned long long imask = __ballot(imp);
-        if (imp) {
-            // events of this chunk in descending frame order after those of later chunks
-            const int higher = __builtin_popcountll(lane == 63 ? 0ull : (imask >> (lane + 1)));
-            const int slot = n + higher;
-            if (slot < cap) out[slot] = make_int2(t, my_next);
-        }
-        n += __builtin_popcountll(imask);
-        if (smask) next_stop = ch * 64 + __builtin_ctzll(smask);
+        notes_walk_chunk(w, ch, lane, valid, imp, active, cap, out);
     }
-    if (lane == 0) counts[row] = n;
+    if (lane == 0) counts[row] = w.n;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@ Evaluation: the evaluator classes of amt_tools/evaluate.py (constructor argument
 unchanged: process_track / average_results / reset_results / finalize(writer, step) / set_save_dir / set_patterns / set_verbose), and a
 batched validation loop that scores a partition on the device: validate_batched for host clips and references, validate_clips for clips
 of device-resident tracks (tracks.TrackBank / PyramidBank, LabelBank, NoteBank), validate_tracks for those tracks whole, one result per
-track, stitched from overlapped clips.
+track, stitched from overlapped clips; sweep_tracks for a grid of onset and frame thresholds over those tracks in one pass of the model.
 
 Every evaluator is split in two:
 
@@ -30,7 +30,7 @@ import numpy as np
 from . import tools
 from .inference import run_offline
 
-__all__ = ['validate', 'validate_batched', 'validate_clips', 'validate_tracks', 'average_results', 'append_results', 'log_results', 'write_results', 'pattern_match',
+__all__ = ['validate', 'validate_batched', 'validate_clips', 'validate_tracks', 'sweep_tracks', 'multipitch_grid_counts', 'average_results', 'append_results', 'log_results', 'write_results', 'pattern_match',
            'Evaluator',
            'ComboEvaluator', 'LossWrapper', 'StackedMultipitchEvaluator', 'MultipitchEvaluator', 'StackedNoteEvaluator', 'NoteEvaluator',
            'TablatureEvaluator', 'SoftmaxAccuracy', 'note_edges', 'match_notes_count', 'N_DECIMALS']
@@ -442,6 +442,34 @@ class MultipitchEvaluator(StackedMultipitchEvaluator):
 
     def evaluate(self, estimated, reference):
         return super().evaluate(np.expand_dims(estimated, axis=-3), np.expand_dims(reference, axis=-3))
+
+
+MAX_GRID_THRESHOLDS = 32       # thresholds per axis of a sweep (amtx_eval_multipitch_grid_counts)
+
+
+def multipitch_grid_counts(prob, ref, thresholds):
+    """(B, K, T) probability maps and reference maps, (G,) thresholds -> (B, G, 3) int64: per clip and threshold the cells active in
+    both maps, in the estimate cut at the threshold (`prob < thr ? 0 : 1`: equality and NaN are active) and in the reference -- the
+    three sums of MultipitchEvaluator on the roll cut at that threshold.  Device tensors: one call of amtx_eval_multipitch_grid_counts,
+    one pass over the maps, a device tensor comes back.  Host arrays / CPU tensors: NumPy, an array comes back."""
+    import torch
+    if torch.is_tensor(prob) and prob.is_cuda:
+        from . import _lib
+        assert ref.is_cuda and prob.shape == ref.shape and prob.dim() == 3
+        est, ref = prob.contiguous().float(), ref.contiguous().float()
+        thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).to(est.device)
+        B, K, T = est.shape
+        counts = torch.empty((B, thr.numel(), 3), dtype=torch.int64, device=est.device)
+        _lib.call('amtx_eval_multipitch_grid_counts', est, ref, B, K, T, thr, thr.numel(), counts, device=est.device)
+        return counts
+    prob, ref = np.asarray(prob, dtype=np.float32), np.asarray(ref) != 0
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    assert prob.shape == ref.shape and prob.ndim == 3 and 1 <= len(thr) <= MAX_GRID_THRESHOLDS
+    out = np.zeros((prob.shape[0], len(thr), 3), dtype=np.int64)
+    for g, t in enumerate(thr):
+        est = ~(prob < t)                          # not `prob >= t`: a NaN is active, as on the device
+        out[:, g, 0], out[:, g, 1], out[:, g, 2] = (est & ref).sum(axis=(1, 2)), est.sum(axis=(1, 2)), ref.sum(axis=(1, 2))
+    return out
 
 
 def _sort_rows(rows):
@@ -1042,3 +1070,133 @@ def validate_tracks(bank, labels, notes, model, evaluator, num_frames, margin, t
         if pending is not None:
             finish(pending)
     return evaluator.average_results()
+
+
+def sweep_tracks(bank, labels, notes, model, evaluator, num_frames, margin, onset_thresholds, frame_thresholds, track_ids=None, batch_size=256,
+                 rank=0, world=1):
+    """Score WHOLE resident tracks at every pair of a grid of onset and frame thresholds, from ONE run of the model: returns
+    {(onset_thr, frame_thr): results}, `results` being what evaluator.average_results() would hold had validate_tracks(exact=True) scored
+    the rank's tracks (position j of `track_ids` belongs to rank j % world) with rolls cut at that pair instead of 0.5.  The
+    evaluator's own tracked results are not touched.
+
+    The thresholds act behind the model, so inference._exact_tracks runs once with want_logits (the exact route only: OnsetsFrames /
+    OnsetsFrames2 in eval mode on a GPU, margin >= 3).  Per track, amtx_pianoroll_fwd(threshold = -1) turns the onset and frame logits
+    into probability maps; then
+      * a MultipitchEvaluator (of tools.KEY_MULTIPITCH) takes its counts for all frame thresholds from ONE
+        multipitch_grid_counts call against labels.clips([t], [0], L_t): its entry depends on the frame threshold only;
+      * the notes of all len(onset_thresholds) * len(frame_thresholds) pairs are decoded by ONE transcribe.decode_notes_grid_async call
+        (pair p = i_onset * len(frame_thresholds) + i_frame), and every NoteEvaluator scores them with one amtx_eval_notes_match of P
+        groups against notes.whole([t]) repeated P times (offsets 0, N, 2N, ...).  A group the matcher refuses (unsupported, bad
+        argument) and a NoteBank with fractional pitches take the host matcher on the same rows, as in validate_tracks; a chunk whose
+        rows overflowed the decoder's first buffer is decoded again into one of the exact size and matched again on the device;
+      * a LossWrapper is ignored: the loss does not depend on a threshold.
+    Only count tensors come back.  Each leaf's results_from_counts makes a track's results, and they are appended and averaged with
+    the evaluators' own functions, so the cell (0.5, 0.5) is bit-equal to validate_tracks(exact=True).
+
+    ValueError before anything is launched: inference._check_exact's, validate_tracks' bank checks, a leaf other than
+    MultipitchEvaluator (of KEY_MULTIPITCH), NoteEvaluator or LossWrapper, an axis with no, a non-finite, a negative or more than
+    MAX_GRID_THRESHOLDS thresholds, and a model that is not on a GPU."""
+    import torch
+    from . import transcribe
+    from .inference import _check_exact, _check_thresholds, _exact_tracks, _frame_times, _model_device, logits_to_map
+    _check_exact(model, margin)
+    leaves = _leaves(evaluator)
+    for e in leaves:
+        if not isinstance(e, (MultipitchEvaluator, NoteEvaluator, LossWrapper)):
+            raise ValueError(f'sweep_tracks scores MultipitchEvaluator, NoteEvaluator and LossWrapper leaves, not {type(e).__name__}')
+        if isinstance(e, MultipitchEvaluator) and e.unpack_key != tools.KEY_MULTIPITCH:
+            raise ValueError(f'sweep_tracks: a MultipitchEvaluator scores \'{tools.KEY_MULTIPITCH}\' against the frame thresholds, not \'{e.unpack_key}\'')
+    _check_banks('sweep_tracks', leaves, bank, labels, notes, relative_times=False)
+    on_thr = _check_thresholds(onset_thresholds, 'sweep_tracks: onset_thresholds', MAX_GRID_THRESHOLDS)
+    fr_thr = _check_thresholds(frame_thresholds, 'sweep_tracks: frame_thresholds', MAX_GRID_THRESHOLDS)
+    device, on_gpu = _model_device(model)
+    if not on_gpu:
+        raise ValueError('sweep_tracks scores device-resident tracks: the model has to be on a GPU')
+    scored = [e for e in leaves if not isinstance(e, LossWrapper)]
+    map_leaves = [e for e in scored if isinstance(e, MultipitchEvaluator)]
+    note_leaves = [e for e in scored if isinstance(e, NoteEvaluator)]
+    F, P = len(fr_thr), len(on_thr) * len(fr_thr)
+    side = transcribe._side_stream(device)
+
+    def enqueue(t, logits, thr_d, pairs_d):
+        """Everything of one track that runs on the device."""
+        L = int(bank.frame_counts[t])
+        mp_prob = logits_to_map(logits[tools.KEY_MULTIPITCH], -1.0)
+        work = {'t': t, 'frame': None, 'chunks': []}
+        if map_leaves:
+            work['frame'] = multipitch_grid_counts(mp_prob, labels.clips([t], [0], L)[tools.KEY_MULTIPITCH], thr_d)
+        if note_leaves:
+            on_prob = logits_to_map(logits[tools.KEY_ONSETS], -1.0)
+            handle = transcribe.decode_notes_grid_async(on_prob, mp_prob, _frame_times(model, L), pairs_d, model.profile.low)
+            whole = notes.whole([t]) if notes.integral else None
+            for p0, n, chunk in handle.chunks:
+                rows, offsets = chunk.device_rows()
+                ref = matches = None
+                if whole is not None:
+                    N = int(whole.total)
+                    ref = (whole.rows[:max(N, 1)].repeat(n, 1), torch.arange(n + 1, dtype=torch.int32, device=device) * N)
+                    matches = [e.match_batch((rows, offsets), ref) for e in note_leaves]
+                work['chunks'].append((p0, n, chunk, rows.shape[0], offsets, matches, ref))
+        work['done'] = torch.cuda.Event()
+        work['done'].record(torch.cuda.current_stream(device))
+        return work
+
+    def finish(work):
+        """A track's counts on the host: ((F, 3) frame counts or None, per note leaf its (P, 3) counts)."""
+        side.wait_event(work['done'])
+        with torch.cuda.stream(side):
+            frame = work['frame'][0].cpu().numpy() if work['frame'] is not None else None
+            host = [(off.cpu().numpy(), [c.cpu().numpy() for c, _ in matches] if matches is not None else None)
+                    for _, _, _, _, off, matches, _ in work['chunks']]
+        per_leaf = [np.zeros((P, 3), dtype=np.int64) for _ in note_leaves]
+        ref_rows = None
+        for (p0, n, chunk, capacity, _, _, ref), (off, counts) in zip(work['chunks'], host):
+            if counts is not None and int(off[-1]) > capacity:
+                # more notes than the chunk's first buffer held: the matcher saw a truncated buffer.  fetch() decodes once more into a
+                # buffer of the exact size (and waits for it), and the matcher runs again on those rows
+                chunk.fetch()
+                counts = [c.cpu().numpy() for c, _ in (e.match_batch(chunk.device_rows(), ref) for e in note_leaves)]
+            for i, e in enumerate(note_leaves):
+                bad = np.ones(n, dtype=bool) if counts is None else counts[i][:, 0] < 0
+                if counts is not None:
+                    per_leaf[i][p0:p0 + n] = counts[i]
+                if bad.any():
+                    if ref_rows is None:
+                        ref_rows = np.asarray(notes.host_whole([work['t']])[0], dtype=np.float64).reshape(-1, 3)
+                    est_rows, est_off, _ = chunk.fetch()          # decodes once more when the first buffer was too small
+                    for g in np.flatnonzero(bad):
+                        a = est_rows[est_off[g]:est_off[g + 1]]
+                        per_leaf[i][p0 + g] = match_notes_count(a[:, 2], a[:, :2], ref_rows[:, 2], ref_rows[:, :2], e.offset_ratio), len(a), len(ref_rows)
+        return frame, per_leaf
+
+    tracked = {(io, jf): [dict() for _ in scored] for io in range(len(on_thr)) for jf in range(F)}
+    with torch.no_grad():
+        mine, _, logits = _exact_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, want_logits=True)
+        thr_d = torch.tensor(fr_thr, dtype=torch.float32).to(device)
+        pairs_d = torch.tensor([[a, b] for a in on_thr for b in fr_thr], dtype=torch.float32).to(device)
+        pending, results = None, []
+        for j, t in enumerate(mine.tolist()):
+            now = enqueue(t, logits[j], thr_d, pairs_d)
+            if pending is not None:
+                results.append(finish(pending))                   # the GPU scores track j meanwhile
+            pending = now
+        if pending is not None:
+            results.append(finish(pending))
+    for frame, per_leaf in results:
+        for (io, jf), cell in tracked.items():
+            for k, e in enumerate(scored):
+                if isinstance(e, MultipitchEvaluator):
+                    new = e.results_from_counts(frame[jf:jf + 1])
+                else:
+                    new = e.results_from_counts(per_leaf[note_leaves.index(e)][io * F + jf:io * F + jf + 1])
+                cell[k] = append_results(cell[k], new)
+    out = {}
+    for (io, jf), cell in tracked.items():
+        if isinstance(evaluator, ComboEvaluator):
+            average = dict()
+            for e, res in zip(scored, cell):
+                ComboEvaluator._merge(average, e.results_key, average_results(res))
+        else:
+            average = average_results(cell[0]) if cell else dict()
+        out[(on_thr[io], fr_thr[jf])] = average
+    return out

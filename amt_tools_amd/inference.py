@@ -14,7 +14,8 @@ Inference drivers.
   amtx_stitch_clips); `_stitch_tracks` is that pass, shared with `evaluate.validate_tracks`.  Segment-wise inference: exact for TabCNN
   (margin >= 4) and for tracks that fit one clip, an approximation for the BiLSTMs of Onsets & Frames.
   With exact=True `_exact_tracks` runs instead: the acoustic half of the Onsets & Frames engine on the same clips, both recurrences once
-  over whole tracks -- whole-track inference.
+  over whole tracks -- whole-track inference.  thresholds=(onset_thr, frame_thr) then cuts the rolls from the
+  whole-track logits at that pair (`logits_to_map`); `evaluate.sweep_tracks` scores a grid of such pairs in one pass (section 6l).
 """
 
 import numpy as np
@@ -355,8 +356,37 @@ def _exact_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=25
     return (mine, maps, logits) if want_logits else (mine, maps)
 
 
+def _check_thresholds(values, what, limit=None):
+    """Decision thresholds as a list of floats: ValueError for none, a non-finite or negative one (amtx_pianoroll_fwd reads a negative
+    threshold as "no cut") and, with `limit`, more than that many."""
+    values = [float(v) for v in np.asarray(values, dtype=np.float64).reshape(-1)]
+    if not values:
+        raise ValueError(f'{what}: at least one threshold')
+    if not all(np.isfinite(v) and v >= 0 for v in values):
+        raise ValueError(f'{what}: thresholds are finite and not negative, not {values}')
+    if limit is not None and len(values) > limit:
+        raise ValueError(f'{what}: {len(values)} thresholds, at most {limit}')
+    return values
+
+
+def logits_to_map(logits, threshold, out=None):
+    """A track's (1, L, n_out) float32 logits -> its (1, n_out, L) map through amtx_pianoroll_fwd: sigmoid, transpose and
+    `s < threshold ? 0 : 1` -- the expression behind every roll of the package; threshold < 0: the probabilities themselves.
+    `out`: a contiguous (1, n_out, L) float32 tensor to write into."""
+    from . import _lib
+    assert logits.dim() == 3 and logits.is_cuda and logits.dtype == torch.float32 and logits.stride(2) == 1
+    B, L, n_out = logits.shape
+    assert B == 1 or logits.stride(0) == L * logits.stride(1)
+    if out is None:
+        out = torch.empty((B, n_out, L), dtype=torch.float32, device=logits.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == B * n_out * L
+    _lib.call('amtx_pianoroll_fwd', logits, logits.stride(1), 0, B, L, n_out, float(threshold), out, device=logits.device)
+    return out
+
+
 @torch.no_grad()
-def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, keep=None, decode_notes=False, times=None, rank=0, world=1, exact=False):
+def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, keep=None, decode_notes=False, times=None, rank=0, world=1, thresholds=None,
+               exact=False):
     """Transcribe WHOLE tracks of `bank` (a tracks.TrackBank / PyramidBank) from overlapped clips of `num_frames` frames: returns
     {track id: predictions} for the tracks this rank owns (position j of `track_ids`, default every track, belongs to rank j % world).
     A track's predictions are host arrays (rows..., L_t) per output key, L_t the track's own frame count, and with decode_notes=True its
@@ -372,16 +402,30 @@ def run_tracks(bank, model, num_frames, margin, track_ids=None, batch_size=256, 
 
     exact=True (OnsetsFrames / OnsetsFrames2 in eval mode on a GPU, margin >= 3): WHOLE-TRACK inference -- the clips run the engine's
     acoustic phase only, both BiLSTMs run once over every whole track (`_exact_tracks`).  `keep` may then also name 'logits': the
-    track's raw logits {key: (L_t, n_out)} come back under that key."""
+    track's raw logits {key: (L_t, n_out)} come back under that key.
+
+    thresholds=(onset_thr, frame_thr) (exact=True only, else ValueError): `onsets` and `multi_pitch` are cut from the whole-track logits
+    at these thresholds instead of 0.5 (logits_to_map), before notes are decoded -- the pair evaluate.sweep_tracks scores.  None: 0.5."""
     from . import transcribe
     decoder_keys = (tools.KEY_ONSETS, tools.KEY_MULTIPITCH, tools.KEY_TABLATURE)
     wanted = None if keep is None else set(keep) | (set(decoder_keys) if decode_notes else set())
     if keep is not None and tools.KEY_MULTIPITCH in keep:
         wanted.add(tools.KEY_TABLATURE)                        # a tablature model's pitch map is expanded from its stitched tablature
     logits = None
+    if thresholds is not None:
+        if not exact:
+            raise ValueError('thresholds are applied to the whole-track logits of the exact route: exact=True')
+        if np.size(thresholds) != 2:
+            raise ValueError('thresholds: the pair (onset threshold, frame threshold)')
+        thresholds = _check_thresholds(thresholds, 'run_tracks')
     if exact:
         want_logits = keep is not None and KEY_LOGITS in keep
-        mine, maps, *rest = _exact_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, want_logits)
+        mine, maps, *rest = _exact_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, want_logits or thresholds is not None)
+        if thresholds is not None and maps is not None:
+            # the rolls again, from the same logits at the chosen thresholds, over the engine's own (cut at 0.5), before anything reads them
+            for j in range(len(mine)):
+                for key, thr in zip((tools.KEY_ONSETS, tools.KEY_MULTIPITCH), thresholds):
+                    logits_to_map(rest[0][j][key], thr, out=maps.track(j, key))
         logits = rest[0] if want_logits else None
     else:
         mine, maps = _stitch_tracks(bank, model, num_frames, margin, track_ids, batch_size, rank, world, wanted)

@@ -22,7 +22,8 @@ import numpy as np
 
 from . import _lib, tools
 
-__all__ = ['NoteTranscriber', 'PitchListWrapper', 'multi_pitch_to_notes', 'decode_notes_batch', 'estimate_hop_length', 'inhibit_activations',
+__all__ = ['NoteTranscriber', 'PitchListWrapper', 'multi_pitch_to_notes', 'decode_notes_batch', 'decode_notes_grid_async', 'decode_notes_grid',
+           'cut_activations', 'estimate_hop_length', 'inhibit_activations',
            'ComboEstimator', 'TablatureWrapper', 'StackedMultiPitchCollapser', 'StackedNoteTranscriber', 'decode_tab_notes_batch_async',
            'decode_tab_notes_batch']
 
@@ -263,23 +264,146 @@ def decode_notes_batch_async(onsets, multi_pitch, times, low=tools.DEFAULT_PIANO
     pairs = torch.empty((B * K, cap, 2), dtype=torch.int32, device=dev)
     counts = torch.empty((B * K,), dtype=torch.int32, device=dev)
     _lib.call('amtx_notes_decode', onsets, multi_pitch, B, K, T, cap, pairs, counts, device=dev)
+    # 1024 notes per clip on average covers any realistic transcription (the synthetic bench clips decode to ~400); a denser batch is
+    # caught in result() through the total the device reports and decoded again into a buffer of the exact size
+    return _rows_of_events(pairs, counts, B, K, cap, ext_d, stride, low, int(rows_capacity) if rows_capacity else max(B * 1024, 1 << 14))
+
+
+def _rows_of_events(pairs, counts, groups, K, cap, ext_d, stride, low, capacity):
+    """amtx_notes_rows on a decoder's event buffers (`groups` clips of K keys, `cap` events per row) -> the _PendingNotes of its rows; the
+    handle's retry runs the same pass into a buffer of another capacity."""
+    import torch
+    dev = pairs.device
 
     def rows_pass(capacity):
         rows = torch.empty((capacity, 3), dtype=torch.float64, device=dev)
         onset_col = torch.empty((capacity,), dtype=torch.float64, device=dev)
-        offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
-        _lib.call('amtx_notes_rows', pairs, counts, B, K, cap, ext_d, stride, int(low), rows, onset_col, capacity, offsets, device=dev)
+        offsets = torch.empty((groups + 1,), dtype=torch.int32, device=dev)
+        _lib.call('amtx_notes_rows', pairs, counts, groups, K, cap, ext_d, stride, int(low), rows, onset_col, capacity, offsets, device=dev)
         return _PendingNotes(rows, offsets, rows_pass, onset_col)
 
-    # 1024 notes per clip on average covers any realistic transcription (the synthetic bench clips decode to ~400); a denser batch is
-    # caught in result() through the total the device reports and decoded again into a buffer of the exact size
-    return rows_pass(int(rows_capacity) if rows_capacity else max(B * 1024, 1 << 14))
+    return rows_pass(capacity)
 
 
 def decode_notes_batch(onsets, multi_pitch, times, low=tools.DEFAULT_PIANO_LOWEST_PITCH):
     """Device path: (B,88,T) fp32 CUDA tensors (onsets may be None) -> list of B (K,3) float64 arrays.
     `times` is one (T,) grid shared by the batch or a (B,T) array."""
     return decode_notes_batch_async(onsets, multi_pitch, times, low).result()
+
+
+def cut_activations(prob, threshold):
+    """Host restatement of the device cut (`s < thr ? 0 : 1` on float32): a {0, 1} float32 map; equality and NaN are active."""
+    return (~(np.asarray(prob, dtype=np.float32) < np.float32(threshold))).astype(np.float32)
+
+
+def _threshold_pairs(pairs):
+    pairs = np.ascontiguousarray(pairs, dtype=np.float32).reshape(-1, 2)
+    if len(pairs) == 0:
+        raise ValueError('at least one (onset threshold, frame threshold) pair')
+    return pairs
+
+
+class _HostGridNotes(object):
+    """decode_notes_grid_async for host maps: multi_pitch_to_notes on every pair's cut rolls, clip by clip."""
+    strings = None
+
+    def __init__(self, on_prob, mp_prob, times, pairs, low):
+        self._args = on_prob, mp_prob, times, pairs, low
+
+    def device_rows(self):
+        return None
+
+    def result(self):
+        on_prob, mp_prob, times, pairs, low = self._args
+        out = []
+        for on_thr, mp_thr in pairs:
+            mp = cut_activations(mp_prob, mp_thr)
+            on = cut_activations(on_prob, on_thr) if on_prob is not None else None
+            out += [multi_pitch_to_notes(mp[b], times, low, None if on is None else on[b]) for b in range(mp.shape[0])]
+        return out
+
+
+class _PendingGridNotes(object):
+    """The handle of decode_notes_grid_async on the device: `chunks` = [(first pair, number of pairs, _PendingNotes)], each chunk's groups
+    being (pair - first pair) * B + clip.  One chunk unless the event buffer of all pairs would exceed the budget."""
+    strings = None
+
+    def __init__(self, chunks):
+        self.chunks = chunks
+
+    def device_rows(self):
+        """_PendingRows.device_rows over all P * B groups.  One chunk: its own buffers, nothing waits.  Several: the chunks' rows are
+        fetched (this waits for the decoder) and put behind one another."""
+        import torch
+        if len(self.chunks) == 1:
+            return self.chunks[0][2].device_rows()
+        rows, offsets, at = [], [], 0
+        for _, _, handle in self.chunks:
+            handle.fetch()                                   # decodes once more when the chunk's first buffer was too small
+            r, off = handle.device_rows()
+            total = int(off[-1])
+            rows.append(r[:total])
+            offsets.append(off[:-1] + at)
+            at += total
+        last = torch.full((1,), at, dtype=torch.int32, device=rows[0].device)
+        return torch.cat(rows + ([rows[0].new_zeros((1, 3))] if at == 0 else [])), torch.cat(offsets + [last])
+
+    def result(self):
+        return [notes for _, _, handle in self.chunks for notes in handle.result()]
+
+
+def decode_notes_grid_async(on_prob, mp_prob, times, pairs, low=tools.DEFAULT_PIANO_LOWEST_PITCH, rows_capacity=None, event_bytes=1 << 30):
+    """decode_notes_batch_async for a table of threshold pairs: `on_prob` (or None) and `mp_prob` are (B, K, T) PROBABILITY maps, `pairs` a
+    (P, 2) table of {onset threshold, frame threshold}; `handle.result()` -> list of P * B (N, 3) float64 arrays, entry p * B + b being
+    what decode_notes_batch gives for clip b on the maps cut at pair p (`prob < thr ? 0 : 1`; without on_prob the onsets are derived
+    from the frame roll and a pair's first entry is unused).  `times`: ONE (T,) grid shared by all clips; a (B, T) array is a ValueError.
+
+    Device tensors: amtx_notes_decode_grid cuts and walks all pairs of a chunk in one launch, amtx_notes_rows takes its output with
+    P_chunk * B clips.  The pairs are chunked so that the event buffer, P_chunk * B * K * capacity * 8 bytes, stays within `event_bytes`
+    (at least one pair per chunk); `rows_capacity`: note rows of a chunk's first buffer.  Host arrays / CPU tensors: a loop over
+    multi_pitch_to_notes."""
+    import torch
+    pairs_d = None
+    if torch.is_tensor(pairs) and pairs.is_cuda:             # a table already on the device (a driver uploads it once)
+        pairs_d = pairs.reshape(-1, 2).float().contiguous()
+        if pairs_d.shape[0] == 0:
+            raise ValueError('at least one (onset threshold, frame threshold) pair')
+    else:
+        pairs = _threshold_pairs(pairs.numpy() if torch.is_tensor(pairs) else pairs)
+    if np.ndim(times) != 1:
+        raise ValueError('decode_notes_grid takes one (T,) time grid for all clips')
+    if not (torch.is_tensor(mp_prob) and mp_prob.is_cuda):
+        host = lambda m: None if m is None else (m.numpy() if torch.is_tensor(m) else np.asarray(m))     # noqa: E731
+        return _HostGridNotes(host(on_prob), host(mp_prob), np.asarray(times), pairs if pairs_d is None else pairs_d.cpu().numpy(), low)
+    assert mp_prob.dim() == 3 and (on_prob is None or (on_prob.is_cuda and on_prob.shape == mp_prob.shape))
+    B, K, T = mp_prob.shape
+    dev = mp_prob.device
+    mp_prob = mp_prob.contiguous().float()
+    if on_prob is not None:
+        on_prob = on_prob.contiguous().float()
+    ext, stride = _extended_grid(times, T)
+    ext_d = _grid_on_device(ext, dev)
+    cap = T // 2 + 2
+    per_chunk = max(1, int(event_bytes) // (B * K * cap * 8))
+    if pairs_d is None:
+        pairs_d = torch.from_numpy(pairs).to(dev)
+    P = pairs_d.shape[0]
+    chunks = []
+    for p0 in range(0, P, per_chunk):
+        n = min(per_chunk, P - p0)
+        events = torch.empty((n * B * K, cap, 2), dtype=torch.int32, device=dev)
+        counts = torch.empty((n * B * K,), dtype=torch.int32, device=dev)
+        _lib.call('amtx_notes_decode_grid', on_prob, mp_prob, B, K, T, pairs_d[p0:p0 + n], n, cap, events, counts, device=dev)
+        # the first buffer: T / 2 notes per (pair, clip) on average, at least the 1024 of decode_notes_batch_async -- a whole track is
+        # longer than a clip, and a low threshold decodes to several times the notes of 0.5; 32 bytes per row, beside K * cap * 8 of events
+        chunks.append((p0, n, _rows_of_events(events, counts, n * B, K, cap, ext_d, stride, low,
+                                              int(rows_capacity) if rows_capacity else max(n * B * max(1024, T // 2), 1 << 14))))
+    return _PendingGridNotes(chunks)
+
+
+def decode_notes_grid(on_prob, mp_prob, times, pairs, low=tools.DEFAULT_PIANO_LOWEST_PITCH, rows_capacity=None, event_bytes=1 << 30):
+    """decode_notes_grid_async(...).result()."""
+    return decode_notes_grid_async(on_prob, mp_prob, times, pairs, low, rows_capacity, event_bytes).result()
 
 
 class NoteTranscriber(object):
